@@ -2,15 +2,21 @@
 """Headline benchmark: 1024x1024 faces/sec of the region-aware StyleGAN2 synthesis (BASELINE.json configs[1]:
 ``Net3.gen_img`` from random W+ codes and random 12-class masks, batch 4 per GPU, randomize_noise=False).
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU — launched by torch.distributed.run, or, when called
-                                                          plainly, bench.py starts that launcher itself as a child process)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                         (N>1: one rank per GPU — launched by torch.distributed.run, or, when called
+                                                         plainly, bench.py starts that launcher itself as a child process)
 
 A step = one ``gen_img`` call on a batch of 4 faces whose codes / masks / weights are already resident in HBM; every step gets a fresh
 one-hot mask tensor object, so the per-frame mask -> region-map conversion runs inside the timed region (no cache hit).
 Frames are independent units: with N GPUs every rank synthesises its own batch (weak scaling, no data-path collective;
 RCCL is used for the start/stop barriers and the max-over-ranks reduction of the elapsed time only).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line: the contract fields (`value` = faces/s over the K steps,
+`ms_per_step` = milliseconds per timed step), the compact `config` and `f16_overflowed`.  ``--dump-outputs DIR`` writes what the last
+timed step returned (``gen_img``'s images and structure features, float32) as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.
+
+With ``--full`` the run goes on after the timed steps and rank 0 prints ONE JSON line with the contract fields plus
   roofline     — dominant kernel (the split-bf16 MFMA implicit-GEMM modulated conv): algorithmic FLOPs of its launches in a step
                  / their HIP-event durations measured inside the timed region, against dense bf16 MFMA peak / 3 MFMAs per product
   cpu_baseline — the faithful 12-pass CPU oracle timed on one face on this host's cores (rank 0, N=1 only)
@@ -18,6 +24,8 @@ Rank 0 prints ONE JSON line with the contract fields plus
                  timed batch against the CPU oracle chain
   clip         — BASELINE configs[4]: a 256-frame clip, frames block-sharded over the ranks, broadcast of the clip's shared W+
                  (latent_avg) and the streamed uint8 gather of the frames to rank 0 INSIDE the timed region (every N)
+and the one-stream pass, soak, in-run A/B, mask sensitivity and PTI figures; the ``--no-*`` / ``--clip`` / ``--soak-seconds`` /
+``--pti-passes`` options choose among these legs and matter with ``--full`` only.
 """
 from __future__ import annotations
 
@@ -218,6 +226,57 @@ class _BoardSampler:
                 "what": "rocm-smi package power / shader clock during the soak (the timed step repeated): the board's power limit, not issue slots, sets the clock"}
 
 
+def _headline(args, ops, bs, world, elapsed):
+    """The contract fields of the result line (plain and --full runs): the K timed steps took `elapsed` seconds (max over the ranks)."""
+    value = bs * world * args.steps / elapsed
+    return {
+        "metric": "1024x1024 faces/sec (StyleGAN2 regional synthesis, gen_img)", "value": round(value, 3), "unit": "faces/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("f32" if ops.MODCONV_MODE != "sb" else "f16+mxfp6x2 (masked 3x3 layers >= 32^2) / bf16x3 (all other layers)" if ops.mx_arith() == 1 else "bf16x3"),
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: StyleGAN2 1024x1024 synthesis from random W+ (Net3.gen_img, randomize_noise=False), "
+                               f"12-region {args.labels} masks (a fresh one-hot mask tensor per step: the mask -> region-map conversion is timed), batch={bs}/GPU; arithmetic = "
+                               + (("split-bf16: fp32 operands split into bf16 hi+lo, 3 bf16 MFMAs per product, fp32 accumulate (max-abs pixel error "
+                                   "6e-5 vs the reference; plain bf16 would miss the 1e-3 bar)"
+                                   + ("; the masked 3x3 layers of width >= 32: f16 MFMA for a1*w1 plus two block-scaled MX-fp6 MFMAs for the cross terms "
+                                      "(csrc/modconv_mx.hip; 2e-4 on the pixels)" if ops.mx_arith() == 1 else "")) if ops.MODCONV_MODE == "sb" else "exact fp32 MFMA"),
+                   "batch_per_gpu": bs, "global_batch": bs * world, "resolution": 1024, "regions": 12, "parallelism": f"frames x{world}",
+                   "streams_per_gpu": args.streams,
+                   "step_overlap": (f"consecutive steps (independent batches) alternate over {args.streams} HIP streams: the latency-bound 4^2-32^2 layers of a "
+                                    "batch run under the large layers of the one before; all K steps complete inside the timed region") if args.streams > 1 else "none"},
+    }
+
+
+def _contract_fields(line):
+    """The contract fields of a result line and its compact `config`, as the stdout line carries them."""
+    out = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline")}
+    out["dtype"] = line["dtype"] if len(line["dtype"]) <= 80 else line["dtype"][:79] + "~"
+    out["data"] = line["data"]
+    cfg = line["config"]
+    out["config"] = {"workload": f"BASELINE configs[1]: StyleGAN2 1024x1024 synthesis from random W+, 12-region masks, batch={cfg['batch_per_gpu']}/GPU",
+                     "batch_per_gpu": cfg["batch_per_gpu"], "global_batch": cfg["global_batch"], "parallelism": cfg["parallelism"], "streams_per_gpu": cfg["streams_per_gpu"]}
+    return out
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs: all arrays together (batch 4: 48 MiB of images + 2 MiB of structure features)
+
+
+def _dump_outputs(path, arrays, suffix=""):
+    """``--dump-outputs``: every tensor of `arrays` as path/<name><suffix>.npy in float32 (float64 stays float64).  Above DUMP_BUDGET_BYTES in all (a larger
+    --batch), each array is replaced by the same fixed, seeded sample of its flattened elements, a share of the budget proportional to its size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+            for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_BUDGET_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, a.size * DUMP_BUDGET_BYTES // total, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def _compact_line(line, one_stream, ksum, steps, detail_path):
     """The ONE stdout line: the contract fields, `roofline` / `cpu_baseline` with scalars only, and the secondary metrics as flat scalars (< 2 000 characters)."""
     def short(v, n=120):
@@ -230,12 +289,7 @@ def _compact_line(line, one_stream, ksum, steps, detail_path):
         for k in path:
             d = d.get(k) if isinstance(d, dict) else None
         return d
-    out = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline")}
-    out["dtype"] = short(line["dtype"], 80)
-    out["data"] = line["data"]
-    cfg = line["config"]
-    out["config"] = {"workload": f"BASELINE configs[1]: StyleGAN2 1024x1024 synthesis from random W+, 12-region masks, batch={cfg['batch_per_gpu']}/GPU",
-                     "batch_per_gpu": cfg["batch_per_gpu"], "global_batch": cfg["global_batch"], "parallelism": cfg["parallelism"], "streams_per_gpu": cfg["streams_per_gpu"]}
+    out = _contract_fields(line)
     roof = line.get("roofline")
     r = scalars(roof, {"bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "launches_per_step", "avg_launch_ms", "algorithmic_gflop_per_launch", "whole_job_frac"})
     if r is not None:
@@ -285,6 +339,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every secondary measurement and check (roofline, CPU baseline, one-stream pass, "
+                                                        "soak, in-run A/B, mask sensitivity, full swap, clip, PTI)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--streams", type=int, default=2, help="HIP streams consecutive steps alternate over (1 = one stream)")
     ap.add_argument("--no-mask-sensitivity", action="store_true", help="skip the two short runs under coarse / i.i.d. region maps")
@@ -306,6 +363,8 @@ def main():
     ap.add_argument("--clip-unit", choices=["swap", "gen"], default="swap",
                     help="per-frame work of the clip: the reference's per-frame swap (2 parses + 2 encodes + mask surgery + mix + synthesis) or synthesis only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _spawn_ranks(args.gpus)
@@ -335,7 +394,7 @@ def main():
     la = seeded.seeded_latent_avg(2, 18)
     net.latent_avg = la.to(dev)
     sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sd_cpu = {"G." + k: v.clone() for k, v in net.G.state_dict().items()}
     net = net.to(dev)
 
@@ -351,11 +410,14 @@ def main():
     _guard_scope = ops.mx_guard_scope()
     guard_all = _guard_scope.__enter__()
 
-    def step():
+    def step_outputs():
         # a fresh tensor OBJECT per step (a view: no copy, no extra kernel): ops.mask_to_labels caches per mask object, and a frame's
         # one-hot mask -> uint8 region map conversion is per-frame work that belongs inside the timed region
         with torch.no_grad():
-            return net.gen_img(None, codes, mask.view_as(mask), randomize_noise=False)[0]
+            return net.gen_img(None, codes, mask.view_as(mask), randomize_noise=False)
+
+    def step():
+        return step_outputs()[0]
 
     # Steps are independent batches; consecutive ones go to alternating HIP streams (runner.StreamPipeline) so that the latency-bound 4^2-32^2
     # layers of one batch run under the large layers of the batch before.  Exactly K steps between the two synchronisation points, every one
@@ -385,12 +447,31 @@ def main():
     with (ops.KernelTimer(only={dom0} if (args.streams > 1 and dom0) else None) if not bare else contextlib.nullcontext()) as kt:
         with pipe:
             for _ in range(args.steps):
-                img = pipe.submit(step)
+                last = pipe.submit(step_outputs)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    img = last[0]
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"images": last[0], "structure_feats": last[2]}, "" if rank == 0 else f"_rank{rank}")
+    del last
+    if not args.full:
+        if dist is not None:
+            t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        assert torch.isfinite(img).all()
+        guard_all.arm()
+        _guard_scope.__exit__(None, None, None)
+        if rank == 0:
+            out = _contract_fields(_headline(args, ops, bs, world, elapsed))
+            out["f16_overflowed"] = bool(guard_all.tripped())
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     if bare:                                   # the overlapped view of the dominant kernel: the same K steps once more, instrumented
         with ops.KernelTimer(only={dom0} if dom0 else None) as kt:
             with pipe:
@@ -933,21 +1014,7 @@ def main():
                              f"median {dt:.1f} s (runs {', '.join(f'{r:.1f}' for r in runs)} s)",
                    "max_abs_pixel_diff_vs_gpu": float(f"{err:.3e}")}
         line = {
-            "metric": "1024x1024 faces/sec (StyleGAN2 regional synthesis, gen_img)", "value": round(value, 3), "unit": "faces/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("f32" if ops.MODCONV_MODE != "sb" else "f16+mxfp6x2 (masked 3x3 layers >= 32^2) / bf16x3 (all other layers)" if ops.mx_arith() == 1 else "bf16x3"),
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: StyleGAN2 1024x1024 synthesis from random W+ (Net3.gen_img, randomize_noise=False), "
-                                   f"12-region {args.labels} masks (a fresh one-hot mask tensor per step: the mask -> region-map conversion is timed), batch={bs}/GPU; arithmetic = "
-                                   + (("split-bf16: fp32 operands split into bf16 hi+lo, 3 bf16 MFMAs per product, fp32 accumulate (max-abs pixel error "
-                                       "6e-5 vs the reference; plain bf16 would miss the 1e-3 bar)"
-                                       + ("; the masked 3x3 layers of width >= 32: f16 MFMA for a1*w1 plus two block-scaled MX-fp6 MFMAs for the cross terms "
-                                          "(csrc/modconv_mx.hip; 2e-4 on the pixels)" if ops.mx_arith() == 1 else "")) if ops.MODCONV_MODE == "sb" else "exact fp32 MFMA"),
-                       "batch_per_gpu": bs, "global_batch": bs * world, "resolution": 1024, "regions": 12, "parallelism": f"frames x{world}",
-                       "streams_per_gpu": args.streams,
-                       "step_overlap": (f"consecutive steps (independent batches) alternate over {args.streams} HIP streams: the latency-bound 4^2-32^2 layers of a "
-                                        "batch run under the large layers of the one before; all K steps complete inside the timed region") if args.streams > 1 else "none"},
+            **_headline(args, ops, bs, world, elapsed),
             "one_stream": one_stream, "soak": soak,
             "f16_range": {"overflowed_in_the_measured_passes": bool(f16_overflowed), "passes_rerun_in_split_bf16": int(ops.mx_fallbacks),
                           "what": "ops.MxGuard: the kernels of the f16-based arithmetic bump a device counter when a value leaves the f16 range; the benchmark brackets "

@@ -227,6 +227,42 @@ def test_bench_compact_line_fits_the_drivers_window_whatever_the_detail_holds():
     assert out["roofline"]["frac_at_soak_sclk"] == round(0.1234 * 2400.0 / 2046.0, 4) and out["soak_joules_per_face"] == round(1223.0 / 1407.4, 3)
 
 
+def test_bench_plain_line_carries_the_contract_fields():
+    """A plain run's line: `value` = faces/s over the K timed steps, `ms_per_step` = milliseconds per timed step, the same fields as the --full line's head."""
+    import argparse
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    from e4s2024_amd import ops
+    args = argparse.Namespace(steps=20, warmup=3, labels="blocky", streams=2)
+    head = bench._headline(args, ops, 4, 1, 0.06)
+    assert head["value"] == round(4 * 20 / 0.06, 3) and head["ms_per_step"] == 3.0 and head["unit"] == "faces/s" and head["higher_is_better"] is True
+    out = bench._contract_fields(head)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert out[k] == head[k] or k == "config", k
+    assert len(json.dumps(out)) < 2000
+
+
+def test_bench_dump_outputs_float32_within_budget_and_seeded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files named after the outputs; above the budget every array becomes the same fixed sample of its elements."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {"images": torch.randn(2, 3, 8, 8, generator=g), "structure_feats": torch.randn(2, 4, 4, 4, generator=g, dtype=torch.float64), "none": None}
+    bench._dump_outputs(str(tmp_path / "a"), outs)
+    img = np.load(tmp_path / "a" / "images.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, outs["images"].numpy())
+    assert np.load(tmp_path / "a" / "structure_feats.npy").dtype == np.float64
+    assert sorted(os.listdir(tmp_path / "a")) == ["images.npy", "structure_feats.npy"]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1000)
+    for d in ("b", "c"):
+        bench._dump_outputs(str(tmp_path / d), outs, "_rank1")
+    s1, s2 = (np.load(tmp_path / d / "images_rank1.npy") for d in ("b", "c"))
+    f1 = np.load(tmp_path / "b" / "structure_feats_rank1.npy")
+    assert np.array_equal(s1, s2) and s1.nbytes + f1.nbytes <= 1000 and s1.size > 0
+    assert np.isin(s1, outs["images"].numpy().reshape(-1)).all()
+
+
 # ------------------------------------------------------------------------------------------------ frame sharding (gloo, world 2)
 def test_shard_range_partitions_every_frame_once():
     from e4s2024_amd.runner import shard_range

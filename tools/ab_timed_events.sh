@@ -1,6 +1,6 @@
 # what do the dominant kernel's events inside the timed region, and a cold start of the timed region, cost the headline?  (round 5)
 R=$GRAFT_REPO_ROOT; cd $R
-F="--steps 20 --warmup 5 --no-cpu-baseline --no-in-run-ab --no-full-swap --no-pti --clip 0 --no-mask-sensitivity"
+F="--full --steps 20 --warmup 5 --no-cpu-baseline --no-in-run-ab --no-full-swap --no-pti --clip 0 --no-mask-sensitivity"
 for rep in 1 2 3; do
   for cfg in "--timed-events dominant" "--timed-events none" "--timed-events dominant --settle-seconds 2" "--timed-events none --settle-seconds 2"; do
     echo "== $cfg"

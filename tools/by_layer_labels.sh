@@ -1,6 +1,6 @@
 # per-layer one-stream times of the masked layers under each kind of region map (bench.py --labels ...): which layers pay for the map
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd $R
-B="--no-cpu-baseline --no-full-swap --no-pti --clip 0 --no-mask-sensitivity --soak-seconds 0 --no-in-run-ab"
+B="--full --no-cpu-baseline --no-full-swap --no-pti --clip 0 --no-mask-sensitivity --soak-seconds 0 --no-in-run-ab"
 for lab in blocky portrait coarse iid; do
   echo "== $lab"; timeout 300 python bench.py $B --labels $lab 2>&1 >/dev/null | grep "^bench detail: " | cut -c15- | python -c "
 import sys,json

@@ -1,6 +1,6 @@
 # Board power / shader clock while the headline step runs (a 12 s soak of bench.py's step on two streams), sampled twice a second with rocm-smi.
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
-B="--no-cpu-baseline --no-full-swap --no-pti --clip 0 --no-mask-sensitivity --no-in-run-ab --soak-seconds ${1:-12} ${2:-}"
+B="--full --no-cpu-baseline --no-full-swap --no-pti --clip 0 --no-mask-sensitivity --no-in-run-ab --soak-seconds ${1:-12} ${2:-}"
 echo "idle:"; rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk|mclk" | head -4
 python bench.py $B > gpurun_out/power_probe_bench.json 2>/dev/null &
 BP=$!
