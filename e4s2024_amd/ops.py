@@ -10,7 +10,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
                   the masked and single-region modulated convolutions, ToRGB, the per-region MLPs' grouped linear, the kernel timing hook —
                   and EVERY switch of every stage (module attributes and their environment variables: tests and tools set them here)
 * ``ops_encode``  rows a8 - a10: the regional-style encoder's and the face parser's operators
-* ``ops_post``    rows f2 / f3: mask surgery, paste-back masks, Pillow's resize, multi-band blend
+* ``ops_post``    rows f2 / f3 / f5: mask surgery, paste-back masks, Pillow's resize, multi-band blend, crop-align / paste into the frame
 * ``ops_grad``    row f1: the native gradients of the synthesis path
 """
 from __future__ import annotations

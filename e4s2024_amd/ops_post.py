@@ -90,15 +90,37 @@ def erode_labels(labels: torch.Tensor, radius: int, bg_classes: Sequence[int] = 
 _pil_tables = {}
 
 
-def _pil_bicubic_tables(in_size: int, out_size: int, device):
-    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for the BICUBIC filter (src/libImaging/Resample.c): per output index the
-    first input index, the tap count and the taps in 22-bit fixed point.  Computed once per (in, out, device) in float64 like the library."""
-    key = (in_size, out_size, str(device))
+def _pil_bicubic_filter(x: float) -> float:
+    """Pillow's ``bicubic_filter`` (a = -0.5, support 2)."""
+    x = abs(x)
+    return ((1.5 * x - 2.5) * x * x + 1.0) if x < 1.0 else ((((x - 5.0) * x + 8.0) * x - 4.0) * -0.5 if x < 2.0 else 0.0)
+
+
+def _pil_sinc(x: float) -> float:
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _pil_lanczos_filter(x: float) -> float:
+    """Pillow's ``lanczos_filter``: the sinc truncated to [-3, 3) and windowed by sinc(x / 3) (not symmetric at the ends, like the library)."""
+    return _pil_sinc(x) * _pil_sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+_PIL_FILTERS = {"bicubic": (_pil_bicubic_filter, 2.0), "lanczos": (_pil_lanczos_filter, 3.0)}
+
+
+def _pil_resample_tables(in_size: int, out_size: int, device, resample: str = "bicubic"):
+    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` (src/libImaging/Resample.c) for one filter: per output index the first input
+    index, the tap count and the taps in 22-bit fixed point.  Computed once per (in, out, filter, device) in float64 like the library."""
+    key = (in_size, out_size, resample, str(device))
     hit = _pil_tables.get(key)
     if hit is None:
+        filt, fsupport = _PIL_FILTERS[resample]
         scale = in_size / out_size
         fscale = max(scale, 1.0)
-        support = 2.0 * fscale
+        support = fsupport * fscale
         ksize = int(math.ceil(support)) * 2 + 1
         xmin, cnt, kk = [], [], []
         ss = 1.0 / fscale
@@ -106,10 +128,7 @@ def _pil_bicubic_tables(in_size: int, out_size: int, device):
             center = (xx + 0.5) * scale
             lo = max(int(center - support + 0.5), 0)
             hi = min(int(center + support + 0.5), in_size)
-            ws = []
-            for x in range(hi - lo):
-                t = abs((x + lo - center + 0.5) * ss)
-                ws.append(((1.5 * t - 2.5) * t * t + 1.0) if t < 1.0 else ((((t - 5.0) * t + 8.0) * t - 4.0) * -0.5 if t < 2.0 else 0.0))
+            ws = [filt((x + lo - center + 0.5) * ss) for x in range(hi - lo)]
             tot = sum(ws)
             if tot != 0.0:
                 ws = [v / tot for v in ws]
@@ -123,10 +142,23 @@ def _pil_bicubic_tables(in_size: int, out_size: int, device):
     return hit
 
 
-def pil_resize(img_u8: torch.Tensor, size) -> torch.Tensor:
+def _pil_bicubic_tables(in_size: int, out_size: int, device):
+    """The BICUBIC tables (Pillow's default resize filter)."""
+    return _pil_resample_tables(in_size, out_size, device, "bicubic")
+
+
+def _pil_lanczos_tables(in_size: int, out_size: int, device):
+    """The LANCZOS tables (support 3; Pillow < 10 called this filter ANTIALIAS)."""
+    return _pil_resample_tables(in_size, out_size, device, "lanczos")
+
+
+def pil_resize(img_u8: torch.Tensor, size, resample: str = "bicubic") -> torch.Tensor:
     """``PIL.Image.resize(size)`` (size = (width, height); Pillow's default BICUBIC with its 8-bit fixed-point arithmetic) of uint8
     ``[bs, H, W, C]`` frames on the device, bit for bit: a horizontal then a vertical pass, each rounded to 8 bits
-    (face_swap_video_pipeline.py:447 softens the swapped face with ``.resize((512, 512)).resize((1024, 1024))``)."""
+    (face_swap_video_pipeline.py:447 softens the swapped face with ``.resize((512, 512)).resize((1024, 1024))``).
+    ``resample="lanczos"``: ``Image.resize(size, LANCZOS)`` (the shrink step of ``crop_align``)."""
+    if resample not in _PIL_FILTERS:
+        raise ValueError(f"pil_resize: resample is one of {sorted(_PIL_FILTERS)}, got {resample!r}")
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or not img_u8.is_cuda:
         raise ValueError("pil_resize: uint8 [bs, H, W, C] CUDA frames")
     wd, ht = int(size[0]), int(size[1])
@@ -135,10 +167,86 @@ def pil_resize(img_u8: torch.Tensor, size) -> torch.Tensor:
         bs, h, w, c = out.shape
         if target == (w if axis == 1 else h):
             continue
-        xmin, cnt, kk, ksize = _pil_bicubic_tables(w if axis == 1 else h, target, out.device)
+        xmin, cnt, kk, ksize = _pil_resample_tables(w if axis == 1 else h, target, out.device, resample)
         nxt = torch.empty((bs, h, target, c) if axis == 1 else (bs, target, w, c), dtype=torch.uint8, device=out.device)
         lib().call("e4s_resample_u8", _p(nxt), _p(out), _p(xmin), _p(cnt), _p(kk), ksize, bs, h, w, c, target, axis, _stream())
         out = nxt
+    return out
+
+
+# ------------------------------------------------------------------------------------ f5: crop-align and paste into the frame (align.hip)
+def _frames_u8(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
+        raise ValueError(f"{name}: expected uint8 [n, H, W, 3] frames, got {t.dtype} {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _plan_checked(plan, frames: torch.Tensor, name: str):
+    from .align import CropPlan
+    if not isinstance(plan, CropPlan):
+        raise TypeError(f"{name}: plan must be an align.CropPlan (align.crop_plan / align.plan_from_landmarks)")
+    n, h, w, _ = frames.shape
+    if len(plan) != n or tuple(plan.frame_hw) != (h, w):
+        raise ValueError(f"{name}: the plan covers {len(plan)} frames of {plan.frame_hw[1]}x{plan.frame_hw[0]}, got {n} of {w}x{h}")
+    qc, ic = (t if t.device == frames.device else t.to(frames.device) for t in (plan.quad_coeffs, plan.inv_coeffs))
+    return qc.contiguous(), ic.contiguous(), plan.boxes.to(torch.int32).cpu().contiguous(), plan.paste_boxes.to(torch.int32).cpu().contiguous()
+
+
+def crop_align(frames_u8: torch.Tensor, plan) -> torch.Tensor:
+    """``crop_image(frame, S, quad)`` (utils/alignment.py:101-147, ``enable_padding=False``) for a batch of video frames on the device, bit for bit
+    with Pillow: uint8 ``[n, H, W, 3]`` frames + ``align.CropPlan`` -> uint8 ``[n, S, S, 3]`` aligned face crops.  A frame whose face quad is 4 S or more
+    across (its diagonal) is first resized by its plan's ``shrink`` with Pillow's LANCZOS (``pil_resize``); every other frame is warped straight from
+    the input, all of them in one launch."""
+    x = _frames_u8(frames_u8, "frames")
+    qc, _, boxes, _ = _plan_checked(plan, x, "crop_align")
+    n, h, w, _ = x.shape
+    s = int(plan.output_size)
+    out = torch.empty((n, s, s, 3), dtype=torch.uint8, device=x.device)
+    if n == 0:
+        return out
+    shrink = [int(v) for v in plan.shrink]
+    i = 0
+    while i < n:
+        j = i + 1
+        if shrink[i] > 1:           # this frame's own resize, then its warp from the resized frame
+            rw, rh = (int(v) for v in plan.resized_wh[i])
+            src = pil_resize(x[i:j], (rw, rh), resample="lanczos")
+            lib().call("e4s_warp_quad_u8", _p(out[i:j]), _p(src), boxes[i:j].data_ptr(), _p(qc[i:j]), 1, rh, rw, s, _stream())
+        else:                       # a run of frames warped from the input as they are
+            while j < n and shrink[j] <= 1:
+                j += 1
+            lib().call("e4s_warp_quad_u8", _p(out[i:j]), _p(x[i:j]), boxes[i:j].data_ptr(), _p(qc[i:j]), j - i, h, w, s, _stream())
+        i = j
+    return out
+
+
+def paste_into_frames(faces_u8: torch.Tensor, frames_u8: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's "op2. paste back" (face_swap_video_pipeline.py:474-483) for a batch on the device, bit for bit with Pillow: each face crop
+    uint8 ``[n, S, S, 3]`` is warped into its frame by ``transform(frame.size, PERSPECTIVE, inv_coeffs, BILINEAR)`` and composited over it as an
+    opaque layer.  Only the quad's bounding box (plus one pixel) is read and written.  ``out=None`` returns new frames; ``out=frames_u8`` pastes
+    in place; any other contiguous uint8 ``[n, H, W, 3]`` buffer receives a copy of the frames, then the faces."""
+    x = _frames_u8(frames_u8, "frames")
+    n, h, w, _ = x.shape
+    _, ic, _, pboxes = _plan_checked(plan, x, "paste_into_frames")
+    s = int(plan.output_size)
+    f = _frames_u8(faces_u8, "faces", (n, s, s, 3))
+    if out is None:
+        out = x.clone()
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch.Tensor")
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"paste_into_frames: out must be a contiguous uint8 [{n}, {h}, {w}, 3] tensor on {x.device}")
+        if out.data_ptr() != x.data_ptr():
+            out.copy_(x)
+    if n:
+        lib().call("e4s_warp_perspective_paste_u8", _p(out), _p(f), pboxes.data_ptr(), _p(ic), n, h, w, s, _stream())
     return out
 
 
@@ -198,4 +306,4 @@ def blending(full_img_u8: torch.Tensor, ori_img: torch.Tensor, mask: torch.Tenso
     return laplacian_blend(full_img_u8, ori_img, mask, 10).clamp_(0, 255).to(torch.uint8)
 
 
-__all__ = ['_labels_u8', 'swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_bicubic_tables', 'pil_resize', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending']
+__all__ = ['_labels_u8', 'swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_resample_tables', '_pil_bicubic_tables', '_pil_lanczos_tables', 'pil_resize', 'crop_align', 'paste_into_frames', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending']

@@ -221,3 +221,24 @@ def paste_back(swapped_u8: torch.Tensor, target_u8: torch.Tensor, content: torch
     pasted = torch.lerp(t.float(), sw, cm)                       # swapped * content + T * (1 - content)
     return ops.blending(t, pasted, bm).permute(0, 2, 3, 1).contiguous()
 
+
+
+@torch.no_grad()
+def swap_frames(net, parser, driven: torch.Tensor, target_frames_u8: torch.Tensor, plan, **swap_batch_kwargs) -> torch.Tensor:
+    """The video pipeline's per-frame loop with ``use_crop=True`` (face_swap_video_pipeline.py:181-210, 404-483) for a batch of video frames:
+
+        crop_align (row f5) -> frames_to_tensor -> swap_batch(mask_surgery=True) -> paste_back -> paste_into_frames (row f5)
+
+    ``driven``: ``[n, 3, 1024, 1024]`` in [-1, 1] as for ``swap_batch``; ``target_frames_u8``: uint8 ``[n, H, W, 3]`` video frames on the device;
+    ``plan``: their ``align.CropPlan`` (``align.plan_from_landmarks``).  Returns uint8 ``[n, H, W, 3]``: the frames with the swapped faces
+    pasted in, every pixel outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch`` (its f16 guard and stream
+    behaviour apply: with ``guard=[]`` the caller checks the guard and repeats the call).  As a ``synth_fn`` of ``runner.run_clip_streamed``:
+    ``lambda shared, i: swap_frames(net, parser, *i)`` with ``frame_inputs(lo, hi) = (driven[lo:hi], frames[lo:hi], plan[lo:hi])``."""
+    for k in ("mask_surgery", "to_uint8"):
+        if k in swap_batch_kwargs:
+            raise TypeError(f"swap_frames: {k} is fixed (the paste needs the uint8 face and the mask-surgery paste masks)")
+    crops = ops.crop_align(target_frames_u8, plan)
+    target = ops.frames_to_tensor(crops)
+    swapped, _, extra = swap_batch(net, parser, driven, target, mask_surgery=True, **swap_batch_kwargs)
+    blended = paste_back(swapped, crops, extra["content"], extra["border"])
+    return ops.paste_into_frames(blended, target_frames_u8, plan)

@@ -512,6 +512,24 @@ E4S_API int e4s_erode_labels(uint8_t* out, const uint8_t* labels, int bs, int h,
 E4S_API int e4s_foreground_masks(float* content, float* border, float* full, const uint8_t* swapped, const uint8_t* hole_mask,
                                  int bs, int h, int w, int radius, void* stream);
 
+/* ---- f5: crop-align of a video frame and the paste back into it (utils/alignment.py:101-147 crop_image; face_swap_video_pipeline.py:181-210,
+ * 474-483).  Pillow's Image.transform(..., BILINEAR) on uint8 RGB, bit for bit (src/libImaging/Geometry.c): output pixel (x, y) is sampled at
+ * (x + 0.5, y + 0.5) mapped through the transform in plain double arithmetic; a sample outside the source window is not taken; otherwise the
+ * bilinear blend of the four neighbours (columns and the first row clamped to the window, the second row used only inside it) is truncated to
+ * 8 bits.  The coefficients are `const void*` = double[n][8] in DEVICE memory (e4s2024_amd/align.py builds them).  The boxes are HOST
+ * int32[n][4] = (x0, y0, x1, y1), checked against the frame before anything is launched; they size the launches (one per 32 frames).
+ *   e4s_warp_quad_u8              : out uint8 [n, size, size, 3] = Image.transform((size, size), QUAD, data, BILINEAR) of the window
+ *                                   `windows[i]` of frames uint8 [n, h, w, 3] (the crop box; Pillow's image.crop(box)); unsampled pixels 0.
+ *                                   xi = a0 + a1 x + a2 y + a3 x y,  yi = a4 + a5 x + a6 y + a7 x y.
+ *   e4s_warp_perspective_paste_u8 : faces uint8 [n, size, size, 3] pasted IN PLACE into frames uint8 [n, h, w, 3]: every frame pixel of
+ *                                   boxes[i] that samples the face under PERSPECTIVE data gets the sample, every other pixel is left alone
+ *                                   (= transform to RGBA + alpha_composite onto the frame).  xi = (a0 x + a1 y + a2) / (a6 x + a7 y + 1),
+ *                                   yi = (a3 x + a4 y + a5) / (a6 x + a7 y + 1). */
+E4S_API int e4s_warp_quad_u8(uint8_t* out, const uint8_t* frames, const int32_t* windows, const void* coeffs, int n, int h, int w, int size,
+                             void* stream);
+E4S_API int e4s_warp_perspective_paste_u8(uint8_t* frames, const uint8_t* faces, const int32_t* boxes, const void* coeffs, int n, int h, int w,
+                                          int size, void* stream);
+
 /* ---- f1: gradients of the one-pass region-modulated convolution (PTI tuning, training/video_swap_ft_coach.py:242-299) -----------
  *     z[b,o,p] = sum_{i,k} W[o,i,k] * s[b,c(p),i] * x[b,i,p+k-pad],   y = d[b,c(p),o] * z        (model.py:389-398, 447-454)
  *     out = leaky_relu(y + noise_weight*noise + act_bias, 0.2) * sqrt(2)                          (model.py:335, 421)
