@@ -5,7 +5,7 @@ Layout
     _lib.py      ctypes binding (fails loudly if the .so is missing: there is no CPU fallback)
     ops.py       tensor-level wrappers (torch = device memory + stream plumbing only)
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
-                 ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``)
+                 ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -41,10 +41,22 @@ OVERRIDES = {
     "swap_face_fine.face_parsing.face_parsing_demo": "swap_face_fine/face_parsing/face_parsing_demo.py",
 }
 
+# the training-loss networks the tuning loops take from the reference (``criteria.*``), redirected the same way
+LOSS_OVERRIDES = {
+    "criteria.lpips": "criteria/lpips/__init__.py",
+    "criteria.lpips.lpips": "criteria/lpips/lpips.py",
+    "criteria.lpips.networks": "criteria/lpips/networks.py",
+    "criteria.lpips.utils": "criteria/lpips/utils.py",
+}
+
+
+def _redirected():
+    return {**OVERRIDES, **LOSS_OVERRIDES}
+
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
     def find_spec(self, fullname, path=None, target=None):
-        rel = OVERRIDES.get(fullname)
+        rel = _redirected().get(fullname)
         if rel is None:
             return None
         file = os.path.join(DROPIN_DIR, rel)
@@ -56,14 +68,14 @@ _finder = None
 
 
 def install(force: bool = False) -> str:
-    """Redirect the hot-path module names (``OVERRIDES``) to the drop-in files.
+    """Redirect the hot-path module names (``OVERRIDES``) and the loss networks' (``LOSS_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the
     END of ``sys.path``).  If an overridden module was already imported from elsewhere, raise unless ``force`` (then it is
     purged so the next import takes the drop-in)."""
     global _finder
-    stale = [m for m in OVERRIDES if m in sys.modules
+    stale = [m for m in _redirected() if m in sys.modules
              and not (getattr(sys.modules[m], "__file__", None) or "").startswith(DROPIN_DIR)]
     if stale:
         if not force:
@@ -93,5 +105,5 @@ def uninstall() -> None:
     if DROPIN_DIR in sys.path:
         sys.path.remove(DROPIN_DIR)
     for m in list(sys.modules):
-        if any(m == s or m.startswith(s + ".") for s in OVERRIDES):
+        if any(m == s or m.startswith(s + ".") for s in _redirected()):
             del sys.modules[m]

@@ -102,6 +102,14 @@ _PROTOS = {
     "e4s_small_map": [c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_ptr],
     "e4s_grouped_linear_bwd": [c_ptr] * 8 + [c_f32, c_f32, c_f32] + [c_int] * 5 + [c_ptr],
     "e4s_grouped_linear": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_int, c_f32] + [c_int] * 4 + [c_ptr],
+    "e4s_lpips_conv1": [c_ptr] * 6 + [c_int] * 4 + [c_ptr],
+    "e4s_lpips_conv1_dgrad": [c_ptr] * 4 + [c_int] * 4 + [c_ptr],
+    "e4s_lpips_maxpool": [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
+    "e4s_lpips_maxpool_bwd_relu": [c_ptr] * 4 + [c_int] * 3 + [c_ptr],
+    "e4s_lpips_head": [c_ptr] * 4 + [c_int] * 3 + [c_f32, c_ptr],
+    "e4s_lpips_sum": [c_ptr, c_ptr, c_int, c_ptr],
+    "e4s_lpips_head_bwd": [c_ptr] * 6 + [c_int] * 3 + [c_f32, c_ptr],
+    "e4s_lpips_relu_mask": [c_ptr, c_ptr, c_i64, c_ptr],
 }
 
 

@@ -892,6 +892,13 @@ static int dispatch2d_sb3(Conv2dSbParams& p, hipStream_t st) {
     return launch2d_sb<KS, S, 1, 1, 2, 2, 4, 3>(p, st);                                                                    // 64 co x 64 px (16 x 4)
 }
 
+// 5x5, stride 1 (LPIPS-AlexNet's conv2 and its data gradient, csrc/lpips.hip): 25 taps of weights per 16-channel chunk, so the 32-co tile (two or three slabs of
+// 25 x 2 x 32 x 16 B = 51 / 77 KB) is the one that leaves room for the patch planes; 16 x 8 pixels (the 32 x 4 tile spills registers, hipcc 7.2)
+template <int NS>
+static int dispatch2d_5x5(Conv2dSbParams& p, hipStream_t st) {
+    return launch2d_sb<5, 1, 1, 1, 1, 4, 4, NS>(p, st);                                                                  // 32 co x 128 px (16 x 8)
+}
+
 static int conv2d_sb_common(int nterms, float* out, const float* x0, const float* x1, int cin0, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2,
                             const float* bias, const float* in_mean, const float* in_rstd, const float* prelu_slope, const float* residual, int act,
                             int bs, int cin, int cout, int h, int w, int ks, int stride, int pad, void* stream, float out_scale = 1.f, int* flags = nullptr) {
@@ -925,13 +932,15 @@ static int conv2d_sb_common(int nterms, float* out, const float* x0, const float
         if (ks == 3 && stride == 2) return dispatch2d_sb3<3, 2>(p, st);
         if (ks == 1 && stride == 1) return dispatch2d_sb3<1, 1>(p, st);
         if (ks == 1 && stride == 2) return dispatch2d_sb3<1, 2>(p, st);
+        if (ks == 5 && stride == 1) return dispatch2d_5x5<3>(p, st);
     } else {
         if (ks == 3 && stride == 1) return dispatch2d_sb<3, 1>(p, st);
         if (ks == 3 && stride == 2) return dispatch2d_sb<3, 2>(p, st);
         if (ks == 1 && stride == 1) return dispatch2d_sb<1, 1>(p, st);
         if (ks == 1 && stride == 2) return dispatch2d_sb<1, 2>(p, st);
+        if (ks == 5 && stride == 1) return dispatch2d_5x5<2>(p, st);
     }
-    return fail(E4S_ERR_ARG, "conv2d_sb: kernel %dx%d stride %d not supported (3x3 / 1x1, stride 1 / 2)", ks, ks, stride);
+    return fail(E4S_ERR_ARG, "conv2d_sb: kernel %dx%d stride %d not supported (3x3 / 1x1, stride 1 / 2; 5x5 stride 1 on the bf16 splits)", ks, ks, stride);
 }
 
 extern "C" int e4s_conv2d_sb(float* out, const float* x0, const float* x1, int cin0, const uint16_t* whi, const uint16_t* wlo, const float* bias,

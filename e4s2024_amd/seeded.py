@@ -24,6 +24,7 @@ import torch
 
 __all__ = [
     "seeded_array",
+    "seeded_lpips_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -117,8 +118,31 @@ _RULES_BISENET = [
 ]
 
 
+# LPIPS-AlexNet (criteria/lpips): He-scaled convolutions, small positive biases (most units stay alive), non-negative lin weights like the trained
+# ones; mean / std are the reference's fixed buffers (networks.py:47-51)
+_RULES_LPIPS = [
+    (r"^net\.mean$", lambda seed, key, shape: np.array([-.030, -.088, -.188], dtype=np.float32).reshape(shape)),
+    (r"^net\.std$", lambda seed, key, shape: np.array([.458, .448, .450], dtype=np.float32).reshape(shape)),
+    (r"^net\.layers\.\d+\.weight$", _fan_in_std(1.4)),
+    (r"^net\.layers\.\d+\.bias$", (0.05, 0.05)),
+    (r"^lin\.\d+\.1\.weight$", _positive(0.0, 0.2)),
+]
+
+
+def seeded_lpips_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for the drop-in ``criteria.lpips.LPIPS`` (its 17-key state_dict)."""
+    shapes = {"net.mean": (1, 3, 1, 1), "net.std": (1, 3, 1, 1)}
+    chans = [3, 64, 192, 384, 256, 256]
+    for i, (li, k) in enumerate(zip((0, 3, 6, 8, 10), (11, 5, 3, 3, 3))):
+        shapes[f"net.layers.{li}.weight"] = (chans[i + 1], chans[i], k, k)
+        shapes[f"net.layers.{li}.bias"] = (chans[i + 1],)
+    for i in range(5):
+        shapes[f"lin.{i}.1.weight"] = (1, chans[i + 1], 1, 1)
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "lpips")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
-    rules = _RULES_NET3 if family == "net3" else _RULES_BISENET
+    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -609,6 +609,30 @@ E4S_API int e4s_wino_weight(float* U, const float* w, int cout, int cin, void* s
 E4S_API int e4s_wino_input(float* V, const float* x, const float* mean, const float* rstd, int bs, int C, int H, int W, void* stream);
 E4S_API int e4s_wino_output(float* y, const float* M, const float* prelu, int bs, int cout, int H, int W, void* stream);
 
+/* LPIPS-AlexNet (criteria/lpips; csrc/lpips.hip) — forward and input gradient; conv2 - conv5 run on e4s_conv2d_sb3 (forward) and e4s_conv2d_sb (data
+ * gradient on the flipped, transposed weights; 5x5 stride 1 is supported there for conv2).  All tensors fp32 NCHW on the device.
+ *   e4s_lpips_conv1        : out [bs][64][ho][wo] = relu(conv(z, w, stride 4, pad 2) + bias), z = (boxmean_f(x) - mean[c]) / std[c], x [bs][3][h][w],
+ *                            f in {1, 2, 4} dividing h and w, ho = (h / f - 7) / 4 + 1; wt [3][11][11][64] (the weight [64][3][11][11] with co innermost)
+ *   e4s_lpips_conv1_dgrad  : gx [bs][3][h][w] = d/dx of sum(g1 * conv1 pre-activation) (g1 already ReLU-masked), the box mean's backward included (written)
+ *   e4s_lpips_maxpool      : MaxPool2d(3, 2), no padding, over planes of h x w (h, w >= 3)
+ *   e4s_lpips_maxpool_bwd_relu : g [planes][h][w] = (add + gather of gpool over the windows whose first maximum is the pixel) * (a > 0); add may be NULL
+ *   e4s_lpips_head         : partial[b * ceil(hw / 32) + i] = scale * (32-pixel block i's sum over pixels of sum_c lin[c] (fx / |fx| - fy / |fy|)^2),
+ *                            |f| = sqrt(sum_c f^2 + 1e-16) + 1e-10; fx, fy [bs][c][hw]
+ *   e4s_lpips_sum          : loss[0] = sum of partial[0 .. n) in a fixed order (one workgroup)
+ *   e4s_lpips_head_bwd     : gx (and gy unless NULL) = d/dfx (d/dfy) of gout[0] * scale * sum over pixels of the same quantity
+ *   e4s_lpips_relu_mask    : g[i] = 0 where a[i] <= 0
+ * No float atomics: the same inputs give the same bits. */
+E4S_API int e4s_lpips_conv1(float* out, const float* x, const float* mean, const float* std, const float* wt, const float* bias, int bs, int h, int w,
+                            int f, void* stream);
+E4S_API int e4s_lpips_conv1_dgrad(float* gx, const float* g1, const float* std, const float* wt, int bs, int h, int w, int f, void* stream);
+E4S_API int e4s_lpips_maxpool(float* out, const float* a, int planes, int h, int w, void* stream);
+E4S_API int e4s_lpips_maxpool_bwd_relu(float* g, const float* gpool, const float* add, const float* a, int planes, int h, int w, void* stream);
+E4S_API int e4s_lpips_head(float* partial, const float* fx, const float* fy, const float* lin, int bs, int c, int hw, float scale, void* stream);
+E4S_API int e4s_lpips_sum(float* loss, const float* partial, int n, void* stream);
+E4S_API int e4s_lpips_head_bwd(float* gx, float* gy, const float* fx, const float* fy, const float* lin, const float* gout, int bs, int c, int hw,
+                               float scale, void* stream);
+E4S_API int e4s_lpips_relu_mask(float* g, const float* a, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
