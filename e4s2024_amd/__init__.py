@@ -5,7 +5,8 @@ Layout
     _lib.py      ctypes binding (fails loudly if the .so is missing: there is no CPU fallback)
     ops.py       tensor-level wrappers (torch = device memory + stream plumbing only)
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
-                 ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``)
+                 ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
+                 ``criteria/id_loss.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -47,6 +48,7 @@ LOSS_OVERRIDES = {
     "criteria.lpips.lpips": "criteria/lpips/lpips.py",
     "criteria.lpips.networks": "criteria/lpips/networks.py",
     "criteria.lpips.utils": "criteria/lpips/utils.py",
+    "criteria.id_loss": "criteria/id_loss.py",
 }
 
 

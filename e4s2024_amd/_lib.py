@@ -110,6 +110,17 @@ _PROTOS = {
     "e4s_lpips_sum": [c_ptr, c_ptr, c_int, c_ptr],
     "e4s_lpips_head_bwd": [c_ptr] * 6 + [c_int] * 3 + [c_f32, c_ptr],
     "e4s_lpips_relu_mask": [c_ptr, c_ptr, c_i64, c_ptr],
+    "e4s_id_resample": [c_ptr] * 6 + [c_int] * 4 + [c_ptr],
+    "e4s_id_resample_adjoint": [c_ptr] * 6 + [c_int] * 5 + [c_ptr],
+    "e4s_id_affine": [c_ptr] * 5 + [c_int] * 3 + [c_ptr],
+    "e4s_id_prelu_bwd": [c_ptr] * 4 + [c_int] * 7 + [c_ptr],
+    "e4s_id_se_bwd": [c_ptr] * 9 + [c_int] * 4 + [c_ptr],
+    "e4s_id_scatter_add": [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
+    "e4s_id_linear": [c_ptr] * 4 + [c_int] * 3 + [c_ptr],
+    "e4s_id_linear_t": [c_ptr] * 3 + [c_int] * 3 + [c_ptr],
+    "e4s_id_head_partial": [c_ptr] * 3 + [c_int, c_i64, c_ptr],
+    "e4s_id_head_sum": [c_ptr] * 4 + [c_int] * 7 + [c_ptr],
+    "e4s_id_head_bwd": [c_ptr] * 5 + [c_int, c_i64, c_f32, c_int, c_ptr],
 }
 
 

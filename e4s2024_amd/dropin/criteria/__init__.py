@@ -1,1 +1,2 @@
-"""Drop-in ``criteria`` package: only ``criteria.lpips`` is provided (the perceptual term of the PTI / W-optimisation losses)."""
+"""Drop-in ``criteria`` package: ``criteria.lpips`` and ``criteria.id_loss`` are provided (the perceptual and identity terms of the PTI /
+W-optimisation losses)."""

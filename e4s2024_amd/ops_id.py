@@ -1,0 +1,513 @@
+"""ArcFace IR-SE50 identity loss (``criteria/id_loss.py::IDLoss`` on ``models/encoders/model_irse.py::Backbone(112, 50, 'ir_se')``) on the HIP
+kernels: forward and gradient with respect to the reconstruction, for the identity term of the PTI and W-optimisation loops
+(training/video_swap_ft_coach.py:179-219, optimization.py:111-146).
+
+    pool -> crop -> pool            csrc/idloss.hip: out = A_y X A_x^T (A [112, H] from PyTorch's adaptive-pool windows, built here in float64) and its adjoint
+    input layer conv 3x3 (+BN)      csrc/conv.hip, three-way split-bf16 (fp32-class: near convergence the gradient is a difference of nearly equal vectors)
+    units: BN -> conv -> PReLU      BN as scale / shift (csrc/idloss.hip, exact for gamma = 0), conv three-way split, PReLU keeps its pre-activation
+           conv (stride s) + BN     BN folded into the weights (no padding after the conv, so the fold is exact); SE gate and shortcut add on csrc/norm.hip
+    output layer BN2d-Linear-BN1d   folded into one [512, 25088] weight once per weight version; GEMV and its transpose in csrc/idloss.hip
+    heads                           csrc/idloss.hip: fixed-order partial sums (bit-identical reruns); the loss lands in a device scalar (no host sync)
+    data gradients                  stride-1 3x3 / 1x1 on csrc/conv.hip (two-way split, flipped transposed weights with the BN scales folded in);
+                                    stride-2 3x3 on csrc/modconv_sb.hip's transposed convolution (two-way split, 1x the MACs); SE and PReLU backward,
+                                    the stride-2 shortcut scatter in csrc/idloss.hip
+
+Weights are a ``Backbone``-shaped module (``IdNet``, or the drop-in ``criteria.id_loss.IDLoss`` / its ``facenet``) or a mapping with the
+reference's 397 keys (``state_dict_keys()``).  They are frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the
+reference puts the network in eval mode); a module left in training mode is refused.
+"""
+from __future__ import annotations
+
+import functools
+import math
+import weakref
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ._lib import lib
+from .ops import _Prepared, _c, _p, _stream
+
+BN_EPS = 1e-5
+SIDE = 112                                   # the network's input side (IDLoss.face_pool_2)
+CROP = ((35, 223), (32, 220))                # IDLoss.extract_feats: rows, columns of the 256 x 256 image
+STAGES = ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3))      # get_blocks(50): (in_channel, depth, units)
+TAP_UNITS = (2, 6, 20, 23)                   # Backbone.forward(multi_scale=True): body outputs that are features as well
+HEAD_BLOCK = 8192                            # e4s_id_head_partial: elements per partial sum
+
+
+def units():
+    """``(in_channel, depth, stride)`` of the 24 ``bottleneck_IR_SE`` units."""
+    out = []
+    for cin, depth, n in STAGES:
+        out.append((cin, depth, 2))
+        out += [(depth, depth, 1)] * (n - 1)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the module (parameter layout only)
+class _SE(nn.Module):
+    def __init__(self, c: int, reduction: int = 16):
+        super().__init__()
+        self.fc1 = nn.Conv2d(c, c // reduction, 1, bias=False)
+        self.fc2 = nn.Conv2d(c // reduction, c, 1, bias=False)
+
+
+class _Unit(nn.Module):
+    def __init__(self, cin: int, depth: int, stride: int):
+        super().__init__()
+        self.shortcut_layer = nn.MaxPool2d(1, stride) if cin == depth else nn.Sequential(nn.Conv2d(cin, depth, 1, stride, bias=False), nn.BatchNorm2d(depth))
+        self.res_layer = nn.Sequential(nn.BatchNorm2d(cin), nn.Conv2d(cin, depth, 3, 1, 1, bias=False), nn.PReLU(depth),
+                                       nn.Conv2d(depth, depth, 3, stride, 1, bias=False), nn.BatchNorm2d(depth), _SE(depth))
+
+
+class IdNet(nn.Module):
+    """``Backbone(112, 50, 'ir_se')`` with the reference's module names, so its ``state_dict`` has the reference's 397 keys in their order.
+    The submodules only hold the weights: ``forward(x, multi_scale)`` runs the HIP kernels (``features_112``: a 112 x 112 input).  It starts
+    without weights and refuses to run until ``load_state_dict`` has filled it."""
+
+    def __init__(self):
+        super().__init__()
+        self.input_layer = nn.Sequential(nn.Conv2d(3, 64, 3, 1, 1, bias=False), nn.BatchNorm2d(64), nn.PReLU(64))
+        self.output_layer = nn.Sequential(nn.BatchNorm2d(512), nn.Dropout(0.6), nn.Flatten(), nn.Linear(512 * 7 * 7, 512), nn.BatchNorm1d(512))
+        self.body = nn.Sequential(*[_Unit(*u) for u in units()])
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        if set(state_dict_keys()) <= set(state_dict.keys()):
+            self._loaded = True
+        return out
+
+    def forward(self, x: torch.Tensor, multi_scale: bool = False):
+        return features_112(x, self, multi_scale)
+
+
+@functools.lru_cache(maxsize=1)
+def _keys_shapes():
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in IdNet().state_dict().items())
+
+
+def state_dict_keys():
+    """The 397 keys of ``Backbone(112, 50, 'ir_se').state_dict()``, in its order."""
+    return [k for k, _ in _keys_shapes()]
+
+
+def state_dict_shapes():
+    """``{key: shape}`` of ``Backbone(112, 50, 'ir_se').state_dict()``."""
+    return dict(_keys_shapes())
+
+
+# ------------------------------------------------------------------------------------------------ weights
+def check_loaded(weights):
+    """``weights`` itself; raises if it is a module whose weights were never loaded (a loss from initial parameters would be a silently wrong
+    objective) or one left in training mode (BatchNorm on batch statistics and active dropout: different arithmetic from the eval-mode
+    reference)."""
+    if isinstance(weights, nn.Module):
+        net = getattr(weights, "facenet", weights)          # the drop-in IDLoss holds the network as ``facenet``
+        if getattr(net, "_loaded", True) is False:
+            raise RuntimeError(f"{type(weights).__name__}: the ArcFace weights were never loaded (nothing is downloaded here); call load_state_dict first")
+        if net.training:
+            raise RuntimeError(f"{type(net).__name__} is in training mode; the identity loss runs the network in eval mode: call .eval()")
+    return weights
+
+
+def _mapping(weights):
+    check_loaded(weights)
+    if isinstance(weights, nn.Module):
+        weights = getattr(weights, "facenet", weights).state_dict()
+    if "input_layer.0.weight" not in weights and "facenet.input_layer.0.weight" in weights:
+        weights = {k[len("facenet."):]: v for k, v in weights.items() if k.startswith("facenet.")}
+    return weights
+
+
+def weight_tensors(weights):
+    """The float tensors of ``weights`` (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
+    sd = _mapping(weights)
+    try:
+        return [sd[k] for k in state_dict_keys() if not k.endswith("num_batches_tracked")]
+    except KeyError as e:
+        raise KeyError(f"ArcFace weights lack {e}: expected the keys of Backbone(112, 50, 'ir_se') (ops_id.state_dict_keys())") from None
+
+
+def weights_key(tensors) -> tuple:
+    """What the prepared copies are keyed on: storage and version of every tensor."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+def _bn(sd, prefix):
+    """Eval-mode BatchNorm as float64 (scale, shift): y = x * scale + shift."""
+    g, b = sd[prefix + ".weight"].double(), sd[prefix + ".bias"].double()
+    mu, var = sd[prefix + ".running_mean"].double(), sd[prefix + ".running_var"].double()
+    s = g / torch.sqrt(var + BN_EPS)
+    return s, b - mu * s
+
+
+def _slabs(n: int, cout: int, cin: int, k: int, device):
+    return tuple(torch.empty(((cin + 15) // 16, k * k, 2, cout, 8), dtype=torch.int16, device=device) for _ in range(n))
+
+
+def _prep_fwd(w, bias_scale=None, bias_shift=None):
+    """Three-way split slabs of ``w * scale[co]`` (+ the shift as bias) for e4s_conv2d_sb3."""
+    cout, cin, k, _ = w.shape
+    if bias_scale is not None:
+        w = (w.double() * bias_scale[:, None, None, None]).float()
+    w = w.contiguous()
+    s3 = _slabs(3, cout, cin, k, w.device)
+    lib().call("e4s_conv_prep_weights_sb3", _p(s3[0]), _p(s3[1]), _p(s3[2]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, k, k, _stream())
+    bias = bias_shift.float().contiguous() if bias_shift is not None else None
+    return s3, bias
+
+
+def _prep_dgrad(w, out_scale=None, in_scale=None):
+    """Two-way split slabs of the data-gradient convolution of ``w [cout, cin, k, k]``: flipped, transposed, times ``out_scale[co]`` (a BN after
+    the conv) and ``in_scale[ci]`` (a BN before it)."""
+    wd = w.double()
+    if out_scale is not None:
+        wd = wd * out_scale[:, None, None, None]
+    if in_scale is not None:
+        wd = wd * in_scale[None, :, None, None]
+    wf = wd.flip(2, 3).transpose(0, 1).float().contiguous()            # [cin][cout][k][k]
+    cin, cout, k, _ = wf.shape
+    s2 = _slabs(2, cin, cout, k, w.device)
+    lib().call("e4s_conv_prep_weights_sb", _p(s2[0]), _p(s2[1]), None, _p(wf), None, None, None, None, 0.0, None, cin, cout, k, k, _stream())
+    return s2
+
+
+def _prep_tconv(w, out_scale):
+    """Slabs of the stride-2 3x3 data gradient for e4s_modconv_tconv_sb: its transposed convolution with weight W_t [ci][co] = w[co][ci] * scale[co],
+    pre-multiplied by sqrt(9 * depth) to cancel the kernel's 1 / sqrt(9 cin)."""
+    depth, cin = w.shape[0], w.shape[1]
+    wt = ((w.double() * out_scale[:, None, None, None]).transpose(0, 1) * math.sqrt(9.0 * depth)).float().contiguous()    # [cin][depth][3][3]
+    whi = torch.empty((1, (depth + 15) // 16, 9, 2, cin, 8), dtype=torch.int16, device=w.device)
+    wlo = torch.empty_like(whi)
+    lib().call("e4s_modconv_prep_weights_sb", _p(whi), _p(wlo), None, _p(wt), None, cin, depth, 0, _stream())
+    return whi, wlo
+
+
+class PreparedIdNet(_Prepared):
+    """The kernels' copies of the ArcFace weights, rebuilt when a tensor changes version or storage: per unit the input BN's scale / shift, three-way
+    split slabs of both convolutions (the second with its BN folded in) and of the shortcut convolution, two-way split slabs of their data gradients
+    (BN scales folded in), the SE and PReLU weights; the output layer folded into one weight and bias."""
+
+    __slots__ = ()
+
+    def get(self, weights):
+        ts = weight_tensors(weights)
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(v.detach(), k) for k, v in _mapping(weights).items() if not k.endswith("num_batches_tracked")}
+        with torch.no_grad():
+            s0, t0 = _bn(sd, "input_layer.1")
+            w0 = sd["input_layer.0.weight"]
+            inp = (_prep_fwd(w0, s0, t0), _prep_dgrad(w0, out_scale=s0), sd["input_layer.2.weight"])
+            us = []
+            for i, (cin, depth, stride) in enumerate(units()):
+                p = f"body.{i}."
+                s1, t1 = _bn(sd, p + "res_layer.0")
+                w1, w2 = sd[p + "res_layer.1.weight"], sd[p + "res_layer.3.weight"]
+                s2, t2 = _bn(sd, p + "res_layer.4")
+                fwd1, _ = _prep_fwd(w1)
+                fwd2 = _prep_fwd(w2, s2, t2)
+                bwd2 = _prep_tconv(w2, s2) if stride == 2 else _prep_dgrad(w2, out_scale=s2)
+                sc = None
+                if cin != depth:
+                    ssc, tsc = _bn(sd, p + "shortcut_layer.1")
+                    wsc = sd[p + "shortcut_layer.0.weight"]
+                    sc = (_prep_fwd(wsc, ssc, tsc), _prep_dgrad(wsc, out_scale=ssc))
+                us.append(dict(cin=cin, depth=depth, stride=stride, bn_scale=s1.float().contiguous(), bn_shift=t1.float().contiguous(), fwd1=fwd1,
+                               bwd1=_prep_dgrad(w1, in_scale=s1), slope=sd[p + "res_layer.2.weight"], fwd2=fwd2, bwd2=bwd2,
+                               fc1=sd[p + "res_layer.5.fc1.weight"].reshape(depth // 16, depth).contiguous(),
+                               fc2=sd[p + "res_layer.5.fc2.weight"].reshape(depth, depth // 16).contiguous(), sc=sc))
+            so, to = _bn(sd, "output_layer.0")
+            s4, t4 = _bn(sd, "output_layer.4")
+            W = sd["output_layer.3.weight"].double()
+            b = sd["output_layer.3.bias"].double()
+            so, to = so.repeat_interleave(49), to.repeat_interleave(49)          # BN2d's channel c covers features c * 49 .. c * 49 + 48 (Flatten)
+            wout = (W * so[None, :] * s4[:, None]).float().contiguous()
+            bout = (((W * to[None, :]).sum(1) + b) * s4 + t4).float().contiguous()
+        return self._publish(key, (inp, tuple(us), wout, bout))
+
+
+_CACHES: "weakref.WeakKeyDictionary[nn.Module, PreparedIdNet]" = weakref.WeakKeyDictionary()
+
+
+def prepare(weights):
+    """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
+    if isinstance(weights, nn.Module):
+        cache = _CACHES.get(weights)
+        if cache is None:
+            cache = _CACHES[weights] = PreparedIdNet()
+        return cache.get(weights)
+    return PreparedIdNet().get(weights)
+
+
+# ------------------------------------------------------------------------------------------------ pre-processing operator
+def _pool_matrix(n_in: int, n_out: int) -> np.ndarray:
+    """AdaptiveAvgPool1d(n_out) on n_in samples: rows are the windows floor(i n_in / n_out) .. ceil((i + 1) n_in / n_out)."""
+    A = np.zeros((n_out, n_in))
+    for i in range(n_out):
+        lo, hi = (i * n_in) // n_out, -((-(i + 1) * n_in) // n_out)
+        A[i, lo:hi] = 1.0 / (hi - lo)
+    return A
+
+
+def axis_matrix(n: int, pooled: bool, crop) -> np.ndarray:
+    """float64 [112, n]: AdaptiveAvgPool(256) (when ``pooled``) -> slice ``crop`` (Python slicing of the 256- or n-long axis) -> AdaptiveAvgPool(112)."""
+    P1 = _pool_matrix(n, 256) if pooled else np.eye(n)
+    m = P1.shape[0]
+    lo, hi = min(crop[0], m), min(crop[1], m)
+    if hi - lo < 1:
+        raise ValueError(f"an image side of {n} leaves nothing of the crop {crop}")
+    return _pool_matrix(hi - lo, SIDE) @ P1[lo:hi]
+
+
+def _bands(A: np.ndarray):
+    """[rows][2] = [lo, hi) of each row's nonzeros and [cols][2] of each column's (empty: [0, 0)); the nonzeros of a row / column are contiguous."""
+    def rng(M):
+        out = np.zeros((M.shape[0], 2), dtype=np.int32)
+        for r in range(M.shape[0]):
+            nz = np.nonzero(M[r])[0]
+            if nz.size:
+                assert nz[-1] - nz[0] + 1 == nz.size, "pre-processing band is not contiguous"
+                out[r] = (nz[0], nz[-1] + 1)
+        return out
+    return rng(A), rng(A.T)
+
+
+_RESAMPLERS = {}
+
+
+def resampler(h: int, w: int, device):
+    """Device copies (ay, ax, row bands y / x, column bands y / x) of the pre-processing operator of an h x w image (cached)."""
+    key = (h, w, str(device))
+    hit = _RESAMPLERS.get(key)
+    if hit is None:
+        pooled = h != 256                       # IDLoss.extract_feats pools when x.shape[2] != 256 (both sides, to 256 x 256)
+        ay, ax = axis_matrix(h, pooled, CROP[0]), axis_matrix(w, pooled, CROP[1])
+        (ry, cy), (rx, cx) = _bands(ay), _bands(ax)
+        T = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)   # noqa: E731
+        hit = _RESAMPLERS[key] = (T(ay), T(ax), T(ry, torch.int32), T(rx, torch.int32), T(cy, torch.int32), T(cx, torch.int32))
+    return hit
+
+
+def _resample(x, R):
+    bs, c, h, w = x.shape
+    out = torch.empty((bs, c, SIDE, SIDE), dtype=torch.float32, device=x.device)
+    lib().call("e4s_id_resample", _p(out), _p(x), _p(R[0]), _p(R[1]), _p(R[2]), _p(R[3]), bs * c, h, w, SIDE, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ forward
+def _conv3(x, slabs, bias, cout, k, stride, residual=None):
+    bs, cin, h, w = x.shape
+    pad = k // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    out = torch.empty((bs, cout, ho, wo), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(bias), None, None, None, _p(residual), 0,
+               bs, cin, cout, h, w, k, stride, pad, _stream())
+    return out
+
+
+def _conv2(x, slabs, cout, k, residual=None):
+    """Stride-1 data-gradient convolution (two-way split)."""
+    bs, cin, h, w = x.shape
+    out = torch.empty((bs, cout, h, w), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv2d_sb", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), None, None, None, None, _p(residual), 0,
+               bs, cin, cout, h, w, k, 1, k // 2, _stream())
+    return out
+
+
+def _affine(x, scale, shift, slope):
+    out = torch.empty_like(x)
+    lib().call("e4s_id_affine", _p(out), _p(x), _p(scale), _p(shift), _p(slope), x.shape[0], x.shape[1], x.shape[2] * x.shape[3], _stream())
+    return out
+
+
+def _unit_fwd(x, U):
+    bs = x.shape[0]
+    depth, stride = U["depth"], U["stride"]
+    a = _affine(x, U["bn_scale"], U["bn_shift"], None)
+    c1 = _conv3(a, U["fwd1"], None, depth, 3, 1)                                   # PReLU's pre-activation, kept for the backward
+    r = _conv3(_affine(c1, None, None, U["slope"]), U["fwd2"][0], U["fwd2"][1], depth, 3, stride)
+    ho, wo = r.shape[2], r.shape[3]
+    pooled = torch.empty((bs, depth), dtype=torch.float32, device=x.device)
+    lib().call("e4s_plane_stats", _p(pooled), None, None, _p(r), bs * depth, ho * wo, 0.0, _stream())
+    gate = torch.empty((bs, depth), dtype=torch.float32, device=x.device)
+    lib().call("e4s_se_gate", _p(gate), _p(pooled), _p(U["fc1"]), _p(U["fc2"]), bs, depth, depth // 16, _stream())
+    if U["sc"] is not None:
+        short, sc_stride = _conv3(x, U["sc"][0][0], U["sc"][0][1], depth, 1, stride), 1
+    else:
+        short, sc_stride = x, stride
+    y = torch.empty_like(r)
+    lib().call("e4s_norm_gate_add", _p(y), _p(r), None, None, _p(gate), _p(short), None, None, sc_stride, None, bs, depth, ho, wo, _stream())
+    return y, (c1, r, pooled, gate)
+
+
+def _features(x112, P, multiscale: bool, save: bool):
+    """The features (flattened, not normalised) of the 112 x 112 input: [tap 2, 6, 20, 23 outputs,] output layer; and what the backward needs."""
+    inp, us, wout, bout = P
+    bs = x112.shape[0]
+    c0 = _conv3(x112, inp[0][0], inp[0][1], 64, 3, 1)
+    a = _affine(c0, None, None, inp[2])
+    taps, saved = [], []
+    for i, U in enumerate(us):
+        a, rec = _unit_fwd(a, U)
+        if save:
+            saved.append(rec)
+        if multiscale and i in TAP_UNITS:
+            taps.append(a.reshape(bs, -1))
+    feat = torch.empty((bs, 512), dtype=torch.float32, device=x112.device)
+    lib().call("e4s_id_linear", _p(feat), _p(a), _p(wout), _p(bout), bs, wout.shape[1], 512, _stream())
+    taps.append(feat)
+    return taps, (c0, saved)
+
+
+def _heads(fx, fy):
+    bs = fx[0].shape[0]
+    nbs = [-(-f.shape[1] // HEAD_BLOCK) for f in fx]
+    part = torch.empty((3 * bs * sum(nbs),), dtype=torch.float32, device=fx[0].device)
+    off = 0
+    for a, b, nb in zip(fx, fy, nbs):
+        lib().call("e4s_id_head_partial", _p(part[off:]), _p(a), _p(b), bs, a.shape[1], _stream())
+        off += 3 * bs * nb
+    loss = torch.empty((), dtype=torch.float32, device=fx[0].device)
+    sim = torch.empty((), dtype=torch.float32, device=fx[0].device)
+    stats = torch.empty((len(fx), bs, 3), dtype=torch.float32, device=fx[0].device)
+    nb5 = nbs + [0] * (5 - len(nbs))
+    lib().call("e4s_id_head_sum", _p(loss), _p(sim), _p(stats), _p(part), bs, len(fx), *nb5, _stream())
+    return loss, sim, stats
+
+
+# ------------------------------------------------------------------------------------------------ backward
+def _unit_bwd(gy, U, rec, bs, h, w):
+    """d loss / d (unit input) from ``gy`` = d loss / d (unit output)."""
+    c1, r, pooled, gate = rec
+    depth, stride, cin = U["depth"], U["stride"], U["cin"]
+    ho, wo = r.shape[2], r.shape[3]
+    dr = torch.empty_like(r)
+    tmp = torch.empty((2, bs, depth), dtype=torch.float32, device=gy.device)
+    lib().call("e4s_id_se_bwd", _p(dr), _p(tmp[0]), _p(tmp[1]), _p(gy), _p(r), _p(pooled), _p(gate), _p(U["fc1"]), _p(U["fc2"]), bs, depth, depth // 16,
+               ho * wo, _stream())
+    gc1 = torch.empty_like(c1)
+    if stride == 2:
+        z = torch.empty((bs, depth, 2 * ho + 1, 2 * wo + 1), dtype=torch.float32, device=gy.device)
+        ones = torch.ones((bs, 1, depth), dtype=torch.float32, device=gy.device)
+        lib().call("e4s_modconv_tconv_sb", _p(z), _p(dr), _p(U["bwd2"][0]), _p(U["bwd2"][1]), _p(ones), bs, depth, depth, ho, wo, _stream())
+        src, sh, sw, off = z, 2 * ho + 1, 2 * wo + 1, 1                     # the forward's padding of 1: rows / columns 1 .. 2 ho of the full transposed conv
+    else:
+        src, sh, sw, off = _conv2(dr, U["bwd2"], depth, 3), h, w, 0
+    lib().call("e4s_id_prelu_bwd", _p(gc1), _p(src), _p(c1), _p(U["slope"]), bs, depth, h, w, sh, sw, off, _stream())
+    if stride == 1:
+        return _conv2(gc1, U["bwd1"], cin, 3, residual=gy)                      # MaxPool2d(1, 1) shortcut: the identity
+    gx = _conv2(gc1, U["bwd1"], cin, 3)
+    gsc = _conv2(gy, U["sc"][1], cin, 1) if U["sc"] is not None else gy         # the 1x1 stride-2 shortcut's data gradient at its output resolution
+    lib().call("e4s_id_scatter_add", _p(gx), _p(gsc), bs * cin, h, w, _stream())
+    return gx
+
+
+def _input_grad(fx, fy, stats, gout, P, state, multiscale: bool):
+    """d loss / d (the 112 x 112 input)."""
+    inp, us, wout, _ = P
+    c0, saved = state
+    bs = c0.shape[0]
+    scale = 1.0 / bs
+    gfeat = torch.empty_like(fx[-1])
+    lib().call("e4s_id_head_bwd", _p(gfeat), _p(fx[-1]), _p(fy[-1]), _p(stats[-1]), _p(gout), bs, 512, scale, 0, _stream())
+    g = torch.empty((bs, 512, 7, 7), dtype=torch.float32, device=c0.device)
+    lib().call("e4s_id_linear_t", _p(g), _p(gfeat), _p(wout), bs, wout.shape[1], 512, _stream())
+    taps = {u: k for k, u in enumerate(TAP_UNITS)} if multiscale else {}
+    h = w = 7
+    for i in range(len(us) - 1, -1, -1):
+        if i in taps:
+            k = taps[i]
+            lib().call("e4s_id_head_bwd", _p(g), _p(fx[k]), _p(fy[k]), _p(stats[k]), _p(gout), bs, fx[k].shape[1], scale, 1, _stream())
+        U = us[i]
+        h, w = h * U["stride"], w * U["stride"]
+        g = _unit_bwd(g, U, saved[i], bs, h, w)
+    gc0 = torch.empty_like(c0)
+    lib().call("e4s_id_prelu_bwd", _p(gc0), _p(g), _p(c0), _p(inp[2]), bs, 64, SIDE, SIDE, SIDE, SIDE, 0, _stream())
+    return _conv2(gc0, inp[1], 3, 3)
+
+
+class _IdLoss(torch.autograd.Function):
+    """(loss, sim_improvement) of IDLoss.forward(y_hat, y); differentiable in ``y_hat`` only (the reference detaches ``y``'s features)."""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, P, R, multiscale):
+        fx, state = _features(_resample(y_hat, R), P, multiscale, save=True)
+        fy, _ = _features(_resample(y, R), P, multiscale, save=False)
+        loss, sim, stats = _heads(fx, fy)
+        ctx.P, ctx.R, ctx.multiscale, ctx.shape, ctx.state = P, R, multiscale, tuple(y_hat.shape), state
+        ctx.save_for_backward(stats, *fx, *fy)
+        ctx.mark_non_differentiable(sim, stats)
+        return loss, sim, stats
+
+    @staticmethod
+    def backward(ctx, gloss, gsim, gstats):
+        if gloss is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        saved = ctx.saved_tensors
+        n = (len(saved) - 1) // 2
+        stats, fx, fy = saved[0], list(saved[1:1 + n]), list(saved[1 + n:])
+        gout = _c(gloss.reshape(1), "grad_output")
+        g112 = _input_grad(fx, fy, stats, gout, ctx.P, ctx.state, ctx.multiscale)
+        bs, c, h, w = ctx.shape
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g112.device)
+        R = ctx.R
+        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g112), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
+        return gx, None, None, None, None
+
+
+def _check(x: torch.Tensor, name: str) -> torch.Tensor:
+    x = _c(x, name)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError(f"{name}: expected [bs >= 1, 3, H, W], got {tuple(x.shape)}")
+    return x
+
+
+def id_loss_terms(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = True):
+    """``(loss, sim_improvement, per_scale)``: the loss (0-d, differentiable in ``y_hat``), IDLoss's similarity improvement (0-d, on the device) and
+    ``per_scale [scales]`` = mean over the batch of 1 - cos per scale (no gradient).  No host synchronisation."""
+    check_loaded(weights)
+    y_hat, y = _check(y_hat, "y_hat"), _check(y.detach(), "y")
+    if y_hat.shape != y.shape:
+        raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ")
+    loss, sim, stats = _IdLoss.apply(y_hat, y, prepare(weights), resampler(y.shape[2], y.shape[3], y.device), bool(multiscale))
+    return loss, sim, (1.0 - stats[..., 2]).mean(1)
+
+
+def id_loss(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = True) -> torch.Tensor:
+    """IDLoss.forward(y_hat, y)'s loss (a 0-d tensor): ``sum over scales of mean_i (1 - cos(f(y_hat_i), f(y_i)))``, five scales with ``multiscale``
+    (body units 2, 6, 20, 23 and the 512-d embedding), the embedding alone without.  ``y_hat``, ``y``: fp32 ``[bs, 3, H, W]`` on the device, pooled
+    to 256 x 256 unless H is 256, cropped and pooled to 112 x 112 as IDLoss.extract_feats does.  Differentiable in ``y_hat`` only."""
+    return id_loss_terms(y_hat, y, weights, multiscale)[0]
+
+
+def features_112(x: torch.Tensor, weights, multiscale: bool = True):
+    """Backbone.forward(x, multi_scale): the l2-normalised features of a 112 x 112 input (no gradient)."""
+    check_loaded(weights)
+    x = _check(x, "x")
+    if x.shape[2:] != (SIDE, SIDE):
+        raise ValueError(f"x: the network takes 112 x 112 inputs, got {tuple(x.shape[2:])}")
+    with torch.no_grad():
+        taps, _ = _features(x, prepare(weights), multiscale, save=False)
+    return [t / t.norm(dim=1, keepdim=True) for t in taps]
+
+
+def id_features(x: torch.Tensor, weights, multiscale: bool = True):
+    """IDLoss.extract_feats(x): the l2-normalised features of an image batch after the pool -> crop -> pool pre-processing (no gradient)."""
+    check_loaded(weights)
+    x = _check(x, "x")
+    with torch.no_grad():
+        x112 = _resample(x, resampler(x.shape[2], x.shape[3], x.device))
+    return features_112(x112, weights, multiscale)
+
+
+__all__ = ["IdNet", "PreparedIdNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes", "axis_matrix", "resampler",
+           "id_features", "features_112", "id_loss", "id_loss_terms", "units"]

@@ -25,6 +25,7 @@ import torch
 __all__ = [
     "seeded_array",
     "seeded_lpips_state_dict",
+    "seeded_irse50_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -141,8 +142,29 @@ def seeded_lpips_state_dict(seed: int) -> Dict[str, torch.Tensor]:
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "lpips")
 
 
+# ArcFace IR-SE50 (models/encoders/model_irse.py::Backbone(112, 50, 'ir_se')): fan-in scaled convolutions / linear, the residual branch's last
+# convolution at a smaller gain so that 24 residual additions keep the activations O(1); eval BatchNorm statistics around the identity
+_RULES_IRSE50 = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"running_var$", (1.0, 1.0 / np.sqrt(12.0))),                    # U(0.5, 1.5)
+    (r"running_mean$", (0.0, 0.1)),
+    (r"(input_layer\.1|output_layer\.[04]|res_layer\.[04]|shortcut_layer\.1)\.weight$", (1.0, 0.1)),
+    (r"(input_layer\.1|output_layer\.[034]|res_layer\.[04]|shortcut_layer\.1)\.bias$", (0.0, 0.1)),
+    (r"(input_layer\.2|res_layer\.2)\.weight$", (0.25, 0.05)),          # PReLU slopes
+    (r"res_layer\.3\.weight$", _fan_in_std(0.5)),
+    (r"\.fc[12]\.weight$", _fan_in_std(1.0)),
+    (r"\.weight$", _fan_in_std(1.0)),
+]
+
+
+def seeded_irse50_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``Backbone(112, 50, 'ir_se')`` (the ArcFace net of criteria/id_loss.py; its 397-key state_dict)."""
+    from .ops_id import state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in state_dict_shapes().items()}, seed, "irse50")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
-    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS}.get(family, _RULES_BISENET)
+    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -633,6 +633,41 @@ E4S_API int e4s_lpips_head_bwd(float* gx, float* gy, const float* fx, const floa
                                float scale, void* stream);
 E4S_API int e4s_lpips_relu_mask(float* g, const float* a, int64_t n, void* stream);
 
+/* ArcFace IR-SE50 identity loss (criteria/id_loss.py; csrc/idloss.hip) — forward and input gradient.  The convolutions run on e4s_conv2d_sb3 (forward)
+ * and e4s_conv2d_sb (stride-1 data gradients on flipped, transposed weights); the stride-2 3x3 data gradient on e4s_modconv_tconv_sb (s = 1, the weight
+ * pre-scaled by sqrt(9 cin)).  All tensors fp32 NCHW on the device.
+ *   e4s_id_resample         : out [planes][no][no] = A_y x A_x^T, x [planes][h][w], ay [no][h], ax [no][w]; ry [no][2], rx [no][2] = [lo, hi) of each row's band
+ *   e4s_id_resample_adjoint : gx [planes][h][w] (+)= A_y^T g A_x; cy [h][2], cx [w][2] = [lo, hi) of each column's band (empty: 0)
+ *   e4s_id_affine           : out = x * scale[c] + shift[c] (scale, shift NULL: x), then PReLU with slope[c] unless slope is NULL; x [bs][C][hw]
+ *   e4s_id_prelu_bwd        : g [bs][C][h][w] = src[bs][C][y + off][x + off] (planes sh x sw) * (pre > 0 ? 1 : slope[c])
+ *   e4s_id_se_bwd           : SEModule backward for r * gate: s = sum_hw g r, v = fc1^T ((fc1 pooled > 0) fc2^T (s gate (1 - gate))) / hw, dr = g gate + v;
+ *                             s, v [bs][C] scratch; fc1 [H][C], fc2 [C][H]; C <= 1024, H <= 64
+ *   e4s_id_scatter_add      : gx [planes][h][w] at (2y, 2x) += src [planes][(h + 1) / 2][(w + 1) / 2]
+ *   e4s_id_linear           : y [bs][N] = x [bs][K] W^T + bias (bias may be NULL); W [N][K]
+ *   e4s_id_linear_t         : gx [bs][K] = g [bs][N] W
+ *   e4s_id_head_partial     : part [bs][ceil(D / 8192)][3] = block sums of fx^2, fy^2, fx fy; fx, fy [bs][D]
+ *   e4s_id_head_sum         : over taps t < ntap (partials concatenated in tap order, nb_t blocks each): stats [ntap][bs][3] = (|x|, |y|, cos),
+ *                             loss[0] = sum_t mean_b (1 - cos), sim[0] = sum_t mean_b (cos - |y|^2 / (|y| |y|))
+ *   e4s_id_head_bwd         : gx [bs][D] (+)= -gout[0] scale (fy / |y| - cos fx / |x|) / |x| with the stats of the tap
+ * No float atomics: the same inputs give the same bits. */
+E4S_API int e4s_id_resample(float* out, const float* x, const float* ay, const float* ax, const int* ry, const int* rx, int planes, int h, int w, int no,
+                            void* stream);
+E4S_API int e4s_id_resample_adjoint(float* gx, const float* g, const float* ay, const float* ax, const int* cy, const int* cx, int planes, int h, int w,
+                                    int no, int accumulate, void* stream);
+E4S_API int e4s_id_affine(float* out, const float* x, const float* scale, const float* shift, const float* slope, int bs, int C, int hw, void* stream);
+E4S_API int e4s_id_prelu_bwd(float* g, const float* src, const float* pre, const float* slope, int bs, int C, int h, int w, int sh, int sw, int off,
+                             void* stream);
+E4S_API int e4s_id_se_bwd(float* dr, float* s, float* v, const float* g, const float* r, const float* pooled, const float* gate, const float* fc1,
+                          const float* fc2, int bs, int C, int H, int hw, void* stream);
+E4S_API int e4s_id_scatter_add(float* gx, const float* src, int planes, int h, int w, void* stream);
+E4S_API int e4s_id_linear(float* y, const float* x, const float* W, const float* bias, int bs, int K, int N, void* stream);
+E4S_API int e4s_id_linear_t(float* gx, const float* g, const float* W, int bs, int K, int N, void* stream);
+E4S_API int e4s_id_head_partial(float* part, const float* fx, const float* fy, int bs, int64_t D, void* stream);
+E4S_API int e4s_id_head_sum(float* loss, float* sim, float* stats, const float* part, int bs, int ntap, int nb0, int nb1, int nb2, int nb3, int nb4,
+                            void* stream);
+E4S_API int e4s_id_head_bwd(float* gx, const float* fx, const float* fy, const float* stats, const float* gout, int bs, int64_t D, float scale,
+                            int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
