@@ -6,7 +6,7 @@ Layout
     ops.py       tensor-level wrappers (torch = device memory + stream plumbing only)
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
-                 ``criteria/id_loss.py``)
+                 ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -49,6 +49,7 @@ LOSS_OVERRIDES = {
     "criteria.lpips.networks": "criteria/lpips/networks.py",
     "criteria.lpips.utils": "criteria/lpips/utils.py",
     "criteria.id_loss": "criteria/id_loss.py",
+    "criteria.face_parsing.face_parsing_loss": "criteria/face_parsing/face_parsing_loss.py",
 }
 
 

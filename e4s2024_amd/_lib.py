@@ -121,6 +121,8 @@ _PROTOS = {
     "e4s_id_head_partial": [c_ptr] * 3 + [c_int, c_i64, c_ptr],
     "e4s_id_head_sum": [c_ptr] * 4 + [c_int] * 7 + [c_ptr],
     "e4s_id_head_bwd": [c_ptr] * 5 + [c_int, c_i64, c_f32, c_int, c_ptr],
+    "e4s_fp_maxpool2": [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
+    "e4s_fp_tap_bwd": [c_ptr] * 6 + [c_int] * 4 + [c_f32, c_ptr],
 }
 
 

@@ -1,0 +1,378 @@
+"""Face-parsing feature loss (``criteria/face_parsing/face_parsing_loss.py::FaceParsingLoss`` on ``criteria/face_parsing/unet.py::unet(feature_scale=4)``)
+on the HIP kernels: forward and gradient with respect to the reconstruction, for the parsing term of the PTI and W-optimisation loops
+(training/video_swap_ft_coach.py:179-219, optimization.py:111-145).
+
+    AdaptiveAvgPool2d(512)          unless H is 512: csrc/idloss.hip's banded resampler out = A_y X A_x^T (A [512, H] from PyTorch's adaptive-pool
+                                    windows, built here in float64; a 2 x 2 box mean at 1024, pixel replication at 256) and its adjoint
+    5 blocks [conv 3x3 + BN + ReLU] x 2, MaxPool2d(2) between them (16, 32, 64, 128, 256 channels)
+                                    conv bias and BN folded into the weights in float64; the 3-channel first convolution on csrc/conv.hip's fp32 kernel,
+                                    the others on its three-way split-bf16 kernel (fp32-class: near convergence the gradient is a difference of nearly
+                                    equal vectors), ReLU in the epilogue; max pool in csrc/fploss.hip
+    taps                            every block's output, flattened per sample and l2-normalised; heads on csrc/idloss.hip (fixed-order partial sums:
+                                    bit-identical reruns; the loss lands in a device scalar, no host sync)
+    data gradients                  per block, csrc/fploss.hip's tap backward (head gradient + the next block's gradient through the max pool to the first
+                                    maximum of each window, times the ReLU mask) -> second conv's data gradient -> ReLU mask -> first conv's data gradient,
+                                    both convolutions on csrc/conv.hip's two-way split on flipped, transposed weights with the BN scales folded in
+
+``y_hat`` and ``y`` run through the network as one batch of ``2 bs``; only ``y_hat``'s activations are kept for the backward.  Weights are a
+``unet``-shaped module (``FaceParsingNet``, or the drop-in ``criteria.face_parsing.face_parsing_loss.FaceParsingLoss`` / its ``G``) or a mapping with
+at least the encoder's keys (``state_dict_keys()`` lists all 136; the decoder's ``up_concat*`` / ``final`` are not used by the loss).  They are
+frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the reference puts the network in eval mode); a module left in
+training mode is refused.
+"""
+from __future__ import annotations
+
+import functools
+import weakref
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ._lib import lib
+from .ops import _Prepared, _c, _p, _stream
+from .ops_id import _bands, _bn, _heads, _pool_matrix, _prep_dgrad, _prep_fwd, weights_key
+
+SIDE = 512                                   # FaceParsingLoss.face_pool: AdaptiveAvgPool2d((512, 512)) unless x.shape[2] == 512
+FILTERS = (16, 32, 64, 128, 256)             # unet(feature_scale=4): [64, 128, 256, 512, 1024] / 4
+BLOCKS = ("conv1", "conv2", "conv3", "conv4", "center")
+N_CLASSES = 19
+
+
+# ------------------------------------------------------------------------------------------------ the module (parameter layout only)
+class _UnetConv2(nn.Module):
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.conv1 = nn.Sequential(nn.Conv2d(cin, cout, 3, 1, 1), nn.BatchNorm2d(cout), nn.ReLU())
+        self.conv2 = nn.Sequential(nn.Conv2d(cout, cout, 3, 1, 1), nn.BatchNorm2d(cout), nn.ReLU())
+
+
+class _UnetUp(nn.Module):
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.conv = _UnetConv2(cin, cout)
+        self.up = nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2)
+
+
+class FaceParsingNet(nn.Module):
+    """``unet(feature_scale=4, n_classes=19)`` with the reference's module names, so its ``state_dict`` has the reference's 136 keys in their order.
+    The submodules only hold the weights: ``extract_feats(x)`` runs the encoder on the HIP kernels.  The decoder (``up_concat*``, ``final``) is kept
+    for the checkpoint's sake only; ``forward`` (the segmentation) is not provided.  It starts without weights and refuses to run until
+    ``load_state_dict`` has filled it."""
+
+    def __init__(self):
+        super().__init__()
+        f = FILTERS
+        self.conv1 = _UnetConv2(3, f[0])
+        self.conv2 = _UnetConv2(f[0], f[1])
+        self.conv3 = _UnetConv2(f[1], f[2])
+        self.conv4 = _UnetConv2(f[2], f[3])
+        self.center = _UnetConv2(f[3], f[4])
+        self.up_concat4 = _UnetUp(f[4], f[3])
+        self.up_concat3 = _UnetUp(f[3], f[2])
+        self.up_concat2 = _UnetUp(f[2], f[1])
+        self.up_concat1 = _UnetUp(f[1], f[0])
+        self.final = nn.Conv2d(f[0], N_CLASSES, 1)
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        if set(encoder_keys()) <= set(state_dict.keys()):
+            self._loaded = True
+        return out
+
+    def forward(self, x):
+        raise NotImplementedError("FaceParsingNet: the segmentation (the unet decoder) is not implemented; the loss uses extract_feats")
+
+    def extract_feats(self, x: torch.Tensor):
+        return unet_features(x, self)
+
+
+@functools.lru_cache(maxsize=1)
+def _keys_shapes():
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in FaceParsingNet().state_dict().items())
+
+
+def state_dict_keys():
+    """The 136 keys of ``unet().state_dict()``, in its order."""
+    return [k for k, _ in _keys_shapes()]
+
+
+def state_dict_shapes():
+    """``{key: shape}`` of ``unet().state_dict()``."""
+    return dict(_keys_shapes())
+
+
+def encoder_keys():
+    """The 70 keys of the five encoder blocks (``extract_feats``' parameters and BatchNorm statistics)."""
+    return [k for k in state_dict_keys() if k.split(".")[0] in BLOCKS]
+
+
+# ------------------------------------------------------------------------------------------------ weights
+def _net(weights):
+    return getattr(weights, "G", weights)          # the drop-in FaceParsingLoss holds the network as ``G``
+
+
+def check_loaded(weights):
+    """``weights`` itself; raises if it is a module whose weights were never loaded (a loss from initial parameters would be a silently wrong
+    objective) or one left in training mode (BatchNorm on batch statistics: different arithmetic from the eval-mode reference)."""
+    if isinstance(weights, nn.Module):
+        net = _net(weights)
+        if getattr(net, "_loaded", True) is False:
+            raise RuntimeError(f"{type(weights).__name__}: the face-parsing weights were never loaded (nothing is downloaded here); call load_state_dict first")
+        if net.training:
+            raise RuntimeError(f"{type(net).__name__} is in training mode; the face-parsing loss runs the network in eval mode: call .eval()")
+    return weights
+
+
+def _mapping(weights):
+    check_loaded(weights)
+    if isinstance(weights, nn.Module):
+        weights = _net(weights).state_dict()
+    if "conv1.conv1.0.weight" not in weights and "G.conv1.conv1.0.weight" in weights:
+        weights = {k[len("G."):]: v for k, v in weights.items() if k.startswith("G.")}
+    return weights
+
+
+def weight_tensors(weights):
+    """The float tensors of the encoder (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
+    sd = _mapping(weights)
+    try:
+        return [sd[k] for k in encoder_keys() if not k.endswith("num_batches_tracked")]
+    except KeyError as e:
+        raise KeyError(f"face-parsing weights lack {e}: expected the keys of unet(feature_scale=4) (ops_fp.state_dict_keys())") from None
+
+
+def _fold(sd, p):
+    """Conv ``p.0`` + eval BatchNorm ``p.1`` as float64 (scale, shift): BN(conv(x) + b) = conv(x) * scale + shift."""
+    s, t = _bn(sd, p + ".1")
+    return s, t + sd[p + ".0.bias"].double() * s
+
+
+def _prep_fp32(w, scale, shift):
+    """The fp32 direct kernel's layout (e4s_conv2d, 3 input channels) of ``w * scale[co]``, the shift as bias."""
+    cout, cin, k, _ = w.shape
+    wf = (w.double() * scale[:, None, None, None]).float().contiguous()
+    wt = torch.empty((cin * k * k * cout,), dtype=torch.float32, device=w.device)
+    bias = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    lib().call("e4s_conv_prep_weights", _p(wt), _p(bias), _p(wf), None, None, None, None, 0.0, _p(shift.float().contiguous()), cout, cin, k, k, _stream())
+    return wt, bias
+
+
+class PreparedFaceParsingNet(_Prepared):
+    """The kernels' copies of the encoder weights, rebuilt when a tensor changes version or storage: per block the forward weights of both convolutions
+    (conv bias and BN folded in; fp32 layout for the 3-channel input, three-way split slabs otherwise) and two-way split slabs of their data gradients
+    (BN scales folded in)."""
+
+    __slots__ = ()
+
+    def get(self, weights):
+        ts = weight_tensors(weights)
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        enc = set(encoder_keys())
+        sd = {k: _c(v.detach(), k) for k, v in _mapping(weights).items() if k in enc and not k.endswith("num_batches_tracked")}
+        blocks = []
+        with torch.no_grad():
+            for i, name in enumerate(BLOCKS):
+                cin, cout = (3 if i == 0 else FILTERS[i - 1]), FILTERS[i]
+                w1, w2 = sd[name + ".conv1.0.weight"], sd[name + ".conv2.0.weight"]
+                s1, t1 = _fold(sd, name + ".conv1")
+                s2, t2 = _fold(sd, name + ".conv2")
+                fwd1 = _prep_fp32(w1, s1, t1) if cin < 16 else _prep_fwd(w1, s1, t1)
+                blocks.append(dict(cin=cin, cout=cout, fwd1=fwd1, fwd2=_prep_fwd(w2, s2, t2), bwd1=_prep_dgrad(w1, out_scale=s1),
+                                   bwd2=_prep_dgrad(w2, out_scale=s2)))
+        return self._publish(key, tuple(blocks))
+
+
+_CACHES: "weakref.WeakKeyDictionary[nn.Module, PreparedFaceParsingNet]" = weakref.WeakKeyDictionary()
+
+
+def prepare(weights):
+    """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
+    if isinstance(weights, nn.Module):
+        cache = _CACHES.get(weights)
+        if cache is None:
+            cache = _CACHES[weights] = PreparedFaceParsingNet()
+        return cache.get(weights)
+    return PreparedFaceParsingNet().get(weights)
+
+
+# ------------------------------------------------------------------------------------------------ input pooling
+_RESAMPLERS = {}
+
+
+def resampler(h: int, w: int, device):
+    """Device copies (ay, ax, row bands y / x, column bands y / x) of AdaptiveAvgPool2d((512, 512)) on an h x w image, or None when h is 512 (the
+    reference then runs the network on the image as it is).  Cached."""
+    if h == SIDE:
+        return None
+    key = (h, w, str(device))
+    hit = _RESAMPLERS.get(key)
+    if hit is None:
+        ay, ax = _pool_matrix(h, SIDE), _pool_matrix(w, SIDE)
+        (ry, cy), (rx, cx) = _bands(ay), _bands(ax)
+        T = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)   # noqa: E731
+        hit = _RESAMPLERS[key] = (T(ay), T(ax), T(ry, torch.int32), T(rx, torch.int32), T(cy, torch.int32), T(cx, torch.int32))
+    return hit
+
+
+def _network_input(xs, R):
+    """The network's input batch: the images of ``xs`` (each [bs, 3, H, W]) one after the other, pooled to 512 x 512 unless H is 512."""
+    bs, c, h, w = xs[0].shape
+    ho, wo = (h, w) if R is None else (SIDE, SIDE)
+    out = torch.empty((bs * len(xs), c, ho, wo), dtype=torch.float32, device=xs[0].device)
+    for i, x in enumerate(xs):
+        dst = out[i * bs:(i + 1) * bs]
+        if R is None:
+            dst.copy_(x)
+        else:
+            lib().call("e4s_id_resample", _p(dst), _p(x), _p(R[0]), _p(R[1]), _p(R[2]), _p(R[3]), bs * c, h, w, SIDE, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ forward
+def _conv_relu(x, B, which):
+    n, cin, h, w = x.shape
+    cout = B["cout"]
+    out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+    if which == 1 and B["cin"] < 16:
+        wt, bias = B["fwd1"]
+        lib().call("e4s_conv2d", _p(out), _p(x), None, cin, _p(wt), _p(bias), None, None, None, None, 1, n, cin, cout, h, w, 3, 1, 1, _stream())
+    else:
+        slabs, bias = B["fwd1"] if which == 1 else B["fwd2"]
+        lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(bias), None, None, None, None, 1,
+                   n, cin, cout, h, w, 3, 1, 1, _stream())
+    return out
+
+
+def _encoder(x, P):
+    """``[(c1, c2)]`` per block: the first convolution's output (its ReLU mask is needed by the backward) and the block output (the tap)."""
+    acts = []
+    a = x
+    for i, B in enumerate(P):
+        c1 = _conv_relu(a, B, 1)
+        c2 = _conv_relu(c1, B, 2)
+        acts.append((c1, c2))
+        if i + 1 < len(P):
+            n, c, h, w = c2.shape
+            a = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+            lib().call("e4s_fp_maxpool2", _p(a), _p(c2), n * c, h, w, _stream())
+    return acts
+
+
+def _conv_dgrad(g, slabs, cout):
+    bs, cin, h, w = g.shape
+    out = torch.empty((bs, cout, h, w), dtype=torch.float32, device=g.device)
+    lib().call("e4s_conv2d_sb", _p(out), _p(g), None, cin, _p(slabs[0]), _p(slabs[1]), None, None, None, None, None, 0, bs, cin, cout, h, w, 3, 1, 1,
+               _stream())
+    return out
+
+
+def _input_grad(acts, P, stats, gout, bs):
+    """d loss / d (the network's input) of the first ``bs`` samples."""
+    g = None
+    for i in range(len(P) - 1, -1, -1):
+        B = P[i]
+        c1, c2 = acts[i]
+        _, c, h, w = c2.shape
+        gz = torch.empty((bs, c, h, w), dtype=torch.float32, device=c2.device)
+        lib().call("e4s_fp_tap_bwd", _p(gz), _p(c2[:bs]), _p(c2[bs:]), _p(stats[i]), _p(gout), _p(g), bs, c, h, w, 1.0 / bs, _stream())
+        gc1 = _conv_dgrad(gz, B["bwd2"], c)
+        lib().call("e4s_lpips_relu_mask", _p(gc1), _p(c1), gc1.numel(), _stream())       # c1[:bs] is the head of c1: same offsets
+        g = _conv_dgrad(gc1, B["bwd1"], B["cin"])
+    return g
+
+
+class _FpLoss(torch.autograd.Function):
+    """(loss, sim_improvement, stats) of FaceParsingLoss.forward(y_hat, y); differentiable in ``y_hat`` only (the reference detaches ``y``'s features)."""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, P, R):
+        bs = y_hat.shape[0]
+        acts = _encoder(_network_input((y_hat, y), R), P)
+        fx = [c2[:bs].reshape(bs, -1) for _, c2 in acts]
+        fy = [c2[bs:].reshape(bs, -1) for _, c2 in acts]
+        loss, sim, stats = _heads(fx, fy)
+        ctx.P, ctx.R, ctx.shape = P, R, tuple(y_hat.shape)
+        ctx.acts = [(c1[:bs], c2) for c1, c2 in acts]              # y's half of c2 is the head's fy; y's c1 is not needed
+        ctx.save_for_backward(stats)
+        ctx.mark_non_differentiable(sim, stats)
+        ctx.set_materialize_grads(False)                                # no zero-filled gradients for sim / stats
+        return loss, sim, stats
+
+    @staticmethod
+    def backward(ctx, gloss, gsim, gstats):
+        if gloss is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        (stats,) = ctx.saved_tensors
+        bs, c, h, w = ctx.shape
+        gout = _c(gloss.reshape(1), "grad_output")
+        g = _input_grad(ctx.acts, ctx.P, stats, gout, bs)
+        ctx.acts = None
+        R = ctx.R
+        if R is None:
+            return g, None, None, None
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
+        return gx, None, None, None
+
+
+def _check(x: torch.Tensor, name: str) -> torch.Tensor:
+    x = _c(x, name)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError(f"{name}: expected [bs >= 1, 3, H, W], got {tuple(x.shape)}")
+    if x.shape[2] == SIDE and x.shape[3] % 16:
+        raise ValueError(f"{name}: a {SIDE}-high image is not pooled (FaceParsingLoss.extract_feats), so its width must be a multiple of 16 for the "
+                         f"four 2 x 2 max pools; got {tuple(x.shape[2:])}")
+    return x
+
+
+def _apply(y_hat, y, weights):
+    check_loaded(weights)
+    y_hat, y = _check(y_hat, "y_hat"), _check(y.detach(), "y")
+    if y_hat.shape != y.shape:
+        raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ")
+    return _FpLoss.apply(y_hat, y, prepare(weights), resampler(y.shape[2], y.shape[3], y.device))
+
+
+def fp_loss_terms(y_hat: torch.Tensor, y: torch.Tensor, weights):
+    """``(loss, sim_improvement, per_tap)``: the loss (0-d, differentiable in ``y_hat``), FaceParsingLoss's similarity improvement (0-d, on the device)
+    and ``per_tap [5]`` = mean over the batch of 1 - cos per encoder block (no gradient).  No host synchronisation."""
+    loss, sim, stats = _apply(y_hat, y, weights)
+    return loss, sim, (1.0 - stats[..., 2]).mean(1)
+
+
+def fp_loss(y_hat: torch.Tensor, y: torch.Tensor, weights) -> torch.Tensor:
+    """FaceParsingLoss.forward(y_hat, y)'s loss (a 0-d tensor): ``sum over the five encoder blocks of mean_i (1 - cos(f(y_hat_i), f(y_i)))``.
+    ``y_hat``, ``y``: fp32 ``[bs, 3, H, W]`` on the device, pooled to 512 x 512 unless H is 512.  Differentiable in ``y_hat`` only."""
+    return _apply(y_hat, y, weights)[0]
+
+
+def unet_features(x: torch.Tensor, weights):
+    """unet.extract_feats(x): the l2-normalised block outputs of the image as it is (H, W multiples of 16; no gradient)."""
+    check_loaded(weights)
+    x = _c(x, "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 16 or x.shape[3] % 16:
+        raise ValueError(f"x: expected [bs, 3, H, W] with H, W multiples of 16, got {tuple(x.shape)}")
+    with torch.no_grad():
+        acts = _encoder(x, prepare(weights))
+    bs = x.shape[0]
+    return [c2.reshape(bs, -1) / c2.reshape(bs, -1).norm(dim=1, keepdim=True) for _, c2 in acts]
+
+
+def fp_features(x: torch.Tensor, weights):
+    """FaceParsingLoss.extract_feats(x): the l2-normalised features after the pooling to 512 x 512 (unless H is 512; no gradient)."""
+    check_loaded(weights)
+    x = _check(x, "x")
+    with torch.no_grad():
+        x512 = _network_input((x,), resampler(x.shape[2], x.shape[3], x.device))
+    return unet_features(x512, weights)
+
+
+__all__ = ["FaceParsingNet", "PreparedFaceParsingNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes",
+           "encoder_keys", "resampler", "fp_features", "unet_features", "fp_loss", "fp_loss_terms"]

@@ -8,8 +8,9 @@ outputs with the gradient kernels of ``csrc/modconv_bwd.hip`` + ``csrc/gemm_sb.h
 (:176-223) L2 term plus, with ``lpips=`` (the drop-in ``criteria.lpips.LPIPS`` with its weights loaded), ``lpips_lambda`` times its LPIPS-AlexNet
 term at three scales (:201-211) — forward and input gradient on the HIP kernels of ``ops_lpips``, on the foreground-masked images as the
 video coach computes it (:188-190); ``style_vector_step`` takes it unmasked, as optimization.py:111-146 does.  With ``id_loss=`` (the drop-in
-``criteria.id_loss.IDLoss`` with its weights loaded) ``id_lambda`` times the ArcFace identity term (:192-195) is added the same way (``ops_id``).
-The parsing network (a UNet parser) plugs in through ``extra_loss``.
+``criteria.id_loss.IDLoss`` with its weights loaded) ``id_lambda`` times the ArcFace identity term (:192-195) is added the same way (``ops_id``),
+and with ``face_parsing=`` (the drop-in ``criteria.face_parsing.face_parsing_loss.FaceParsingLoss`` with its weights loaded) ``face_parsing_lambda``
+times the unet face-parsing feature term (:212-216, ``ops_fp``).  That completes ``calc_loss``'s objective; ``extra_loss`` remains for anything else.
 
 Several GPUs: one process per GPU, each on its own frame; the one exchange step is the gradient average before the
 optimiser step (``sync_gradients``: a few large flat all-reduces over RCCL, not one per tensor).  That is a batch-of-N Adam step, not
@@ -23,7 +24,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import ops, ops_id, ops_lpips
+from . import ops, ops_fp, ops_id, ops_lpips
 
 
 def trainable_parameters(net):
@@ -37,7 +38,7 @@ def _id_multiscale(id_loss) -> bool:
 
 
 def _loss(net, style_vectors, mask, target, foreground_mask, l2_lambda, extra_loss, randomize_noise, lpips=None, lpips_lambda: float = 0.8,
-          id_loss=None, id_lambda: float = 0.1):
+          id_loss=None, id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
     codes = net.cal_style_codes(style_vectors)
     recon, _, _ = net.gen_img(None, codes, mask, randomize_noise=randomize_noise)
     a, b = (recon, target) if foreground_mask is None else (recon * foreground_mask, target * foreground_mask)
@@ -46,6 +47,8 @@ def _loss(net, style_vectors, mask, target, foreground_mask, l2_lambda, extra_lo
         loss = loss + lpips_lambda * ops_lpips.lpips_multiscale(a, b, lpips)
     if id_loss is not None:                                                  # calc_loss :192-195 (loss_id), on the masked images
         loss = loss + id_lambda * ops_id.id_loss(a, b, id_loss, _id_multiscale(id_loss))
+    if face_parsing is not None:                                             # calc_loss :212-216 (loss_face_parsing), on the masked images
+        loss = loss + face_parsing_lambda * ops_fp.fp_loss(a, b, face_parsing)
     if extra_loss is not None:
         loss = loss + extra_loss(recon, target)
     return loss, recon
@@ -112,12 +115,13 @@ class GraphedPTIStep:
 
     def __init__(self, net, optimizer, style_vectors, mask, target, foreground_mask=None, l2_lambda: float = 1.0, extra_loss=None,
                  randomize_noise: bool = True, warmup: int = 3, warm_inputs=None, lpips=None, lpips_lambda: float = 0.8, id_loss=None,
-                 id_lambda: float = 0.1):
+                 id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
         """``warm_inputs``: the frames of the eager steps that precede the capture, as ``(style_vectors, mask, target[, foreground_mask])``
         tuples (default: the example frame ``warmup`` times).  They are real optimiser steps: a loop passes its own first frames here
         (``tune_clip``) and continues with the replayed step from the next one; ``self.warm_losses`` holds their losses.
         ``lpips`` / ``lpips_lambda``: the LPIPS term as in ``pti_step`` (its kernels are captured with the rest of the step).  Load the LPIPS
-        weights before constructing the step: the captured graph reads copies prepared from them, and a replay after they have changed raises."""
+        weights before constructing the step: the captured graph reads copies prepared from them, and a replay after they have changed raises.
+        ``id_loss`` / ``face_parsing`` and their lambdas: the identity and face-parsing terms, under the same rule."""
         if mask.dtype != torch.uint8:
             raise TypeError("GraphedPTIStep needs the uint8 region map (ops.mask_to_labels(onehot)), not a float mask")
         # the LPIPS weights are prepared (re-laid-out) once, before the capture, and the graph reads those copies: weights loaded later would not
@@ -126,10 +130,13 @@ class GraphedPTIStep:
         self._lpips_key = ops_lpips.weights_key(self._lpips_tensors)
         self._id_tensors = ops_id.weight_tensors(id_loss) if id_loss is not None else []         # the same for the ArcFace weights
         self._id_key = ops_id.weights_key(self._id_tensors)
+        self._fp_tensors = ops_fp.weight_tensors(face_parsing) if face_parsing is not None else []   # and for the face-parsing weights
+        self._fp_key = ops_fp.weights_key(self._fp_tensors)
         self.net = net
         self.static = [style_vectors.clone(), mask.clone(), target.clone()] + ([foreground_mask.clone()] if foreground_mask is not None else [])
         fg = self.static[3] if foreground_mask is not None else None
-        args = (net, self.static[0], self.static[1], self.static[2], fg, l2_lambda, extra_loss, randomize_noise, lpips, lpips_lambda, id_loss, id_lambda)
+        args = (net, self.static[0], self.static[1], self.static[2], fg, l2_lambda, extra_loss, randomize_noise, lpips, lpips_lambda, id_loss, id_lambda,
+                face_parsing, face_parsing_lambda)
         self.stream = torch.cuda.Stream()                 # warm-up and capture on one stream of our own (see graphs.GraphedCall)
         ops.prepare_stream_context(self.stream)
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -166,6 +173,9 @@ class GraphedPTIStep:
         if ops_id.weights_key(self._id_tensors) != self._id_key:
             raise RuntimeError("GraphedPTIStep: the ArcFace (id_loss) weights changed after the capture (the graph reads copies prepared from the old "
                                "ones); capture a new step")
+        if ops_fp.weights_key(self._fp_tensors) != self._fp_key:
+            raise RuntimeError("GraphedPTIStep: the face-parsing weights changed after the capture (the graph reads copies prepared from the old "
+                               "ones); capture a new step")
         if len(new) != len(self.static):
             raise ValueError("foreground_mask must be given iff the step was captured with one")
         for dst, src in zip(self.static, new):
@@ -184,20 +194,23 @@ class GraphedPTIStep:
 def pti_step(net, optimizer: torch.optim.Optimizer, style_vectors: torch.Tensor, mask: torch.Tensor, target: torch.Tensor,
              foreground_mask: Optional[torch.Tensor] = None, l2_lambda: float = 1.0,
              extra_loss: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None, group=None, lpips=None,
-             lpips_lambda: float = 0.8, id_loss=None, id_lambda: float = 0.1):
+             lpips_lambda: float = 0.8, id_loss=None, id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
     """One optimiser step.  ``style_vectors [bs, 12, 1280]``, ``mask`` one-hot ``[bs, 12, 512, 512]`` (or uint8 labels),
     ``target [bs, 3, 1024, 1024]`` in [-1, 1]; ``foreground_mask [bs, 1, 1024, 1024]`` restricts the loss as at :283-288.
     ``lpips``: a loaded ``criteria.lpips.LPIPS`` (or its state_dict) adds ``lpips_lambda * sum_{i<3} LPIPS(pool_i(a), pool_i(b))`` on the
     masked images ``a``, ``b`` (video_swap_ft_coach.py:188-211).  ``id_loss``: a loaded ``criteria.id_loss.IDLoss`` (or a ``Backbone``
-    state_dict) adds ``id_lambda * IDLoss(a, b)`` (:192-195).  ``extra_loss(recon, target)`` gets the unmasked images.
+    state_dict) adds ``id_lambda * IDLoss(a, b)`` (:192-195).  ``face_parsing``: a loaded ``criteria.face_parsing.face_parsing_loss.FaceParsingLoss``
+    (or a ``unet`` state_dict) adds ``face_parsing_lambda * FaceParsingLoss(a, b)`` (:212-216).  ``extra_loss(recon, target)`` gets the unmasked images.
     Inside a ``torch.distributed`` process group every rank passes its own frame and the gradients are averaged before the update.
     Returns ``(loss value, reconstruction)``."""
     if lpips is not None:
         ops_lpips.check_loaded(lpips)
     if id_loss is not None:
         ops_id.check_loaded(id_loss)
+    if face_parsing is not None:
+        ops_fp.check_loaded(face_parsing)
     loss, recon = _loss(net, style_vectors, mask, target, foreground_mask, l2_lambda, extra_loss, True,   # the coach calls gen_img with fresh noise
-                        lpips, lpips_lambda, id_loss, id_lambda)
+                        lpips, lpips_lambda, id_loss, id_lambda, face_parsing, face_parsing_lambda)
     optimizer.zero_grad()
     loss.backward()
     sync_gradients([p for g in optimizer.param_groups for p in g["params"]], group)
@@ -207,18 +220,23 @@ def pti_step(net, optimizer: torch.optim.Optimizer, style_vectors: torch.Tensor,
 
 def style_vector_step(net, optimizer: torch.optim.Optimizer, latent: torch.Tensor, mask: torch.Tensor, target: torch.Tensor,
                       l2_lambda: float = 1.0, extra_loss: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
-                      randomize_noise: bool = True, lpips=None, lpips_lambda: float = 0.8, id_loss=None, id_lambda: float = 0.1):
+                      randomize_noise: bool = True, lpips=None, lpips_lambda: float = 0.8, id_loss=None, id_lambda: float = 0.1, face_parsing=None,
+                      face_parsing_lambda: float = 0.1):
     """One step of the reference's W-optimisation (``Optimizer.optim_W_online``, optimization.py:321-349): the per-region style
     vectors ``latent [bs, 12, 1280]`` (``requires_grad``, held by ``optimizer``) are tuned so that ``gen_img(cal_style_codes(latent))``
     matches ``target``; the network's own parameters are left alone (they are not in ``optimizer``).  ``lpips``: adds
     ``lpips_lambda * sum_{i<3} LPIPS(pool_i(recon), pool_i(target))`` on the unmasked images (optimization.py:111-146); ``id_loss``:
-    ``id_lambda * IDLoss(recon, target)``, unmasked as well (optimization.py:115)."""
+    ``id_lambda * IDLoss(recon, target)``, unmasked as well (optimization.py:115); ``face_parsing``: ``face_parsing_lambda *
+    FaceParsingLoss(recon, target)``, unmasked (optimization.py:135-139)."""
     if lpips is not None:
         ops_lpips.check_loaded(lpips)
     if id_loss is not None:
         ops_id.check_loaded(id_loss)
+    if face_parsing is not None:
+        ops_fp.check_loaded(face_parsing)
     optimizer.zero_grad()
-    loss, recon = _loss(net, latent, mask, target, None, l2_lambda, extra_loss, randomize_noise, lpips, lpips_lambda, id_loss, id_lambda)
+    loss, recon = _loss(net, latent, mask, target, None, l2_lambda, extra_loss, randomize_noise, lpips, lpips_lambda, id_loss, id_lambda,
+                        face_parsing, face_parsing_lambda)
     loss.backward()
     optimizer.step()
     return loss.detach(), recon.detach()
@@ -241,11 +259,12 @@ def prepare_clip(labels: torch.Tensor, erode_radius: Optional[int] = None, size=
 def tune_clip(net, optimizer, images: torch.Tensor, labels: torch.Tensor, style_vectors: torch.Tensor, steps: int,
               erode_radius: Optional[int] = None, l2_lambda: float = 1.0, extra_loss=None, group=None, graphed: Optional[bool] = None,
               randomize_noise: bool = True, step_fn=None, on_epoch=None, local_only: bool = False, lpips=None, lpips_lambda: float = 0.8,
-              id_loss=None, id_lambda: float = 0.1):
+              id_loss=None, id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
     """The fine-tuning loop of ``VideoSwapPTICoach.train_e4s`` (training/video_swap_ft_coach.py:242-317) for the part on the hot path:
     ``steps`` passes over the clip's frames, one optimiser step per frame — ``cal_style_codes`` -> ``gen_img`` on the (eroded) region map ->
     L2 against the frame under the foreground weight (+ ``lpips_lambda`` x the three-scale LPIPS-AlexNet term when ``lpips`` is given,
-    + ``id_lambda`` x the ArcFace identity term when ``id_loss`` is given, + ``extra_loss`` for the parsing net of ``calc_loss``) ->
+    + ``id_lambda`` x the ArcFace identity term when ``id_loss`` is given, + ``face_parsing_lambda`` x the face-parsing term when ``face_parsing``
+    is given, + ``extra_loss``) ->
     backward -> Adam.  ``images [n, 3, 1024, 1024]`` in [-1, 1], ``labels`` uint8 ``[n, 512, 512]``, ``style_vectors [n, 12, 1280]``.
 
     Several GPUs (BASELINE configs[3]: 32 frames on 4 GPUs): every rank holds the whole clip's inputs or at least its own block; rank ``r``
@@ -262,6 +281,8 @@ def tune_clip(net, optimizer, images: torch.Tensor, labels: torch.Tensor, style_
         ops_lpips.check_loaded(lpips)
     if id_loss is not None:
         ops_id.check_loaded(id_loss)
+    if face_parsing is not None:
+        ops_fp.check_loaded(face_parsing)
     distributed = (not local_only) and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0
@@ -290,7 +311,7 @@ def tune_clip(net, optimizer, images: torch.Tensor, labels: torch.Tensor, style_
         ex = frame(sched[EAGER_FIRST][1])
         step = GraphedPTIStep(net, optimizer, ex[0], ex[1], ex[2], ex[3], l2_lambda, extra_loss, randomize_noise,
                               warm_inputs=[frame(i) for _, i in sched[:EAGER_FIRST]], lpips=lpips, lpips_lambda=lpips_lambda,
-                              id_loss=id_loss, id_lambda=id_lambda)
+                              id_loss=id_loss, id_lambda=id_lambda, face_parsing=face_parsing, face_parsing_lambda=face_parsing_lambda)
         warm_losses = list(step.warm_losses)
     done = 0
     history = []
@@ -314,7 +335,7 @@ def tune_clip(net, optimizer, images: torch.Tensor, labels: torch.Tensor, style_
                 loss = None
                 if have:
                     loss, _ = _loss(net, style_vectors[f:f + 1], maps[i:i + 1], images[f:f + 1], fgs[i:i + 1], l2_lambda, extra_loss, randomize_noise,
-                                    lpips, lpips_lambda, id_loss, id_lambda)
+                                    lpips, lpips_lambda, id_loss, id_lambda, face_parsing, face_parsing_lambda)
                     loss.backward()
                 if distributed:
                     sync_gradients(params, group, active_ranks=active)

@@ -26,6 +26,7 @@ __all__ = [
     "seeded_array",
     "seeded_lpips_state_dict",
     "seeded_irse50_state_dict",
+    "seeded_unet_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -163,8 +164,27 @@ def seeded_irse50_state_dict(seed: int) -> Dict[str, torch.Tensor]:
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in state_dict_shapes().items()}, seed, "irse50")
 
 
+# face-parsing unet (criteria/face_parsing/unet.py::unet(feature_scale=4)): He-scaled convolutions (ReLU keeps about half of each layer alive, so
+# the tap RMS stays O(1) through the ten conv + BN + ReLU layers), small conv biases, eval BatchNorm statistics around the identity
+_RULES_UNET = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"running_var$", (1.0, 1.0 / np.sqrt(12.0))),                    # U(0.5, 1.5)
+    (r"running_mean$", (0.0, 0.1)),
+    (r"\.conv[12]\.1\.weight$", (1.0, 0.1)),                         # BatchNorm gamma
+    (r"\.conv[12]\.1\.bias$", (0.0, 0.1)),                           # BatchNorm beta
+    (r"\.bias$", (0.0, 0.05)),                                        # convolution / transposed convolution biases
+    (r"\.weight$", _fan_in_std(1.4)),
+]
+
+
+def seeded_unet_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``unet(feature_scale=4)`` (the face-parsing net of criteria/face_parsing/face_parsing_loss.py; its 136-key state_dict)."""
+    from .ops_fp import state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in state_dict_shapes().items()}, seed, "unet")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
-    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50}.get(family, _RULES_BISENET)
+    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -668,6 +668,20 @@ E4S_API int e4s_id_head_sum(float* loss, float* sim, float* stats, const float* 
 E4S_API int e4s_id_head_bwd(float* gx, const float* fx, const float* fy, const float* stats, const float* gout, int bs, int64_t D, float scale,
                             int accumulate, void* stream);
 
+/* Face-parsing feature loss (criteria/face_parsing/face_parsing_loss.py on the unet encoder; csrc/fploss.hip) — forward and input gradient.  The input
+ * pooling and its adjoint run on e4s_id_resample(_adjoint) (no = 512), the heads on e4s_id_head_partial / e4s_id_head_sum, the convolutions on
+ * e4s_conv2d (3 input channels, fp32), e4s_conv2d_sb3 (forward) and e4s_conv2d_sb (data gradients); the first convolution's ReLU mask on
+ * e4s_lpips_relu_mask.  All tensors fp32 NCHW on the device.
+ *   e4s_fp_maxpool2 : out [planes][h / 2][w / 2] = MaxPool2d(2) of a [planes][h][w] (h, w even; a 8-byte aligned)
+ *   e4s_fp_tap_bwd  : g [bs][C][h][w] = (-gout[0] scale (fy / |y| - cos fx / |x|) / |x| + gpool routed to the first maximum (row-major) of each 2 x 2
+ *                     window of fx) * (fx > 0); fx, fy [bs][C][h][w] the block output (ReLU'd) of y_hat and y, stats [bs][3] = (|x|, |y|, cos) of
+ *                     the tap (e4s_id_head_sum), gpool [bs][C][h / 2][w / 2] the gradient of the next block's input or NULL (h, w even; g, fx, fy
+ *                     8-byte aligned)
+ * No float atomics: the same inputs give the same bits. */
+E4S_API int e4s_fp_maxpool2(float* out, const float* a, int planes, int h, int w, void* stream);
+E4S_API int e4s_fp_tap_bwd(float* g, const float* fx, const float* fy, const float* stats, const float* gout, const float* gpool, int bs, int C, int h,
+                           int w, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
