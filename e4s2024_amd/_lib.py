@@ -123,7 +123,26 @@ _PROTOS = {
     "e4s_id_head_bwd": [c_ptr] * 5 + [c_int, c_i64, c_f32, c_int, c_ptr],
     "e4s_fp_maxpool2": [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
     "e4s_fp_tap_bwd": [c_ptr] * 6 + [c_int] * 4 + [c_f32, c_ptr],
+    # multi-target heads: (…, ys, tw, k, frame, fstride, nframes, …) — ys / tw are host arrays (targets())
+    "e4s_lpips_head_multi": [c_ptr] * 4 + [c_int, c_ptr, c_i64, c_int, c_ptr] + [c_int] * 3 + [c_f32, c_ptr],
+    "e4s_lpips_head_multi_bwd": [c_ptr] * 4 + [c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr] + [c_int] * 3 + [c_f32, c_ptr],
+    "e4s_id_head_partial_multi": [c_ptr] * 4 + [c_int, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr],
+    "e4s_id_head_sum_multi": [c_ptr] * 4 + [c_int] * 8 + [c_ptr],
+    "e4s_id_head_bwd_multi": [c_ptr] * 4 + [c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_int, c_i64, c_f32, c_int, c_ptr],
+    "e4s_fp_tap_bwd_multi": [c_ptr] * 4 + [c_int, c_ptr, c_i64, c_int] + [c_ptr] * 3 + [c_int] * 4 + [c_f32, c_ptr],
+    "e4s_pix_mse_multi": [c_ptr] * 5 + [c_int, c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr],
+    "e4s_pix_mse_multi_bwd": [c_ptr] * 5 + [c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_i64, c_ptr],
 }
+
+MAX_TARGETS = 4                    # csrc/targets.h
+
+
+def targets(ptrs, weights):
+    """The ``(ys, tw, k)`` arguments of the multi-target entry points: host arrays of the targets' device pointers and of their weights."""
+    k = len(ptrs)
+    if not 1 <= k <= MAX_TARGETS or len(weights) != k:
+        raise ValueError(f"1 .. {MAX_TARGETS} targets with one weight each, got {k} targets and {len(weights)} weights")
+    return (c_ptr * k)(*ptrs), (c_f32 * k)(*[float(w) for w in weights]), k
 
 
 def declared_symbols(header: str = HEADER):

@@ -15,6 +15,7 @@
 // of the stride-1 3x3 / 1x1 convolutions on flipped, transposed weights) and the stride-2 3x3 data gradient on modconv_sb.hip's transposed convolution
 // (e4s_modconv_tconv_sb: split-bf16 at 1x the MACs, no zero insertion).
 #include "common.h"
+#include "targets.h"
 
 using namespace e4s;
 
@@ -296,7 +297,151 @@ __global__ __launch_bounds__(256) void id_head_bwd_kernel(float* __restrict__ gx
     }
 }
 
+// The multi-target heads (targets.h): one read of fx against k targets, target j weighted by w_j in the loss and the gradient.  Partials and stats carry
+// MS floats per entry: |x|^2 (|x|), then (|y_j|^2, x.y_j) ((|y_j|, cos_j)) per target; unused targets are 0.
+constexpr int MS = 1 + 2 * MAX_TARGETS;
+
+// part[(b * nblk + blk) * MS + ...] = block sums of x^2, then y_j^2, x.y_j per target
+__global__ __launch_bounds__(256) void id_head_partial_multi_kernel(float* __restrict__ part, const float* __restrict__ fx, const Targets tg, int64_t D) {
+    __shared__ float red[256];
+    const int blk = blockIdx.x, b = blockIdx.y, nblk = gridDim.x;
+    const float* xp = fx + (size_t)b * D;
+    const int64_t e0 = (int64_t)blk * HB, e1 = min<int64_t>(D, e0 + HB);
+    float* o = part + ((size_t)b * nblk + blk) * MS;
+    float sxx = 0.f;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
+        const float u = xp[e];
+        sxx = fmaf(u, u, sxx);
+    }
+    sxx = bsum256(sxx, red);
+    if (threadIdx.x == 0) o[0] = sxx;
+    for (int j = 0; j < MAX_TARGETS; ++j) {
+        float syy = 0.f, sxy = 0.f;
+        if (j < tg.k) {
+            const float* yp = target_base(tg, j) + (size_t)b * D;
+            for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
+                const float u = xp[e], v = yp[e];
+                syy = fmaf(v, v, syy);
+                sxy = fmaf(u, v, sxy);
+            }
+            syy = bsum256(syy, red);
+            sxy = bsum256(sxy, red);
+        }
+        if (threadIdx.x == 0) {
+            o[1 + 2 * j] = syy;
+            o[2 + 2 * j] = sxy;
+        }
+    }
+}
+
+// one workgroup: stats[(t * bs + b) * MS + ...] = |x|, then (|y_j|, cos_j) per target; loss_out[0] = sum_t sum_j w_j mean_b (1 - cos_j)
+__global__ __launch_bounds__(256) void id_head_sum_multi_kernel(float* __restrict__ loss_out, float* __restrict__ stats, const float* __restrict__ part,
+                                                                const Targets tg, int bs, int ntap, int nb0, int nb1, int nb2, int nb3, int nb4) {
+    __shared__ float red[256];
+    const int nbs[5] = {nb0, nb1, nb2, nb3, nb4};
+    float loss = 0.f;
+    size_t off = 0;
+    for (int t = 0; t < ntap; ++t) {
+        const int nb = nbs[t];
+        float lt[MAX_TARGETS] = {0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < bs; ++b) {
+            const float* pp = part + off + (size_t)b * nb * MS;
+            float* st = stats + ((size_t)t * bs + b) * MS;
+            float sxx = 0.f;
+            for (int i = threadIdx.x; i < nb; i += 256) sxx += pp[MS * i];
+            sxx = bsum256(sxx, red);
+            const float nx = sqrtf(sxx);
+            if (threadIdx.x == 0) st[0] = nx;
+#pragma unroll
+            for (int j = 0; j < MAX_TARGETS; ++j) {
+                float syy = 0.f, sxy = 0.f;
+                for (int i = threadIdx.x; i < nb; i += 256) {
+                    syy += pp[MS * i + 1 + 2 * j];
+                    sxy += pp[MS * i + 2 + 2 * j];
+                }
+                syy = bsum256(syy, red);
+                sxy = bsum256(sxy, red);
+                const float ny = sqrtf(syy);
+                const float c = j < tg.k ? sxy / (nx * ny) : 0.f;
+                if (threadIdx.x == 0) {
+                    st[1 + 2 * j] = ny;
+                    st[2 + 2 * j] = c;
+                }
+                lt[j] += 1.f - c;
+            }
+        }
+        for (int j = 0; j < tg.k; ++j) loss += tg.w[j] * (lt[j] / (float)bs);
+        off += (size_t)bs * nb * MS;
+    }
+    if (threadIdx.x == 0) loss_out[0] = loss;
+}
+
+// gx[b, e] (+)= -gout[0] scale sum_j w_j (fy_j / |y_j| - cos_j fx / |x|) / |x| from the multi-target stats of the tap
+__global__ __launch_bounds__(256) void id_head_bwd_multi_kernel(float* __restrict__ gx, const float* __restrict__ fx, const Targets tg,
+                                                                const float* __restrict__ stats, const float* __restrict__ gout, int64_t D, float scale,
+                                                                int accumulate) {
+    const int b = blockIdx.y;
+    const float* st = stats + (size_t)b * MS;
+    const float nx = st[0];
+    const float* yp[MAX_TARGETS];
+    float kk[MAX_TARGETS], ix[MAX_TARGETS], iy[MAX_TARGETS];
+#pragma unroll
+    for (int j = 0; j < MAX_TARGETS; ++j) {
+        const bool on = j < tg.k;
+        yp[j] = on ? target_base(tg, j) + (size_t)b * D : fx + (size_t)b * D;
+        kk[j] = on ? -gout[0] * scale * tg.w[j] / nx : 0.f;
+        ix[j] = on ? st[2 + 2 * j] / nx : 0.f;
+        iy[j] = on ? 1.f / st[1 + 2 * j] : 0.f;
+    }
+    const int nt = tg.k;
+    const size_t base = (size_t)b * D;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < D; e += (int64_t)gridDim.x * 256) {
+        const float x = fx[base + e];
+        float v = kk[0] * (yp[0][e] * iy[0] - x * ix[0]);
+#pragma unroll
+        for (int j = 1; j < MAX_TARGETS; ++j)
+            if (j < nt) v += kk[j] * (yp[j][e] * iy[j] - x * ix[j]);
+        gx[base + e] = accumulate ? gx[base + e] + v : v;
+    }
+}
+
 }  // namespace
+
+extern "C" int e4s_id_head_partial_multi(float* part, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                         int bs, int64_t D, void* stream) {
+    E4S_REQUIRE(part && fx, "id_head_partial_multi: null tensor");
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && D >= 1 && cdiv64(D, HB) <= (1 << 20), "id_head_partial_multi: bad size");
+    Targets tg;
+    if (const int st = make_targets(tg, ys, tw, k, frame, fstride, nframes, "id_head_partial_multi")) return st;
+    if (bs == 0) return 0;
+    hipLaunchKernelGGL(id_head_partial_multi_kernel, dim3((unsigned)cdiv64(D, HB), bs), dim3(256), 0, (hipStream_t)stream, part, fx, tg, D);
+    return check_launch("id_head_partial_multi");
+}
+
+extern "C" int e4s_id_head_sum_multi(float* loss, float* stats, const float* part, const float* tw, int k, int bs, int ntap, int nb0, int nb1, int nb2,
+                                     int nb3, int nb4, void* stream) {
+    E4S_REQUIRE(loss && stats && part, "id_head_sum_multi: null tensor");
+    E4S_REQUIRE(bs >= 1 && bs <= 65535 && ntap >= 1 && ntap <= 5, "id_head_sum_multi: bad size");
+    const int nbs[5] = {nb0, nb1, nb2, nb3, nb4};
+    for (int t = 0; t < ntap; ++t) E4S_REQUIRE(nbs[t] >= 1, "id_head_sum_multi: tap %d has no partials", t);
+    const float* dummy[MAX_TARGETS] = {part, part, part, part};       // only the weights and the count are read here
+    Targets tg;
+    if (const int st = make_targets(tg, dummy, tw, k, nullptr, 0, 1, "id_head_sum_multi")) return st;
+    hipLaunchKernelGGL(id_head_sum_multi_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, stats, part, tg, bs, ntap, nb0, nb1, nb2, nb3, nb4);
+    return check_launch("id_head_sum_multi");
+}
+
+extern "C" int e4s_id_head_bwd_multi(float* gx, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                     const float* stats, const float* gout, int bs, int64_t D, float scale, int accumulate, void* stream) {
+    E4S_REQUIRE(gx && fx && stats && gout, "id_head_bwd_multi: null tensor");
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && D >= 1, "id_head_bwd_multi: bad size");
+    Targets tg;
+    if (const int st = make_targets(tg, ys, tw, k, frame, fstride, nframes, "id_head_bwd_multi")) return st;
+    if (bs == 0) return 0;
+    const int gxs = (int)(cdiv64(D, 256) < 1024 ? cdiv64(D, 256) : 1024);
+    hipLaunchKernelGGL(id_head_bwd_multi_kernel, dim3(gxs, bs), dim3(256), 0, (hipStream_t)stream, gx, fx, tg, stats, gout, D, scale, accumulate);
+    return check_launch("id_head_bwd_multi");
+}
 
 extern "C" int e4s_id_resample(float* out, const float* x, const float* ay, const float* ax, const int* ry, const int* rx, int planes, int h, int w, int no,
                                void* stream) {

@@ -11,6 +11,7 @@
 //   relu mask  g *= (a > 0) after a data-gradient convolution
 // Convolutions 2 - 5 and their data gradients run on conv.hip (e4s_conv2d_sb3 forward, e4s_conv2d_sb on the flipped, transposed weights backward).
 #include "common.h"
+#include "targets.h"
 
 using namespace e4s;
 
@@ -279,6 +280,107 @@ __global__ __launch_bounds__(256) void lpips_head_bwd_kernel(float* __restrict__
     }
 }
 
+// The multi-target heads: one read of fx against k targets (targets.h), target j weighted by w_j.  With k = 1 and w = 1 they give the single head's bits.
+// partial[b * gridDim.x + blockIdx.x] = scale * sum over the block's HP pixels of sum_j w_j sum_c lin_c (fx_c / nx - fy_jc / ny_j)^2
+__global__ __launch_bounds__(256) void lpips_head_multi_kernel(float* __restrict__ partial, const float* __restrict__ fx, const Targets tg,
+                                                               const float* __restrict__ lin, int c, int hw, float scale) {
+#pragma clang fp contract(off)      // as in lpips_head_kernel: x == y_j gives exactly 0 for that target
+    __shared__ float buf[256];
+    const int b = blockIdx.y, q = threadIdx.x / HP;
+    const int p = blockIdx.x * HP + threadIdx.x % HP;
+    const bool on = p < hw;
+    const size_t off = (size_t)b * c * hw + (on ? p : 0);
+    const float* xp = fx + off;
+    float sx = 0.f;
+    for (int k = q; k < c; k += HS) {
+        const float u = xp[(size_t)k * hw];
+        sx = fmaf(u, u, sx);
+    }
+    sx = slice_sum(sx, buf);
+    const float nx = 1.f / (sqrtf(sx + 1e-16f) + 1e-10f);
+    float tot = 0.f;
+    for (int j = 0; j < tg.k; ++j) {
+        const float* yp = target_base(tg, j) + off;
+        float sy = 0.f;
+        for (int k = q; k < c; k += HS) {
+            const float v = yp[(size_t)k * hw];
+            sy = fmaf(v, v, sy);
+        }
+        sy = slice_sum(sy, buf);
+        const float ny = 1.f / (sqrtf(sy + 1e-16f) + 1e-10f);
+        float d = 0.f;
+        for (int k = q; k < c; k += HS) {
+            const float t = xp[(size_t)k * hw] * nx - yp[(size_t)k * hw] * ny;
+            d = fmaf(lin[k] * t, t, d);
+        }
+        d = slice_sum(d, buf);
+        tot += tg.w[j] * d;
+    }
+    const float s = block_sum256(on && q == 0 ? tot * scale : 0.f, buf);
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = s;
+}
+
+// gx = d/dfx of scale gout sum_j w_j sum_c lin_c (u_c - v_jc)^2 in one pass: with A_c = sum_j a_jc, a_jc = 2 scale gout w_j lin_c (u_c - v_jc),
+//   gfx_c = A_c nx - fx_c nx^2 / rx sum_c' A_c' fx_c'   (the single head's formula is linear in a)
+__global__ __launch_bounds__(256) void lpips_head_multi_bwd_kernel(float* __restrict__ gx, const float* __restrict__ fx, const Targets tg,
+                                                                   const float* __restrict__ lin, const float* __restrict__ gout, int c, int hw, float scale) {
+#pragma clang fp contract(off)
+    __shared__ float buf[256];
+    const int b = blockIdx.y, q = threadIdx.x / HP;
+    const int p = blockIdx.x * HP + threadIdx.x % HP;
+    const bool on = p < hw;
+    const size_t off = (size_t)b * c * hw + (on ? p : 0);
+    const float* xp = fx + off;
+    float sx = 0.f;
+    for (int k = q; k < c; k += HS) {
+        const float u = xp[(size_t)k * hw];
+        sx = fmaf(u, u, sx);
+    }
+    sx = slice_sum(sx, buf);
+    const float rx = sqrtf(sx + 1e-16f);
+    const float nx = 1.f / (rx + 1e-10f);
+    const float s2 = 2.f * scale * gout[0];
+    const float* yp[MAX_TARGETS];
+    float ny[MAX_TARGETS], sw[MAX_TARGETS];
+#pragma unroll
+    for (int j = 0; j < MAX_TARGETS; ++j) {
+        yp[j] = xp;
+        ny[j] = 0.f;
+        sw[j] = 0.f;
+        if (j < tg.k) {
+            yp[j] = target_base(tg, j) + off;
+            float sy = 0.f;
+            for (int k = q; k < c; k += HS) {
+                const float v = yp[j][(size_t)k * hw];
+                sy = fmaf(v, v, sy);
+            }
+            sy = slice_sum(sy, buf);
+            ny[j] = 1.f / (sqrtf(sy + 1e-16f) + 1e-10f);
+            sw[j] = s2 * tg.w[j];
+        }
+    }
+    const int nt = tg.k;
+    auto A = [&](int k, float u) {
+        float a = sw[0] * lin[k] * (u * nx - yp[0][(size_t)k * hw] * ny[0]);
+#pragma unroll
+        for (int j = 1; j < MAX_TARGETS; ++j)
+            if (j < nt) a += sw[j] * lin[k] * (u * nx - yp[j][(size_t)k * hw] * ny[j]);
+        return a;
+    };
+    float dx = 0.f;
+    for (int k = q; k < c; k += HS) {
+        const float u = xp[(size_t)k * hw];
+        dx = fmaf(A(k, u), u, dx);
+    }
+    dx = slice_sum(dx, buf);
+    if (!on) return;
+    const float cx = dx * nx * nx / rx;
+    for (int k = q; k < c; k += HS) {
+        const float u = xp[(size_t)k * hw];
+        gx[off + (size_t)k * hw] = A(k, u) * nx - u * cx;
+    }
+}
+
 __global__ __launch_bounds__(256) void lpips_relu_mask_kernel(float* __restrict__ g, const float* __restrict__ a, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         if (!(a[i] > 0.f)) g[i] = 0.f;
@@ -358,6 +460,28 @@ extern "C" int e4s_lpips_head_bwd(float* gx, float* gy, const float* fx, const f
     if (bs == 0) return 0;
     hipLaunchKernelGGL(lpips_head_bwd_kernel, dim3(cdiv(hw, HP), bs), dim3(256), 0, (hipStream_t)stream, gx, gy, fx, fy, lin, gout, c, hw, scale);
     return check_launch("lpips_head_bwd");
+}
+
+extern "C" int e4s_lpips_head_multi(float* partial, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                    const float* lin, int bs, int c, int hw, float scale, void* stream) {
+    E4S_REQUIRE(partial && fx && lin, "lpips_head_multi: null tensor");
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && c >= 1 && hw >= 1, "lpips_head_multi: bad size");
+    Targets tg;
+    if (const int st = make_targets(tg, ys, tw, k, frame, fstride, nframes, "lpips_head_multi")) return st;
+    if (bs == 0) return 0;
+    hipLaunchKernelGGL(lpips_head_multi_kernel, dim3(cdiv(hw, HP), bs), dim3(256), 0, (hipStream_t)stream, partial, fx, tg, lin, c, hw, scale);
+    return check_launch("lpips_head_multi");
+}
+
+extern "C" int e4s_lpips_head_multi_bwd(float* gx, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                        const float* lin, const float* gout, int bs, int c, int hw, float scale, void* stream) {
+    E4S_REQUIRE(gx && fx && lin && gout, "lpips_head_multi_bwd: null tensor");
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && c >= 1 && hw >= 1, "lpips_head_multi_bwd: bad size");
+    Targets tg;
+    if (const int st = make_targets(tg, ys, tw, k, frame, fstride, nframes, "lpips_head_multi_bwd")) return st;
+    if (bs == 0) return 0;
+    hipLaunchKernelGGL(lpips_head_multi_bwd_kernel, dim3(cdiv(hw, HP), bs), dim3(256), 0, (hipStream_t)stream, gx, fx, tg, lin, gout, c, hw, scale);
+    return check_launch("lpips_head_multi_bwd");
 }
 
 extern "C" int e4s_lpips_relu_mask(float* g, const float* a, int64_t n, void* stream) {

@@ -26,16 +26,17 @@ class ClipBatch:
     target_mask: Optional[torch.Tensor] = None
     driven_style: Optional[torch.Tensor] = None
     target_style: Optional[torch.Tensor] = None
+    driven_recolor: Optional[torch.Tensor] = None      # the recoloured driven frames (imgs/D_recolor_%04d.png), the PTI recolor term's targets
 
     def __len__(self):
-        for t in (self.target, self.driven, self.target_mask, self.driven_mask, self.target_style, self.driven_style):
+        for t in (self.target, self.driven, self.target_mask, self.driven_mask, self.target_style, self.driven_style, self.driven_recolor):
             if t is not None:
                 return int(t.shape[0])
         return 0
 
     def to(self, device):
         return ClipBatch(*[None if t is None else t.to(device, non_blocking=True) for t in
-                           (self.driven, self.target, self.driven_mask, self.target_mask, self.driven_style, self.target_style)])
+                           (self.driven, self.target, self.driven_mask, self.target_mask, self.driven_style, self.target_style, self.driven_recolor)])
 
 
 def _to_u8_hwc(img: torch.Tensor) -> np.ndarray:
@@ -45,7 +46,8 @@ def _to_u8_hwc(img: torch.Tensor) -> np.ndarray:
 
 
 def dump(clip: ClipBatch, exp_dir: str, first_index: int = 0) -> None:
-    """Write ``imgs/{D,T}_%04d.png``, ``mask/{D,T}_mask_%04d.png`` and ``styleVec/{D,T}_style_vec_%04d.pt`` for the frames of ``clip``."""
+    """Write ``imgs/{D,T}_%04d.png``, ``mask/{D,T}_mask_%04d.png`` and ``styleVec/{D,T}_style_vec_%04d.pt`` for the frames of ``clip``, and
+    ``imgs/D_recolor_%04d.png`` when it has recoloured frames (face_swap_video_pipeline.py:306-310)."""
     from PIL import Image
     for sub in ("imgs", "mask", "styleVec"):
         os.makedirs(os.path.join(exp_dir, sub), exist_ok=True)
@@ -58,11 +60,14 @@ def dump(clip: ClipBatch, exp_dir: str, first_index: int = 0) -> None:
                 Image.fromarray(msk[k].detach().cpu().numpy().astype(np.uint8)).save(os.path.join(exp_dir, "mask", f"{tag}_mask_{i:04d}.png"))
             if vec is not None:
                 torch.save(vec[k:k + 1].detach().cpu().float(), os.path.join(exp_dir, "styleVec", f"{tag}_style_vec_{i:04d}.pt"))
+        if clip.driven_recolor is not None:
+            Image.fromarray(_to_u8_hwc(clip.driven_recolor[k])).save(os.path.join(exp_dir, "imgs", f"D_recolor_{i:04d}.png"))
 
 
 def load(exp_dir: str, first_index: int = 0, count: Optional[int] = None, device="cpu", size: int = 1024) -> ClipBatch:
     """Read back what ``dump`` (or the reference) wrote; missing kinds stay ``None``.  Images are resized to ``size`` like the
-    reference does on load (``Image.open(...).convert("RGB").resize((1024, 1024))``, :408-411)."""
+    reference does on load (``Image.open(...).convert("RGB").resize((1024, 1024))``, :408-411); the recoloured frames are converted as the
+    coach's ``im2tensor(std=False)`` does (utils/torch_utils.py:94: ``x / 127.5 - 1``)."""
     from PIL import Image
 
     def frames(pattern):
@@ -79,6 +84,13 @@ def load(exp_dir: str, first_index: int = 0, count: Optional[int] = None, device
         arr = np.stack([np.asarray(Image.open(f).convert("RGB").resize((size, size))) for f in fs])
         return (torch.from_numpy(arr).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5            # ToTensor + Normalize(.5, .5)
 
+    def recolored():
+        fs = frames(os.path.join(exp_dir, "imgs", "D_recolor_%04d.png"))
+        if not fs:
+            return None
+        arr = np.stack([np.asarray(Image.open(f).convert("RGB").resize((size, size))) for f in fs])
+        return torch.from_numpy(arr).permute(0, 3, 1, 2).float() / 127.5 - 1.0                    # im2tensor(std=False)
+
     def masks(tag):
         fs = frames(os.path.join(exp_dir, "mask", tag + "_mask_%04d.png"))
         return torch.from_numpy(np.stack([np.asarray(Image.open(f)) for f in fs]).astype(np.uint8)) if fs else None
@@ -87,4 +99,4 @@ def load(exp_dir: str, first_index: int = 0, count: Optional[int] = None, device
         fs = frames(os.path.join(exp_dir, "styleVec", tag + "_style_vec_%04d.pt"))
         return torch.cat([torch.load(f, map_location="cpu").float() for f in fs]) if fs else None
 
-    return ClipBatch(images("D"), images("T"), masks("D"), masks("T"), styles("D"), styles("T")).to(device)
+    return ClipBatch(images("D"), images("T"), masks("D"), masks("T"), styles("D"), styles("T"), recolored()).to(device)

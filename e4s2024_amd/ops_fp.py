@@ -29,9 +29,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from typing import Optional
+
+from . import ops_id
 from ._lib import lib
 from .ops import _Prepared, _c, _p, _stream
 from .ops_id import _bands, _bn, _heads, _pool_matrix, _prep_dgrad, _prep_fwd, weights_key
+from .ops_multi import call_args, check_frame, check_targets, target_rows
 
 SIDE = 512                                   # FaceParsingLoss.face_pool: AdaptiveAvgPool2d((512, 512)) unless x.shape[2] == 512
 FILTERS = (16, 32, 64, 128, 256)             # unet(feature_scale=4): [64, 128, 256, 512, 1024] / 4
@@ -273,15 +277,19 @@ def _conv_dgrad(g, slabs, cout):
     return out
 
 
-def _input_grad(acts, P, stats, gout, bs):
-    """d loss / d (the network's input) of the first ``bs`` samples."""
+def _input_grad(acts, P, stats, gout, bs, tap_bwd=None):
+    """d loss / d (the network's input) of the first ``bs`` samples.  ``tap_bwd(gz, i, gpool)``: writes block i's tap gradient in place of the
+    single-target one (the multi-target loss)."""
     g = None
     for i in range(len(P) - 1, -1, -1):
         B = P[i]
         c1, c2 = acts[i]
         _, c, h, w = c2.shape
         gz = torch.empty((bs, c, h, w), dtype=torch.float32, device=c2.device)
-        lib().call("e4s_fp_tap_bwd", _p(gz), _p(c2[:bs]), _p(c2[bs:]), _p(stats[i]), _p(gout), _p(g), bs, c, h, w, 1.0 / bs, _stream())
+        if tap_bwd is None:
+            lib().call("e4s_fp_tap_bwd", _p(gz), _p(c2[:bs]), _p(c2[bs:]), _p(stats[i]), _p(gout), _p(g), bs, c, h, w, 1.0 / bs, _stream())
+        else:
+            tap_bwd(gz, i, g)
         gc1 = _conv_dgrad(gz, B["bwd2"], c)
         lib().call("e4s_lpips_relu_mask", _p(gc1), _p(c1), gc1.numel(), _stream())       # c1[:bs] is the head of c1: same offsets
         g = _conv_dgrad(gc1, B["bwd1"], B["cin"])
@@ -320,6 +328,67 @@ class _FpLoss(torch.autograd.Function):
         gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         lib().call("e4s_id_resample_adjoint", _p(gx), _p(g), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
         return gx, None, None, None
+
+
+class _FpLossMulti(torch.autograd.Function):
+    """sum_j tw[j] FaceParsingLoss(y_hat, y_j) from the targets' cached block outputs; differentiable in ``y_hat`` only."""
+
+    @staticmethod
+    def forward(ctx, y_hat, P, R, ys, tw, frame):
+        bs = y_hat.shape[0]
+        acts = _encoder(_network_input((y_hat,), R), P)
+        fx = [c2.reshape(bs, -1) for _, c2 in acts]
+        loss, stats = ops_id.heads_multi(fx, ys, tw, frame)
+        ctx.P, ctx.R, ctx.shape, ctx.ys, ctx.tw, ctx.frame = P, R, tuple(y_hat.shape), ys, tw, frame
+        ctx.acts = acts
+        ctx.save_for_backward(stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        (stats,) = ctx.saved_tensors
+        bs, c, h, w = ctx.shape
+        gout = _c(gloss.reshape(1), "grad_output")
+        acts = ctx.acts
+
+        def tap_bwd(gz, i, gpool):
+            c2 = acts[i][1]
+            lib().call("e4s_fp_tap_bwd_multi", _p(gz), _p(c2), *call_args([y[i] for y in ctx.ys], ctx.tw, ctx.frame, bs), _p(stats[i]), _p(gout),
+                       _p(gpool), bs, c2.shape[1], c2.shape[2], c2.shape[3], 1.0 / bs, _stream())
+        g = _input_grad(acts, ctx.P, stats, gout, bs, tap_bwd)
+        ctx.acts = None
+        R = ctx.R
+        if R is None:
+            return g, None, None, None, None, None
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
+        return gx, None, None, None, None, None
+
+
+def target_features(images: torch.Tensor, weights):
+    """The raw block outputs of ``images`` ``[n, 3, H, W]`` that ``fp_loss_multi`` reads for a target: five ``[n, D]`` tensors.  Computed a frame at a
+    time; no gradient."""
+    check_loaded(weights)
+    images = _check(images.detach(), "images")
+    P, R = prepare(weights), resampler(images.shape[2], images.shape[3], images.device)
+    with torch.no_grad():
+        return target_rows(lambda x: [c2.reshape(x.shape[0], -1) for _, c2 in _encoder(_network_input((x.contiguous(),), R), P)], images)
+
+
+def fp_loss_multi(y_hat: torch.Tensor, targets, tw, weights, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sum_j tw[j] * fp_loss(y_hat, y_j)`` (0-d, differentiable in ``y_hat`` only) with one encoder pass and input gradient of ``y_hat``:
+    ``targets[j] = target_features(y_j, weights)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
+    check_loaded(weights)
+    y_hat = _check(y_hat, "y_hat")
+    frame = check_frame(frame, y_hat.device)
+    bs = y_hat.shape[0]
+    side_h, side_w = (y_hat.shape[2], y_hat.shape[3]) if y_hat.shape[2] == SIDE else (SIDE, SIDE)
+    P = prepare(weights)
+    dims = [B["cout"] * (side_h >> i) * (side_w >> i) for i, B in enumerate(P)]
+    ys = check_targets([torch.empty((bs, d), device="meta") for d in dims], targets, tw, frame, "fp_loss_multi")
+    return _FpLossMulti.apply(y_hat, P, resampler(y_hat.shape[2], y_hat.shape[3], y_hat.device), ys, [float(w) for w in tw], frame)
 
 
 def _check(x: torch.Tensor, name: str) -> torch.Tensor:
@@ -375,4 +444,4 @@ def fp_features(x: torch.Tensor, weights):
 
 
 __all__ = ["FaceParsingNet", "PreparedFaceParsingNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes",
-           "encoder_keys", "resampler", "fp_features", "unet_features", "fp_loss", "fp_loss_terms"]
+           "encoder_keys", "resampler", "fp_features", "unet_features", "fp_loss", "fp_loss_terms", "target_features", "fp_loss_multi"]

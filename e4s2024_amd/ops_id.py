@@ -26,8 +26,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ._lib import lib
+from typing import Optional
+
+from ._lib import lib, targets as _host_targets
 from .ops import _Prepared, _c, _p, _stream
+from .ops_multi import call_args, check_frame, check_targets, target_rows
 
 BN_EPS = 1e-5
 SIDE = 112                                   # the network's input side (IDLoss.face_pool_2)
@@ -411,22 +414,25 @@ def _unit_bwd(gy, U, rec, bs, h, w):
     return gx
 
 
-def _input_grad(fx, fy, stats, gout, P, state, multiscale: bool):
-    """d loss / d (the 112 x 112 input)."""
+def _input_grad(fx, fy, stats, gout, P, state, multiscale: bool, head_bwd=None):
+    """d loss / d (the 112 x 112 input).  ``head_bwd(g, k, scale, accumulate)``: writes (adds) tap k's head gradient to ``g`` in place of the
+    single-target head (the multi-target loss)."""
     inp, us, wout, _ = P
     c0, saved = state
     bs = c0.shape[0]
     scale = 1.0 / bs
+    if head_bwd is None:
+        def head_bwd(g, k, scale, accumulate):
+            lib().call("e4s_id_head_bwd", _p(g), _p(fx[k]), _p(fy[k]), _p(stats[k]), _p(gout), bs, fx[k].shape[1], scale, accumulate, _stream())
     gfeat = torch.empty_like(fx[-1])
-    lib().call("e4s_id_head_bwd", _p(gfeat), _p(fx[-1]), _p(fy[-1]), _p(stats[-1]), _p(gout), bs, 512, scale, 0, _stream())
+    head_bwd(gfeat, len(fx) - 1, scale, 0)
     g = torch.empty((bs, 512, 7, 7), dtype=torch.float32, device=c0.device)
     lib().call("e4s_id_linear_t", _p(g), _p(gfeat), _p(wout), bs, wout.shape[1], 512, _stream())
     taps = {u: k for k, u in enumerate(TAP_UNITS)} if multiscale else {}
     h = w = 7
     for i in range(len(us) - 1, -1, -1):
         if i in taps:
-            k = taps[i]
-            lib().call("e4s_id_head_bwd", _p(g), _p(fx[k]), _p(fy[k]), _p(stats[k]), _p(gout), bs, fx[k].shape[1], scale, 1, _stream())
+            head_bwd(g, taps[i], scale, 1)
         U = us[i]
         h, w = h * U["stride"], w * U["stride"]
         g = _unit_bwd(g, U, saved[i], bs, h, w)
@@ -462,6 +468,88 @@ class _IdLoss(torch.autograd.Function):
         R = ctx.R
         lib().call("e4s_id_resample_adjoint", _p(gx), _p(g112), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
         return gx, None, None, None, None
+
+
+MULTI_STATS = 9                              # e4s_id_head_*_multi: |x|^2 (|x|), then (|y_j|^2, x.y_j) ((|y_j|, cos_j)) for 4 targets
+
+
+def _feature_dims(multiscale: bool):
+    """Per-sample sizes of the features: the outputs of the TAP_UNITS (with ``multiscale``), then the 512-d embedding."""
+    dims, side = [], SIDE
+    for i, (_, depth, stride) in enumerate(units()):
+        side //= stride
+        if multiscale and i in TAP_UNITS:
+            dims.append(depth * side * side)
+    return dims + [512]
+
+
+def heads_multi(fx, ys, tw, frame):
+    """(loss, stats [ntap][bs][9]) of the multi-target heads: ``ys[j][t]`` is target j's tap t (also used by ``ops_fp``)."""
+    bs = fx[0].shape[0]
+    nbs = [-(-f.shape[1] // HEAD_BLOCK) for f in fx]
+    part = torch.empty((MULTI_STATS * bs * sum(nbs),), dtype=torch.float32, device=fx[0].device)
+    off = 0
+    for t, (a, nb) in enumerate(zip(fx, nbs)):
+        lib().call("e4s_id_head_partial_multi", _p(part[off:]), _p(a), *call_args([y[t] for y in ys], tw, frame, bs), bs, a.shape[1], _stream())
+        off += MULTI_STATS * bs * nb
+    loss = torch.empty((), dtype=torch.float32, device=fx[0].device)
+    stats = torch.empty((len(fx), bs, MULTI_STATS), dtype=torch.float32, device=fx[0].device)
+    _, ws, k = _host_targets([0] * len(tw), tw)
+    lib().call("e4s_id_head_sum_multi", _p(loss), _p(stats), _p(part), ws, k, bs, len(fx), *(nbs + [0] * (5 - len(nbs))), _stream())
+    return loss, stats
+
+
+class _IdLossMulti(torch.autograd.Function):
+    """sum_j tw[j] IDLoss(y_hat, y_j) from the targets' cached features; differentiable in ``y_hat`` only."""
+
+    @staticmethod
+    def forward(ctx, y_hat, P, R, multiscale, ys, tw, frame):
+        fx, state = _features(_resample(y_hat, R), P, multiscale, save=True)
+        loss, stats = heads_multi(fx, ys, tw, frame)
+        ctx.P, ctx.R, ctx.multiscale, ctx.shape, ctx.state, ctx.ys, ctx.tw, ctx.frame = P, R, multiscale, tuple(y_hat.shape), state, ys, tw, frame
+        ctx.save_for_backward(stats, *fx)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None, None
+        saved = ctx.saved_tensors
+        stats, fx = saved[0], list(saved[1:])
+        gout = _c(gloss.reshape(1), "grad_output")
+        bs = fx[0].shape[0]
+
+        def head_bwd(g, k, scale, accumulate):
+            lib().call("e4s_id_head_bwd_multi", _p(g), _p(fx[k]), *call_args([y[k] for y in ctx.ys], ctx.tw, ctx.frame, bs), _p(stats[k]), _p(gout), bs,
+                       fx[k].shape[1], scale, accumulate, _stream())
+        g112 = _input_grad(fx, None, None, gout, ctx.P, ctx.state, ctx.multiscale, head_bwd)
+        bs, c, h, w = ctx.shape
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g112.device)
+        R = ctx.R
+        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g112), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
+        return gx, None, None, None, None, None, None
+
+
+def target_features(images: torch.Tensor, weights, multiscale: bool = True):
+    """The raw (not normalised) features of ``images`` ``[n, 3, H, W]`` that ``id_loss_multi`` reads for a target: a list of ``[n, D]`` tensors
+    (five with ``multiscale``, the embedding alone without).  Computed a frame at a time; no gradient."""
+    check_loaded(weights)
+    images = _check(images.detach(), "images")
+    P, R = prepare(weights), resampler(images.shape[2], images.shape[3], images.device)
+    with torch.no_grad():
+        return target_rows(lambda x: _features(_resample(x.contiguous(), R), P, bool(multiscale), save=False)[0], images)
+
+
+def id_loss_multi(y_hat: torch.Tensor, targets, tw, weights, multiscale: bool = True, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sum_j tw[j] * id_loss(y_hat, y_j)`` (0-d, differentiable in ``y_hat`` only) with one network pass and input gradient of ``y_hat``:
+    ``targets[j] = target_features(y_j, weights, multiscale)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
+    check_loaded(weights)
+    y_hat = _check(y_hat, "y_hat")
+    frame = check_frame(frame, y_hat.device)
+    bs = y_hat.shape[0]
+    ys = check_targets([torch.empty((bs, d), device="meta") for d in _feature_dims(multiscale)], targets, tw, frame, "id_loss_multi")
+    return _IdLossMulti.apply(y_hat, prepare(weights), resampler(y_hat.shape[2], y_hat.shape[3], y_hat.device), bool(multiscale), ys,
+                              [float(w) for w in tw], frame)
 
 
 def _check(x: torch.Tensor, name: str) -> torch.Tensor:
@@ -510,4 +598,4 @@ def id_features(x: torch.Tensor, weights, multiscale: bool = True):
 
 
 __all__ = ["IdNet", "PreparedIdNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes", "axis_matrix", "resampler",
-           "id_features", "features_112", "id_loss", "id_loss_terms", "units"]
+           "id_features", "features_112", "id_loss", "id_loss_terms", "units", "target_features", "id_loss_multi", "heads_multi"]

@@ -21,6 +21,7 @@ import torch
 
 from ._lib import lib
 from .ops import _Prepared, _c, _p, _stream
+from .ops_multi import call_args, check_frame, check_targets, target_rows
 
 LAYERS = (0, 3, 6, 8, 10)                 # AlexNet ``features`` indices of the five convolutions
 CHANNELS = (64, 192, 384, 256, 256)
@@ -239,6 +240,84 @@ class _LpipsScale(torch.autograd.Function):
         return gx, gy, None, None, None
 
 
+class _LpipsScaleMulti(torch.autograd.Function):
+    """sum_j tw[j] LPIPS(boxmean_f(x), target j) from the targets' cached taps; the gradient with respect to ``x`` only."""
+
+    @staticmethod
+    def forward(ctx, x, P, lins, f, ys, tw, frame):
+        fx = _features(x, P, f)
+        bs = x.shape[0]
+        counts = [bs * ((a.shape[2] * a.shape[3] + 31) // 32) for a in fx]
+        partial = torch.empty((sum(counts),), dtype=torch.float32, device=x.device)
+        off = 0
+        for t, (a, lin, n) in enumerate(zip(fx, lins, counts)):
+            hw = a.shape[2] * a.shape[3]
+            lib().call("e4s_lpips_head_multi", _p(partial[off:]), _p(a), *call_args([y[t] for y in ys], tw, frame, bs), _p(lin), bs, a.shape[1], hw,
+                       1.0 / (bs * hw), _stream())
+            off += n
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        lib().call("e4s_lpips_sum", _p(loss), _p(partial), off, _stream())
+        ctx.P, ctx.lins, ctx.f, ctx.shape, ctx.ys, ctx.tw, ctx.frame = P, lins, f, tuple(x.shape), ys, tw, frame
+        ctx.save_for_backward(*fx)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None, None
+        fx = list(ctx.saved_tensors)
+        gout = _c(gout.reshape(1), "grad_output")
+        gxt = [torch.empty_like(a) for a in fx]
+        for t, a in enumerate(fx):
+            hw = a.shape[2] * a.shape[3]
+            lib().call("e4s_lpips_head_multi_bwd", _p(gxt[t]), _p(a), *call_args([y[t] for y in ctx.ys], ctx.tw, ctx.frame, a.shape[0]), _p(ctx.lins[t]),
+                       _p(gout), a.shape[0], a.shape[1], hw, 1.0 / (a.shape[0] * hw), _stream())
+        return _input_grad(fx, gxt, ctx.P, ctx.f, ctx.shape), None, None, None, None, None, None
+
+
+def target_features(images: torch.Tensor, weights, scales: int = 3):
+    """The raw AlexNet taps of ``images`` ``[n, 3, H, W]`` at the ``scales`` box-mean factors 1, 2, 4 — what ``lpips_multiscale_multi`` reads for a target:
+    a flat list, scale-major (five taps per scale), of tensors ``[n, C, h, w]``.  Computed a frame at a time; no gradient."""
+    check_loaded(weights)
+    if not 1 <= scales <= 3:
+        raise ValueError(f"scales must be 1, 2 or 3, got {scales}")
+    for i in range(scales):
+        _check(images, "images", 1 << i)
+    P = prepare(weights)
+    with torch.no_grad():
+        return target_rows(lambda x: [t for i in range(scales) for t in _features(x.contiguous(), P, 1 << i)], images.detach())
+
+
+def lpips_multiscale_multi(x: torch.Tensor, targets, tw, weights, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sum_j tw[j] * lpips_multiscale(x, y_j)`` (0-d, differentiable in ``x`` only) with one AlexNet forward pass and input gradient of ``x``:
+    ``targets[j] = target_features(y_j, weights)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
+    check_loaded(weights)
+    x = _check(x, "x", 1)
+    scales = len(targets[0]) // 5 if targets else 0
+    if not 1 <= scales <= 3 or any(len(t) != 5 * scales for t in targets):
+        raise ValueError("targets: each must be a target_features list of 5, 10 or 15 taps")
+    for i in range(scales):
+        _check(x, "x", 1 << i)
+    frame = check_frame(frame, x.device)
+    P, lins = prepare(weights), lin_weights(weights)
+    loss = None
+    for i in range(scales):
+        f = 1 << i
+        shapes = [(x.shape[0], c, side_h, side_w) for c, side_h, side_w in _tap_shapes(x.shape[2] // f, x.shape[3] // f)]
+        ys = check_targets([torch.empty(s, device="meta") for s in shapes], [t[5 * i:5 * i + 5] for t in targets], tw, frame, "lpips_multiscale_multi")
+        t = _LpipsScaleMulti.apply(x, P, lins, f, ys, [float(w) for w in tw], frame)
+        loss = t if loss is None else loss + t
+    return loss
+
+
+def _tap_shapes(h: int, w: int):
+    """(C, h, w) of the five taps of an h x w (scaled) image."""
+    h1, w1 = _conv_out(h, 0), _conv_out(w, 0)
+    h2, w2 = _pool_out(h1), _pool_out(w1)
+    h3, w3 = _pool_out(h2), _pool_out(w2)
+    return [(CHANNELS[0], h1, w1), (CHANNELS[1], h2, w2), (CHANNELS[2], h3, w3), (CHANNELS[3], h3, w3), (CHANNELS[4], h3, w3)]
+
+
 def features(x: torch.Tensor, weights, factor: int = 1):
     """The five normalised AlexNet taps of ``x`` (``BaseNet.forward``; no gradient).  ``weights``: a ``BaseNet`` / ``LPIPS`` module or mapping."""
     check_loaded(weights)
@@ -288,4 +367,5 @@ def lpips_multiscale(x: torch.Tensor, y: torch.Tensor, weights, scales: int = 3,
     return loss
 
 
-__all__ = ["PreparedLpips", "check_loaded", "weights_key", "weight_tensors", "prepare", "lin_weights", "features", "lpips", "lpips_multiscale", "state_dict_keys", "LAYERS", "CHANNELS"]
+__all__ = ["PreparedLpips", "check_loaded", "weights_key", "weight_tensors", "prepare", "lin_weights", "features", "lpips", "lpips_multiscale", "state_dict_keys", "LAYERS", "CHANNELS",
+           "target_features", "lpips_multiscale_multi"]

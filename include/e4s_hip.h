@@ -682,6 +682,37 @@ E4S_API int e4s_fp_maxpool2(float* out, const float* a, int planes, int h, int w
 E4S_API int e4s_fp_tap_bwd(float* g, const float* fx, const float* fy, const float* stats, const float* gout, const float* gpool, int bs, int C, int h,
                            int w, float scale, void* stream);
 
+/* Multi-target loss heads (csrc/lpips.hip, idloss.hip, fploss.hip, pixloss.hip): one reconstruction against k (1 .. 4) targets, target j weighted by tw[j]
+ * — the driven and the recoloured frame of the PTI objective share the reconstruction's forward pass and input gradient.  ys [k] and tw [k] are HOST
+ * arrays (device pointers, weights), read at the call.  Target j of sample b starts at ys[j] + f * fstride + b * (per-sample size) with f = *frame (a
+ * device int32, e.g. written before a graph replay to pick a frame of a clip-wide feature cache, clamped to [0, nframes)), or f = 0 when frame is NULL.
+ *   e4s_lpips_head_multi      : partial [bs][ceil(hw / 32)] as e4s_lpips_head, the per-pixel distance summed over the targets with their weights
+ *   e4s_lpips_head_multi_bwd  : gx [bs][c][hw] = d/dfx of that sum times gout[0] (no target gradient)
+ *   e4s_id_head_partial_multi : part [bs][ceil(D / 8192)][9] = block sums of fx^2, then (fy_j^2, fx fy_j) per target (unused targets 0)
+ *   e4s_id_head_sum_multi     : stats [ntap][bs][9] = |x|, then (|y_j|, cos_j); loss[0] = sum_t sum_j tw[j] mean_b (1 - cos_j)
+ *   e4s_id_head_bwd_multi     : gx [bs][D] (+)= -gout[0] scale sum_j tw[j] (fy_j / |y_j| - cos_j fx / |x|) / |x|
+ *   e4s_fp_tap_bwd_multi      : e4s_fp_tap_bwd with that summed head gradient; stats [bs][9] of the tap (targets 8-byte aligned, fstride even)
+ *   e4s_pix_mse_multi         : partial [bs C][ceil(hw / 4096)], summing (e4s_lpips_sum) to sum_j tw[j] mean((x fg - y_j)^2); x, y_j [bs][C][hw], the
+ *                               targets already weighted (y fg), fg [bs][1][hw] or NULL (1); bs C <= 65535
+ *   e4s_pix_mse_multi_bwd     : gx [bs][C][hw] = gout[0] 2 / (bs C hw) sum_j tw[j] (x fg - y_j) fg
+ * No float atomics: the same inputs give the same bits; k = 1 with weight 1 gives the single-target heads' values. */
+E4S_API int e4s_lpips_head_multi(float* partial, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                 const float* lin, int bs, int c, int hw, float scale, void* stream);
+E4S_API int e4s_lpips_head_multi_bwd(float* gx, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                     const float* lin, const float* gout, int bs, int c, int hw, float scale, void* stream);
+E4S_API int e4s_id_head_partial_multi(float* part, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                      int bs, int64_t D, void* stream);
+E4S_API int e4s_id_head_sum_multi(float* loss, float* stats, const float* part, const float* tw, int k, int bs, int ntap, int nb0, int nb1, int nb2,
+                                  int nb3, int nb4, void* stream);
+E4S_API int e4s_id_head_bwd_multi(float* gx, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                  const float* stats, const float* gout, int bs, int64_t D, float scale, int accumulate, void* stream);
+E4S_API int e4s_fp_tap_bwd_multi(float* g, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
+                                 const float* stats, const float* gout, const float* gpool, int bs, int C, int h, int w, float scale, void* stream);
+E4S_API int e4s_pix_mse_multi(float* partial, const float* x, const float* fg, const float* const* ys, const float* tw, int k, const int* frame,
+                              int64_t fstride, int nframes, int bs, int C, int64_t hw, void* stream);
+E4S_API int e4s_pix_mse_multi_bwd(float* gx, const float* x, const float* fg, const float* const* ys, const float* tw, int k, const int* frame,
+                                  int64_t fstride, int nframes, const float* gout, int bs, int C, int64_t hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
