@@ -4,6 +4,7 @@ Pillow's bicubic resize and the multi-band blend (``csrc/maskops.hip``).  Refere
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional, Sequence
 
@@ -306,4 +307,127 @@ def blending(full_img_u8: torch.Tensor, ori_img: torch.Tensor, mask: torch.Tenso
     return laplacian_blend(full_img_u8, ori_img, mask, 10).clamp_(0, 255).to(torch.uint8)
 
 
-__all__ = ['_labels_u8', 'swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_resample_tables', '_pil_bicubic_tables', '_pil_lanczos_tables', 'pil_resize', 'crop_align', 'paste_into_frames', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending']
+# ------------------------------------------------------------------------------------ f6: the image caller's soft paste masks and uint8 blends (softmask.hip)
+_soft_weights = {}
+_class_luts = {}
+FACIAL_CLASSES = (1, 2, 3, 5, 6, 8, 9)        # Trick.get_facial_mask_from_seg19 (utils/paste_back_tricks.py:191): lips, brows, eyes, nose, skin, neck, teeth
+
+
+def _soft_erosion_weights(kernel_size: int, device) -> torch.Tensor:
+    """``SoftErosion.__init__``'s ``weight`` buffer (utils/paste_back_tricks.py:20-30), float32 on the host with its own expressions, transposed for
+    the kernel.  Built once per (size, device), so that no host-to-device copy happens inside a hipGraph capture."""
+    key = (int(kernel_size), str(device))
+    wt = _soft_weights.get(key)
+    if wt is None:
+        r = kernel_size // 2
+        yy, xx = torch.meshgrid(torch.arange(0., kernel_size), torch.arange(0., kernel_size), indexing="ij")
+        dist = torch.sqrt((xx - r) ** 2 + (yy - r) ** 2)          # float32 throughout, like the module
+        cone = dist.max() - dist
+        cone /= cone.sum()
+        wt = _soft_weights[key] = cone.t().contiguous().to(device)
+    return wt
+
+
+def _softer_checked(kernel_size, threshold, iterations):
+    if not isinstance(kernel_size, int) or kernel_size % 2 != 1 or not 3 <= kernel_size <= 33:
+        raise ValueError(f"soft_erosion: kernel_size is an odd integer in 3..33, got {kernel_size!r}")
+    if not isinstance(iterations, int) or iterations < 1:
+        raise ValueError(f"soft_erosion: iterations is an integer >= 1, got {iterations!r}")
+    return int(kernel_size), float(threshold), int(iterations)
+
+
+def soft_erosion(x: torch.Tensor, kernel_size: int = 15, threshold: float = 0.6, iterations: int = 1):
+    """``SoftErosion(kernel_size, threshold, iterations)(x)`` (utils/paste_back_tricks.py:17-43; MegaFS) for float32 ``[bs, C, H, W]`` on the device,
+    every plane on its own: ``iterations - 1`` times ``x = min(x, conv(x))`` with the cone-weighted ``kernel_size``² kernel, ``c = conv(x)``,
+    ``hard = c >= threshold``, ``soft = 1`` where hard, else ``c / max(c over the plane's not-hard pixels)``.  Returns ``(soft, hard)``: float32 and
+    bool ``[bs, C, H, W]``.  No host synchronisation (the reference's ``x[~mask].max()`` is one); capturable in a hipGraph.
+
+    The reference normalises by the maximum over the whole tensor but is only ever called with ``[1, 1, H, W]``; per plane is the batch form of that.
+    Two departures, both where the reference misbehaves: a plane in which EVERY pixel passes the threshold comes back as all ones (the reference
+    raises on ``max()`` of an empty tensor), and a plane whose below-threshold maximum is 0 — an all-zero mask, no face — gives 0 at those pixels
+    (the reference returns NaN from 0 / 0), so that a paste through such a mask leaves the target untouched."""
+    k, thr, it = _softer_checked(kernel_size, threshold, iterations)
+    x = _c(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"soft_erosion: expected a float32 [bs, C, H, W] tensor, got {tuple(x.shape)}")
+    bs, ch, h, w = x.shape
+    soft = torch.empty_like(x)
+    hard = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if x.numel() == 0:
+        return soft, hard.bool()
+    wt = _soft_erosion_weights(k, x.device)
+    nbytes = ctypes.c_int64(0)
+    lib().call("e4s_soft_erosion_scratch_bytes", bs * ch, h, w, it, ctypes.byref(nbytes))
+    scratch = torch.empty((nbytes.value // 4,), dtype=torch.float32, device=x.device)
+    lib().call("e4s_soft_erosion", _p(soft), _p(hard), _p(x), _p(wt), _p(scratch), bs * ch, h, w, k, thr, it, _stream())
+    return soft, hard.view(torch.bool)
+
+
+def soft_paste_masks(swapped: torch.Tensor, hole_mask: Optional[torch.Tensor] = None, radius: int = 2, kernel_size: int = 15, threshold: float = 0.6,
+                     iterations: int = 1):
+    """The paste masks of the two-image caller: the foreground of ``_past_back`` (Face_swap_with_two_imgs.py:178-182: everything but background /
+    ear-ring / hair / ear / neck, the hole forced to foreground) through ``_create_masks(..., 'expansion', radius)`` (:784-792), whose masks all pass
+    through ``SoftErosion``: ``full = soft(dilate)``, ``border = clip(full - soft(erode), 0, 1)``, ``content = soft(foreground)``.
+    ``swapped`` / ``hole_mask``: uint8 ``[bs, H, W]``.  Returns float32 ``[bs, 1, H, W]`` ``(content, border, full)``; the three planes of a face are
+    softened in one ``soft_erosion`` call."""
+    _softer_checked(kernel_size, threshold, iterations)
+    fg, hard_border, hard_full = foreground_masks(swapped, hole_mask, radius)
+    if fg.shape[0] == 0:
+        return fg, hard_border, hard_full
+    planes = torch.cat([hard_full, hard_full - hard_border, fg], dim=1)          # (dilated, eroded, foreground): binary, so eroded = full - border exactly
+    s, _ = soft_erosion(planes, kernel_size, threshold, iterations)
+    full = s[:, 0:1]
+    return s[:, 2:3].contiguous(), (full - s[:, 1:2]).clamp_(0, 1), full.contiguous()
+
+
+def _class_lut(classes, device) -> torch.Tensor:
+    key = (tuple(classes), str(device))
+    lut = _class_luts.get(key)
+    if lut is None:
+        t = torch.zeros(256, dtype=torch.float32)
+        t[list(classes)] = 1.0
+        lut = _class_luts[key] = t.to(device)
+    return lut
+
+
+def facial_mask12(labels: torch.Tensor, size=None, **softer) -> torch.Tensor:
+    """``Trick.get_facial_mask_from_seg19(labels, size, SoftErosion(**softer))`` (utils/paste_back_tricks.py:173-200) for uint8 ``[bs, H, W]`` 12-class
+    maps: 1 on lips, brows, eyes, nose, skin, neck and teeth, bilinear resize to ``size = (H', W')`` with ``align_corners=True``, then
+    ``soft_erosion`` (its defaults are the image caller's ``mask_softer``).  Returns float32 ``[bs, 1, H', W']``."""
+    unknown = set(softer) - {"kernel_size", "threshold", "iterations"}
+    if unknown:
+        raise TypeError(f"facial_mask12: unexpected arguments {sorted(unknown)}")
+    _softer_checked(softer.get("kernel_size", 15), softer.get("threshold", 0.6), softer.get("iterations", 1))
+    m = _labels_u8(labels, "labels")
+    mask = _class_lut(FACIAL_CLASSES, m.device)[m.long()][:, None]
+    if size is not None:
+        size = (int(size[0]), int(size[1]))
+        if mask.shape[0] and tuple(mask.shape[-2:]) != size:
+            from .ops_encode import bilinear_resize
+            mask = bilinear_resize(mask, size, align_corners=True)
+        elif not mask.shape[0]:
+            mask = mask.new_empty((0, 1) + size)
+    return soft_erosion(mask, **softer)[0]
+
+
+def blend_with_mask(bottom_u8: torch.Tensor, up_u8: torch.Tensor, mask: torch.Tensor, up_ratio: float = 1.0) -> torch.Tensor:
+    """``Trick.blending_two_images_with_mask(bottom, up, up_ratio, mask)`` (utils/paste_back_tricks.py:131-147) for uint8 ``[n, H, W, 3]`` frames and a
+    float32 ``[n, 1 or 3, H, W]`` mask, bit for bit with numpy: NaN in the mask counts as 0, ``m = mask * up_ratio``, ``trunc(bottom * (1 - m) + up * m)``
+    in float32 (clamped to [0, 255] first: the same wherever the reference is defined).  ``bottom = T, up = swapped, up_ratio = 1`` is the crop paste
+    ``np.uint8(swapped * content + T * (1 - content))`` of Face_swap_with_two_imgs.py:216-217."""
+    b = _frames_u8(bottom_u8, "bottom")
+    u = _frames_u8(up_u8, "up", b.shape)
+    m = _c(mask, "mask")
+    n, h, w, _ = b.shape
+    if m.dim() != 4 or m.shape[0] != n or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (h, w):
+        raise ValueError(f"blend_with_mask: expected a float32 [{n}, 1 or 3, {h}, {w}] mask, got {tuple(m.shape)}")
+    if not 0.0 <= float(up_ratio) <= 1.0:
+        raise ValueError(f"blend_with_mask: up_ratio {up_ratio} is not in [0, 1]")
+    out = torch.empty_like(b)
+    if n:
+        lib().call("e4s_blend_u8", _p(out), _p(b), _p(u), _p(m), float(up_ratio), n, h, w, m.shape[1], _stream())
+    return out
+
+
+__all__ = ['_labels_u8', 'swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_resample_tables', '_pil_bicubic_tables', '_pil_lanczos_tables', 'pil_resize', 'crop_align', 'paste_into_frames', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending',
+           'FACIAL_CLASSES', 'soft_erosion', 'soft_paste_masks', 'facial_mask12', 'blend_with_mask']

@@ -16,6 +16,9 @@ import torch
 from . import ops
 
 DEFAULT_COMP_INDICES = tuple(sorted(set(range(12)) - {0, 4, 11}))      # face_swap_video_pipeline.py:436: keep target background, hair, ear-rings
+# the two-image caller (Face_swap_with_two_imgs.py:469-472): it also keeps the target's eye glasses (10) and, with colour transfer, its neck and ears
+IMAGE_COMP_INDICES = tuple(sorted(set(range(12)) - {0, 10, 4, 11}))
+IMAGE_COMP_INDICES_CT = tuple(sorted(set(range(12)) - {0, 10, 4, 8, 7, 11}))
 
 
 TWO_STREAMS = True               # (module attributes; ``swap_batch`` also takes them as arguments)
@@ -53,13 +56,16 @@ def _selector(device, comp_indices, n):
 
 
 def mix_style_vectors(target_vec: torch.Tensor, driven_vec: torch.Tensor, comp_indices: Sequence[int] = DEFAULT_COMP_INDICES,
-                      below_face_interpolation: bool = False) -> torch.Tensor:
+                      below_face_interpolation: bool = False, ear_interpolation: bool = True) -> torch.Tensor:
     """``swap_comp_style_vector`` (swap_face_fine/swap_face_mask.py:336-367) for a batch, without host synchronisation:
     take the listed components from the driven face; ears (7) = mean of both; ear-rings (11) from the target; neck (8) optionally the
-    mean; teeth (9) from the target when the driven face has none (its style vector sums to exactly 0)."""
+    mean; teeth (9) from the target when the driven face has none (its style vector sums to exactly 0).
+    ``ear_interpolation=False``: the two-image caller's ``_swap_comp_style_vector`` (Face_swap_with_two_imgs.py:416-453), which does not
+    average the ears: they follow ``comp_indices`` like any other component."""
     sel = _selector(target_vec.device, comp_indices, target_vec.shape[1])
     out = torch.where(sel[None, :, None], driven_vec, target_vec)
-    out[:, 7, :] = (target_vec[:, 7, :] + driven_vec[:, 7, :]) / 2
+    if ear_interpolation:
+        out[:, 7, :] = (target_vec[:, 7, :] + driven_vec[:, 7, :]) / 2
     out[:, 11, :] = target_vec[:, 11, :]
     if below_face_interpolation:
         out[:, 8, :] = (target_vec[:, 8, :] + driven_vec[:, 8, :]) / 2
@@ -71,16 +77,18 @@ def mix_style_vectors(target_vec: torch.Tensor, driven_vec: torch.Tensor, comp_i
 @torch.no_grad()
 def swap_batch(net, parser, driven: torch.Tensor, target: torch.Tensor, comp_indices: Sequence[int] = DEFAULT_COMP_INDICES,
                randomize_noise: bool = False, to_uint8: bool = True, timings: Optional[dict] = None, mask_surgery: bool = False,
-               paste_radius: int = 5, two_streams: Optional[bool] = None, batched: Optional[bool] = None, guard: Optional[list] = None):
+               paste_radius: int = 5, two_streams: Optional[bool] = None, batched: Optional[bool] = None, guard: Optional[list] = None,
+               ear_interpolation: bool = True):
     """``driven`` / ``target``: ``[bs, 3, 1024, 1024]`` in [-1, 1] on the device.  Returns uint8 ``[bs, 1024, 1024, 3]`` frames
     (or the float image) and the 12-class region maps the synthesis used; with ``mask_surgery`` a third value
     ``{"hole_mask", "hole_map", "lines", "content", "border", "full"}`` (the reference's paste-back inputs, :456-463).
+    ``ear_interpolation`` goes to ``mix_style_vectors``.
 
     f16 range (``ops.MxGuard``): parser, encoder and the masked synthesis layers run in f16-based split arithmetic.  The batch is bracketed by ONE
     guard; by default the call waits for it at its end and re-runs the whole batch in the split-bf16 arithmetic if a value left the f16 range
     (``ops.mx_fallbacks`` counts those).  Callers that keep several batches in flight pass ``guard=[]``: the armed guard is appended instead of
     awaited, and the caller checks ``guard[-1].tripped()`` where it synchronises anyway, repeating the call under ``with ops.mx_exact():``."""
-    args = (net, parser, driven, target, comp_indices, randomize_noise, to_uint8, timings, mask_surgery, paste_radius, two_streams, batched)
+    args = (net, parser, driven, target, comp_indices, randomize_noise, to_uint8, timings, mask_surgery, paste_radius, two_streams, batched, ear_interpolation)
     if guard is None and ops.mx_guard_owned():        # a caller up the stack brackets this batch with its own guard (runner.run_clip_streamed, bench.py)
         return _swap_batch_once(*args)
     with ops.mx_guard_scope() as g:
@@ -92,11 +100,13 @@ def swap_batch(net, parser, driven: torch.Tensor, target: torch.Tensor, comp_ind
     if g.tripped():
         ops.mx_fallbacks += 1
         with ops.mx_exact():        # (the exact re-run leaves the caller's `timings` alone: its stage marks belong to the first pass)
-            out = _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise, to_uint8, None, mask_surgery, paste_radius, two_streams, batched)
+            out = _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise, to_uint8, None, mask_surgery, paste_radius, two_streams, batched,
+                                   ear_interpolation)
     return out
 
 
-def _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise, to_uint8, timings, mask_surgery, paste_radius, two_streams, batched):
+def _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise, to_uint8, timings, mask_surgery, paste_radius, two_streams, batched,
+                     ear_interpolation=True):
     def mark(name):
         if timings is not None:
             ev = torch.cuda.Event(enable_timing=True)
@@ -181,7 +191,7 @@ def _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise,
         vec_d, _ = net.get_style_vectors(driven, lab_d)
         vec_t, _ = net.get_style_vectors(target, lab_t)
         mark("encode_x2")
-    codes = net.cal_style_codes(mix_style_vectors(vec_t, vec_d, comp_indices))
+    codes = net.cal_style_codes(mix_style_vectors(vec_t, vec_d, comp_indices, ear_interpolation=ear_interpolation))
     mark("mix+mlps")
     extra = None
     lab = lab_t
@@ -222,7 +232,6 @@ def paste_back(swapped_u8: torch.Tensor, target_u8: torch.Tensor, content: torch
     return ops.blending(t, pasted, bm).permute(0, 2, 3, 1).contiguous()
 
 
-
 @torch.no_grad()
 def swap_frames(net, parser, driven: torch.Tensor, target_frames_u8: torch.Tensor, plan, **swap_batch_kwargs) -> torch.Tensor:
     """The video pipeline's per-frame loop with ``use_crop=True`` (face_swap_video_pipeline.py:181-210, 404-483) for a batch of video frames:
@@ -242,3 +251,86 @@ def swap_frames(net, parser, driven: torch.Tensor, target_frames_u8: torch.Tenso
     swapped, _, extra = swap_batch(net, parser, driven, target, mask_surgery=True, **swap_batch_kwargs)
     blended = paste_back(swapped, crops, extra["content"], extra["border"])
     return ops.paste_into_frames(blended, target_frames_u8, plan)
+
+
+# ------------------------------------------------------------------------------------ f6: the two-image caller (Face_swap_with_two_imgs.py)
+def _crops_checked(name, *frames):
+    a = frames[0]
+    for f in frames:
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or f.shape != a.shape:
+            raise ValueError(f"{name}: the frames are uint8 [bs, H, W, 3] of one shape")
+
+
+@torch.no_grad()
+def paste_back_soft(swapped_u8: torch.Tensor, target_u8: torch.Tensor, labels: torch.Tensor, hole_mask: Optional[torch.Tensor] = None,
+                    radius: int = 2) -> torch.Tensor:
+    """The image caller's ``_past_back`` (Face_swap_with_two_imgs.py:159-219) up to its multi-band blend, on the device:
+
+        content, border = soft_paste_masks(labels, hole_mask, radius)    (:177-191; every mask through SoftErosion, radius 2 where the video uses 5)
+        content, border -> bilinear to the frame size (align_corners=False)                                                      (:202-206)
+        pasted = uint8(swapped * content + T * (1 - content))            (:216-217; truncated to 8 bits, no 512 x 512 Pillow round trip)
+        out    = blending(T, pasted, mask=border)                        (:218-219)
+
+    ``swapped_u8`` / ``target_u8``: uint8 ``[bs, 1024, 1024, 3]``; ``labels`` / ``hole_mask``: uint8 ``[bs, h, w]`` (the swapped map and hole of
+    ``swap_batch(..., mask_surgery=True)``).  Returns uint8 ``[bs, 1024, 1024, 3]``."""
+    _crops_checked("paste_back_soft", swapped_u8, target_u8)
+    bs, h, w, _ = swapped_u8.shape
+    content, border, _ = ops.soft_paste_masks(labels, hole_mask, radius)
+    if content.shape[0] != bs:
+        raise ValueError(f"paste_back_soft: {content.shape[0]} label maps for {bs} frames")
+    if bs == 0:
+        return torch.empty_like(target_u8)
+    cm = ops.bilinear_resize(content, (h, w), align_corners=False)
+    bm = ops.bilinear_resize(border, (h, w), align_corners=False)
+    pasted = ops.blend_with_mask(target_u8, swapped_u8, cm, 1.0)
+    t = target_u8.permute(0, 3, 1, 2).contiguous()
+    return ops.blending(t, pasted.permute(0, 3, 1, 2).float(), bm).permute(0, 2, 3, 1).contiguous()
+
+
+@torch.no_grad()
+def color_blend(swapped_u8: torch.Tensor, recolored_u8: torch.Tensor, labels: torch.Tensor, edge: Optional[torch.Tensor] = None,
+                up_ratio: float = 0.75) -> torch.Tensor:
+    """Step 2 of ``face_swap_pipeline`` (Face_swap_with_two_imgs.py:912-924): the colour-transferred face blended over the swapped one,
+
+        mask = clip(facial_mask12(labels, frame size) - edge, 0, 1);   out = blend_with_mask(swapped, recolored, mask, up_ratio)
+
+    ``edge``: the caller's ``Trick.get_edge(swapped)`` image scaled to [0, 1] as a float ``[bs, H, W]`` or ``[bs, 1, H, W]`` tensor (the edge
+    detector is cv2 code and stays with the caller), or None for no high-frequency cut-out."""
+    _crops_checked("color_blend", swapped_u8, recolored_u8)
+    bs, h, w, _ = swapped_u8.shape
+    mask = ops.facial_mask12(labels, (h, w))
+    if edge is not None:
+        if not isinstance(edge, torch.Tensor) or not edge.is_floating_point() or edge.numel() != bs * h * w:
+            raise ValueError(f"color_blend: edge is a float [{bs}, 1, {h}, {w}] tensor in [0, 1]")
+        mask = (mask - edge.to(mask.dtype).reshape(mask.shape)).clamp_(0, 1)
+    return ops.blend_with_mask(swapped_u8, recolored_u8, mask, up_ratio)
+
+
+@torch.no_grad()
+def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tensor, plan, recolor_fn=None, **swap_batch_kwargs) -> torch.Tensor:
+    """The two-image caller's chain (``FaceSwap.face_swap_pipeline``, Face_swap_with_two_imgs.py:796-963, without its inpainting / Blender / GPEN
+    networks) for a batch of target images, all on the device:
+
+        crop_align -> frames_to_tensor -> swap_batch(mask_surgery=True, ear_interpolation=False, comp_indices=IMAGE_COMP_INDICES[_CT])
+        [-> color_blend(swapped, recolor_fn(swapped, crops), labels)]                  (:909-924, when ``recolor_fn`` is given)
+        -> paste_back_soft(swapped map, hole)                                          (:938)
+        -> paste_back_soft(all-skin rectangle map, no hole)                            (:883, :958)
+        -> paste_into_frames
+
+    ``driven``: ``[n, 3, 1024, 1024]`` in [-1, 1]; ``target_images_u8``: uint8 ``[n, H, W, 3]`` on the device; ``plan``: their ``align.CropPlan``;
+    ``recolor_fn(swapped_u8, crops_u8) -> uint8 [n, 1024, 1024, 3]``: the caller's colour transfer.  Returns uint8 ``[n, H, W, 3]``, every pixel
+    outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch``, with the guard and stream behaviour of ``swap_frames``."""
+    for k in ("mask_surgery", "to_uint8", "ear_interpolation", "comp_indices"):
+        if k in swap_batch_kwargs:
+            raise TypeError(f"swap_images: {k} is fixed (the image caller's style mix, and the paste needs the uint8 face and the mask-surgery hole)")
+    crops = ops.crop_align(target_images_u8, plan)
+    target = ops.frames_to_tensor(crops)
+    # (mask_surgery=True also computes the video caller's hard radius-5 paste masks, which this path does not use: one byte-wise launch per batch,
+    # < 0.1 ms, accepted rather than giving swap_batch another switch)
+    swapped, lab, extra = swap_batch(net, parser, driven, target, mask_surgery=True, ear_interpolation=False,
+                                     comp_indices=IMAGE_COMP_INDICES_CT if recolor_fn is not None else IMAGE_COMP_INDICES, **swap_batch_kwargs)
+    if recolor_fn is not None:
+        swapped = color_blend(swapped, recolor_fn(swapped, crops), lab)
+    pasted = paste_back_soft(swapped, crops, lab, extra["hole_mask"])
+    pasted = paste_back_soft(pasted, crops, torch.full_like(lab, 6), None)
+    return ops.paste_into_frames(pasted, target_images_u8, plan)

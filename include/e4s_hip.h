@@ -512,6 +512,27 @@ E4S_API int e4s_erode_labels(uint8_t* out, const uint8_t* labels, int bs, int h,
 E4S_API int e4s_foreground_masks(float* content, float* border, float* full, const uint8_t* swapped, const uint8_t* hole_mask,
                                  int bs, int h, int w, int radius, void* stream);
 
+/* ---- f6: the two-image caller's paste-back (Face_swap_with_two_imgs.py:159-219, 775-794, 909-924): soft paste masks and uint8 blends ------
+ * e4s_soft_erosion: SoftErosion.forward (utils/paste_back_tricks.py:17-43) for `planes` independent float32 planes [planes, h, w]:
+ *   (iterations - 1) x  x = min(x, conv(x));  c = conv(x)  (kernel_size^2 cone weights, zero padding kernel_size / 2);
+ *   hard = c >= threshold (uint8 {0,1}; may be NULL);  soft = 1 where hard, else c / max(c over the not-hard pixels of THIS plane).
+ *   weights_t : float32 [kernel_size, kernel_size], the module's `weight` buffer TRANSPOSED (weights_t[kx][ky]), built on the host exactly as the
+ *               constructor builds it ((dist.max() - dist) / sum in float32)
+ *   scratch   : e4s_soft_erosion_scratch_bytes(planes, h, w, iterations) bytes: the per-workgroup partial maxima and, for iterations > 1, the
+ *               intermediate planes.  soft must not alias x.
+ *   kernel_size odd, 3..33; iterations >= 1.  No host synchronisation (capturable); the maximum is reduced in a fixed order and holds for any finite input.
+ *   Where the reference misbehaves: a plane in which every pixel passes the threshold is all ones (the reference raises on max() of an empty
+ *   tensor); a plane whose below-threshold maximum is 0 (an all-zero mask) gives 0 at those pixels (the reference: 0 / 0 = NaN).
+ * e4s_blend_u8: Trick.blending_two_images_with_mask (:131-147): out = trunc(clamp(bottom * (1 - m) + up * m, 0, 255)), m = nan_to_0(mask) * up_ratio,
+ *   in float32 with every product and sum rounded on its own (numpy's arithmetic).  bottom, up, out: uint8 [n, h, w, 3]; mask: float32
+ *   [n, mask_channels, h, w], mask_channels 1 or 3; up_ratio in [0, 1].  With bottom = T, up = swapped, up_ratio = 1 it is the crop paste
+ *   np.uint8(swapped * content + T * (1 - content)) of Face_swap_with_two_imgs.py:216-217. */
+E4S_API int e4s_soft_erosion_scratch_bytes(int planes, int h, int w, int iterations, int64_t* bytes);
+E4S_API int e4s_soft_erosion(float* soft, uint8_t* hard, const float* x, const float* weights_t, float* scratch, int planes, int h, int w,
+                             int kernel_size, float threshold, int iterations, void* stream);
+E4S_API int e4s_blend_u8(uint8_t* out, const uint8_t* bottom, const uint8_t* up, const float* mask, float up_ratio, int n, int h, int w,
+                         int mask_channels, void* stream);
+
 /* ---- f5: crop-align of a video frame and the paste back into it (utils/alignment.py:101-147 crop_image; face_swap_video_pipeline.py:181-210,
  * 474-483).  Pillow's Image.transform(..., BILINEAR) on uint8 RGB, bit for bit (src/libImaging/Geometry.c): output pixel (x, y) is sampled at
  * (x + 0.5, y + 0.5) mapped through the transform in plain double arithmetic; a sample outside the source window is not taken; otherwise the
