@@ -440,12 +440,14 @@ class _Prepared:
 
     @staticmethod
     def _tensors(payload):
-        out = []
-        for v in payload:
-            for t in (v if isinstance(v, (tuple, list)) else (v,)):
-                if isinstance(t, torch.Tensor):
-                    out.append(t)
-        return out
+        """Every tensor of ``payload``, through any nesting of tuples, lists and dicts, in order."""
+        if isinstance(payload, torch.Tensor):
+            return [payload]
+        if isinstance(payload, dict):
+            payload = tuple(payload.values())
+        if isinstance(payload, (tuple, list)):
+            return [t for v in payload for t in _Prepared._tensors(v)]
+        return []
 
 
 class PreparedWeights(_Prepared):

@@ -18,24 +18,23 @@ on the HIP kernels: forward and gradient with respect to the reconstruction, for
 ``unet``-shaped module (``FaceParsingNet``, or the drop-in ``criteria.face_parsing.face_parsing_loss.FaceParsingLoss`` / its ``G``) or a mapping with
 at least the encoder's keys (``state_dict_keys()`` lists all 136; the decoder's ``up_concat*`` / ``final`` are not used by the loss).  They are
 frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the reference puts the network in eval mode); a module left in
-training mode is refused.
+training mode is refused.  The weight cache, BN folding, split-bf16 weight preparation and convolution wrapper, the resampler, the heads and
+the multi-target helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_id``.
 """
 from __future__ import annotations
 
 import functools
-import weakref
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from typing import Optional
 
-from . import ops_id
+from . import lossnet
 from ._lib import lib
+from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_sb, cos_heads, cos_heads_multi, pool_matrix, prep_dgrad, prep_fwd,
+                      relu_mask, target_rows, weights_key)
 from .ops import _Prepared, _c, _p, _stream
-from .ops_id import _bands, _bn, _heads, _pool_matrix, _prep_dgrad, _prep_fwd, weights_key
-from .ops_multi import call_args, check_frame, check_targets, target_rows
 
 SIDE = 512                                   # FaceParsingLoss.face_pool: AdaptiveAvgPool2d((512, 512)) unless x.shape[2] == 512
 FILTERS = (16, 32, 64, 128, 256)             # unet(feature_scale=4): [64, 128, 256, 512, 1024] / 4
@@ -151,7 +150,7 @@ def weight_tensors(weights):
 
 def _fold(sd, p):
     """Conv ``p.0`` + eval BatchNorm ``p.1`` as float64 (scale, shift): BN(conv(x) + b) = conv(x) * scale + shift."""
-    s, t = _bn(sd, p + ".1")
+    s, t = bn_fold(sd, p + ".1")
     return s, t + sd[p + ".0.bias"].double() * s
 
 
@@ -187,42 +186,24 @@ class PreparedFaceParsingNet(_Prepared):
                 w1, w2 = sd[name + ".conv1.0.weight"], sd[name + ".conv2.0.weight"]
                 s1, t1 = _fold(sd, name + ".conv1")
                 s2, t2 = _fold(sd, name + ".conv2")
-                fwd1 = _prep_fp32(w1, s1, t1) if cin < 16 else _prep_fwd(w1, s1, t1)
-                blocks.append(dict(cin=cin, cout=cout, fwd1=fwd1, fwd2=_prep_fwd(w2, s2, t2), bwd1=_prep_dgrad(w1, out_scale=s1),
-                                   bwd2=_prep_dgrad(w2, out_scale=s2)))
+                fwd1 = _prep_fp32(w1, s1, t1) if cin < 16 else prep_fwd(w1, s1, t1)
+                blocks.append(dict(cin=cin, cout=cout, fwd1=fwd1, fwd2=prep_fwd(w2, s2, t2), bwd1=prep_dgrad(w1, out_scale=s1),
+                                   bwd2=prep_dgrad(w2, out_scale=s2)))
         return self._publish(key, tuple(blocks))
-
-
-_CACHES: "weakref.WeakKeyDictionary[nn.Module, PreparedFaceParsingNet]" = weakref.WeakKeyDictionary()
 
 
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    if isinstance(weights, nn.Module):
-        cache = _CACHES.get(weights)
-        if cache is None:
-            cache = _CACHES[weights] = PreparedFaceParsingNet()
-        return cache.get(weights)
-    return PreparedFaceParsingNet().get(weights)
+    return lossnet.prepare(PreparedFaceParsingNet, weights)
 
 
 # ------------------------------------------------------------------------------------------------ input pooling
-_RESAMPLERS = {}
-
-
 def resampler(h: int, w: int, device):
-    """Device copies (ay, ax, row bands y / x, column bands y / x) of AdaptiveAvgPool2d((512, 512)) on an h x w image, or None when h is 512 (the
-    reference then runs the network on the image as it is).  Cached."""
+    """AdaptiveAvgPool2d((512, 512)) on an h x w image (a cached ``lossnet.Resampler``), or None when h is 512 (the reference then runs the network
+    on the image as it is)."""
     if h == SIDE:
         return None
-    key = (h, w, str(device))
-    hit = _RESAMPLERS.get(key)
-    if hit is None:
-        ay, ax = _pool_matrix(h, SIDE), _pool_matrix(w, SIDE)
-        (ry, cy), (rx, cx) = _bands(ay), _bands(ax)
-        T = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)   # noqa: E731
-        hit = _RESAMPLERS[key] = (T(ay), T(ax), T(ry, torch.int32), T(rx, torch.int32), T(cy, torch.int32), T(cx, torch.int32))
-    return hit
+    return lossnet.resampler(h, w, SIDE, device, lambda: (pool_matrix(h, SIDE), pool_matrix(w, SIDE)))
 
 
 def _network_input(xs, R):
@@ -235,23 +216,20 @@ def _network_input(xs, R):
         if R is None:
             dst.copy_(x)
         else:
-            lib().call("e4s_id_resample", _p(dst), _p(x), _p(R[0]), _p(R[1]), _p(R[2]), _p(R[3]), bs * c, h, w, SIDE, _stream())
+            R.apply(x, out=dst)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ forward
 def _conv_relu(x, B, which):
-    n, cin, h, w = x.shape
-    cout = B["cout"]
-    out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
     if which == 1 and B["cin"] < 16:
+        n, cin, h, w = x.shape
+        cout = B["cout"]
+        out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
         wt, bias = B["fwd1"]
         lib().call("e4s_conv2d", _p(out), _p(x), None, cin, _p(wt), _p(bias), None, None, None, None, 1, n, cin, cout, h, w, 3, 1, 1, _stream())
-    else:
-        slabs, bias = B["fwd1"] if which == 1 else B["fwd2"]
-        lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(bias), None, None, None, None, 1,
-                   n, cin, cout, h, w, 3, 1, 1, _stream())
-    return out
+        return out
+    return conv_sb(x, *B["fwd1" if which == 1 else "fwd2"], k=3, relu=True)
 
 
 def _encoder(x, P):
@@ -269,14 +247,6 @@ def _encoder(x, P):
     return acts
 
 
-def _conv_dgrad(g, slabs, cout):
-    bs, cin, h, w = g.shape
-    out = torch.empty((bs, cout, h, w), dtype=torch.float32, device=g.device)
-    lib().call("e4s_conv2d_sb", _p(out), _p(g), None, cin, _p(slabs[0]), _p(slabs[1]), None, None, None, None, None, 0, bs, cin, cout, h, w, 3, 1, 1,
-               _stream())
-    return out
-
-
 def _input_grad(acts, P, stats, gout, bs, tap_bwd=None):
     """d loss / d (the network's input) of the first ``bs`` samples.  ``tap_bwd(gz, i, gpool)``: writes block i's tap gradient in place of the
     single-target one (the multi-target loss)."""
@@ -290,10 +260,15 @@ def _input_grad(acts, P, stats, gout, bs, tap_bwd=None):
             lib().call("e4s_fp_tap_bwd", _p(gz), _p(c2[:bs]), _p(c2[bs:]), _p(stats[i]), _p(gout), _p(g), bs, c, h, w, 1.0 / bs, _stream())
         else:
             tap_bwd(gz, i, g)
-        gc1 = _conv_dgrad(gz, B["bwd2"], c)
-        lib().call("e4s_lpips_relu_mask", _p(gc1), _p(c1), gc1.numel(), _stream())       # c1[:bs] is the head of c1: same offsets
-        g = _conv_dgrad(gc1, B["bwd1"], B["cin"])
+        gc1 = conv_sb(gz, B["bwd2"], k=3)
+        relu_mask(gc1, c1)                                             # c1[:bs] is the head of c1: same offsets
+        g = conv_sb(gc1, B["bwd1"], k=3)
     return g
+
+
+def _image_grad(g, R, shape):
+    """d loss / d image from ``g`` = d loss / d (the network's input)."""
+    return g if R is None else R.adjoint(g, shape)
 
 
 class _FpLoss(torch.autograd.Function):
@@ -305,7 +280,7 @@ class _FpLoss(torch.autograd.Function):
         acts = _encoder(_network_input((y_hat, y), R), P)
         fx = [c2[:bs].reshape(bs, -1) for _, c2 in acts]
         fy = [c2[bs:].reshape(bs, -1) for _, c2 in acts]
-        loss, sim, stats = _heads(fx, fy)
+        loss, sim, stats = cos_heads(fx, fy)
         ctx.P, ctx.R, ctx.shape = P, R, tuple(y_hat.shape)
         ctx.acts = [(c1[:bs], c2) for c1, c2 in acts]              # y's half of c2 is the head's fy; y's c1 is not needed
         ctx.save_for_backward(stats)
@@ -318,16 +293,11 @@ class _FpLoss(torch.autograd.Function):
         if gloss is None or not ctx.needs_input_grad[0]:
             return None, None, None, None
         (stats,) = ctx.saved_tensors
-        bs, c, h, w = ctx.shape
+        bs = ctx.shape[0]
         gout = _c(gloss.reshape(1), "grad_output")
         g = _input_grad(ctx.acts, ctx.P, stats, gout, bs)
         ctx.acts = None
-        R = ctx.R
-        if R is None:
-            return g, None, None, None
-        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
-        return gx, None, None, None
+        return _image_grad(g, ctx.R, ctx.shape), None, None, None
 
 
 class _FpLossMulti(torch.autograd.Function):
@@ -338,7 +308,7 @@ class _FpLossMulti(torch.autograd.Function):
         bs = y_hat.shape[0]
         acts = _encoder(_network_input((y_hat,), R), P)
         fx = [c2.reshape(bs, -1) for _, c2 in acts]
-        loss, stats = ops_id.heads_multi(fx, ys, tw, frame)
+        loss, stats = cos_heads_multi(fx, ys, tw, frame)
         ctx.P, ctx.R, ctx.shape, ctx.ys, ctx.tw, ctx.frame = P, R, tuple(y_hat.shape), ys, tw, frame
         ctx.acts = acts
         ctx.save_for_backward(stats)
@@ -349,7 +319,7 @@ class _FpLossMulti(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None
         (stats,) = ctx.saved_tensors
-        bs, c, h, w = ctx.shape
+        bs = ctx.shape[0]
         gout = _c(gloss.reshape(1), "grad_output")
         acts = ctx.acts
 
@@ -359,12 +329,7 @@ class _FpLossMulti(torch.autograd.Function):
                        _p(gpool), bs, c2.shape[1], c2.shape[2], c2.shape[3], 1.0 / bs, _stream())
         g = _input_grad(acts, ctx.P, stats, gout, bs, tap_bwd)
         ctx.acts = None
-        R = ctx.R
-        if R is None:
-            return g, None, None, None, None, None
-        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
-        return gx, None, None, None, None, None
+        return _image_grad(g, ctx.R, ctx.shape), None, None, None, None, None
 
 
 def target_features(images: torch.Tensor, weights):
@@ -392,9 +357,7 @@ def fp_loss_multi(y_hat: torch.Tensor, targets, tw, weights, frame: Optional[tor
 
 
 def _check(x: torch.Tensor, name: str) -> torch.Tensor:
-    x = _c(x, name)
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError(f"{name}: expected [bs >= 1, 3, H, W], got {tuple(x.shape)}")
+    x = check_image(x, name)
     if x.shape[2] == SIDE and x.shape[3] % 16:
         raise ValueError(f"{name}: a {SIDE}-high image is not pooled (FaceParsingLoss.extract_feats), so its width must be a multiple of 16 for the "
                          f"four 2 x 2 max pools; got {tuple(x.shape[2:])}")

@@ -14,13 +14,13 @@ kernels: forward and gradient with respect to the reconstruction, for the identi
 
 Weights are a ``Backbone``-shaped module (``IdNet``, or the drop-in ``criteria.id_loss.IDLoss`` / its ``facenet``) or a mapping with the
 reference's 397 keys (``state_dict_keys()``).  They are frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the
-reference puts the network in eval mode); a module left in training mode is refused.
+reference puts the network in eval mode); a module left in training mode is refused.  The weight cache, BN folding, split-bf16 weight preparation
+and convolution wrapper, the resampler, the heads and the multi-target helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_fp``.
 """
 from __future__ import annotations
 
 import functools
 import math
-import weakref
 
 import numpy as np
 import torch
@@ -28,16 +28,18 @@ import torch.nn as nn
 
 from typing import Optional
 
-from ._lib import lib, targets as _host_targets
-from .ops import _Prepared, _c, _p, _stream
-from .ops_multi import call_args, check_frame, check_targets, target_rows
+from . import lossnet
+from ._lib import lib
+from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_sb, cos_heads, cos_heads_multi as heads_multi, pool_matrix,
+                      prep_dgrad, prep_fwd, target_rows, weights_key)
 
-BN_EPS = 1e-5
+_pool_matrix, _bands = pool_matrix, lossnet.bands       # their names before they moved to lossnet, kept for callers outside the package
+from .ops import _Prepared, _c, _p, _stream
+
 SIDE = 112                                   # the network's input side (IDLoss.face_pool_2)
 CROP = ((35, 223), (32, 220))                # IDLoss.extract_feats: rows, columns of the 256 x 256 image
 STAGES = ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3))      # get_blocks(50): (in_channel, depth, units)
 TAP_UNITS = (2, 6, 20, 23)                   # Backbone.forward(multi_scale=True): body outputs that are features as well
-HEAD_BLOCK = 8192                            # e4s_id_head_partial: elements per partial sum
 
 
 def units():
@@ -136,50 +138,6 @@ def weight_tensors(weights):
         raise KeyError(f"ArcFace weights lack {e}: expected the keys of Backbone(112, 50, 'ir_se') (ops_id.state_dict_keys())") from None
 
 
-def weights_key(tensors) -> tuple:
-    """What the prepared copies are keyed on: storage and version of every tensor."""
-    return tuple((t.data_ptr(), t._version) for t in tensors)
-
-
-def _bn(sd, prefix):
-    """Eval-mode BatchNorm as float64 (scale, shift): y = x * scale + shift."""
-    g, b = sd[prefix + ".weight"].double(), sd[prefix + ".bias"].double()
-    mu, var = sd[prefix + ".running_mean"].double(), sd[prefix + ".running_var"].double()
-    s = g / torch.sqrt(var + BN_EPS)
-    return s, b - mu * s
-
-
-def _slabs(n: int, cout: int, cin: int, k: int, device):
-    return tuple(torch.empty(((cin + 15) // 16, k * k, 2, cout, 8), dtype=torch.int16, device=device) for _ in range(n))
-
-
-def _prep_fwd(w, bias_scale=None, bias_shift=None):
-    """Three-way split slabs of ``w * scale[co]`` (+ the shift as bias) for e4s_conv2d_sb3."""
-    cout, cin, k, _ = w.shape
-    if bias_scale is not None:
-        w = (w.double() * bias_scale[:, None, None, None]).float()
-    w = w.contiguous()
-    s3 = _slabs(3, cout, cin, k, w.device)
-    lib().call("e4s_conv_prep_weights_sb3", _p(s3[0]), _p(s3[1]), _p(s3[2]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, k, k, _stream())
-    bias = bias_shift.float().contiguous() if bias_shift is not None else None
-    return s3, bias
-
-
-def _prep_dgrad(w, out_scale=None, in_scale=None):
-    """Two-way split slabs of the data-gradient convolution of ``w [cout, cin, k, k]``: flipped, transposed, times ``out_scale[co]`` (a BN after
-    the conv) and ``in_scale[ci]`` (a BN before it)."""
-    wd = w.double()
-    if out_scale is not None:
-        wd = wd * out_scale[:, None, None, None]
-    if in_scale is not None:
-        wd = wd * in_scale[None, :, None, None]
-    wf = wd.flip(2, 3).transpose(0, 1).float().contiguous()            # [cin][cout][k][k]
-    cin, cout, k, _ = wf.shape
-    s2 = _slabs(2, cin, cout, k, w.device)
-    lib().call("e4s_conv_prep_weights_sb", _p(s2[0]), _p(s2[1]), None, _p(wf), None, None, None, None, 0.0, None, cin, cout, k, k, _stream())
-    return s2
-
-
 def _prep_tconv(w, out_scale):
     """Slabs of the stride-2 3x3 data gradient for e4s_modconv_tconv_sb: its transposed convolution with weight W_t [ci][co] = w[co][ci] * scale[co],
     pre-multiplied by sqrt(9 * depth) to cancel the kernel's 1 / sqrt(9 cin)."""
@@ -206,29 +164,29 @@ class PreparedIdNet(_Prepared):
             return hit
         sd = {k: _c(v.detach(), k) for k, v in _mapping(weights).items() if not k.endswith("num_batches_tracked")}
         with torch.no_grad():
-            s0, t0 = _bn(sd, "input_layer.1")
+            s0, t0 = bn_fold(sd, "input_layer.1")
             w0 = sd["input_layer.0.weight"]
-            inp = (_prep_fwd(w0, s0, t0), _prep_dgrad(w0, out_scale=s0), sd["input_layer.2.weight"])
+            inp = (prep_fwd(w0, s0, t0), prep_dgrad(w0, out_scale=s0), sd["input_layer.2.weight"])
             us = []
             for i, (cin, depth, stride) in enumerate(units()):
                 p = f"body.{i}."
-                s1, t1 = _bn(sd, p + "res_layer.0")
+                s1, t1 = bn_fold(sd, p + "res_layer.0")
                 w1, w2 = sd[p + "res_layer.1.weight"], sd[p + "res_layer.3.weight"]
-                s2, t2 = _bn(sd, p + "res_layer.4")
-                fwd1, _ = _prep_fwd(w1)
-                fwd2 = _prep_fwd(w2, s2, t2)
-                bwd2 = _prep_tconv(w2, s2) if stride == 2 else _prep_dgrad(w2, out_scale=s2)
+                s2, t2 = bn_fold(sd, p + "res_layer.4")
+                fwd1, _ = prep_fwd(w1)
+                fwd2 = prep_fwd(w2, s2, t2)
+                bwd2 = _prep_tconv(w2, s2) if stride == 2 else prep_dgrad(w2, out_scale=s2)
                 sc = None
                 if cin != depth:
-                    ssc, tsc = _bn(sd, p + "shortcut_layer.1")
+                    ssc, tsc = bn_fold(sd, p + "shortcut_layer.1")
                     wsc = sd[p + "shortcut_layer.0.weight"]
-                    sc = (_prep_fwd(wsc, ssc, tsc), _prep_dgrad(wsc, out_scale=ssc))
+                    sc = (prep_fwd(wsc, ssc, tsc), prep_dgrad(wsc, out_scale=ssc))
                 us.append(dict(cin=cin, depth=depth, stride=stride, bn_scale=s1.float().contiguous(), bn_shift=t1.float().contiguous(), fwd1=fwd1,
-                               bwd1=_prep_dgrad(w1, in_scale=s1), slope=sd[p + "res_layer.2.weight"], fwd2=fwd2, bwd2=bwd2,
+                               bwd1=prep_dgrad(w1, in_scale=s1), slope=sd[p + "res_layer.2.weight"], fwd2=fwd2, bwd2=bwd2,
                                fc1=sd[p + "res_layer.5.fc1.weight"].reshape(depth // 16, depth).contiguous(),
                                fc2=sd[p + "res_layer.5.fc2.weight"].reshape(depth, depth // 16).contiguous(), sc=sc))
-            so, to = _bn(sd, "output_layer.0")
-            s4, t4 = _bn(sd, "output_layer.4")
+            so, to = bn_fold(sd, "output_layer.0")
+            s4, t4 = bn_fold(sd, "output_layer.4")
             W = sd["output_layer.3.weight"].double()
             b = sd["output_layer.3.bias"].double()
             so, to = so.repeat_interleave(49), to.repeat_interleave(49)          # BN2d's channel c covers features c * 49 .. c * 49 + 48 (Flatten)
@@ -237,95 +195,29 @@ class PreparedIdNet(_Prepared):
         return self._publish(key, (inp, tuple(us), wout, bout))
 
 
-_CACHES: "weakref.WeakKeyDictionary[nn.Module, PreparedIdNet]" = weakref.WeakKeyDictionary()
-
-
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    if isinstance(weights, nn.Module):
-        cache = _CACHES.get(weights)
-        if cache is None:
-            cache = _CACHES[weights] = PreparedIdNet()
-        return cache.get(weights)
-    return PreparedIdNet().get(weights)
+    return lossnet.prepare(PreparedIdNet, weights)
 
 
 # ------------------------------------------------------------------------------------------------ pre-processing operator
-def _pool_matrix(n_in: int, n_out: int) -> np.ndarray:
-    """AdaptiveAvgPool1d(n_out) on n_in samples: rows are the windows floor(i n_in / n_out) .. ceil((i + 1) n_in / n_out)."""
-    A = np.zeros((n_out, n_in))
-    for i in range(n_out):
-        lo, hi = (i * n_in) // n_out, -((-(i + 1) * n_in) // n_out)
-        A[i, lo:hi] = 1.0 / (hi - lo)
-    return A
-
-
 def axis_matrix(n: int, pooled: bool, crop) -> np.ndarray:
     """float64 [112, n]: AdaptiveAvgPool(256) (when ``pooled``) -> slice ``crop`` (Python slicing of the 256- or n-long axis) -> AdaptiveAvgPool(112)."""
-    P1 = _pool_matrix(n, 256) if pooled else np.eye(n)
+    P1 = pool_matrix(n, 256) if pooled else np.eye(n)
     m = P1.shape[0]
     lo, hi = min(crop[0], m), min(crop[1], m)
     if hi - lo < 1:
         raise ValueError(f"an image side of {n} leaves nothing of the crop {crop}")
-    return _pool_matrix(hi - lo, SIDE) @ P1[lo:hi]
-
-
-def _bands(A: np.ndarray):
-    """[rows][2] = [lo, hi) of each row's nonzeros and [cols][2] of each column's (empty: [0, 0)); the nonzeros of a row / column are contiguous."""
-    def rng(M):
-        out = np.zeros((M.shape[0], 2), dtype=np.int32)
-        for r in range(M.shape[0]):
-            nz = np.nonzero(M[r])[0]
-            if nz.size:
-                assert nz[-1] - nz[0] + 1 == nz.size, "pre-processing band is not contiguous"
-                out[r] = (nz[0], nz[-1] + 1)
-        return out
-    return rng(A), rng(A.T)
-
-
-_RESAMPLERS = {}
+    return pool_matrix(hi - lo, SIDE) @ P1[lo:hi]
 
 
 def resampler(h: int, w: int, device):
-    """Device copies (ay, ax, row bands y / x, column bands y / x) of the pre-processing operator of an h x w image (cached)."""
-    key = (h, w, str(device))
-    hit = _RESAMPLERS.get(key)
-    if hit is None:
-        pooled = h != 256                       # IDLoss.extract_feats pools when x.shape[2] != 256 (both sides, to 256 x 256)
-        ay, ax = axis_matrix(h, pooled, CROP[0]), axis_matrix(w, pooled, CROP[1])
-        (ry, cy), (rx, cx) = _bands(ay), _bands(ax)
-        T = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)   # noqa: E731
-        hit = _RESAMPLERS[key] = (T(ay), T(ax), T(ry, torch.int32), T(rx, torch.int32), T(cy, torch.int32), T(cx, torch.int32))
-    return hit
-
-
-def _resample(x, R):
-    bs, c, h, w = x.shape
-    out = torch.empty((bs, c, SIDE, SIDE), dtype=torch.float32, device=x.device)
-    lib().call("e4s_id_resample", _p(out), _p(x), _p(R[0]), _p(R[1]), _p(R[2]), _p(R[3]), bs * c, h, w, SIDE, _stream())
-    return out
+    """The pre-processing operator of an h x w image (a cached ``lossnet.Resampler`` to 112 x 112)."""
+    pooled = h != 256                           # IDLoss.extract_feats pools when x.shape[2] != 256 (both sides, to 256 x 256)
+    return lossnet.resampler(h, w, SIDE, device, lambda: (axis_matrix(h, pooled, CROP[0]), axis_matrix(w, pooled, CROP[1])))
 
 
 # ------------------------------------------------------------------------------------------------ forward
-def _conv3(x, slabs, bias, cout, k, stride, residual=None):
-    bs, cin, h, w = x.shape
-    pad = k // 2
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-    out = torch.empty((bs, cout, ho, wo), dtype=torch.float32, device=x.device)
-    lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(bias), None, None, None, _p(residual), 0,
-               bs, cin, cout, h, w, k, stride, pad, _stream())
-    return out
-
-
-def _conv2(x, slabs, cout, k, residual=None):
-    """Stride-1 data-gradient convolution (two-way split)."""
-    bs, cin, h, w = x.shape
-    out = torch.empty((bs, cout, h, w), dtype=torch.float32, device=x.device)
-    lib().call("e4s_conv2d_sb", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), None, None, None, None, _p(residual), 0,
-               bs, cin, cout, h, w, k, 1, k // 2, _stream())
-    return out
-
-
 def _affine(x, scale, shift, slope):
     out = torch.empty_like(x)
     lib().call("e4s_id_affine", _p(out), _p(x), _p(scale), _p(shift), _p(slope), x.shape[0], x.shape[1], x.shape[2] * x.shape[3], _stream())
@@ -336,15 +228,15 @@ def _unit_fwd(x, U):
     bs = x.shape[0]
     depth, stride = U["depth"], U["stride"]
     a = _affine(x, U["bn_scale"], U["bn_shift"], None)
-    c1 = _conv3(a, U["fwd1"], None, depth, 3, 1)                                   # PReLU's pre-activation, kept for the backward
-    r = _conv3(_affine(c1, None, None, U["slope"]), U["fwd2"][0], U["fwd2"][1], depth, 3, stride)
+    c1 = conv_sb(a, U["fwd1"], k=3)                                                # PReLU's pre-activation, kept for the backward
+    r = conv_sb(_affine(c1, None, None, U["slope"]), *U["fwd2"], k=3, stride=stride)
     ho, wo = r.shape[2], r.shape[3]
     pooled = torch.empty((bs, depth), dtype=torch.float32, device=x.device)
     lib().call("e4s_plane_stats", _p(pooled), None, None, _p(r), bs * depth, ho * wo, 0.0, _stream())
     gate = torch.empty((bs, depth), dtype=torch.float32, device=x.device)
     lib().call("e4s_se_gate", _p(gate), _p(pooled), _p(U["fc1"]), _p(U["fc2"]), bs, depth, depth // 16, _stream())
     if U["sc"] is not None:
-        short, sc_stride = _conv3(x, U["sc"][0][0], U["sc"][0][1], depth, 1, stride), 1
+        short, sc_stride = conv_sb(x, *U["sc"][0], k=1, stride=stride), 1
     else:
         short, sc_stride = x, stride
     y = torch.empty_like(r)
@@ -356,7 +248,7 @@ def _features(x112, P, multiscale: bool, save: bool):
     """The features (flattened, not normalised) of the 112 x 112 input: [tap 2, 6, 20, 23 outputs,] output layer; and what the backward needs."""
     inp, us, wout, bout = P
     bs = x112.shape[0]
-    c0 = _conv3(x112, inp[0][0], inp[0][1], 64, 3, 1)
+    c0 = conv_sb(x112, *inp[0], k=3)
     a = _affine(c0, None, None, inp[2])
     taps, saved = [], []
     for i, U in enumerate(us):
@@ -369,22 +261,6 @@ def _features(x112, P, multiscale: bool, save: bool):
     lib().call("e4s_id_linear", _p(feat), _p(a), _p(wout), _p(bout), bs, wout.shape[1], 512, _stream())
     taps.append(feat)
     return taps, (c0, saved)
-
-
-def _heads(fx, fy):
-    bs = fx[0].shape[0]
-    nbs = [-(-f.shape[1] // HEAD_BLOCK) for f in fx]
-    part = torch.empty((3 * bs * sum(nbs),), dtype=torch.float32, device=fx[0].device)
-    off = 0
-    for a, b, nb in zip(fx, fy, nbs):
-        lib().call("e4s_id_head_partial", _p(part[off:]), _p(a), _p(b), bs, a.shape[1], _stream())
-        off += 3 * bs * nb
-    loss = torch.empty((), dtype=torch.float32, device=fx[0].device)
-    sim = torch.empty((), dtype=torch.float32, device=fx[0].device)
-    stats = torch.empty((len(fx), bs, 3), dtype=torch.float32, device=fx[0].device)
-    nb5 = nbs + [0] * (5 - len(nbs))
-    lib().call("e4s_id_head_sum", _p(loss), _p(sim), _p(stats), _p(part), bs, len(fx), *nb5, _stream())
-    return loss, sim, stats
 
 
 # ------------------------------------------------------------------------------------------------ backward
@@ -404,12 +280,12 @@ def _unit_bwd(gy, U, rec, bs, h, w):
         lib().call("e4s_modconv_tconv_sb", _p(z), _p(dr), _p(U["bwd2"][0]), _p(U["bwd2"][1]), _p(ones), bs, depth, depth, ho, wo, _stream())
         src, sh, sw, off = z, 2 * ho + 1, 2 * wo + 1, 1                     # the forward's padding of 1: rows / columns 1 .. 2 ho of the full transposed conv
     else:
-        src, sh, sw, off = _conv2(dr, U["bwd2"], depth, 3), h, w, 0
+        src, sh, sw, off = conv_sb(dr, U["bwd2"], k=3), h, w, 0
     lib().call("e4s_id_prelu_bwd", _p(gc1), _p(src), _p(c1), _p(U["slope"]), bs, depth, h, w, sh, sw, off, _stream())
     if stride == 1:
-        return _conv2(gc1, U["bwd1"], cin, 3, residual=gy)                      # MaxPool2d(1, 1) shortcut: the identity
-    gx = _conv2(gc1, U["bwd1"], cin, 3)
-    gsc = _conv2(gy, U["sc"][1], cin, 1) if U["sc"] is not None else gy         # the 1x1 stride-2 shortcut's data gradient at its output resolution
+        return conv_sb(gc1, U["bwd1"], k=3, residual=gy)                        # MaxPool2d(1, 1) shortcut: the identity
+    gx = conv_sb(gc1, U["bwd1"], k=3)
+    gsc = conv_sb(gy, U["sc"][1], k=1) if U["sc"] is not None else gy           # the 1x1 stride-2 shortcut's data gradient at its output resolution
     lib().call("e4s_id_scatter_add", _p(gx), _p(gsc), bs * cin, h, w, _stream())
     return gx
 
@@ -438,7 +314,7 @@ def _input_grad(fx, fy, stats, gout, P, state, multiscale: bool, head_bwd=None):
         g = _unit_bwd(g, U, saved[i], bs, h, w)
     gc0 = torch.empty_like(c0)
     lib().call("e4s_id_prelu_bwd", _p(gc0), _p(g), _p(c0), _p(inp[2]), bs, 64, SIDE, SIDE, SIDE, SIDE, 0, _stream())
-    return _conv2(gc0, inp[1], 3, 3)
+    return conv_sb(gc0, inp[1], k=3)
 
 
 class _IdLoss(torch.autograd.Function):
@@ -446,9 +322,9 @@ class _IdLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y_hat, y, P, R, multiscale):
-        fx, state = _features(_resample(y_hat, R), P, multiscale, save=True)
-        fy, _ = _features(_resample(y, R), P, multiscale, save=False)
-        loss, sim, stats = _heads(fx, fy)
+        fx, state = _features(R.apply(y_hat), P, multiscale, save=True)
+        fy, _ = _features(R.apply(y), P, multiscale, save=False)
+        loss, sim, stats = cos_heads(fx, fy)
         ctx.P, ctx.R, ctx.multiscale, ctx.shape, ctx.state = P, R, multiscale, tuple(y_hat.shape), state
         ctx.save_for_backward(stats, *fx, *fy)
         ctx.mark_non_differentiable(sim, stats)
@@ -463,14 +339,7 @@ class _IdLoss(torch.autograd.Function):
         stats, fx, fy = saved[0], list(saved[1:1 + n]), list(saved[1 + n:])
         gout = _c(gloss.reshape(1), "grad_output")
         g112 = _input_grad(fx, fy, stats, gout, ctx.P, ctx.state, ctx.multiscale)
-        bs, c, h, w = ctx.shape
-        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g112.device)
-        R = ctx.R
-        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g112), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
-        return gx, None, None, None, None
-
-
-MULTI_STATS = 9                              # e4s_id_head_*_multi: |x|^2 (|x|), then (|y_j|^2, x.y_j) ((|y_j|, cos_j)) for 4 targets
+        return ctx.R.adjoint(g112, ctx.shape), None, None, None, None
 
 
 def _feature_dims(multiscale: bool):
@@ -483,28 +352,12 @@ def _feature_dims(multiscale: bool):
     return dims + [512]
 
 
-def heads_multi(fx, ys, tw, frame):
-    """(loss, stats [ntap][bs][9]) of the multi-target heads: ``ys[j][t]`` is target j's tap t (also used by ``ops_fp``)."""
-    bs = fx[0].shape[0]
-    nbs = [-(-f.shape[1] // HEAD_BLOCK) for f in fx]
-    part = torch.empty((MULTI_STATS * bs * sum(nbs),), dtype=torch.float32, device=fx[0].device)
-    off = 0
-    for t, (a, nb) in enumerate(zip(fx, nbs)):
-        lib().call("e4s_id_head_partial_multi", _p(part[off:]), _p(a), *call_args([y[t] for y in ys], tw, frame, bs), bs, a.shape[1], _stream())
-        off += MULTI_STATS * bs * nb
-    loss = torch.empty((), dtype=torch.float32, device=fx[0].device)
-    stats = torch.empty((len(fx), bs, MULTI_STATS), dtype=torch.float32, device=fx[0].device)
-    _, ws, k = _host_targets([0] * len(tw), tw)
-    lib().call("e4s_id_head_sum_multi", _p(loss), _p(stats), _p(part), ws, k, bs, len(fx), *(nbs + [0] * (5 - len(nbs))), _stream())
-    return loss, stats
-
-
 class _IdLossMulti(torch.autograd.Function):
     """sum_j tw[j] IDLoss(y_hat, y_j) from the targets' cached features; differentiable in ``y_hat`` only."""
 
     @staticmethod
     def forward(ctx, y_hat, P, R, multiscale, ys, tw, frame):
-        fx, state = _features(_resample(y_hat, R), P, multiscale, save=True)
+        fx, state = _features(R.apply(y_hat), P, multiscale, save=True)
         loss, stats = heads_multi(fx, ys, tw, frame)
         ctx.P, ctx.R, ctx.multiscale, ctx.shape, ctx.state, ctx.ys, ctx.tw, ctx.frame = P, R, multiscale, tuple(y_hat.shape), state, ys, tw, frame
         ctx.save_for_backward(stats, *fx)
@@ -523,28 +376,24 @@ class _IdLossMulti(torch.autograd.Function):
             lib().call("e4s_id_head_bwd_multi", _p(g), _p(fx[k]), *call_args([y[k] for y in ctx.ys], ctx.tw, ctx.frame, bs), _p(stats[k]), _p(gout), bs,
                        fx[k].shape[1], scale, accumulate, _stream())
         g112 = _input_grad(fx, None, None, gout, ctx.P, ctx.state, ctx.multiscale, head_bwd)
-        bs, c, h, w = ctx.shape
-        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g112.device)
-        R = ctx.R
-        lib().call("e4s_id_resample_adjoint", _p(gx), _p(g112), _p(R[0]), _p(R[1]), _p(R[4]), _p(R[5]), bs * c, h, w, SIDE, 0, _stream())
-        return gx, None, None, None, None, None, None
+        return ctx.R.adjoint(g112, ctx.shape), None, None, None, None, None, None
 
 
 def target_features(images: torch.Tensor, weights, multiscale: bool = True):
     """The raw (not normalised) features of ``images`` ``[n, 3, H, W]`` that ``id_loss_multi`` reads for a target: a list of ``[n, D]`` tensors
     (five with ``multiscale``, the embedding alone without).  Computed a frame at a time; no gradient."""
     check_loaded(weights)
-    images = _check(images.detach(), "images")
+    images = check_image(images.detach(), "images")
     P, R = prepare(weights), resampler(images.shape[2], images.shape[3], images.device)
     with torch.no_grad():
-        return target_rows(lambda x: _features(_resample(x.contiguous(), R), P, bool(multiscale), save=False)[0], images)
+        return target_rows(lambda x: _features(R.apply(x.contiguous()), P, bool(multiscale), save=False)[0], images)
 
 
 def id_loss_multi(y_hat: torch.Tensor, targets, tw, weights, multiscale: bool = True, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sum_j tw[j] * id_loss(y_hat, y_j)`` (0-d, differentiable in ``y_hat`` only) with one network pass and input gradient of ``y_hat``:
     ``targets[j] = target_features(y_j, weights, multiscale)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
     check_loaded(weights)
-    y_hat = _check(y_hat, "y_hat")
+    y_hat = check_image(y_hat, "y_hat")
     frame = check_frame(frame, y_hat.device)
     bs = y_hat.shape[0]
     ys = check_targets([torch.empty((bs, d), device="meta") for d in _feature_dims(multiscale)], targets, tw, frame, "id_loss_multi")
@@ -552,18 +401,11 @@ def id_loss_multi(y_hat: torch.Tensor, targets, tw, weights, multiscale: bool = 
                               [float(w) for w in tw], frame)
 
 
-def _check(x: torch.Tensor, name: str) -> torch.Tensor:
-    x = _c(x, name)
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError(f"{name}: expected [bs >= 1, 3, H, W], got {tuple(x.shape)}")
-    return x
-
-
 def id_loss_terms(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = True):
     """``(loss, sim_improvement, per_scale)``: the loss (0-d, differentiable in ``y_hat``), IDLoss's similarity improvement (0-d, on the device) and
     ``per_scale [scales]`` = mean over the batch of 1 - cos per scale (no gradient).  No host synchronisation."""
     check_loaded(weights)
-    y_hat, y = _check(y_hat, "y_hat"), _check(y.detach(), "y")
+    y_hat, y = check_image(y_hat, "y_hat"), check_image(y.detach(), "y")
     if y_hat.shape != y.shape:
         raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ")
     loss, sim, stats = _IdLoss.apply(y_hat, y, prepare(weights), resampler(y.shape[2], y.shape[3], y.device), bool(multiscale))
@@ -580,7 +422,7 @@ def id_loss(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = Tr
 def features_112(x: torch.Tensor, weights, multiscale: bool = True):
     """Backbone.forward(x, multi_scale): the l2-normalised features of a 112 x 112 input (no gradient)."""
     check_loaded(weights)
-    x = _check(x, "x")
+    x = check_image(x, "x")
     if x.shape[2:] != (SIDE, SIDE):
         raise ValueError(f"x: the network takes 112 x 112 inputs, got {tuple(x.shape[2:])}")
     with torch.no_grad():
@@ -591,9 +433,9 @@ def features_112(x: torch.Tensor, weights, multiscale: bool = True):
 def id_features(x: torch.Tensor, weights, multiscale: bool = True):
     """IDLoss.extract_feats(x): the l2-normalised features of an image batch after the pool -> crop -> pool pre-processing (no gradient)."""
     check_loaded(weights)
-    x = _check(x, "x")
+    x = check_image(x, "x")
     with torch.no_grad():
-        x112 = _resample(x, resampler(x.shape[2], x.shape[3], x.device))
+        x112 = resampler(x.shape[2], x.shape[3], x.device).apply(x)
     return features_112(x112, weights, multiscale)
 
 

@@ -11,17 +11,18 @@ optimization.py:111-146).
 Weights are a ``state_dict``-shaped mapping or a module with the reference's layout: ``net.mean``, ``net.std``,
 ``net.layers.{0,3,6,8,10}.{weight,bias}``, ``lin.{0..4}.1.weight``.  They are frozen: no weight gradient is computed.
 Every launch goes on the current stream with no host synchronisation, so the term can be captured in a hipGraph (``pti.GraphedPTIStep``).
+The weight cache, the split-bf16 weight preparation and convolution wrapper and the multi-target helpers are ``lossnet``'s.
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional
 
 import torch
 
+from . import lossnet
 from ._lib import lib
+from .lossnet import call_args, check_frame, check_image, check_targets, conv_sb, relu_mask, sum_partials, target_rows, weights_key
 from .ops import _Prepared, _c, _p, _stream
-from .ops_multi import call_args, check_frame, check_targets, target_rows
 
 LAYERS = (0, 3, 6, 8, 10)                 # AlexNet ``features`` indices of the five convolutions
 CHANNELS = (64, 192, 384, 256, 256)
@@ -59,20 +60,10 @@ def _tensors(weights):
     return ts[:12], ts[12:]
 
 
-def weights_key(tensors) -> tuple:
-    """What the prepared copies are keyed on, for ``tensors = weight_tensors(weights)``: storage and version of every tensor."""
-    return tuple((t.data_ptr(), t._version) for t in tensors)
-
-
 def weight_tensors(weights):
     """The network and lin tensors of ``weights`` (see ``weights_key``)."""
     net, lin = _tensors(weights)
     return net + lin
-
-
-def _slabs(n: int, w: torch.Tensor):
-    cout, cin, kh, kw = w.shape
-    return tuple(torch.empty(((cin + 15) // 16, kh * kw, 2, cout, 8), dtype=torch.int16, device=w.device) for _ in range(n))
 
 
 class PreparedLpips(_Prepared):
@@ -97,30 +88,15 @@ class PreparedLpips(_Prepared):
         w1t = ws[0].permute(1, 2, 3, 0).contiguous()                   # [3][11][11][64]
         fwd, bwd = [], []
         for w in ws[1:]:
-            cout, cin, k, _ = w.shape
-            s3 = _slabs(3, w)
-            lib().call("e4s_conv_prep_weights_sb3", _p(s3[0]), _p(s3[1]), _p(s3[2]), None, _p(w), None, None, None, None, 0.0, None,
-                       cout, cin, k, k, _stream())
-            wf = w.flip(2, 3).transpose(0, 1).contiguous()              # [cin][cout][k][k]: the data gradient is a convolution with these
-            s2 = _slabs(2, wf)
-            lib().call("e4s_conv_prep_weights_sb", _p(s2[0]), _p(s2[1]), None, _p(wf), None, None, None, None, 0.0, None, cin, cout, k, k, _stream())
-            fwd.append(s3)
-            bwd.append(s2)
+            fwd.append(lossnet.prep_fwd(w)[0])
+            bwd.append(lossnet.prep_dgrad(w))                  # the data gradient is a convolution with the flipped, transposed weights
         payload = (mean, std, w1t, tuple(bs), tuple(fwd), tuple(bwd))
         return self._publish(key, payload)
 
 
-_CACHES: "weakref.WeakKeyDictionary[torch.nn.Module, PreparedLpips]" = weakref.WeakKeyDictionary()
-
-
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    if isinstance(weights, torch.nn.Module):
-        cache = _CACHES.get(weights)
-        if cache is None:
-            cache = _CACHES[weights] = PreparedLpips()
-        return cache.get(weights)
-    return PreparedLpips().get(weights)
+    return lossnet.prepare(PreparedLpips, weights)
 
 
 def lin_weights(weights):
@@ -142,17 +118,7 @@ def _pool_out(side: int) -> int:
 
 
 def _conv(x, slabs, bias, i: int, relu: bool, residual=None):
-    bs, cin, h, w = x.shape
-    cout = slabs[0].shape[3]
-    out = torch.empty((bs, cout, h, w), dtype=torch.float32, device=x.device)      # stride 1, "same" padding
-    k = KERNELS[i]
-    if len(slabs) == 3:
-        lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(bias), None, None, None, _p(residual),
-                   1 if relu else 0, bs, cin, cout, h, w, k, 1, PADS[i], _stream())
-    else:
-        lib().call("e4s_conv2d_sb", _p(out), _p(x), None, cin, _p(slabs[0]), _p(slabs[1]), _p(bias), None, None, None, _p(residual),
-                   1 if relu else 0, bs, cin, cout, h, w, k, 1, PADS[i], _stream())
-    return out
+    return conv_sb(x, slabs, bias, k=KERNELS[i], pad=PADS[i], relu=relu, residual=residual)      # stride 1, "same" padding
 
 
 def _maxpool(a):
@@ -184,9 +150,7 @@ def _head(fx, fy, lins):
         hw = a.shape[2] * a.shape[3]
         lib().call("e4s_lpips_head", _p(partial[off:]), _p(a), _p(b), _p(lin), bs, a.shape[1], hw, 1.0 / (bs * hw), _stream())
         off += n
-    loss = torch.empty((), dtype=torch.float32, device=fx[0].device)
-    lib().call("e4s_lpips_sum", _p(loss), _p(partial), off, _stream())
-    return loss
+    return sum_partials(partial, off)
 
 
 def _input_grad(taps, gtaps, P, f: int, shape):
@@ -194,11 +158,11 @@ def _input_grad(taps, gtaps, P, f: int, shape):
     _, std, w1t, _, _, bwd = P
     a1, a2, a3, a4, a5 = taps
     g5 = gtaps[4]
-    lib().call("e4s_lpips_relu_mask", _p(g5), _p(a5), g5.numel(), _stream())
+    relu_mask(g5, a5)
     g4 = _conv(g5, bwd[3], None, 4, False, residual=gtaps[3])
-    lib().call("e4s_lpips_relu_mask", _p(g4), _p(a4), g4.numel(), _stream())
+    relu_mask(g4, a4)
     g3 = _conv(g4, bwd[2], None, 3, False, residual=gtaps[2])
-    lib().call("e4s_lpips_relu_mask", _p(g3), _p(a3), g3.numel(), _stream())
+    relu_mask(g3, a3)
     gp2 = _conv(g3, bwd[1], None, 2, False)
     g2 = torch.empty_like(a2)
     lib().call("e4s_lpips_maxpool_bwd_relu", _p(g2), _p(gp2), _p(gtaps[1]), _p(a2), a2.shape[0] * a2.shape[1], a2.shape[2], a2.shape[3], _stream())
@@ -255,8 +219,7 @@ class _LpipsScaleMulti(torch.autograd.Function):
             lib().call("e4s_lpips_head_multi", _p(partial[off:]), _p(a), *call_args([y[t] for y in ys], tw, frame, bs), _p(lin), bs, a.shape[1], hw,
                        1.0 / (bs * hw), _stream())
             off += n
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        lib().call("e4s_lpips_sum", _p(loss), _p(partial), off, _stream())
+        loss = sum_partials(partial, off)
         ctx.P, ctx.lins, ctx.f, ctx.shape, ctx.ys, ctx.tw, ctx.frame = P, lins, f, tuple(x.shape), ys, tw, frame
         ctx.save_for_backward(*fx)
         return loss
@@ -328,9 +291,7 @@ def features(x: torch.Tensor, weights, factor: int = 1):
 
 
 def _check(x: torch.Tensor, name: str, factor: int) -> torch.Tensor:
-    x = _c(x, name)
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError(f"{name}: expected [bs >= 1, 3, H, W], got {tuple(x.shape)}")
+    x = check_image(x, name)
     h, w = x.shape[2], x.shape[3]
     if h % factor or w % factor:
         raise ValueError(f"{name}: the sides {h} x {w} must be divisible by {factor}")

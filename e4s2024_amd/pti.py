@@ -20,6 +20,7 @@ the reference's N sequential batch-1 steps, so result parity with the reference 
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Callable, Optional
 
 import torch
@@ -27,6 +28,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import ops, ops_fp, ops_id, ops_lpips, ops_multi
+from .lossnet import weights_key
 
 
 def trainable_parameters(net):
@@ -39,18 +41,38 @@ def _id_multiscale(id_loss) -> bool:
     return bool(getattr(getattr(id_loss, "opts", None), "id_loss_multiscale", True))
 
 
+# One loss-network term of calc_loss: ``module`` (the weights) and ``lam``; ``name``: its TargetCache attribute, ``label``: its name in messages;
+# ``loss(a, b, module)``, ``loss_multi(a, targets, tw, module, frame)`` and ``target_features(images, module)`` of its ops module.
+_Term = namedtuple("_Term", "module lam name label check_loaded weight_tensors loss loss_multi target_features")
+
+
+def _terms(lpips=None, lpips_lambda: float = 0.8, id_loss=None, id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
+    """The loss-network terms that have a module, in the order they are summed: LPIPS (calc_loss :201-211), identity (:192-195), face-parsing
+    (:212-216)."""
+    ms = _id_multiscale(id_loss)
+    table = (_Term(lpips, lpips_lambda, "lpips", "LPIPS", ops_lpips.check_loaded, ops_lpips.weight_tensors, ops_lpips.lpips_multiscale,
+                   ops_lpips.lpips_multiscale_multi, ops_lpips.target_features),
+             _Term(id_loss, id_lambda, "id", "ArcFace (id_loss)", ops_id.check_loaded, ops_id.weight_tensors,
+                   lambda a, b, m: ops_id.id_loss(a, b, m, ms), lambda a, ys, tw, m, frame: ops_id.id_loss_multi(a, ys, tw, m, ms, frame),
+                   lambda images, m: ops_id.target_features(images, m, ms)),
+             _Term(face_parsing, face_parsing_lambda, "fp", "face-parsing", ops_fp.check_loaded, ops_fp.weight_tensors, ops_fp.fp_loss,
+                   ops_fp.fp_loss_multi, ops_fp.target_features))
+    return [t for t in table if t.module is not None]
+
+
+def _check_loaded(terms):
+    for t in terms:
+        t.check_loaded(t.module)
+
+
 def _loss(net, style_vectors, mask, target, foreground_mask, l2_lambda, extra_loss, randomize_noise, lpips=None, lpips_lambda: float = 0.8,
           id_loss=None, id_lambda: float = 0.1, face_parsing=None, face_parsing_lambda: float = 0.1):
     codes = net.cal_style_codes(style_vectors)
     recon, _, _ = net.gen_img(None, codes, mask, randomize_noise=randomize_noise)
     a, b = (recon, target) if foreground_mask is None else (recon * foreground_mask, target * foreground_mask)
     loss = l2_lambda * F.mse_loss(a, b)                                      # calc_loss :196-199 (loss_l2)
-    if lpips is not None:                                                    # calc_loss :201-211 (loss_lpips), on the masked images
-        loss = loss + lpips_lambda * ops_lpips.lpips_multiscale(a, b, lpips)
-    if id_loss is not None:                                                  # calc_loss :192-195 (loss_id), on the masked images
-        loss = loss + id_lambda * ops_id.id_loss(a, b, id_loss, _id_multiscale(id_loss))
-    if face_parsing is not None:                                             # calc_loss :212-216 (loss_face_parsing), on the masked images
-        loss = loss + face_parsing_lambda * ops_fp.fp_loss(a, b, face_parsing)
+    for t in _terms(lpips, lpips_lambda, id_loss, id_lambda, face_parsing, face_parsing_lambda):     # on the masked images
+        loss = loss + t.lam * t.loss(a, b, t.module)
     if extra_loss is not None:
         loss = loss + extra_loss(recon, target)
     return loss, recon
@@ -68,23 +90,20 @@ class TargetCache:
             raise ValueError("TargetCache: the target images must have the same shape")
         self.n = n
         self.images = [(t * foreground_mask if foreground_mask is not None else t).contiguous() for t in images]
-        self._tensors = [(m, ops_lpips.weight_tensors(m) if m is not None else []) for m in (lpips,)] + \
-                        [(m, ops_id.weight_tensors(m) if m is not None else []) for m in (id_loss,)] + \
-                        [(m, ops_fp.weight_tensors(m) if m is not None else []) for m in (face_parsing,)]
-        self._key = self._weights_key()
-        self.lpips = [ops_lpips.target_features(t, lpips) for t in self.images] if lpips is not None else None
-        self.id = [ops_id.target_features(t, id_loss, _id_multiscale(id_loss)) for t in self.images] if id_loss is not None else None
-        self.fp = [ops_fp.target_features(t, face_parsing) for t in self.images] if face_parsing is not None else None
+        terms = _terms(lpips=lpips, id_loss=id_loss, face_parsing=face_parsing)
+        self._modules = (lpips, id_loss, face_parsing)
+        self._tensors = [w for t in terms for w in t.weight_tensors(t.module)]
+        self._key = weights_key(self._tensors)
+        self.lpips = self.id = self.fp = None                    # per term: a target_features list per image of ``images``
+        for t in terms:
+            setattr(self, t.name, [t.target_features(im, t.module) for im in self.images])
         self.frame = torch.zeros((1,), dtype=torch.int32, device=images[0].device)
-
-    def _weights_key(self):
-        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for _, ts in self._tensors)
 
     def check(self, lpips=None, id_loss=None, face_parsing=None):
         """Raises unless the cache holds features for exactly these loss modules, with the weights it was built from."""
-        if any(m is not g for (m, _), g in zip(self._tensors, (lpips, id_loss, face_parsing))):
+        if any(m is not g for m, g in zip(self._modules, (lpips, id_loss, face_parsing))):
             raise ValueError("TargetCache: built for other loss modules than the step's")
-        if self._weights_key() != self._key:
+        if weights_key(self._tensors) != self._key:
             raise RuntimeError("TargetCache: the loss weights changed after the target features were cached; build a new cache")
 
     def select(self, i: int):
@@ -119,14 +138,11 @@ def recolor_objective(recon, target, recolor, foreground_mask, mask, l2_lambda: 
     recolor_lambda * calc_loss(recolor, recon, fg)`` (video_swap_ft_coach.py:277-287) — see ``_loss_recolor``.  ``mask`` (the region map) is read only
     without a ``foreground_mask``; ``cache`` replaces ``target`` / ``recolor`` (then at its device frame index)."""
     rl = float(recolor_lambda)
+    terms = _terms(lpips, lpips_lambda, id_loss, id_lambda, face_parsing, face_parsing_lambda)
     if foreground_mask is None:
         loss = l2_lambda * F.mse_loss(recon, target)
-        if lpips is not None:
-            loss = loss + lpips_lambda * ops_lpips.lpips_multiscale(recon, target, lpips)
-        if id_loss is not None:
-            loss = loss + id_lambda * ops_id.id_loss(recon, target, id_loss, _id_multiscale(id_loss))
-        if face_parsing is not None:
-            loss = loss + face_parsing_lambda * ops_fp.fp_loss(recon, target, face_parsing)
+        for t in terms:
+            loss = loss + t.lam * t.loss(recon, target, t.module)
         labels = mask if mask.dtype == torch.uint8 else ops.mask_to_labels(mask)
         fg = prepare_clip(labels, None, recon.shape[-2:])[1]
         tgt, tw = TargetCache([recolor], fg, lpips, id_loss, face_parsing), [rl]
@@ -140,12 +156,8 @@ def recolor_objective(recon, target, recolor, foreground_mask, mask, l2_lambda: 
     # the targets' weights are (1, recolor_lambda), the term lambdas stay outside as in _loss: with recolor_lambda = 0 the heads give _loss's bits
     term = l2_lambda * ops_multi.mse_multi(recon, fg, tgt.images, tw, frame)
     loss = term if loss is None else loss + term
-    if lpips is not None:
-        loss = loss + lpips_lambda * ops_lpips.lpips_multiscale_multi(a, tgt.lpips, tw, lpips, frame)
-    if id_loss is not None:
-        loss = loss + id_lambda * ops_id.id_loss_multi(a, tgt.id, tw, id_loss, _id_multiscale(id_loss), frame)
-    if face_parsing is not None:
-        loss = loss + face_parsing_lambda * ops_fp.fp_loss_multi(a, tgt.fp, tw, face_parsing, frame)
+    for t in terms:
+        loss = loss + t.lam * t.loss_multi(a, getattr(tgt, t.name), tw, t.module, frame)
     if extra_loss is not None:
         loss = loss + extra_loss(recon, target)
     return loss
@@ -232,14 +244,10 @@ class GraphedPTIStep:
         example and of the warm-up steps), which is written to the cache's device index before the replay."""
         if mask.dtype != torch.uint8:
             raise TypeError("GraphedPTIStep needs the uint8 region map (ops.mask_to_labels(onehot)), not a float mask")
-        # the LPIPS weights are prepared (re-laid-out) once, before the capture, and the graph reads those copies: weights loaded later would not
-        # reach the replays, so the step remembers which weights it was captured with and refuses to replay after they change
-        self._lpips_tensors = ops_lpips.weight_tensors(lpips) if lpips is not None else []
-        self._lpips_key = ops_lpips.weights_key(self._lpips_tensors)
-        self._id_tensors = ops_id.weight_tensors(id_loss) if id_loss is not None else []         # the same for the ArcFace weights
-        self._id_key = ops_id.weights_key(self._id_tensors)
-        self._fp_tensors = ops_fp.weight_tensors(face_parsing) if face_parsing is not None else []   # and for the face-parsing weights
-        self._fp_key = ops_fp.weights_key(self._fp_tensors)
+        # the loss networks' weights are prepared (re-laid-out) once, before the capture, and the graph reads those copies: weights loaded later would
+        # not reach the replays, so the step remembers which weights it was captured with and refuses to replay after they change
+        self._watched = [(t.label, ts, weights_key(ts)) for t in _terms(lpips=lpips, id_loss=id_loss, face_parsing=face_parsing)
+                         for ts in [t.weight_tensors(t.module)]]
         self.net = net
         self.static = [style_vectors.clone(), mask.clone(), target.clone()] + ([foreground_mask.clone()] if foreground_mask is not None else [])
         fg = self.static[3] if foreground_mask is not None else None
@@ -300,15 +308,10 @@ class GraphedPTIStep:
         if (frame is not None) != (self.cache is not None):
             raise ValueError("GraphedPTIStep: frame must be given iff the step was captured with a target cache")
         new = [style_vectors, mask, target] + ([foreground_mask] if foreground_mask is not None else []) + ([recolor] if recolor is not None else [])
-        if ops_lpips.weights_key(self._lpips_tensors) != self._lpips_key:
-            raise RuntimeError("GraphedPTIStep: the LPIPS weights changed after the capture (the graph reads copies prepared from the old ones); "
-                               "capture a new step")
-        if ops_id.weights_key(self._id_tensors) != self._id_key:
-            raise RuntimeError("GraphedPTIStep: the ArcFace (id_loss) weights changed after the capture (the graph reads copies prepared from the old "
-                               "ones); capture a new step")
-        if ops_fp.weights_key(self._fp_tensors) != self._fp_key:
-            raise RuntimeError("GraphedPTIStep: the face-parsing weights changed after the capture (the graph reads copies prepared from the old "
-                               "ones); capture a new step")
+        for label, ts, key in self._watched:
+            if weights_key(ts) != key:
+                raise RuntimeError(f"GraphedPTIStep: the {label} weights changed after the capture (the graph reads copies prepared from the old "
+                                   "ones); capture a new step")
         if len(new) != len(self.static):
             raise ValueError("foreground_mask must be given iff the step was captured with one")
         if self.cache is not None:
@@ -342,12 +345,7 @@ def pti_step(net, optimizer: torch.optim.Optimizer, style_vectors: torch.Tensor,
     the foreground weight (video_swap_ft_coach.py:274-287) — ``foreground_mask``, or without one the weight ``prepare_clip`` computes from ``mask``.
     Inside a ``torch.distributed`` process group every rank passes its own frame and the gradients are averaged before the update.
     Returns ``(loss value, reconstruction)``."""
-    if lpips is not None:
-        ops_lpips.check_loaded(lpips)
-    if id_loss is not None:
-        ops_id.check_loaded(id_loss)
-    if face_parsing is not None:
-        ops_fp.check_loaded(face_parsing)
+    _check_loaded(_terms(lpips=lpips, id_loss=id_loss, face_parsing=face_parsing))
     if recolor is not None:
         _check_recolor(recolor, target, "pti_step")
         loss, recon = _loss_recolor(net, style_vectors, mask, target, foreground_mask, l2_lambda, extra_loss, True, lpips, lpips_lambda, id_loss,
@@ -372,12 +370,7 @@ def style_vector_step(net, optimizer: torch.optim.Optimizer, latent: torch.Tenso
     ``lpips_lambda * sum_{i<3} LPIPS(pool_i(recon), pool_i(target))`` on the unmasked images (optimization.py:111-146); ``id_loss``:
     ``id_lambda * IDLoss(recon, target)``, unmasked as well (optimization.py:115); ``face_parsing``: ``face_parsing_lambda *
     FaceParsingLoss(recon, target)``, unmasked (optimization.py:135-139)."""
-    if lpips is not None:
-        ops_lpips.check_loaded(lpips)
-    if id_loss is not None:
-        ops_id.check_loaded(id_loss)
-    if face_parsing is not None:
-        ops_fp.check_loaded(face_parsing)
+    _check_loaded(_terms(lpips=lpips, id_loss=id_loss, face_parsing=face_parsing))
     optimizer.zero_grad()
     loss, recon = _loss(net, latent, mask, target, None, l2_lambda, extra_loss, randomize_noise, lpips, lpips_lambda, id_loss, id_lambda,
                         face_parsing, face_parsing_lambda)
@@ -426,12 +419,7 @@ def tune_clip(net, optimizer, images: torch.Tensor, labels: torch.Tensor, style_
     ``step_fn(net, optimizer, vec, map, image, fg, group, active) -> loss`` replaces the step (tests); with ``recolor`` it also gets the frame's
     ``recolor=`` as a keyword.  Returns the mean loss of each pass."""
     from .runner import shard_range
-    if lpips is not None:
-        ops_lpips.check_loaded(lpips)
-    if id_loss is not None:
-        ops_id.check_loaded(id_loss)
-    if face_parsing is not None:
-        ops_fp.check_loaded(face_parsing)
+    _check_loaded(_terms(lpips=lpips, id_loss=id_loss, face_parsing=face_parsing))
     distributed = (not local_only) and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 
 import fp_model as M
 from conftest import install_dropin, load_golden
-from e4s2024_amd import ops_fp, ops_id, seeded
+from e4s2024_amd import lossnet, ops_fp, seeded
 
 
 @pytest.fixture(scope="module")
@@ -42,10 +42,10 @@ def test_restatement_matches_fixture(g16, sd, side):
 def test_pooling_operator(side):
     """AdaptiveAvgPool2d((512, 512)) as the banded matrices the GPU resampler reads."""
     x = torch.from_numpy(np.random.RandomState(side).standard_normal((1, 3, side, side)))
-    A = torch.from_numpy(ops_id._pool_matrix(side, ops_fp.SIDE))
+    A = torch.from_numpy(lossnet.pool_matrix(side, ops_fp.SIDE))
     got = torch.einsum("iy,bcyx,jx->bcij", A, x, A)
     assert (got - M.preprocess(x)).abs().max().item() <= 1e-12
-    rows, cols = ops_id._bands(A.numpy())
+    rows, cols = lossnet.bands(A.numpy())
     assert 1 <= (rows[:, 1] - rows[:, 0]).min() and (rows[:, 1] - rows[:, 0]).max() <= -(-side // 512) + 1
     assert ((cols[:, 1] - cols[:, 0]) >= 1).all()
 

@@ -576,3 +576,47 @@ def test_chain_supported_knows_the_last_layer():
     from e4s2024_amd import ops
     assert ops.chain_supported(64, 64, 512, 512, False) and not ops.chain_supported(64, 64, 512, 512, False, last=True)
     assert ops.chain_supported(32, 32, 1024, 1024, False, last=True) and not ops.chain_supported(32, 32, 1024, 1024, False)
+
+
+def test_prepared_tensors_walks_nested_payloads():
+    """``_Prepared._tensors`` (what a second stream's first hit calls ``record_stream`` on) finds every tensor of the loss networks' nested payloads
+    exactly once, and gives a flat synthesis-style payload's tensors as the one-level walk did."""
+    from e4s2024_amd import ops
+    n = [0]
+
+    def t():
+        n[0] += 1
+        return torch.full((2,), float(n[0]))
+
+    def slabs(k):
+        return tuple(t() for _ in range(k))
+
+    def check(payload, want):
+        got = ops._Prepared._tensors(payload)
+        assert len(got) == len(want) and all(a is b for a, b in zip(got, want))
+
+    mean, std, w1t, biases, fwd, bwd = t(), t(), t(), slabs(5), (slabs(3), slabs(3)), (slabs(2), slabs(2))      # PreparedLpips
+    check((mean, std, w1t, biases, fwd, bwd), [mean, std, w1t, *biases, *fwd[0], *fwd[1], *bwd[0], *bwd[1]])
+
+    def unit(sc):                                                                                               # PreparedIdNet
+        return dict(cin=64, depth=64, stride=2, bn_scale=t(), fwd1=slabs(3), slope=t(), fwd2=(slabs(3), t()), bwd2=slabs(2),
+                    sc=((slabs(3), t()), slabs(2)) if sc else None)
+    first = n[0]
+    inp, us, wout, bout = ((slabs(3), t()), slabs(2), t()), (unit(True), unit(False)), t(), t()
+    want = [*inp[0][0], inp[0][1], *inp[1], inp[2]]
+    for U in us:
+        want += [U["bn_scale"], *U["fwd1"], U["slope"], *U["fwd2"][0], U["fwd2"][1], *U["bwd2"]]
+        if U["sc"] is not None:
+            want += [*U["sc"][0][0], U["sc"][0][1], *U["sc"][1]]
+    want += [wout, bout]
+    check((inp, us, wout, bout), want)
+    assert len(want) == n[0] - first == 37 and len({id(x) for x in want}) == len(want)      # every tensor made for it, each once
+
+    blocks = tuple(dict(cin=3, cout=16, fwd1=(t(), t()), fwd2=(slabs(3), t()), bwd1=slabs(2), bwd2=slabs(2)) for _ in range(2))   # PreparedFaceParsingNet
+    check(blocks, [x for B in blocks for x in (*B["fwd1"], *B["fwd2"][0], B["fwd2"][1], *B["bwd1"], *B["bwd2"])])
+
+    wt, wsq, whi, wlo = t(), t(), t(), t()                                                                      # flat: tensors, one level of tuples, None, scalars
+    flat = (wt, wsq, (whi, wlo), None, 3, [t()])
+    one_level = [x for v in flat for x in (v if isinstance(v, (tuple, list)) else (v,)) if isinstance(x, torch.Tensor)]
+    check(flat, one_level)
+    assert len(one_level) == 5

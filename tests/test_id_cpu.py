@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 import id_model as M
 from conftest import install_dropin, load_golden
-from e4s2024_amd import ops_id, seeded
+from e4s2024_amd import lossnet, ops_id, seeded
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +47,7 @@ def test_preprocessing_operator(side):
     got = torch.einsum("iy,bcyx,jx->bcij", torch.from_numpy(ay), x, torch.from_numpy(ax))
     want = M.preprocess(x)
     assert (got - want).abs().max().item() <= 1e-12
-    (ry, cy), (rx, cx) = ops_id._bands(ay), ops_id._bands(ax)
+    (ry, cy), (rx, cx) = lossnet.bands(ay), lossnet.bands(ax)
     for A, rows, cols in ((ay, ry, cy), (ax, rx, cx)):
         for i in range(A.shape[0]):
             assert np.count_nonzero(A[i]) == rows[i, 1] - rows[i, 0] and A[i, rows[i, 0]:rows[i, 1]].all()
