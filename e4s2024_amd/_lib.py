@@ -61,6 +61,11 @@ _PROTOS = {
     "e4s_soft_erosion_scratch_bytes": [c_int] * 4 + [c_ptr],
     "e4s_soft_erosion": [c_ptr] * 5 + [c_int] * 4 + [c_f32, c_int, c_ptr],
     "e4s_blend_u8": [c_ptr] * 4 + [c_f32] + [c_int] * 4 + [c_ptr],
+    "e4s_grey_morph": [c_ptr, c_ptr] + [c_int] * 5 + [c_ptr],
+    "e4s_ct_moments_scratch_bytes": [c_int] * 3 + [c_ptr],
+    "e4s_ct_moments": [c_ptr] * 3 + [c_int] * 3 + [c_ptr],
+    "e4s_ct_solve": [c_ptr] * 3 + [c_int] * 4 + [c_ptr],
+    "e4s_ct_apply": [c_ptr] * 5 + [c_int] * 3 + [c_ptr],
     "e4s_mconv_unfold": [c_ptr] * 4 + [c_int] * 7 + [c_ptr],
     "e4s_mconv_scale": [c_ptr] * 9 + [c_int, c_ptr, c_ptr] + [c_int] * 8 + [c_ptr],
     "e4s_style_tables_bwd": [c_ptr] * 14 + [c_f32] * 3 + [c_int] * 5 + [c_ptr],

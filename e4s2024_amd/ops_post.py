@@ -429,5 +429,133 @@ def blend_with_mask(bottom_u8: torch.Tensor, up_u8: torch.Tensor, mask: torch.Te
     return out
 
 
-__all__ = ['_labels_u8', 'swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_resample_tables', '_pil_bicubic_tables', '_pil_lanczos_tables', 'pil_resize', 'crop_align', 'paste_into_frames', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending',
+# ------------------------------------------------------------------------------------ f7: the image caller's skin colour transfer (colortransfer.hip)
+CT_MODES = ("lct", "mkl")
+# every other ct_mode of the reference needs code this project cannot pin: cv2 colour conversions / bilateral filter, random rotations, a network
+CT_MODES_UNSUPPORTED = ("rct", "mix", "sot", "idt", "adaptive", "blender")
+GREY_MORPH_MAX_RADIUS = 16
+_CT_CHUNK = 4096
+
+
+def _radius_checked(radius, name):
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= GREY_MORPH_MAX_RADIUS:
+        raise ValueError(f"{name}: radius is an integer in 0..{GREY_MORPH_MAX_RADIUS}, got {radius!r}")
+    return radius
+
+
+def _ct_mode_checked(ct_mode, name):
+    if ct_mode not in CT_MODES:
+        why = " (it needs cv2, random rotations or a network: not on the device)" if ct_mode in CT_MODES_UNSUPPORTED else ""
+        raise ValueError(f"{name}: ct_mode is one of {list(CT_MODES)}, got {ct_mode!r}{why}")
+    return CT_MODES.index(ct_mode)
+
+
+def _grey_morph(x: torch.Tensor, radius: int, op: int, name: str) -> torch.Tensor:
+    _radius_checked(radius, name)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: x must be a torch.Tensor")
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError(f"{name}: expected float32 [..., H, W] planes, got {x.dtype} {tuple(x.shape)}")
+    x = _c(x, "x")
+    h, w = x.shape[-2:]
+    out = torch.empty_like(x)
+    if x.numel():
+        lib().call("e4s_grey_morph", _p(out), _p(x), x.numel() // (h * w), h, w, radius, op, _stream())
+    return out
+
+
+def grey_dilate(x: torch.Tensor, radius: int) -> torch.Tensor:
+    """``dilation(x, ones(2r+1, 2r+1), engine='convolution')`` (utils/morphology.py:23-108) on float32 ``[..., H, W]`` planes: the flat maximum filter
+    with the 'geodesic' border (pixels outside the image are ignored), exact.  ``radius`` 0 .. 16; 0 is a copy."""
+    return _grey_morph(x, radius, 0, "grey_dilate")
+
+
+def grey_erode(x: torch.Tensor, radius: int) -> torch.Tensor:
+    """``erosion(x, ones(2r+1, 2r+1), engine='convolution')`` (utils/morphology.py:111-198): the flat minimum filter, as ``grey_dilate``."""
+    return _grey_morph(x, radius, 1, "grey_erode")
+
+
+def soft_expansion_masks(mask: torch.Tensor, radius: int, kernel_size: int = 15, threshold: float = 0.6, iterations: int = 1):
+    """``_create_masks(mask, 'expansion', radius)`` (Face_swap_with_two_imgs.py:784-792) for a FLOAT mask ``[bs, 1, H, W]`` (``soft_paste_masks`` is the
+    same for a label map): ``full = soft(dilate(mask))``, ``border = clip(full - soft(erode(mask)), 0, 1)``, ``content = soft(mask)``, the three planes
+    of a face softened in one ``soft_erosion`` call.  Returns float32 ``[bs, 1, H, W]`` ``(content, border, full)``."""
+    _radius_checked(radius, "soft_expansion_masks")
+    _softer_checked(kernel_size, threshold, iterations)
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("soft_expansion_masks: mask must be a torch.Tensor")
+    if mask.dtype != torch.float32 or mask.dim() != 4 or mask.shape[1] != 1:
+        raise ValueError(f"soft_expansion_masks: expected a float32 [bs, 1, H, W] mask, got {mask.dtype} {tuple(mask.shape)}")
+    m = _c(mask, "mask")
+    if m.shape[0] == 0:
+        return m, torch.empty_like(m), torch.empty_like(m)
+    planes = torch.cat([grey_dilate(m, radius), grey_erode(m, radius), m], dim=1)
+    s, _ = soft_erosion(planes, kernel_size, threshold, iterations)
+    full = s[:, 0:1]
+    return s[:, 2:3].contiguous(), (full - s[:, 1:2]).clamp_(0, 1), full.contiguous()
+
+
+def _ct_inputs(name, src_u8, trg_u8, src_mask, trg_mask):
+    for nm, t in (("src", src_u8), ("trg", trg_u8)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {nm} must be a torch.Tensor")
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
+            raise ValueError(f"{name}: {nm}: expected uint8 [bs, H, W, 3] frames, got {t.dtype} {tuple(t.shape)}")
+    if src_u8.shape != trg_u8.shape:
+        raise ValueError(f"{name}: src {tuple(src_u8.shape)} and trg {tuple(trg_u8.shape)} frames differ in shape")
+    bs, h, w, _ = src_u8.shape
+    for nm, t in (("src_mask", src_mask), ("trg_mask", trg_mask)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {nm} must be a torch.Tensor")
+        if t.dtype != torch.float32 or tuple(t.shape) != (bs, 1, h, w):
+            raise ValueError(f"{name}: {nm}: expected a float32 [{bs}, 1, {h}, {w}] mask, got {t.dtype} {tuple(t.shape)}")
+    for nm, t in (("src", src_u8), ("trg", trg_u8), ("src_mask", src_mask), ("trg_mask", trg_mask)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: {nm} must be a CUDA tensor")
+    return src_u8.contiguous(), trg_u8.contiguous(), src_mask.contiguous(), trg_mask.contiguous()
+
+
+def color_transfer_coefficients(src_u8: torch.Tensor, trg_u8: torch.Tensor, src_mask: torch.Tensor, trg_mask: torch.Tensor, ct_mode: str) -> torch.Tensor:
+    """The linear map of ``skin_color_transfer``: float64 ``[bs, 15]`` = ``(A [3, 3] row-major, mu_src [3], mu_trg [3])`` with
+    ``y = A (v - mu_src) + mu_trg`` for ``v = (u8 * mask) / 255``.  The statistics run over ALL pixels of each image, like the reference's; they are summed
+    in float64 in a fixed order (bitwise reproducible) and never leave the device."""
+    mode = _ct_mode_checked(ct_mode, "color_transfer_coefficients")
+    s, t, sm, tm = _ct_inputs("color_transfer_coefficients", src_u8, trg_u8, src_mask, trg_mask)
+    bs, h, w, _ = s.shape
+    coef = torch.empty((bs, 15), dtype=torch.float64, device=s.device)
+    if bs == 0:
+        return coef
+    nbytes = ctypes.c_int64(0)
+    lib().call("e4s_ct_moments_scratch_bytes", bs, h, w, ctypes.byref(nbytes))
+    part = torch.empty((2, nbytes.value // 8), dtype=torch.float64, device=s.device)
+    lib().call("e4s_ct_moments", _p(part[0]), _p(s), _p(sm), bs, h, w, _stream())
+    lib().call("e4s_ct_moments", _p(part[1]), _p(t), _p(tm), bs, h, w, _stream())
+    lib().call("e4s_ct_solve", _p(coef), _p(part[0]), _p(part[1]), bs, h, w, mode, _stream())
+    return coef
+
+
+def skin_color_transfer(src_u8: torch.Tensor, trg_u8: torch.Tensor, src_mask: torch.Tensor, trg_mask: torch.Tensor, ct_mode: str = "lct",
+                        with_q: bool = True):
+    """Steps 3 - 6a of ``_color_transfer``'s arithmetic branch (Face_swap_with_two_imgs.py:555-568) for ``ct_mode`` 'lct' (``linear_color_transfer``,
+    mode 'pca', swap_face_fine/color_transfer.py:345-381) or 'mkl' (``color_transfer_mkl``, :218-246) on the device:
+
+        src = (D * src_mask) / 255, trg = (T * trg_mask) / 255;   q = uint8(skin_color_transfer(src, trg, ct_mode))      (truncated)
+        composed = D * (1 - src_mask) + q * src_mask                                                                     (numpy's float32 arithmetic)
+
+    ``src_u8`` (D, the swapped face) / ``trg_u8`` (T): uint8 ``[bs, H, W, 3]``; the masks float32 ``[bs, 1, H, W]``.  Returns ``(composed, q)``: float32
+    ``[bs, 3, H, W]`` (the layout ``blending`` takes) and uint8 ``[bs, H, W, 3]`` (None with ``with_q=False``).  The other modes of the reference go through
+    cv2, random rotations or a network and raise ``ValueError``."""
+    _ct_mode_checked(ct_mode, "skin_color_transfer")
+    s, t, sm, tm = _ct_inputs("skin_color_transfer", src_u8, trg_u8, src_mask, trg_mask)
+    bs, h, w, _ = s.shape
+    composed = torch.empty((bs, 3, h, w), dtype=torch.float32, device=s.device)
+    q = torch.empty_like(s) if with_q else None
+    if bs == 0:
+        return composed, q
+    coef = color_transfer_coefficients(s, t, sm, tm, ct_mode)
+    lib().call("e4s_ct_apply", _p(composed), _p(q), _p(s), _p(sm), _p(coef), bs, h, w, _stream())
+    return composed, q
+
+
+__all__ = ['CT_MODES', 'CT_MODES_UNSUPPORTED', 'GREY_MORPH_MAX_RADIUS', 'grey_dilate', 'grey_erode', 'soft_expansion_masks', 'color_transfer_coefficients',
+           'skin_color_transfer', '_labels_u8','swap_head_mask', 'foreground_masks', 'frames_to_tensor', 'PTI_BG_CLASSES', 'erode_labels', '_pil_tables', '_pil_resample_tables', '_pil_bicubic_tables', '_pil_lanczos_tables', 'pil_resize', 'crop_align', 'paste_into_frames', 'pyr_down', 'pyr_up', 'laplacian_blend', 'blending',
            'FACIAL_CLASSES', 'soft_erosion', 'soft_paste_masks', 'facial_mask12', 'blend_with_mask']

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import ops
+from . import ops, ops_post
 
 DEFAULT_COMP_INDICES = tuple(sorted(set(range(12)) - {0, 4, 11}))      # face_swap_video_pipeline.py:436: keep target background, hair, ear-rings
 # the two-image caller (Face_swap_with_two_imgs.py:469-472): it also keeps the target's eye glasses (10) and, with colour transfer, its neck and ears
@@ -81,7 +81,8 @@ def swap_batch(net, parser, driven: torch.Tensor, target: torch.Tensor, comp_ind
                ear_interpolation: bool = True):
     """``driven`` / ``target``: ``[bs, 3, 1024, 1024]`` in [-1, 1] on the device.  Returns uint8 ``[bs, 1024, 1024, 3]`` frames
     (or the float image) and the 12-class region maps the synthesis used; with ``mask_surgery`` a third value
-    ``{"hole_mask", "hole_map", "lines", "content", "border", "full"}`` (the reference's paste-back inputs, :456-463).
+    ``{"hole_mask", "hole_map", "lines", "content", "border", "full", "target_labels"}`` (the reference's paste-back inputs, :456-463, and the
+    target's own 12-class map, which the image caller's colour transfer needs).
     ``ear_interpolation`` goes to ``mix_style_vectors``.
 
     f16 range (``ops.MxGuard``): parser, encoder and the masked synthesis layers run in f16-based split arithmetic.  The batch is bracketed by ONE
@@ -198,7 +199,7 @@ def _swap_batch_once(net, parser, driven, target, comp_indices, randomize_noise,
     if mask_surgery:
         lab, hole, hole_map, lines = ops.swap_head_mask(lab_d, lab_t)
         content, border, full = ops.foreground_masks(lab, hole, paste_radius)
-        extra = {"hole_mask": hole, "hole_map": hole_map, "lines": lines, "content": content, "border": border, "full": full}
+        extra = {"hole_mask": hole, "hole_map": hole_map, "lines": lines, "content": content, "border": border, "full": full, "target_labels": lab_t}
         mark("mask_surgery")
     img, _, _ = net.gen_img(None, codes, lab, randomize_noise=randomize_noise)
     mark("gen_img")
@@ -306,30 +307,74 @@ def color_blend(swapped_u8: torch.Tensor, recolored_u8: torch.Tensor, labels: to
     return ops.blend_with_mask(swapped_u8, recolored_u8, mask, up_ratio)
 
 
+CT_FACE_CLASSES = (1, 2, 3, 5, 6, 9, 7, 8)        # _color_transfer's face (Face_swap_with_two_imgs.py:540-541): facial_mask12's classes plus the ears
+CT_BORDER_RADIUS = 10                             # :549
+
+
 @torch.no_grad()
-def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tensor, plan, recolor_fn=None, **swap_batch_kwargs) -> torch.Tensor:
+def color_transfer(swapped_u8: torch.Tensor, target_u8: torch.Tensor, swapped_labels: torch.Tensor, target_labels: torch.Tensor,
+                   ct_mode: str = "lct") -> torch.Tensor:
+    """The arithmetic branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:537-572) for ``ct_mode`` 'lct' / 'mkl', on the device:
+
+        md, mt = the face classes of the swapped / the target map, bilinear to the frame size (align_corners=False)                  (:540-547)
+        border = soft_expansion_masks(md, radius 10)[1]                                                                             (:549)
+        composed, _ = skin_color_transfer(D, T, md, mt, ct_mode)                                                                    (:555-568)
+        out = blending(D, composed, mask=border)                                                                                    (:570)
+
+    ``swapped_u8`` (D) / ``target_u8`` (T): uint8 ``[bs, 1024, 1024, 3]``; the maps uint8 ``[bs, h, w]`` (``lab`` and ``extra["target_labels"]`` of
+    ``swap_batch(..., mask_surgery=True)``).  Returns uint8 ``[bs, 1024, 1024, 3]``.  No host synchronisation; capturable in a hipGraph.  The reference's
+    default mode (the Blender network) and its cv2 / random-rotation modes raise ``ValueError``."""
+    ops_post._ct_mode_checked(ct_mode, "color_transfer")
+    _crops_checked("color_transfer", swapped_u8, target_u8)
+    bs, h, w, _ = swapped_u8.shape
+    ld, lt = ops._labels_u8(swapped_labels, "swapped_labels"), ops._labels_u8(target_labels, "target_labels")
+    if ld.shape != lt.shape or ld.shape[0] != bs:
+        raise ValueError(f"color_transfer: {tuple(ld.shape)} and {tuple(lt.shape)} label maps for {bs} frames")
+    if bs == 0:
+        return torch.empty_like(swapped_u8)
+    lut = ops_post._class_lut(CT_FACE_CLASSES, ld.device)
+    both = lut[torch.cat([ld, lt]).long()][:, None]
+    both = ops.bilinear_resize(both, (h, w), align_corners=False) if tuple(both.shape[-2:]) != (h, w) else both
+    md, mt = both[:bs], both[bs:]
+    border = ops.soft_expansion_masks(md, CT_BORDER_RADIUS)[1]
+    composed, _ = ops.skin_color_transfer(swapped_u8, target_u8, md, mt, ct_mode, with_q=False)
+    d = swapped_u8.permute(0, 3, 1, 2).contiguous()
+    return ops.blending(d, composed, border).permute(0, 2, 3, 1).contiguous()
+
+
+@torch.no_grad()
+def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tensor, plan, recolor_fn=None, ct_mode: Optional[str] = None,
+                **swap_batch_kwargs) -> torch.Tensor:
     """The two-image caller's chain (``FaceSwap.face_swap_pipeline``, Face_swap_with_two_imgs.py:796-963, without its inpainting / Blender / GPEN
     networks) for a batch of target images, all on the device:
 
         crop_align -> frames_to_tensor -> swap_batch(mask_surgery=True, ear_interpolation=False, comp_indices=IMAGE_COMP_INDICES[_CT])
-        [-> color_blend(swapped, recolor_fn(swapped, crops), labels)]                  (:909-924, when ``recolor_fn`` is given)
+        [-> color_blend(swapped, recolored, labels)]                                   (:909-924, when ``ct_mode`` or ``recolor_fn`` is given)
         -> paste_back_soft(swapped map, hole)                                          (:938)
         -> paste_back_soft(all-skin rectangle map, no hole)                            (:883, :958)
         -> paste_into_frames
 
     ``driven``: ``[n, 3, 1024, 1024]`` in [-1, 1]; ``target_images_u8``: uint8 ``[n, H, W, 3]`` on the device; ``plan``: their ``align.CropPlan``;
-    ``recolor_fn(swapped_u8, crops_u8) -> uint8 [n, 1024, 1024, 3]``: the caller's colour transfer.  Returns uint8 ``[n, H, W, 3]``, every pixel
-    outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch``, with the guard and stream behaviour of ``swap_frames``."""
+    ``ct_mode`` 'lct' / 'mkl': step 2 on the device, ``recolored = color_transfer(swapped, crops, swapped map, target map, ct_mode)``;
+    ``recolor_fn(swapped_u8, crops_u8) -> uint8 [n, 1024, 1024, 3]``: a colour transfer of the caller's own instead (the reference's other modes need cv2
+    or a network); passing both raises ``TypeError``.  Returns uint8 ``[n, H, W, 3]``, every pixel outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch``, with the guard and stream behaviour of ``swap_frames``."""
     for k in ("mask_surgery", "to_uint8", "ear_interpolation", "comp_indices"):
         if k in swap_batch_kwargs:
             raise TypeError(f"swap_images: {k} is fixed (the image caller's style mix, and the paste needs the uint8 face and the mask-surgery hole)")
+    if ct_mode is not None and recolor_fn is not None:
+        raise TypeError("swap_images: ct_mode and recolor_fn are two ways to do step 2, the colour transfer: pass one of them")
+    if ct_mode is not None:
+        ops_post._ct_mode_checked(ct_mode, "swap_images")
+    recolor = ct_mode is not None or recolor_fn is not None
     crops = ops.crop_align(target_images_u8, plan)
     target = ops.frames_to_tensor(crops)
     # (mask_surgery=True also computes the video caller's hard radius-5 paste masks, which this path does not use: one byte-wise launch per batch,
     # < 0.1 ms, accepted rather than giving swap_batch another switch)
     swapped, lab, extra = swap_batch(net, parser, driven, target, mask_surgery=True, ear_interpolation=False,
-                                     comp_indices=IMAGE_COMP_INDICES_CT if recolor_fn is not None else IMAGE_COMP_INDICES, **swap_batch_kwargs)
-    if recolor_fn is not None:
+                                     comp_indices=IMAGE_COMP_INDICES_CT if recolor else IMAGE_COMP_INDICES, **swap_batch_kwargs)
+    if ct_mode is not None:
+        swapped = color_blend(swapped, color_transfer(swapped, crops, lab, extra["target_labels"], ct_mode), lab)
+    elif recolor_fn is not None:
         swapped = color_blend(swapped, recolor_fn(swapped, crops), lab)
     pasted = paste_back_soft(swapped, crops, lab, extra["hole_mask"])
     pasted = paste_back_soft(pasted, crops, torch.full_like(lab, 6), None)

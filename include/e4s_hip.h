@@ -734,6 +734,27 @@ E4S_API int e4s_pix_mse_multi(float* partial, const float* x, const float* fg, c
 E4S_API int e4s_pix_mse_multi_bwd(float* gx, const float* x, const float* fg, const float* const* ys, const float* tw, int k, const int* frame,
                                   int64_t fstride, int nframes, const float* gout, int bs, int C, int64_t hw, void* stream);
 
+/* f7: the two-image caller's skin colour transfer for ct_mode 'lct' / 'mkl' (Face_swap_with_two_imgs.py:537-572, swap_face_fine/color_transfer.py:218-246,
+ * 345-381, utils/morphology.py:23-198; csrc/colortransfer.hip).
+ *   e4s_grey_morph   : out [planes][h][w] = flat (2 radius + 1)^2 maximum (op 0, dilation) or minimum (op 1, erosion) of x, pixels outside the image ignored
+ *                      (the 'geodesic' border); radius 0 .. 16, 0 = a copy; any h, w >= 1.  Exact.  out must not alias x.
+ *   e4s_ct_moments   : partial [bs][nchunk][9] doubles = per pixel chunk the sums of v_0, v_1, v_2, v_0 v_0, v_0 v_1, v_0 v_2, v_1 v_1, v_1 v_2, v_2 v_2 with
+ *                      v_c = (float(frame[b][p][c]) * mask[b][p]) / 255.0f in float32 (a true division); frame uint8 [bs][h][w][3], mask float [bs][1][h][w];
+ *                      nchunk = ceil(h w / 4096).  e4s_ct_moments_scratch_bytes: the size of `partial` for one call.
+ *   e4s_ct_solve     : coef [bs][15] doubles = (A row-major [3][3], mu_src [3], mu_trg [3]) from the two partial buffers, summed in a fixed order:
+ *                      mode 0 (lct, 'pca'):  C = cov / N + 1e-5 I,  A = sqrtm(C_trg) inv(sqrtm(C_src))
+ *                      mode 1 (mkl):         a, b = cov / (N - 1) of src, trg, eigenvalues clipped to DBL_EPSILON,
+ *                                            A^T = a^-1/2 (a^1/2 b a^1/2)^1/2 a^-1/2
+ *                      by cyclic Jacobi sweeps in float64, so that y = A (v - mu_src) + mu_trg.  One wave per image, no host round trip.
+ *   e4s_ct_apply     : per pixel and channel v as above, y in float64 rounded to float32 and clipped to [0, 1], q = trunc(y * 255.0f);
+ *                      composed [bs][3][h][w] = float(frame) * (1 - mask) + float(q) * mask in float32 without contraction; q_u8 [bs][h][w][3] or NULL.
+ * partial and coef hold doubles (8-byte aligned; void* in this header).  No float atomics: the same inputs give the same bits. */
+E4S_API int e4s_grey_morph(float* out, const float* x, int planes, int h, int w, int radius, int op, void* stream);
+E4S_API int e4s_ct_moments_scratch_bytes(int bs, int h, int w, int64_t* bytes);
+E4S_API int e4s_ct_moments(void* partial, const uint8_t* frame, const float* mask, int bs, int h, int w, void* stream);
+E4S_API int e4s_ct_solve(void* coef, const void* partial_src, const void* partial_trg, int bs, int h, int w, int mode, void* stream);
+E4S_API int e4s_ct_apply(float* composed, uint8_t* q_u8, const uint8_t* frame, const float* mask, const void* coef, int bs, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
