@@ -387,7 +387,7 @@ static int launch_small_cin(float* out, const float* x, const float* wt, const f
 extern "C" int e4s_conv2d(float* out, const float* x0, const float* x1, int cin0, const float* wt, const float* bias, const float* in_mean,
                           const float* in_rstd, const float* prelu_slope, const float* residual, int act, int bs, int cin, int cout, int h, int w,
                           int ks, int stride, int pad, void* stream) {
-    E4S_REQUIRE(out && x0 && wt, "conv2d: null tensor");
+    E4S_REQUIRE(wt && (bs == 0 || (out && x0)), "conv2d: null tensor");      // (an empty batch has no storage: its pointers may be null)
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "conv2d: bad size");
     E4S_REQUIRE(stride == 1 || stride == 2, "conv2d: stride %d not supported (1 or 2)", stride);
     E4S_REQUIRE(pad >= 0 && pad <= ks, "conv2d: bad padding");
@@ -681,6 +681,11 @@ __global__ __launch_bounds__(64 * WC * WP, 2) void conv2d_sb_kernel(const Conv2d
         }
     };
     bool ovf = false;      // (NS = 4) a staged activation left the f16 range
+    // (NS = 4) the padding channels of the last chunk hold a clamped real channel's RAW values (m = 0, r = 1 above): harmless in bf16, where they meet zero weights,
+    // but a raw value beyond the f16 range would become an infinity — a false range report, and inf * 0 = NaN in every output.  They are staged as exact zeros.
+    // (A zero scale for those channels in load_chunk would be stateless and cover every arithmetic, but it costs every instantiation ~16 VGPRs — the scale stops
+    // being the constant 1 of the launches without norm-on-load — and made <3,2,2,1,1,4,5,1,3> spill; this form leaves the NS = 2 / 3 code as it was.)
+    int cleft = p.cin;     // (NS = 4) channels that exist from the chunk being staged onwards (chunks are staged in order)
     auto store_chunk = [&](const float (&xs)[CKS2][C::EPT], const unsigned (&ws)[C::WPT][4], const float (&m)[CKS2], const float (&r)[CKS2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < C::EPT; ++j) {
@@ -690,9 +695,11 @@ __global__ __launch_bounds__(64 * WC * WP, 2) void conv2d_sb_kernel(const Conv2d
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
                     // padding stays exactly 0: the normalisation applies to in-bounds pixels only
-                    const float t0 = ginb[j] ? (xs[2 * c][j] - m[2 * c]) * r[2 * c] : 0.f;
-                    const float t1 = ginb[j] ? (xs[2 * c + 1][j] - m[2 * c + 1]) * r[2 * c + 1] : 0.f;
+                    float t0 = ginb[j] ? (xs[2 * c][j] - m[2 * c]) * r[2 * c] : 0.f;
+                    float t1 = ginb[j] ? (xs[2 * c + 1][j] - m[2 * c + 1]) * r[2 * c + 1] : 0.f;
                     if constexpr (NS == 4) {
+                        if (2 * c >= cleft) t0 = 0.f;
+                        if (2 * c + 1 >= cleft) t1 = 0.f;
                         c2_split2_f16(t0, t1, h[c], l[c]);
                         const unsigned em = h[c] & 0x7c007c00u;            // an f16 exponent field of 31: the value rounded to infinity
                         ovf |= (em & 0xffffu) == 0x7c00u || (em >> 16) == 0x7c00u;
@@ -720,6 +727,7 @@ __global__ __launch_bounds__(64 * WC * WP, 2) void conv2d_sb_kernel(const Conv2d
             const int idx = tid + v * C::NT;
             if (idx < C::W4) wsm[idx] = make_uint4(ws[v][0], ws[v][1], ws[v][2], ws[v][3]);
         }
+        if constexpr (NS == 4) cleft -= CKS2;
     };
     auto compute_chunk = [&]() __attribute__((always_inline)) {
         const uint4* whalf = wsm + khalf * C::TN + wc * CB * 32 + l5;
@@ -902,7 +910,7 @@ static int dispatch2d_5x5(Conv2dSbParams& p, hipStream_t st) {
 static int conv2d_sb_common(int nterms, float* out, const float* x0, const float* x1, int cin0, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2,
                             const float* bias, const float* in_mean, const float* in_rstd, const float* prelu_slope, const float* residual, int act,
                             int bs, int cin, int cout, int h, int w, int ks, int stride, int pad, void* stream, float out_scale = 1.f, int* flags = nullptr) {
-    E4S_REQUIRE(out && x0 && w0 && w1 && (nterms != 3 || w2), "conv2d_sb: null tensor");
+    E4S_REQUIRE(w0 && w1 && (nterms != 3 || w2) && (bs == 0 || (out && x0)), "conv2d_sb: null tensor");      // (an empty batch has no storage)
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "conv2d_sb: bad size");
     E4S_REQUIRE(stride == 1 || stride == 2, "conv2d_sb: stride %d not supported (1 or 2)", stride);
     E4S_REQUIRE(pad >= 0 && pad <= ks, "conv2d_sb: bad padding");
