@@ -6,7 +6,8 @@ Layout
     ops.py       tensor-level wrappers (torch = device memory + stream plumbing only)
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
-                 ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``)
+                 ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
+                 ``swap_face_fine/Blender/model_center/semantic_tools.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -52,9 +53,15 @@ LOSS_OVERRIDES = {
     "criteria.face_parsing.face_parsing_loss": "criteria/face_parsing/face_parsing_loss.py",
 }
 
+# Blender recolouring, stage 1 (row f8): the helpers of the reference's Referencer.forward, with the semantic colour reference on the device.  The rest of
+# swap_face_fine.Blender (the FPN, the Res-U-Net, BlenderInfer) stays the reference's own, run by stock PyTorch
+RECOLOR_OVERRIDES = {
+    "swap_face_fine.Blender.model_center.semantic_tools": "swap_face_fine/Blender/model_center/semantic_tools.py",
+}
+
 
 def _redirected():
-    return {**OVERRIDES, **LOSS_OVERRIDES}
+    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -71,7 +78,8 @@ _finder = None
 
 
 def install(force: bool = False) -> str:
-    """Redirect the hot-path module names (``OVERRIDES``) and the loss networks' (``LOSS_OVERRIDES``) to the drop-in files.
+    """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring helpers' (``RECOLOR_OVERRIDES``) to
+    the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

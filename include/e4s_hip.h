@@ -755,6 +755,29 @@ E4S_API int e4s_ct_moments(void* partial, const uint8_t* frame, const float* mas
 E4S_API int e4s_ct_solve(void* coef, const void* partial_src, const void* partial_trg, int bs, int h, int w, int mode, void* stream);
 E4S_API int e4s_ct_apply(float* composed, uint8_t* q_u8, const uint8_t* frame, const float* mask, const void* coef, int bs, int h, int w, void* stream);
 
+/* f8: Blender recolouring, stage 1 — the semantic colour reference `get_color_refer` (swap_face_fine/Blender/model_center/semantic_tools.py:50-167) and the
+ * reference channels of `Referencer.forward`'s packages (referencer.py:73-81; csrc/colorref.hip).  Nine parts p (skin hair eye nose lip tooth ear brow
+ * inpainting); parts_a / parts_t uint8 [bs][9][H][W] 0/1 masks; feats float [bs][256][h][w] with h * w <= 4096; img_t float [bs][3][H][W], ImageNet-normalised.
+ * Maps are brought to h x w by the nearest pick floor(i * (float(H) / h)).  Every sample is processed on its own.
+ *   e4s_colorref_scratch_bytes : the size of `scratch` (counts, pixel lists, unit rows, rgb_T); 16-byte aligned, shared by the calls below.
+ *   e4s_colorref_lists   : per (sample, part) the ascending pixel lists of A and T and their counts; present uint8 [bs][9] = both counts > 0.
+ *   e4s_colorref_rows    : per pixel the 256 channels minus their mean, divided by max(norm, 1e-8); rgb_T = clamp(img_t * std + mean, 0, 1);
+ *                          inv_target float [bs][3][h][w] = rgb_T * nearest(sum of the nine T masks), or NULL.  D must be 256.
+ *   e4s_colorref_attend  : refs float [bs][9][3][h][w] (the caller zeroes it): at A's pixels a of a present part
+ *                              sum_t softmax_t(tau c[a][t]) rgb_T[t],  c = the rows' dot product, a T row counting as zero where A's mask of the part is 0
+ *                          by an online softmax with a running maximum (any tau); tau is *tau_dev when tau_dev is not NULL (read on the device).
+ *                          inv_parts float [bs][9][3][h][w] (zeroed by the caller) or NULL: at T's pixels t, sum_a softmax_a(tau c[a][t]) refs[p][a].
+ *   e4s_colorref_sum_parts : inv [bs][3][h][w] = inv_parts summed over the parts in ascending order.
+ *   e4s_colorref_package : out float [bs][6][H][W] = bilinear (align_corners) resize of (sum of refs 0..7, refs 8), zero where fewer than two parts are present.
+ * No atomics, no host synchronisation; grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph. */
+E4S_API int e4s_colorref_scratch_bytes(int bs, int h, int w, int64_t* bytes);
+E4S_API int e4s_colorref_lists(void* scratch, uint8_t* present, const uint8_t* parts_a, const uint8_t* parts_t, int bs, int H, int W, int h, int w, void* stream);
+E4S_API int e4s_colorref_rows(void* scratch, float* inv_target, const float* feats_a, const float* feats_t, const float* img_t, const uint8_t* parts_t,
+                              int bs, int D, int H, int W, int h, int w, void* stream);
+E4S_API int e4s_colorref_attend(float* refs, float* inv_parts, const void* scratch, float tau, const float* tau_dev, int bs, int h, int w, void* stream);
+E4S_API int e4s_colorref_sum_parts(float* inv, const float* inv_parts, int bs, int h, int w, void* stream);
+E4S_API int e4s_colorref_package(float* out, const float* refs, const uint8_t* present, int bs, int H, int W, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
