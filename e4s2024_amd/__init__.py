@@ -7,7 +7,7 @@ Layout
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
                  ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
-                 ``swap_face_fine/Blender/model_center/semantic_tools.py``)
+                 ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -54,14 +54,19 @@ LOSS_OVERRIDES = {
 }
 
 # Blender recolouring, stage 1 (row f8): the helpers of the reference's Referencer.forward, with the semantic colour reference on the device.  The rest of
-# swap_face_fine.Blender (the FPN, the Res-U-Net, BlenderInfer) stays the reference's own, run by stock PyTorch
+# swap_face_fine.Blender (the FPN, BlenderInfer) stays the reference's own, run by stock PyTorch
 RECOLOR_OVERRIDES = {
     "swap_face_fine.Blender.model_center.semantic_tools": "swap_face_fine/Blender/model_center/semantic_tools.py",
 }
 
+# stage 2 (row f9): the Res-U-Net that turns the packages into the recoloured image, eval-mode forward on the device
+RECOLOR_NET_OVERRIDES = {
+    "swap_face_fine.Blender.model_center.res_u_net": "swap_face_fine/Blender/model_center/res_u_net.py",
+}
+
 
 def _redirected():
-    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES}
+    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -78,8 +83,8 @@ _finder = None
 
 
 def install(force: bool = False) -> str:
-    """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring helpers' (``RECOLOR_OVERRIDES``) to
-    the drop-in files.
+    """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
+    ``RECOLOR_NET_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -110,6 +110,29 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
     return s < in_size - 1 ? s : in_size - 1;
 }
 
+// Source coordinates of F.interpolate(mode='bilinear') along one axis, float32 as ATen forms them (norm.hip's e4s_bilinear_resize, resunet.hip's x2 upsampling):
+// the two source indices and the weight of the second.  The roundings are written out (no contraction left to the compiler, which fuses the product into the
+// subtraction of i0 at some call sites and not at others): src is rounded before i0 is taken off, as e4s_bilinear_resize has always compiled it.
+__device__ __forceinline__ void bilinear_coord(int dst, float scale, int align, int in_size, int& i0, int& i1, float& l1) {
+#pragma clang fp contract(off)
+    float src = align ? (float)dst * scale : fmaf((float)dst + 0.5f, scale, -0.5f);
+    if (!align && src < 0.f) src = 0.f;
+    i0 = (int)src;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    l1 = src - (float)i0;
+}
+
+// The bilinear blend of four neighbours, ATen's upsample_bilinear2d expression hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11), with its roundings
+// written out so that every kernel that inlines it gives the same bits: one fused multiply-add per row, the two rows multiplied and added unfused (the
+// form e4s_bilinear_resize has always compiled to).
+__device__ __forceinline__ float bilinear_blend(float v00, float v01, float v10, float v11, float ly, float lx) {
+#pragma clang fp contract(off)
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float top = fmaf(lx, v01, hx * v00), bottom = fmaf(hx, v10, lx * v11);
+    return hy * top + ly * bottom;
+}
+
 // Phase timestamps for kernel tuning (tools/phase_prof.py).  Only in the -DE4S_PHASE_PROF build (lib/libe4s_hip_prof.so); the
 // product library compiles these to nothing.
 #ifdef E4S_PHASE_PROF

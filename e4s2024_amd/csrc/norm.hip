@@ -583,14 +583,7 @@ extern "C" int e4s_masked_avg_pool(float* out, const float* feats, const uint8_t
 // ------------------------------------------------------------------------------------ bilinear resize
 // F.interpolate(mode='bilinear') for both align_corners settings (no antialias), planes = bs*C.
 //   align_corners=False: src = max(0, (dst + 0.5) * in/out - 0.5)      align_corners=True: src = dst * (in-1)/(out-1)
-__device__ __forceinline__ void bilinear_coord(int dst, float scale, int align, int in_size, int& i0, int& i1, float& l1) {
-    float src = align ? (float)dst * scale : ((float)dst + 0.5f) * scale - 0.5f;
-    if (!align && src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
+// bilinear_coord, bilinear_blend: common.h (csrc/resunet.hip upsamples with the same arithmetic)
 
 __global__ __launch_bounds__(256) void bilinear_kernel(float* __restrict__ out, const float* __restrict__ in, int ih, int iw, int oh, int ow,
                                                        float sy, float sx, int align) {
@@ -601,10 +594,9 @@ __global__ __launch_bounds__(256) void bilinear_kernel(float* __restrict__ out, 
     float ly, lx;
     bilinear_coord(y, sy, align, ih, y0, y1, ly);
     bilinear_coord(x, sx, align, iw, x0, x1, lx);
-    const float hy = 1.f - ly, hx = 1.f - lx;
     const float* p = in + (size_t)blockIdx.z * ih * iw;
-    // ATen upsample_bilinear2d: w00*v00 + w01*v01 + w10*v10 + w11*v11 grouped per row
-    const float v = hy * (hx * p[(size_t)y0 * iw + x0] + lx * p[(size_t)y0 * iw + x1]) + ly * (hx * p[(size_t)y1 * iw + x0] + lx * p[(size_t)y1 * iw + x1]);
+    // ATen upsample_bilinear2d: w00*v00 + w01*v01 + w10*v10 + w11*v11 grouped per row (bilinear_blend, common.h)
+    const float v = bilinear_blend(p[(size_t)y0 * iw + x0], p[(size_t)y0 * iw + x1], p[(size_t)y1 * iw + x0], p[(size_t)y1 * iw + x1], ly, lx);
     out[((size_t)blockIdx.z * oh + y) * ow + x] = v;
 }
 

@@ -1,4 +1,4 @@
-"""Row f8: Blender recolouring, stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
+"""Rows f8 and f9: Blender recolouring.  Stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
 
 ``color_reference`` is ``get_color_refer`` (swap_face_fine/Blender/model_center/semantic_tools.py:50-167): per facial part a masked cross-attention from the
 animated image's pixels A to the target's pixels T, ``ref_p[:, a] = sum_t softmax_t(tau cos(x_a, y_t)) rgb_T[:, t]``, and its inverse.  ``blender_part_masks`` and
@@ -11,15 +11,37 @@ Two departures from the reference, both where its result is not a function of it
 * with two or more parts present but no ``inpainting`` pixels on one side the reference raises ``KeyError``; here ``inpaint_ref`` is zero.
 
 ``light=True`` (the top-1000 subsampling) is the same tie problem at batch 1 and is not offered.  Supported: 256 feature channels, ``h * w <= 4096``.
+
+Row f9, stage 2 — the network that consumes the packages, ``ResUNet`` (swap_face_fine/Blender/model_center/res_u_net.py), eval mode, forward only
+(``blender_unet``, ``blender_recolor``).  Seven residual blocks and a 1x1 sigmoid head; every convolution on csrc/conv.hip's three-way split-bf16 kernel
+(fp32-class, no range guard, so nothing is read back), the glue on csrc/resunet.hip:
+
+    input block        c1 = relu(bn1(conv1(x)))                   bn1 and conv1.bias folded into conv1's weights, ReLU in the epilogue
+                       out = conv2(c1) + b2 + sqz(x)              sqz: the 1x1 shortcut on the raw input, added in conv2's epilogue
+    residual block     a = relu(bn1(x))                           e4s_resunet_preact: a pass of its own, x itself still feeds the shortcut
+                       c1 = relu(bn2(conv1(a)))                   bn2 and conv1.bias folded, the block's stride
+                       out = conv2(c1) + b2 + sqz(x)              sqz at the block's stride
+    decoder block      x = cat(up2(low), skip) is never formed: e4s_resunet_up_cat_preact writes a = relu(bn1(x)) and up2(low) in one pass, and sqz reads
+                       (up2(low), skip) through the convolution's two input pointers.  The shortcut is taken in this direct form; the commuted one,
+                       up2(W0 low) + W1 skip, was not measured and is not used.
+    head               sigmoid(W x + b)                           e4s_resunet_head (full-precision exponential)
+
+BatchNorm runs on its running statistics; a module in training mode is refused.  Prepared weights are cached per module and parameter version
+(``lossnet.prepare`` / ``weights_key``); the width (64, or 16 for the reference's ``small_FPN``) is read off the weights.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
+import torch.nn as nn
+import torch.nn.functional as F
 
+from . import lossnet
 from ._lib import lib
-from .ops import _p, _stream
+from .lossnet import bn_fold, prep_fwd, weights_key
+from .ops import _Prepared, _c, _p, _stream
 from .ops_post import GREY_MORPH_MAX_RADIUS, grey_dilate
 
 BLENDER_PARTS = ("skin", "hair", "eye", "nose", "lip", "tooth", "ear", "brow", "inpainting")
@@ -222,4 +244,225 @@ def blender_packages(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.T
     return packages, (inv, inv_target)
 
 
-__all__ = ["BLENDER_PARTS", "BLENDER_PART_IDS", "COLORREF_CHANNELS", "COLORREF_MAX_PIXELS", "blender_part_masks", "color_reference", "blender_packages"]
+# ------------------------------------------------------------------------------------------------ row f9: the Res-U-Net
+RESUNET_WIDTHS = (64, 16)                    # ResUNet(args): 64, or 16 with args.small_FPN
+RESUNET_IN_CHANNELS = 12
+_ENCODER = ("res_en_layer2", "res_en_layer3", "res_bridge_layer")
+_DECODER = ("res_de_layer3", "res_de_layer2", "res_de_layer1")
+
+
+class _Block(nn.Module):
+    """The parameters of one residual block under the reference's names.  ``first``: the input block (conv1 -> bn1 -> relu -> conv2, no pre-activation);
+    otherwise bn1 -> relu -> conv1 (stride) -> bn2 -> relu -> conv2.  Both add ``sqz_layer``, a 1x1 convolution of the block's raw input at its stride."""
+
+    def __init__(self, cin: int, cout: int, stride: int = 1, first: bool = False):
+        super().__init__()
+        self.first, self.stride = first, stride
+        if first:
+            self.conv1 = nn.Conv2d(cin, cout, 3, 1, 1)
+            self.bn1 = nn.BatchNorm2d(cout)
+        else:
+            self.bn1 = nn.BatchNorm2d(cin)
+            self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1)
+            self.bn2 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1)
+        self.sqz_layer = nn.Conv2d(cin, cout, 1, stride, 0) if cin != cout else nn.Sequential()       # the network's blocks all change the width
+
+    def forward(self, x):
+        if self.first:
+            y = F.relu(self.bn1(self.conv1(x)))
+        else:
+            y = F.relu(self.bn2(self.conv1(F.relu(self.bn1(x)))))
+        return self.conv2(y) + self.sqz_layer(x)
+
+
+class ResUNet(nn.Module):
+    """The recolouring network's Res-U-Net with the reference's ``state_dict`` keys and shapes (``latest_netG.pth``'s ``unet.*`` entries, the prefix taken
+    off, load with ``strict=True``).  ``width`` 64, or 16 for ``small_FPN``.  ``forward`` is the plain PyTorch composition — what the tests and the timing
+    compare ``blender_unet`` with; ``blender_unet(packages, module)`` runs the same weights on the HIP kernels."""
+
+    def __init__(self, width: int = 64):
+        super().__init__()
+        if width not in RESUNET_WIDTHS:
+            raise ValueError(f"ResUNet: width {width}, expected one of {RESUNET_WIDTHS}")
+        w = self.width = width
+        self.input_encoder_layer = _Block(RESUNET_IN_CHANNELS, w, first=True)
+        self.res_en_layer2 = _Block(w, 2 * w, 2)
+        self.res_en_layer3 = _Block(2 * w, 4 * w, 2)
+        self.res_bridge_layer = _Block(4 * w, 8 * w, 2)
+        self.res_de_layer3 = _Block(8 * w + 4 * w, 4 * w)
+        self.res_de_layer2 = _Block(4 * w + 2 * w, 2 * w)
+        self.res_de_layer1 = _Block(2 * w + w, w)
+        self.output_decoder_layer = nn.Sequential(nn.Conv2d(w, 3, 1), nn.Sigmoid())
+
+    def forward(self, pkgs):
+        skips = [self.input_encoder_layer(pkgs)]
+        for name in _ENCODER:
+            skips.append(getattr(self, name)(skips[-1]))
+        x = skips.pop()
+        for name in _DECODER:
+            x = getattr(self, name)(torch.cat([F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True), skips.pop()], dim=1))
+        return self.output_decoder_layer(x)
+
+
+@functools.lru_cache(maxsize=2)
+def _keys_shapes(width):
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in ResUNet(width).state_dict().items())
+
+
+def resunet_state_dict_shapes(width: int = 64):
+    """``{key: shape}`` of ``ResUNet(width).state_dict()``, in its order."""
+    return dict(_keys_shapes(width))
+
+
+def _resunet_mapping(weights):
+    if isinstance(weights, nn.Module):
+        return weights.state_dict()
+    if "input_encoder_layer.conv1.weight" not in weights and "unet.input_encoder_layer.conv1.weight" in weights:
+        return {k[len("unet."):]: v for k, v in weights.items() if k.startswith("unet.")}
+    return weights
+
+
+def _resunet_checked(name, weights):
+    """(mapping, width) of ``weights``: a module with the network's keys (``ResUNet``, the drop-in) in eval mode, or a mapping."""
+    if isinstance(weights, nn.Module):
+        if weights.training:
+            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; batch statistics are not offered: call .eval()")
+    elif not hasattr(weights, "keys"):
+        raise TypeError(f"{name}: weights must be a module or a mapping with the Res-U-Net's keys, got {type(weights).__name__}")
+    sd = _resunet_mapping(weights)
+    first = sd.get("input_encoder_layer.conv1.weight")
+    if first is None:
+        raise KeyError(f"{name}: the weights lack 'input_encoder_layer.conv1.weight': expected the keys of ResUNet (ops.resunet_state_dict_shapes())")
+    width = int(first.shape[0])
+    if width not in RESUNET_WIDTHS or tuple(first.shape[1:]) != (RESUNET_IN_CHANNELS, 3, 3):
+        raise ValueError(f"{name}: the first convolution is {tuple(first.shape)}: the network's width must be one of {RESUNET_WIDTHS}")
+    return sd, width
+
+
+def resunet_weight_tensors(weights):
+    """The float tensors of the network (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
+    sd, width = _resunet_checked("blender_unet", weights)
+    try:
+        return [sd[k] for k in resunet_state_dict_shapes(width) if not k.endswith("num_batches_tracked")]
+    except KeyError as e:
+        raise KeyError(f"blender_unet: the weights lack {e}: expected the keys of ResUNet({width})") from None
+
+
+class PreparedResUNet(_Prepared):
+    """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  Per block: ``pre`` the float32 (scale, shift) of
+    the pre-activation BatchNorm (None for the input block), ``conv1`` with the BatchNorm after it and its own bias folded in (float64), ``conv2`` and
+    ``sqz`` with their biases, all as three-way split slabs; ``head`` the output convolution's weight [3, width] and bias."""
+
+    __slots__ = ()
+
+    def get(self, weights):
+        ts = resunet_weight_tensors(weights)
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd, width = _resunet_checked("blender_unet", weights)
+        sd = {k: _c(sd[k].detach(), k) for k in resunet_state_dict_shapes(width) if not k.endswith("num_batches_tracked")}
+        blocks = {}
+        with torch.no_grad():
+            for name in ("input_encoder_layer",) + _ENCODER + _DECODER:
+                first = name == "input_encoder_layer"
+                pre = None
+                if not first:
+                    s, t = bn_fold(sd, name + ".bn1")
+                    pre = (s.float().contiguous(), t.float().contiguous())
+                s, t = bn_fold(sd, name + (".bn1" if first else ".bn2"))
+                blocks[name] = dict(pre=pre, stride=2 if name in _ENCODER else 1,
+                                    conv1=prep_fwd(sd[name + ".conv1.weight"], s, t + sd[name + ".conv1.bias"].double() * s),
+                                    conv2=prep_fwd(sd[name + ".conv2.weight"], None, sd[name + ".conv2.bias"]),
+                                    sqz=prep_fwd(sd[name + ".sqz_layer.weight"], None, sd[name + ".sqz_layer.bias"]))
+            head = (sd["output_decoder_layer.0.weight"].reshape(3, width).contiguous(), sd["output_decoder_layer.0.bias"].contiguous())
+        return self._publish(key, dict(width=width, blocks=blocks, head=head))
+
+
+def _conv3(x0, prepared, *, k, stride=1, relu=False, residual=None, x1=None):
+    """``e4s_conv2d_sb3`` on prepared ``(slabs, bias)``; input channels from ``x0`` then ``x1`` (a concatenation that is never formed)."""
+    slabs, bias = prepared
+    bs, c0, h, w = x0.shape
+    cin = c0 + (x1.shape[1] if x1 is not None else 0)
+    cout, pad = slabs[0].shape[3], k // 2
+    out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x0.device)
+    lib().call("e4s_conv2d_sb3", _p(out), _p(x0), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, None, _p(residual), 1 if relu else 0,
+               bs, cin, cout, h, w, k, stride, pad, _stream())
+    return out
+
+
+def _block(B, x, act, x1=None):
+    """conv1 (+ folded BatchNorm, ReLU) on ``act``, the 1x1 shortcut on the raw input (``x``, or ``x`` and ``x1``), conv2 + bias + shortcut."""
+    c1 = _conv3(act, B["conv1"], k=3, stride=B["stride"], relu=True)
+    shortcut = _conv3(x, B["sqz"], k=1, stride=B["stride"], x1=x1)
+    return _conv3(c1, B["conv2"], k=3, residual=shortcut)
+
+
+def _unet_forward(P, x):
+    blocks = P["blocks"]
+    skips = [_block(blocks["input_encoder_layer"], x, x)]
+    for name in _ENCODER:
+        B, x = blocks[name], skips[-1]
+        bs, c, h, w = x.shape
+        act = torch.empty_like(x)
+        lib().call("e4s_resunet_preact", _p(act), _p(x), _p(B["pre"][0]), _p(B["pre"][1]), bs, c, h * w, _stream())
+        skips.append(_block(B, x, act))
+    x = skips.pop()
+    for name in _DECODER:
+        B, skip = blocks[name], skips.pop()
+        bs, c_low, h, w = x.shape
+        c_skip = skip.shape[1]
+        up = torch.empty((bs, c_low, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        act = torch.empty((bs, c_low + c_skip, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        lib().call("e4s_resunet_up_cat_preact", _p(act), _p(up), _p(x), _p(skip), _p(B["pre"][0]), _p(B["pre"][1]), bs, c_low, c_skip, h, w, _stream())
+        x = _block(B, up, act, x1=skip)
+    bs, c, h, w = x.shape
+    out = torch.empty((bs, 3, h, w), dtype=torch.float32, device=x.device)
+    lib().call("e4s_resunet_head", _p(out), _p(x), _p(P["head"][0]), _p(P["head"][1]), bs, c, h * w, _stream())
+    return out
+
+
+def _unet_checked(name, packages, weights):
+    _tensor_checked(name, "packages", packages, torch.float32, 4, f"float32 [bs, {RESUNET_IN_CHANNELS}, H, W] packages")
+    bs, c, H, W = packages.shape
+    if c != RESUNET_IN_CHANNELS:
+        raise ValueError(f"{name}: packages: expected float32 [bs, {RESUNET_IN_CHANNELS}, H, W] packages, got {tuple(packages.shape)}")
+    if H < 8 or W < 8 or H % 8 or W % 8:
+        raise ValueError(f"{name}: packages are {H} x {W}: both sizes must be multiples of 8 (three stride-2 blocks), at least 8")
+    ts = resunet_weight_tensors(weights)
+    if any(t.device != packages.device for t in ts):
+        raise RuntimeError(f"{name}: device mismatch: packages on {packages.device}, the weights on {sorted({str(t.device) for t in ts})}")
+    _cuda_checked(name, packages=packages)
+
+
+def blender_unet(packages: torch.Tensor, weights) -> torch.Tensor:
+    """``ResUNet.forward`` (res_u_net.py:96-108) in eval mode on the device: float32 ``[bs, 3, H, W]`` in [0, 1] from the float32 ``[bs, 12, H, W]``
+    ``packages`` of ``blender_packages``; ``H`` and ``W`` multiples of 8.  ``weights``: a module with the network's keys (``ResUNet``, the drop-in
+    ``res_u_net.ResUNet``) or a mapping; the width is read off them.  Forward only, no gradient.  Every argument is checked before any launch; no host
+    synchronisation, the same inputs give the same bits, and after one eager call (which prepares the weights) the call captures in a graph."""
+    name = "blender_unet"
+    _unet_checked(name, packages, weights)
+    bs, _, H, W = packages.shape
+    if bs == 0:
+        return torch.empty((0, 3, H, W), dtype=torch.float32, device=packages.device)
+    with torch.no_grad():
+        return _unet_forward(lossnet.prepare(PreparedResUNet, weights), packages.detach().contiguous())
+
+
+def blender_recolor(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Tensor, labels_t: torch.Tensor, feats_a: torch.Tensor, feats_t: torch.Tensor,
+                    tau, weights):
+    """``Blender.forward`` after its FPN calls: ``(pred, packages, (inv, inv_target))`` with ``packages`` and the pair from ``blender_packages`` and
+    ``pred = blender_unet(packages, weights)``.  ``H`` and ``W`` multiples of 8."""
+    name = "blender_recolor"
+    _resunet_checked(name, weights)
+    if isinstance(img_t, torch.Tensor) and img_t.dim() == 4 and (img_t.shape[2] % 8 or img_t.shape[3] % 8):
+        raise ValueError(f"{name}: images are {img_t.shape[2]} x {img_t.shape[3]}: both sizes must be multiples of 8")
+    packages, pair = blender_packages(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau)
+    return blender_unet(packages, weights), packages, pair
+
+
+__all__ = ["BLENDER_PARTS", "BLENDER_PART_IDS", "COLORREF_CHANNELS", "COLORREF_MAX_PIXELS", "blender_part_masks", "color_reference", "blender_packages",
+           "RESUNET_WIDTHS", "ResUNet", "PreparedResUNet", "resunet_state_dict_shapes", "resunet_weight_tensors", "blender_unet", "blender_recolor"]

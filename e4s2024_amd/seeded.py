@@ -27,6 +27,7 @@ __all__ = [
     "seeded_lpips_state_dict",
     "seeded_irse50_state_dict",
     "seeded_unet_state_dict",
+    "seeded_resunet_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -183,8 +184,39 @@ def seeded_unet_state_dict(seed: int) -> Dict[str, torch.Tensor]:
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in state_dict_shapes().items()}, seed, "unet")
 
 
+# Res-U-Net of the recolouring network (swap_face_fine/Blender/model_center/res_u_net.py): fan-in scaled convolutions; eval BatchNorm values chosen to
+# catch a wrong fold — gamma over +-1.5 with one channel per layer exactly 0 and about half negative (a pre-activation written as (x - m) * s divides by
+# zero there), beta and running_mean over +-0.5, running_var over [0.5, 2]; the head convolution at a gain that spreads the sigmoid's output over (0, 1)
+# (at the default initialisation every output sits at 0.5 +- 0.04)
+RESUNET_HEAD_GAIN = 2.0
+
+
+def _gamma_with_a_zero(seed, key, shape):
+    a = seeded_array(seed, key, shape, 0.0, 1.5 / _SQRT3)
+    a[_rs(seed, key + "#zero").randint(shape[0])] = 0.0
+    return a
+
+
+_RULES_RESUNET = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"running_var$", (1.25, 0.75 / _SQRT3)),                         # U(0.5, 2)
+    (r"running_mean$", (0.0, 0.5 / _SQRT3)),                          # U(-0.5, 0.5)
+    (r"\.bn[12]\.weight$", _gamma_with_a_zero),
+    (r"\.bn[12]\.bias$", (0.0, 0.5 / _SQRT3)),
+    (r"\.bias$", (0.0, 0.1)),                                         # convolution biases
+    (r"^output_decoder_layer\.0\.weight$", _fan_in_std(RESUNET_HEAD_GAIN)),
+    (r"\.weight$", _fan_in_std(1.0)),
+]
+
+
+def seeded_resunet_state_dict(seed: int, width: int = 64) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for the recolouring ``ResUNet`` (``ops.ResUNet(width)``: the reference's keys; width 64, or 16 for ``small_FPN``)."""
+    from .ops_recolor import resunet_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in resunet_state_dict_shapes(width).items()}, seed, "resunet")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
-    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET}.get(family, _RULES_BISENET)
+    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

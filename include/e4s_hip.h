@@ -778,6 +778,21 @@ E4S_API int e4s_colorref_attend(float* refs, float* inv_parts, const void* scrat
 E4S_API int e4s_colorref_sum_parts(float* inv, const float* inv_parts, int bs, int h, int w, void* stream);
 E4S_API int e4s_colorref_package(float* out, const float* refs, const uint8_t* present, int bs, int H, int W, int h, int w, void* stream);
 
+/* f9: Blender recolouring, stage 2 — the glue of the Res-U-Net (swap_face_fine/Blender/model_center/res_u_net.py; csrc/resunet.hip) between its convolutions,
+ * which run on e4s_conv2d_sb3.  fp32 NCHW, eval BatchNorm as (scale, shift) per channel.
+ *   e4s_resunet_preact        : act [bs][C][hw] = max(x * scale[c] + shift[c], 0), the bn1 -> relu at the head of a ResBlock (x itself feeds the shortcut).
+ *                               Not e4s_id_affine with a zero slope: that writes -0.0 for a negative value.
+ *   e4s_resunet_up_cat_preact : u = bilinear x2 of low [bs][c_low][h][w] with align_corners (F.upsample_bilinear; e4s_bilinear_resize's float32 coordinates,
+ *                               scale (h - 1) / (2h - 1), 0 when h == 1); up [bs][c_low][2h][2w] = u (up may be NULL);
+ *                               act [bs][c_low + c_skip][2h][2w] = max(cat(u, skip) * scale[c] + shift[c], 0), skip [bs][c_skip][2h][2w].
+ *   e4s_resunet_head          : out [bs][3][hw] = sigmoid(w[3][C] . x[bs][C][hw] + b[3]) with the full-precision exponential; C is 64 or 16.
+ * 16-byte accesses along the pixel axis where the pointers (and, for preact / head, hw % 4 == 0) allow, one element per lane otherwise.  No atomics, no host
+ * synchronisation, grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_resunet_preact(float* act, const float* x, const float* scale, const float* shift, int bs, int C, int hw, void* stream);
+E4S_API int e4s_resunet_up_cat_preact(float* act, float* up, const float* low, const float* skip, const float* scale, const float* shift, int bs, int c_low,
+                                      int c_skip, int h, int w, void* stream);
+E4S_API int e4s_resunet_head(float* out, const float* x, const float* w, const float* b, int bs, int C, int hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
