@@ -7,7 +7,8 @@ Layout
     dropin/      files with the reference's module paths (``models/networks.py``, ``models/stylegan2/model.py``,
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
                  ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
-                 ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``)
+                 ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``,
+                 ``swap_face_fine/Blender/model_center/backbone.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -54,7 +55,7 @@ LOSS_OVERRIDES = {
 }
 
 # Blender recolouring, stage 1 (row f8): the helpers of the reference's Referencer.forward, with the semantic colour reference on the device.  The rest of
-# swap_face_fine.Blender (the FPN, BlenderInfer) stays the reference's own, run by stock PyTorch
+# swap_face_fine.Blender (referencer.py, blener.py, inference.py) stays the reference's own and runs on the three drop-ins
 RECOLOR_OVERRIDES = {
     "swap_face_fine.Blender.model_center.semantic_tools": "swap_face_fine/Blender/model_center/semantic_tools.py",
 }
@@ -64,9 +65,14 @@ RECOLOR_NET_OVERRIDES = {
     "swap_face_fine.Blender.model_center.res_u_net": "swap_face_fine/Blender/model_center/res_u_net.py",
 }
 
+# stage 3 (row f10): the feature networks (AdaptiveFeatureGenerator at the reference's default arguments, SmallFPN), eval-mode forward on the device
+RECOLOR_FPN_OVERRIDES = {
+    "swap_face_fine.Blender.model_center.backbone": "swap_face_fine/Blender/model_center/backbone.py",
+}
+
 
 def _redirected():
-    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES}
+    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -84,7 +90,7 @@ _finder = None
 
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
-    ``RECOLOR_NET_OVERRIDES``) to the drop-in files.
+    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -32,15 +32,16 @@ def weights_key(tensors) -> tuple:
 _CACHES = {}                                 # cache class -> WeakKeyDictionary[module, cache]
 
 
-def prepare(cache_cls, weights):
-    """Prepared copies (``cache_cls().get``) for ``weights``, cached on a module; a plain mapping is prepared on every call."""
+def prepare(cache_cls, weights, *checked):
+    """Prepared copies (``cache_cls().get``) for ``weights``, cached on a module; a plain mapping is prepared on every call.  ``checked``: what the
+    caller's own validation of ``weights`` already produced, handed to ``get`` so that it is not made twice."""
     if not isinstance(weights, torch.nn.Module):
-        return cache_cls().get(weights)
+        return cache_cls().get(weights, *checked)
     per_module = _CACHES.setdefault(cache_cls, weakref.WeakKeyDictionary())
     cache = per_module.get(weights)
     if cache is None:
         cache = per_module[weights] = cache_cls()
-    return cache.get(weights)
+    return cache.get(weights, *checked)
 
 
 def bn_fold(sd, prefix):

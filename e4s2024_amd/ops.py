@@ -12,7 +12,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_encode``  rows a8 - a10: the regional-style encoder's and the face parser's operators
 * ``ops_post``    rows f2 / f3 / f5: mask surgery, paste-back masks, Pillow's resize, multi-band blend, crop-align / paste into the frame
 * ``ops_grad``    row f1: the native gradients of the synthesis path
-* ``ops_recolor`` rows f8 / f9: Blender recolouring — the semantic colour reference and the Res-U-Net (resolved on first use, like any name a stage module defines late)
+* ``ops_recolor`` rows f8 / f9 / f10: Blender recolouring — the semantic colour reference, the Res-U-Net and the SPADE feature network (resolved on first use, like any name a stage module defines late)
 """
 from __future__ import annotations
 

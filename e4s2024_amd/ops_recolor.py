@@ -1,4 +1,4 @@
-"""Rows f8 and f9: Blender recolouring.  Stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
+"""Rows f8, f9 and f10: Blender recolouring.  Stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
 
 ``color_reference`` is ``get_color_refer`` (swap_face_fine/Blender/model_center/semantic_tools.py:50-167): per facial part a masked cross-attention from the
 animated image's pixels A to the target's pixels T, ``ref_p[:, a] = sum_t softmax_t(tau cos(x_a, y_t)) rgb_T[:, t]``, and its inverse.  ``blender_part_masks`` and
@@ -28,6 +28,20 @@ Row f9, stage 2 — the network that consumes the packages, ``ResUNet`` (swap_fa
 
 BatchNorm runs on its running statistics; a module in training mode is refused.  Prepared weights are cached per module and parameter version
 (``lossnet.prepare`` / ``weights_key``); the width (64, or 16 for the reference's ``small_FPN``) is read off the weights.
+
+Row f10, stage 3 — the feature network that produces ``feats_a`` / ``feats_t``, ``AdaptiveFeatureGenerator`` (swap_face_fine/Blender/model_center/backbone.py)
+at the reference's default arguments, or ``SmallFPN``; eval mode, forward only (``blender_fpn``, ``blender_features``, ``blender_forward``).  Its 19
+convolutions (five of the encoder, seven of the blocks, one gamma | beta per norm) run on csrc/conv.hip's three-way split-bf16 kernel, the glue on csrc/spade.hip.  That convolution pads with zeros only; the SPADE blocks pad
+by reflection, so the glue WRITES reflection-padded planes and the convolution runs on them with ``pad=0``:
+
+    encoder layer      x = leaky0.2(inorm(conv(x)))               e4s_plane_stats, then e4s_spade_modulate without gamma / beta; layer5 without the activation
+    shared MLPs        actv_n = relu(conv3x3(reflpad1(nearest(img))))   all seven norms in one launch (e4s_spade_shared), written padded: gamma and beta
+                                                                  depend on the image alone
+    SPADE norm         gamma | beta = one convolution 128 -> 2C on actv_n's padded slice; act(inorm(x) (1 + gamma) + beta) in e4s_spade_modulate, padded for
+                       conv_0 / conv_1 (leaky), unpadded with the identity for the 1x1 conv_s
+    block              out = conv_1(...) + bias + x_s in one epilogue (the convolution's residual pointer); norm_0 and norm_s share the statistics of x
+
+Spectral norm in eval mode makes no power iteration: ``weight_orig / (u . W v)`` is folded on the host in float64 when the weights are prepared.
 """
 from __future__ import annotations
 
@@ -382,12 +396,13 @@ class PreparedResUNet(_Prepared):
         return self._publish(key, dict(width=width, blocks=blocks, head=head))
 
 
-def _conv3(x0, prepared, *, k, stride=1, relu=False, residual=None, x1=None):
-    """``e4s_conv2d_sb3`` on prepared ``(slabs, bias)``; input channels from ``x0`` then ``x1`` (a concatenation that is never formed)."""
+def _conv3(x0, prepared, *, k, stride=1, relu=False, residual=None, x1=None, pad=None):
+    """``e4s_conv2d_sb3`` on prepared ``(slabs, bias)``; input channels from ``x0`` then ``x1`` (a concatenation that is never formed).  Zero padding
+    ``k // 2`` unless ``pad`` says otherwise (0 for an input that carries its reflection padding)."""
     slabs, bias = prepared
     bs, c0, h, w = x0.shape
     cin = c0 + (x1.shape[1] if x1 is not None else 0)
-    cout, pad = slabs[0].shape[3], k // 2
+    cout, pad = slabs[0].shape[3], k // 2 if pad is None else pad
     out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x0.device)
     lib().call("e4s_conv2d_sb3", _p(out), _p(x0), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, None, _p(residual), 1 if relu else 0,
                bs, cin, cout, h, w, k, stride, pad, _stream())
@@ -464,5 +479,373 @@ def blender_recolor(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
     return blender_unet(packages, weights), packages, pair
 
 
+# ------------------------------------------------------------------------------------------------ row f10: the feature network
+FPN_CHANNELS = COLORREF_CHANNELS             # both feature networks end in 256 channels
+SPADE_HIDDEN = 128                           # SPADE's nhidden (normalization.py:113)
+IN_EPS = 1e-5                                # nn.InstanceNorm2d
+_FPN_LAYERS = (("layer1", 3, 64, 1), ("layer2", 64, 128, 2), ("layer3", 128, 256, 1), ("layer4", 256, 512, 2), ("layer5", 512, 512, 1))
+_FPN_BLOCKS = (("head_0", 512, 512), ("G_middle_0", 512, 512), ("G_middle_1", 512, 256))
+_FPN_PREFIXES = ("referencer.FPN.", "FPN.")
+
+
+def _fpn_norms():
+    """The seven SPADE norms in the order their shared first layers are stacked for ``e4s_spade_shared``."""
+    return tuple(f"{b}.{n}" for b, fin, fout in _FPN_BLOCKS for n in ("norm_0", "norm_1") + (("norm_s",) if fin != fout else ()))
+
+
+class _SPADE(nn.Module):
+    """``SPADE('spadeinstance3x3', norm_nc, 3)`` (cmodules/normalization.py:87-155) under the reference's parameter names."""
+
+    def __init__(self, norm_nc: int, label_nc: int = 3):
+        super().__init__()
+        self.param_free_norm = nn.InstanceNorm2d(norm_nc, affine=False)
+        self.mlp_shared = nn.Sequential(nn.ReflectionPad2d(1), nn.Conv2d(label_nc, SPADE_HIDDEN, 3), nn.ReLU())
+        self.pad = nn.ReflectionPad2d(1)
+        self.mlp_gamma = nn.Conv2d(SPADE_HIDDEN, norm_nc, 3)
+        self.mlp_beta = nn.Conv2d(SPADE_HIDDEN, norm_nc, 3)
+
+    def forward(self, x, seg):
+        actv = self.pad(self.mlp_shared(F.interpolate(seg, size=x.shape[2:], mode="nearest")))
+        return self.param_free_norm(x) * (1 + self.mlp_gamma(actv)) + self.mlp_beta(actv)
+
+
+class _SPADEBlock(nn.Module):
+    """``SPADEResnetBlock(fin, fout, opt)`` (cmodules/architecture.py:19-96) with ``pad_type='nozero'``, spectral norm and no SE layer."""
+
+    def __init__(self, fin: int, fout: int):
+        super().__init__()
+        self.learned_shortcut = fin != fout
+        fmid = min(fin, fout)
+        self.pad = nn.ReflectionPad2d(1)
+        self.conv_0 = nn.utils.spectral_norm(nn.Conv2d(fin, fmid, 3))
+        self.conv_1 = nn.utils.spectral_norm(nn.Conv2d(fmid, fout, 3))
+        if self.learned_shortcut:
+            self.conv_s = nn.utils.spectral_norm(nn.Conv2d(fin, fout, 1, bias=False))
+        self.norm_0 = _SPADE(fin)
+        self.norm_1 = _SPADE(fmid)
+        if self.learned_shortcut:
+            self.norm_s = _SPADE(fin)
+
+    def forward(self, x, seg):
+        x_s = self.conv_s(self.norm_s(x, seg)) if self.learned_shortcut else x
+        dx = self.conv_0(self.pad(F.leaky_relu(self.norm_0(x, seg), 0.2)))
+        dx = self.conv_1(self.pad(F.leaky_relu(self.norm_1(dx, seg), 0.2)))
+        return x_s + dx
+
+
+class BlenderFPN(nn.Module):
+    """The recolouring network's feature network, ``AdaptiveFeatureGenerator`` (backbone.py:13-79) at the reference's default arguments, with its
+    ``state_dict`` keys and shapes (``latest_netG.pth``'s ``referencer.FPN.*`` entries, the prefix taken off, load with ``strict=True``): five
+    spectral-normalised convolutions with InstanceNorm and LeakyReLU(0.2) between them, then three SPADE residual blocks conditioned on the image itself.
+    ``forward`` is the plain PyTorch composition — what the tests and the timing compare ``blender_fpn`` with; ``blender_fpn(img, module)`` runs the same
+    weights on the HIP kernels.  In eval mode spectral norm makes no power iteration: the weight is ``weight_orig / (u . W v)``."""
+
+    def __init__(self):
+        super().__init__()
+        for name, cin, cout, stride in _FPN_LAYERS:
+            setattr(self, name, nn.Sequential(nn.utils.spectral_norm(nn.Conv2d(cin, cout, 3, stride, 1, bias=False)), nn.InstanceNorm2d(cout, affine=False)))
+        self.actvn = nn.LeakyReLU(0.2, False)
+        for name, fin, fout in _FPN_BLOCKS:
+            setattr(self, name, _SPADEBlock(fin, fout))
+
+    def forward(self, img, seg=None):
+        seg = img if seg is None else seg
+        x = self.layer1(img)
+        for name, *_ in _FPN_LAYERS[1:]:
+            x = getattr(self, name)(self.actvn(x))
+        for name, *_ in _FPN_BLOCKS:
+            x = getattr(self, name)(x, seg)
+        return x
+
+
+class SmallFPN(nn.Module):
+    """``SmallFPN`` (backbone.py:82-90), the feature network of ``small_FPN``: two 1x1 stride-2 convolutions with bias, 3 -> 256 -> 256."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, FPN_CHANNELS, 1, stride=2, padding=0)
+        self.conv2 = nn.Conv2d(FPN_CHANNELS, FPN_CHANNELS, 1, stride=2, padding=0)
+
+    def forward(self, x, y=None):
+        return self.conv2(self.conv1(x))
+
+
+class BlenderNet(nn.Module):
+    """A holder with the layout of ``Blender`` (blener.py) and of ``latest_netG.pth``: ``referencer.trainable_tao``, ``referencer.FPN.*``, ``unet.*``.
+    It has no forward of its own: ``blender_forward(..., weights=BlenderNet().eval())``."""
+
+    def __init__(self, small_FPN: bool = False):
+        super().__init__()
+        self.referencer = nn.Module()
+        self.referencer.trainable_tao = nn.Parameter(torch.tensor(1.))
+        self.referencer.FPN = SmallFPN() if small_FPN else BlenderFPN()
+        self.unet = ResUNet(16 if small_FPN else 64)
+
+
+@functools.lru_cache(maxsize=2)
+def _fpn_keys_shapes(small):
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in (SmallFPN() if small else BlenderFPN()).state_dict().items())
+
+
+def fpn_state_dict_shapes(small: bool = False):
+    """``{key: shape}`` of ``BlenderFPN().state_dict()`` (``SmallFPN()`` with ``small``), in its order."""
+    return dict(_fpn_keys_shapes(bool(small)))
+
+
+def _fpn_mapping(weights):
+    sd = weights.state_dict() if isinstance(weights, nn.Module) else weights
+    if "layer1.0.weight_orig" in sd or "conv1.weight" in sd:
+        return sd
+    for prefix in _FPN_PREFIXES:
+        if prefix + "layer1.0.weight_orig" in sd or prefix + "conv1.weight" in sd:
+            return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    return sd
+
+
+def _fpn_checked(name, weights):
+    """(mapping, small) of ``weights``: a module with a feature network's keys (``BlenderFPN``, ``SmallFPN``, the drop-ins) in eval mode, or a mapping."""
+    if isinstance(weights, nn.Module):
+        if weights.training:
+            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; spectral norm's power iteration is not offered: call .eval()")
+    elif not hasattr(weights, "keys"):
+        raise TypeError(f"{name}: weights must be a module or a mapping with the feature network's keys, got {type(weights).__name__}")
+    sd = _fpn_mapping(weights)
+    if "layer1.0.weight_orig" in sd:
+        return sd, False
+    if "conv1.weight" in sd:
+        return sd, True
+    raise KeyError(f"{name}: the weights have neither 'layer1.0.weight_orig' (BlenderFPN) nor 'conv1.weight' (SmallFPN): expected the keys of "
+                   f"ops.fpn_state_dict_shapes(), bare or prefixed with one of {_FPN_PREFIXES}")
+
+
+def _fpn_validated(name, weights):
+    """(mapping, small, tensors in key order) of ``weights``, keys, shapes and dtypes checked: made once per call and handed on."""
+    sd, small = _fpn_checked(name, weights)
+    out = []
+    for k, shape in fpn_state_dict_shapes(small).items():
+        t = sd.get(k)
+        if t is None:
+            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {'SmallFPN' if small else 'BlenderFPN'}")
+        if tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"{name}: '{k}' is {t.dtype} {tuple(t.shape)}, expected float32 {shape}")
+        out.append(t)
+    return sd, small, out
+
+
+def fpn_weight_tensors(weights, name: str = "blender_fpn"):
+    """The tensors of the feature network in key order, their shapes checked: what ``weights_key`` watches."""
+    return _fpn_validated(name, weights)[2]
+
+
+def _sigma_folded(sd, prefix):
+    """Eval-mode spectral norm: ``weight_orig / sigma`` with ``sigma = u . (W_mat v)`` from the stored vectors, formed in float64, as float32."""
+    w = sd[prefix + ".weight_orig"].double()
+    sigma = torch.dot(sd[prefix + ".weight_u"].double(), torch.mv(w.reshape(w.shape[0], -1), sd[prefix + ".weight_v"].double()))
+    return (w / sigma).float()
+
+
+class PreparedFPN(_Prepared):
+    """The kernels' copies of a feature network's weights, rebuilt when a tensor changes version or storage.  ``BlenderFPN``: ``layers`` the five
+    convolutions with sigma folded in, per block ``conv_0`` / ``conv_1`` (with bias) and ``conv_s`` likewise and per norm the gamma and beta convolutions
+    concatenated into one of ``2 C`` outputs, all as three-way split slabs; ``shared`` the first layers of the seven norms stacked ``[7 * 128, 3, 3, 3]``
+    with their biases.  ``SmallFPN``: its two convolutions."""
+
+    __slots__ = ()
+
+    def get(self, weights, checked=None):
+        sd, small, ts = checked if checked is not None else _fpn_validated("blender_fpn", weights)
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k in fpn_state_dict_shapes(small)}
+        with torch.no_grad():
+            if small:
+                return self._publish(key, dict(small=True, convs=[prep_fwd(sd[f"{n}.weight"], None, sd[f"{n}.bias"]) for n in ("conv1", "conv2")]))
+            layers = [dict(conv=prep_fwd(_sigma_folded(sd, name + ".0")), stride=stride) for name, _, _, stride in _FPN_LAYERS]
+            norms = _fpn_norms()
+            blocks = []
+            for name, fin, fout in _FPN_BLOCKS:
+                B = dict(conv_0=prep_fwd(_sigma_folded(sd, name + ".conv_0"), None, sd[name + ".conv_0.bias"]),
+                         conv_1=prep_fwd(_sigma_folded(sd, name + ".conv_1"), None, sd[name + ".conv_1.bias"]),
+                         conv_s=prep_fwd(_sigma_folded(sd, name + ".conv_s")) if fin != fout else None)
+                for n in ("norm_0", "norm_1") + (("norm_s",) if fin != fout else ()):
+                    p = f"{name}.{n}"
+                    B[n] = (norms.index(p), prep_fwd(torch.cat([sd[p + ".mlp_gamma.weight"], sd[p + ".mlp_beta.weight"]]), None,
+                                                     torch.cat([sd[p + ".mlp_gamma.bias"], sd[p + ".mlp_beta.bias"]])))
+                blocks.append(B)
+            shared = (torch.cat([sd[p + ".mlp_shared.1.weight"] for p in norms]).contiguous(), torch.cat([sd[p + ".mlp_shared.1.bias"] for p in norms]).contiguous())
+        return self._publish(key, dict(small=False, layers=layers, blocks=blocks, shared=shared, nnorms=len(norms)))
+
+
+def _plane_stats(x):
+    bs, c, h, w = x.shape
+    mean = torch.empty((bs * c,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    lib().call("e4s_plane_stats", _p(mean), _p(rstd), None, _p(x), bs * c, h * w, IN_EPS, _stream())
+    return mean, rstd
+
+
+def _modulate(x, stats, gamma_beta, leaky, padded):
+    """``e4s_spade_modulate``: act((x - mean) rstd (1 + gamma) + beta), or the plain InstanceNorm without ``gamma_beta``; padded by reflection or not."""
+    bs, c, h, w = x.shape
+    out = torch.empty((bs, c, h + 2, w + 2) if padded else (bs, c, h, w), dtype=torch.float32, device=x.device)
+    lib().call("e4s_spade_modulate", _p(out), _p(x), _p(stats[0]), _p(stats[1]), _p(gamma_beta), bs, c, h, w, 1 if leaky else 0, 1 if padded else 0, _stream())
+    return out
+
+
+def _fpn_forward(P, img):
+    if P["small"]:
+        return _conv3(_conv3(img, P["convs"][0], k=1, stride=2), P["convs"][1], k=1, stride=2)
+    x = img
+    for i, L in enumerate(P["layers"]):                                 # conv -> InstanceNorm -> LeakyReLU; layer5 ends with its InstanceNorm
+        y = _conv3(x, L["conv"], k=3, stride=L["stride"])
+        x = _modulate(y, _plane_stats(y), None, leaky=i + 1 < len(P["layers"]), padded=False)
+    bs, _, h, w = x.shape
+    # gamma and beta depend on the image alone: the first layers of all seven norms in one launch, each norm's slice a contiguous padded batch
+    actv = torch.empty((P["nnorms"], bs, SPADE_HIDDEN, h + 2, w + 2), dtype=torch.float32, device=x.device)
+    lib().call("e4s_spade_shared", _p(actv), _p(img), _p(P["shared"][0]), _p(P["shared"][1]), bs, P["nnorms"], img.shape[2], img.shape[3], h, w, _stream())
+
+    def spade(norm, src, stats, leaky, padded):
+        idx, gb = norm
+        return _modulate(src, stats, _conv3(actv[idx], gb, k=3, pad=0), leaky, padded)
+
+    for B in P["blocks"]:
+        stats = _plane_stats(x)                                         # norm_0 and norm_s normalise the same x
+        dx = _conv3(spade(B["norm_0"], x, stats, True, True), B["conv_0"], k=3, pad=0)
+        a1 = spade(B["norm_1"], dx, _plane_stats(dx), True, True)
+        shortcut = _conv3(spade(B["norm_s"], x, stats, False, False), B["conv_s"], k=1) if B["conv_s"] is not None else x
+        x = _conv3(a1, B["conv_1"], k=3, pad=0, residual=shortcut)
+    return x
+
+
+def fpn_output_size(H: int, W: int):
+    """The feature map of an ``H x W`` image: two stride-2 layers (3x3 with padding 1, or SmallFPN's 1x1 without: the same sizes)."""
+    return ((H - 1) // 2 + 1 - 1) // 2 + 1 if H >= 1 else 0, ((W - 1) // 2 + 1 - 1) // 2 + 1 if W >= 1 else 0
+
+
+def _fpn_image_checked(name, nm, img):
+    _tensor_checked(name, nm, img, torch.float32, 4, "a float32 [bs, 3, H, W] image")
+    if img.shape[1] != 3:
+        raise ValueError(f"{name}: {nm}: expected a float32 [bs, 3, H, W] image, got {tuple(img.shape)}")
+    h, w = fpn_output_size(img.shape[2], img.shape[3])
+    if h < 2 or w < 2:
+        raise ValueError(f"{name}: {nm} is {img.shape[2]} x {img.shape[3]}: its feature map would be {h} x {w}, reflection padding needs at least 2 x 2")
+    return h, w
+
+
+def _fpn_checked_all(name, weights, **images):
+    """Every check of a feature-network call, once; returns the validated weights for ``_fpn_prepared``."""
+    checked = _fpn_validated(name, weights)
+    ts = checked[2]
+    for nm, img in images.items():
+        _fpn_image_checked(name, nm, img)
+    shapes = {tuple(img.shape) for img in images.values()}
+    if len(shapes) != 1:
+        raise ValueError(f"{name}: the images differ in shape: {sorted(shapes)}")
+    for nm, img in images.items():
+        if any(t.device != img.device for t in ts):
+            raise RuntimeError(f"{name}: device mismatch: {nm} on {img.device}, the weights on {sorted({str(t.device) for t in ts})}")
+    _cuda_checked(name, **images)
+    return checked
+
+
+def _fpn_run(img, prepared):
+    """``prepared``: a callable that gives the prepared weights (not called for an empty batch, which has nothing to launch)."""
+    bs, _, H, W = img.shape
+    if bs == 0:
+        return torch.empty((0, FPN_CHANNELS) + fpn_output_size(H, W), dtype=torch.float32, device=img.device)
+    with torch.no_grad():
+        return _fpn_forward(prepared(), img.detach().contiguous())
+
+
+def _features_run(img_a, img_t, weights, checked, flip_target):
+    """The two FPN calls on weights validated by the caller and prepared once for both."""
+    P = []
+
+    def prepared():
+        if not P:
+            P.append(lossnet.prepare(PreparedFPN, weights, checked))
+        return P[0]
+
+    feats_a = _fpn_run(img_a, prepared)
+    return feats_a, _fpn_run(torch.flip(img_t, dims=[-1]) if flip_choice(flip_target) else img_t, prepared)
+
+
+def blender_fpn(img: torch.Tensor, weights) -> torch.Tensor:
+    """``AdaptiveFeatureGenerator.forward(img, img)`` (backbone.py:60-79, the reference's default arguments) or ``SmallFPN.forward`` in eval mode on the
+    device: float32 ``[bs, 256, h, w]`` features of a float32 ``[bs, 3, H, W]`` image, ``h = ceil(ceil(H / 2) / 2)`` (at least 2).  ``weights``: a module
+    with a feature network's keys (``BlenderFPN``, ``SmallFPN``, the drop-ins of ``backbone.py``) in eval mode, or a mapping, bare or with the keys of
+    ``latest_netG.pth`` (``referencer.FPN.``) or of the referencer (``FPN.``); which of the two networks is read off the keys.  A module's prepared weights
+    are cached per parameter version; a mapping is prepared on every call.  Forward only, no gradient.  Every argument is checked before any launch; no
+    host synchronisation, the same inputs give the same bits, and after one eager call (which prepares the weights) the call captures in a graph."""
+    checked = _fpn_checked_all("blender_fpn", weights, img=img)
+    return _fpn_run(img, lambda: lossnet.prepare(PreparedFPN, weights, checked))
+
+
+def flip_choice(flip_target=None) -> bool:
+    """Whether the target is mirrored before its features are taken.  ``None`` is ``Referencer.forward``'s rule (referencer.py:32-35): one
+    ``np.random.rand()``, no flip below 0.5."""
+    if flip_target is None:
+        import numpy as np
+        return not np.random.rand() < 0.5
+    if not isinstance(flip_target, bool):
+        raise TypeError(f"flip_target is True, False or None, got {type(flip_target).__name__}")
+    return flip_target
+
+
+def blender_features(img_a: torch.Tensor, img_t: torch.Tensor, weights, flip_target=None):
+    """The two FPN calls of ``Referencer.forward`` (referencer.py:29-36): ``(feats_a, feats_t)``, each exactly ``blender_fpn`` of ``img_a`` and of ``img_t``
+    or, when the target is flipped, of ``flip(img_t, -1)``; the features are not flipped back (the reference's line that would is commented out).
+    ``flip_target`` True / False decides; ``None`` draws like the reference (``flip_choice``), after the first call as it does, so a caller who seeds NumPy
+    gets the reference's choice."""
+    name = "blender_features"
+    if flip_target is not None and not isinstance(flip_target, bool):
+        raise TypeError(f"{name}: flip_target is True, False or None, got {type(flip_target).__name__}")
+    return _features_run(img_a, img_t, weights, _fpn_checked_all(name, weights, img_a=img_a, img_t=img_t), flip_target)
+
+
+def _blender_weights(name, weights):
+    """(FPN weights, tau, Res-U-Net weights) of a module or mapping with ``latest_netG.pth``'s layout."""
+    if isinstance(weights, nn.Module):
+        if weights.training:
+            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode: call .eval()")
+        ref = getattr(weights, "referencer", None)
+        if ref is None or not hasattr(ref, "FPN") or not hasattr(ref, "trainable_tao") or not hasattr(weights, "unet"):
+            raise TypeError(f"{name}: {type(weights).__name__} has no referencer.FPN, referencer.trainable_tao and unet (the layout of Blender)")
+        return ref.FPN, ref.trainable_tao.detach(), weights.unet
+    if not hasattr(weights, "keys"):
+        raise TypeError(f"{name}: weights must be a module or a mapping with the layout of latest_netG.pth, got {type(weights).__name__}")
+    if "referencer.trainable_tao" not in weights:
+        raise KeyError(f"{name}: the weights lack 'referencer.trainable_tao': expected the keys of latest_netG.pth (referencer.FPN.*, unet.*)")
+    return weights, weights["referencer.trainable_tao"].detach(), weights
+
+
+def blender_forward(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Tensor, labels_t: torch.Tensor, weights, flip_target=None):
+    """The whole of ``Blender.forward`` (blener.py:13-24) on the device: ``(pred, packages, (inv, inv_target))`` = ``blender_features`` followed by
+    ``blender_recolor`` with ``tau = referencer.trainable_tao`` (read by the kernel, never on the host).  ``weights``: a module (``BlenderNet``, the
+    reference's ``Blender`` over the drop-ins) in eval mode or a mapping with ``latest_netG.pth``'s layout: ``referencer.FPN.*``,
+    ``referencer.trainable_tao``, ``unet.*``.  Images float32 ``[bs, 3, H, W]`` with ``H`` and ``W`` multiples of 8, labels uint8 ``[bs, H, W]``."""
+    name = "blender_forward"
+    fpn, tau, unet = _blender_weights(name, weights)
+    if flip_target is not None and not isinstance(flip_target, bool):
+        raise TypeError(f"{name}: flip_target is True, False or None, got {type(flip_target).__name__}")
+    _resunet_checked(name, unet)
+    for nm, t in (("img_a", img_a), ("img_t", img_t)):
+        _fpn_image_checked(name, nm, t)
+    if img_t.shape[2] % 8 or img_t.shape[3] % 8:
+        raise ValueError(f"{name}: images are {img_t.shape[2]} x {img_t.shape[3]}: both sizes must be multiples of 8")
+    _labels_checked(name, labels_a, labels_t)
+    checked = _fpn_checked_all(name, fpn, img_a=img_a, img_t=img_t)
+    _cuda_checked(name, labels_a=labels_a, labels_t=labels_t)
+    if tau.numel() != 1 or tau.dtype != torch.float32 or tau.device != img_t.device:
+        raise ValueError(f"{name}: referencer.trainable_tao is one float32 element on the images' device, got {tau.dtype} {tuple(tau.shape)} on {tau.device}")
+    feats_a, feats_t = _features_run(img_a, img_t, fpn, checked, flip_target)
+    return blender_recolor(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau.reshape(1), unet)
+
+
 __all__ = ["BLENDER_PARTS", "BLENDER_PART_IDS", "COLORREF_CHANNELS", "COLORREF_MAX_PIXELS", "blender_part_masks", "color_reference", "blender_packages",
-           "RESUNET_WIDTHS", "ResUNet", "PreparedResUNet", "resunet_state_dict_shapes", "resunet_weight_tensors", "blender_unet", "blender_recolor"]
+           "RESUNET_WIDTHS", "ResUNet", "PreparedResUNet", "resunet_state_dict_shapes", "resunet_weight_tensors", "blender_unet", "blender_recolor",
+           "FPN_CHANNELS", "BlenderFPN", "SmallFPN", "BlenderNet", "PreparedFPN", "fpn_state_dict_shapes", "fpn_weight_tensors", "fpn_output_size",
+           "flip_choice", "blender_fpn", "blender_features", "blender_forward"]

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import ops, ops_post
+from . import ops, ops_post, ops_recolor
 
 DEFAULT_COMP_INDICES = tuple(sorted(set(range(12)) - {0, 4, 11}))      # face_swap_video_pipeline.py:436: keep target background, hair, ear-rings
 # the two-image caller (Face_swap_with_two_imgs.py:469-472): it also keeps the target's eye glasses (10) and, with colour transfer, its neck and ears
@@ -379,3 +379,46 @@ def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tenso
     pasted = paste_back_soft(swapped, crops, lab, extra["hole_mask"])
     pasted = paste_back_soft(pasted, crops, torch.full_like(lab, 6), None)
     return ops.paste_into_frames(pasted, target_images_u8, plan)
+
+
+BLENDER_SIZE = 256                      # BlenderInfer.infer_image resizes everything to 256 x 256 (inference.py:101-105)
+
+
+def blender_infer_inputs(img_a_u8: torch.Tensor, img_t_u8: torch.Tensor, labels_a_u8: torch.Tensor, labels_t_u8: torch.Tensor):
+    """The network inputs of ``BlenderInfer.infer_image`` (inference.py:101-114) for a batch, on the device: ``(img_a, img_t, labels_a, labels_t)``, float32
+    ``[bs, 3, 256, 256]`` and uint8 ``[bs, 256, 256]``, from uint8 ``[bs, H, W, 3]`` images and uint8 ``[bs, H, W]`` 19-class maps.
+
+    Everything goes through ``PIL.Image.resize((256, 256))`` with Pillow's default BICUBIC (``ops.pil_resize``, bit for bit).  That includes the label maps,
+    as mode-``L`` images: an oddity of the reference (a bicubic blend of class ids invents classes along every border), kept because the network was
+    trained and is run behind it.  The images then take ``ToTensor`` and ``Normalize`` in their order, in float32: ``(u8 / 255 - mean) / std``."""
+    name = "blender_infer_image"
+    for nm, t in (("img_a_u8", img_a_u8), ("img_t_u8", img_t_u8)):
+        ops_post._frames_u8(t, f"{name}: {nm}")
+    for nm, t in (("labels_a_u8", labels_a_u8), ("labels_t_u8", labels_t_u8)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {nm} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: {nm} must be a CUDA tensor")
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError(f"{name}: {nm}: expected a uint8 [bs, H, W] label map, got {t.dtype} {tuple(t.shape)}")
+    bs = img_a_u8.shape[0]
+    if any(t.shape[0] != bs for t in (img_t_u8, labels_a_u8, labels_t_u8)):
+        raise ValueError(f"{name}: the four inputs hold {[t.shape[0] for t in (img_a_u8, img_t_u8, labels_a_u8, labels_t_u8)]} samples")
+    size = (BLENDER_SIZE, BLENDER_SIZE)
+    _, _, mean, std = ops_recolor._consts(img_a_u8.device)
+    # a tensor as the divisor: by a Python scalar PyTorch multiplies by the rounded reciprocal on the device, which is not ToTensor's division on the host
+    full = torch.full((1,), 255.0, dtype=torch.float32, device=img_a_u8.device)
+    imgs = [((ops.pil_resize(t, size).permute(0, 3, 1, 2).float() / full) - mean) / std for t in (img_a_u8, img_t_u8)]
+    labels = [ops.pil_resize(t[..., None], size)[..., 0].contiguous() for t in (labels_a_u8, labels_t_u8)]
+    return imgs[0].contiguous(), imgs[1].contiguous(), labels[0], labels[1]
+
+
+@torch.no_grad()
+def blender_infer_image(weights, img_a_u8: torch.Tensor, img_t_u8: torch.Tensor, labels_a_u8: torch.Tensor, labels_t_u8: torch.Tensor,
+                        flip_target=None) -> torch.Tensor:
+    """``BlenderInfer.infer_image`` (inference.py:96-121) for a batch on the device: the colour of ``img_t`` transferred to ``img_a``, uint8
+    ``[bs, 256, 256, 3]`` = ``uint8(pred * 255)`` (truncating) of ``ops.blender_forward`` on ``blender_infer_inputs``.  ``weights`` and ``flip_target`` as
+    ``ops.blender_forward`` takes them (``ops.BlenderNet().eval()`` with ``latest_netG.pth`` loaded, or the reference's ``Blender`` over the drop-ins)."""
+    img_a, img_t, labels_a, labels_t = blender_infer_inputs(img_a_u8, img_t_u8, labels_a_u8, labels_t_u8)
+    pred, _, _ = ops.blender_forward(img_a, img_t, labels_a, labels_t, weights, flip_target)
+    return (pred * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()

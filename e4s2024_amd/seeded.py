@@ -28,6 +28,8 @@ __all__ = [
     "seeded_irse50_state_dict",
     "seeded_unet_state_dict",
     "seeded_resunet_state_dict",
+    "seeded_fpn_state_dict",
+    "seeded_small_fpn_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -215,8 +217,53 @@ def seeded_resunet_state_dict(seed: int, width: int = 64) -> Dict[str, torch.Ten
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in resunet_state_dict_shapes(width).items()}, seed, "resunet")
 
 
+# Feature network of the recolouring network (swap_face_fine/Blender/model_center/backbone.py).  A spectral-normalised convolution stores weight_orig and the
+# vectors u, v of the power iteration; in eval mode the weight is weight_orig / sigma with sigma = u . W v.  u and v are unit vectors; for random u, v and a
+# random W that product is a small number of either sign, so weight_orig is a fan-in scaled matrix W0 moved along u v^T until u . W v is FPN_SIGMA exactly
+# (in float64): what a trained layer looks like, a leading singular component of that size on top of the bulk.  FPN_SIGMA is not 1, so that a sigma left out
+# shows.  The SPADE first layers get He scale (a ReLU follows), biases are large enough to matter.
+FPN_SIGMA = 1.25
+
+
+def _unit_vector(seed, key, shape):
+    a = seeded_array(seed, key, shape, dist="normal").astype(np.float64)
+    return (a / np.linalg.norm(a)).astype(np.float32)
+
+
+def _spectral_weight(seed, key, shape):
+    base = key[:-len("_orig")]
+    w0 = _fan_in_std(1.0)(seed, key, shape).astype(np.float64).reshape(shape[0], -1)
+    u = _unit_vector(seed, base + "_u", (w0.shape[0],)).astype(np.float64)
+    v = _unit_vector(seed, base + "_v", (w0.shape[1],)).astype(np.float64)
+    w = w0 + (FPN_SIGMA - u @ w0 @ v) / ((u @ u) * (v @ v)) * np.outer(u, v)
+    return w.reshape(shape).astype(np.float32)
+
+
+_RULES_FPN = [
+    (r"\.weight_orig$", _spectral_weight),
+    (r"\.weight_[uv]$", _unit_vector),
+    (r"\.mlp_shared\.1\.weight$", _fan_in_std(1.4)),
+    (r"\.bias$", (0.0, 0.2)),
+    (r"\.weight$", _fan_in_std(1.0)),
+]
+
+
+def seeded_fpn_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for the recolouring feature network (``ops.BlenderFPN()``: the reference's ``AdaptiveFeatureGenerator`` keys at its default
+    arguments); every spectral-normalised convolution has unit ``weight_u`` / ``weight_v`` and ``sigma = FPN_SIGMA``."""
+    from .ops_recolor import fpn_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in fpn_state_dict_shapes(False).items()}, seed, "fpn")
+
+
+def seeded_small_fpn_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.SmallFPN()`` (the reference's ``SmallFPN`` keys)."""
+    from .ops_recolor import fpn_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in fpn_state_dict_shapes(True).items()}, seed, "fpn")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
-    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET}.get(family, _RULES_BISENET)
+    rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
+             "fpn": _RULES_FPN}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -793,6 +793,24 @@ E4S_API int e4s_resunet_up_cat_preact(float* act, float* up, const float* low, c
                                       int c_skip, int h, int w, void* stream);
 E4S_API int e4s_resunet_head(float* out, const float* x, const float* w, const float* b, int bs, int C, int hw, void* stream);
 
+/* f10: Blender recolouring, stage 3 — the glue of the feature network (swap_face_fine/Blender/model_center/backbone.py, cmodules/architecture.py,
+ * cmodules/normalization.py; csrc/spade.hip) between its convolutions, which run on e4s_conv2d_sb3.  That kernel pads with zeros only; the SPADE blocks pad by
+ * reflection, so both calls can write reflection-padded planes [C][h + 2][w + 2] (index -1 is 1, index n is n - 2) for a convolution with pad = 0.
+ *   e4s_spade_shared   : the first layer of nnorms SPADE norms in one launch.  seg = nearest pick of img [bs][3][H][W] at h x w (F.interpolate mode='nearest':
+ *                        floor(dst * (H / h)) in float32, clamped), actv = relu(conv3x3(reflpad1(seg)) + bias) with weight [nnorms * 128][3][3][3] and bias
+ *                        [nnorms * 128], written padded as actv [nnorms][bs][128][h + 2][w + 2] (one norm's slice is a contiguous batch).  Each output sums
+ *                        bias, then 27 fused multiply-adds in (input channel, row, column) order.  h, w >= 2.
+ *   e4s_spade_modulate : out = act((x - mean) * rstd * (1 + gamma) + beta) for x [bs][C][h][w], mean / rstd [bs * C] (e4s_plane_stats), gamma_beta
+ *                        [bs][2C][h][w] = gamma | beta (NULL: the plain InstanceNorm (x - mean) * rstd); act = v > 0 ? v : 0.2 v with leaky, identity
+ *                        without; out [bs][C][h][w], or with padded [bs][C][h + 2][w + 2] (then h, w >= 2).  Every operation is rounded on its own: the
+ *                        difference, the product with rstd, 1 + gamma, the product, the sum, the activation's product.  16-byte loads along a row when
+ *                        w % 4 == 0 and the pointers allow, one element per lane otherwise: the same bits.
+ * No atomics, no host synchronisation, grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.
+ * bs == 0 returns at once. */
+E4S_API int e4s_spade_shared(float* actv, const float* img, const float* weight, const float* bias, int bs, int nnorms, int H, int W, int h, int w, void* stream);
+E4S_API int e4s_spade_modulate(float* out, const float* x, const float* mean, const float* rstd, const float* gamma_beta, int bs, int C, int h, int w, int leaky,
+                               int padded, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
