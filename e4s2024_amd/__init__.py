@@ -8,7 +8,7 @@ Layout
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
                  ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
                  ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``,
-                 ``swap_face_fine/Blender/model_center/backbone.py``)
+                 ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -70,9 +70,14 @@ RECOLOR_FPN_OVERRIDES = {
     "swap_face_fine.Blender.model_center.backbone": "swap_face_fine/Blender/model_center/backbone.py",
 }
 
+# row f11: the Real-ESRGAN step behind the recolouring network (RealESRBatchInfer), without basicsr and cv2
+ENHANCE_OVERRIDES = {
+    "swap_face_fine.realesr.image_infer": "swap_face_fine/realesr/image_infer.py",
+}
+
 
 def _redirected():
-    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES}
+    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -90,7 +95,7 @@ _finder = None
 
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
-    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``) to the drop-in files.
+    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``) and the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -77,6 +77,10 @@ _PROTOS = {
     "e4s_resunet_head": [c_ptr] * 4 + [c_int] * 3 + [c_ptr],
     "e4s_spade_shared": [c_ptr] * 4 + [c_int] * 6 + [c_ptr],
     "e4s_spade_modulate": [c_ptr] * 5 + [c_int] * 6 + [c_ptr],
+    "e4s_esr_input": [c_ptr, c_ptr] + [c_int] * 5 + [c_ptr],
+    "e4s_esr_scale_add": [c_ptr] * 3 + [c_int] * 2 + [c_ptr],
+    "e4s_esr_up2": [c_ptr, c_ptr] + [c_int] * 3 + [c_ptr],
+    "e4s_esr_tail": [c_ptr] * 5 + [c_int] * 3 + [c_ptr],
     "e4s_mconv_unfold":[c_ptr] * 4 + [c_int] * 7 + [c_ptr],
     "e4s_mconv_scale": [c_ptr] * 9 + [c_int, c_ptr, c_ptr] + [c_int] * 8 + [c_ptr],
     "e4s_style_tables_bwd": [c_ptr] * 14 + [c_f32] * 3 + [c_int] * 5 + [c_ptr],

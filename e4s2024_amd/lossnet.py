@@ -44,6 +44,11 @@ def prepare(cache_cls, weights, *checked):
     return cache.get(weights, *checked)
 
 
+def caches_of(module):
+    """The caches ``prepare`` holds for ``module`` and the modules under it (``ops.invalidate_weight_caches`` empties them)."""
+    return [per_module[m] for per_module in _CACHES.values() for m in module.modules() if m in per_module]
+
+
 def bn_fold(sd, prefix):
     """Eval-mode BatchNorm as float64 (scale, shift): y = x * scale + shift."""
     g, b = sd[prefix + ".weight"].double(), sd[prefix + ".bias"].double()

@@ -12,7 +12,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_encode``  rows a8 - a10: the regional-style encoder's and the face parser's operators
 * ``ops_post``    rows f2 / f3 / f5: mask surgery, paste-back masks, Pillow's resize, multi-band blend, crop-align / paste into the frame
 * ``ops_grad``    row f1: the native gradients of the synthesis path
-* ``ops_recolor`` rows f8 / f9 / f10: Blender recolouring — the semantic colour reference, the Res-U-Net and the SPADE feature network (resolved on first use, like any name a stage module defines late)
+* ``ops_recolor`` rows f8 - f11: Blender recolouring — the semantic colour reference, the Res-U-Net, the SPADE feature network and the Real-ESRGAN step (resolved on first use, like any name a stage module defines late)
 """
 from __future__ import annotations
 
@@ -372,7 +372,8 @@ def invalidate_weight_caches(module: torch.nn.Module) -> int:
     """Drop every re-laid-out weight copy held by the drop-in modules under ``module`` (they are rebuilt by the next forward).  Needed only
     after writing parameters behind autograd's back between two ``no_grad`` forwards — ``p.data.copy_(...)``, an EMA update, a replay of a
     captured optimiser step (``pti.GraphedPTIStep`` does it itself) — which leaves no trace the caches could key on; ``load_state_dict``,
-    ordinary in-place ops and any training forward are tracked."""
+    ordinary in-place ops and any training forward are tracked.  The copies ``lossnet.prepare`` keeps for the modules under ``module`` (the frozen loss
+    networks, the recolouring networks) are dropped too."""
     seen = set()
 
     def drop(v) -> int:
@@ -387,7 +388,8 @@ def invalidate_weight_caches(module: torch.nn.Module) -> int:
             return sum(drop(c) for c in v.values())
         return 0
 
-    return sum(drop(v) for m in module.modules() for v in vars(m).values())
+    from . import lossnet                  # (imports this module: resolved here, not at import time)
+    return sum(drop(v) for m in module.modules() for v in vars(m).values()) + sum(drop(c) for c in lossnet.caches_of(module))
 
 
 class _Prepared:

@@ -845,7 +845,266 @@ def blender_forward(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
     return blender_recolor(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau.reshape(1), unet)
 
 
+# ------------------------------------------------------------------------------------------------ row f11: the Real-ESRGAN step
+RRDB_FEAT = 64                               # RRDBNet(num_feat=64, num_grow_ch=32, scale=4): the only configuration the reference builds
+RRDB_GROW = 32
+RRDB_SLAB = RRDB_FEAT + 4 * RRDB_GROW        # planes of a dense block's slab: x, x1 .. x4
+RRDB_SLOPE = 0.2
+_RRDB_PREFIXES = ("params_ema.", "params.")
+
+
+class _RDB(nn.Module):
+    """``ResidualDenseBlock(64, 32)`` of basicsr's rrdbnet_arch under its parameter names."""
+
+    def __init__(self):
+        super().__init__()
+        for k in range(1, 6):
+            setattr(self, f"conv{k}", nn.Conv2d(RRDB_FEAT + (k - 1) * RRDB_GROW, RRDB_GROW if k < 5 else RRDB_FEAT, 3, 1, 1))
+
+    def forward(self, x):
+        xs = [x]
+        for k in range(1, 5):
+            xs.append(F.leaky_relu(getattr(self, f"conv{k}")(torch.cat(xs, 1)), RRDB_SLOPE))
+        return self.conv5(torch.cat(xs, 1)) * 0.2 + x
+
+
+class _RRDB(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.rdb1, self.rdb2, self.rdb3 = _RDB(), _RDB(), _RDB()
+
+    def forward(self, x):
+        return self.rdb3(self.rdb2(self.rdb1(x))) * 0.2 + x
+
+
+class RRDBNet(nn.Module):
+    """``RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4)`` of basicsr's rrdbnet_arch with its ``state_dict`` keys and shapes
+    (``RealESRGAN_x4plus.pth``'s ``params_ema``, load with ``strict=True``): 702 tensors at 23 blocks.  ``forward`` is the plain PyTorch composition — what the
+    tests and the timing compare ``realesr_forward`` with; ``realesr_forward(x, module)`` runs the same weights on the HIP kernels."""
+
+    def __init__(self, num_block: int = 23):
+        super().__init__()
+        if isinstance(num_block, bool) or not isinstance(num_block, int) or num_block < 1:
+            raise ValueError(f"RRDBNet: num_block is a positive int, got {num_block!r}")
+        self.num_block = num_block
+        self.conv_first = nn.Conv2d(3, RRDB_FEAT, 3, 1, 1)
+        self.body = nn.Sequential(*[_RRDB() for _ in range(num_block)])
+        self.conv_body = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
+        self.conv_up1 = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
+        self.conv_up2 = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
+        self.conv_hr = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
+        self.conv_last = nn.Conv2d(RRDB_FEAT, 3, 3, 1, 1)
+
+    def forward(self, x):
+        feat = self.conv_first(x)
+        feat = feat + self.conv_body(self.body(feat))
+        feat = F.leaky_relu(self.conv_up1(F.interpolate(feat, scale_factor=2, mode="nearest")), RRDB_SLOPE)
+        feat = F.leaky_relu(self.conv_up2(F.interpolate(feat, scale_factor=2, mode="nearest")), RRDB_SLOPE)
+        return self.conv_last(F.leaky_relu(self.conv_hr(feat), RRDB_SLOPE))
+
+
+@functools.lru_cache(maxsize=4)
+def _rrdb_keys_shapes(num_block):
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in RRDBNet(num_block).state_dict().items())
+
+
+def rrdbnet_state_dict_shapes(num_block: int = 23):
+    """``{key: shape}`` of ``RRDBNet(num_block).state_dict()``, in its order."""
+    return dict(_rrdb_keys_shapes(num_block))
+
+
+def _rrdb_validated(name, weights):
+    """(mapping, block count, tensors in key order) of ``weights``: a module with the network's keys (``RRDBNet``) or a mapping, bare or a checkpoint with
+    ``params_ema`` / ``params``; keys, shapes and dtypes checked.  The block count is read off the keys."""
+    if isinstance(weights, nn.Module):
+        sd = weights.state_dict()
+    elif hasattr(weights, "keys"):
+        sd = weights
+        if "conv_first.weight" not in sd:
+            for prefix in _RRDB_PREFIXES:
+                if isinstance(sd.get(prefix[:-1]), dict):                  # the checkpoint file as torch.load gives it
+                    sd = sd[prefix[:-1]]
+                    break
+                if prefix + "conv_first.weight" in sd:
+                    sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+                    break
+    else:
+        raise TypeError(f"{name}: weights must be a module or a mapping with RRDBNet's keys, got {type(weights).__name__}")
+    if "conv_first.weight" not in sd:
+        raise KeyError(f"{name}: the weights lack 'conv_first.weight': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
+    num_block = 0
+    while f"body.{num_block}.rdb1.conv1.weight" in sd:
+        num_block += 1
+    if num_block < 1:
+        raise KeyError(f"{name}: the weights lack 'body.0.rdb1.conv1.weight': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
+    out = []
+    for k, shape in rrdbnet_state_dict_shapes(num_block).items():
+        t = sd.get(k)
+        if t is None:
+            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of RRDBNet({num_block})")
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"{name}: '{k}' is {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}, expected float32 {shape}")
+        out.append(t)
+    return sd, num_block, out
+
+
+def rrdbnet_weight_tensors(weights, name: str = "realesr_forward"):
+    """The tensors of the network in key order, their shapes checked: what ``weights_key`` watches."""
+    return _rrdb_validated(name, weights)[2]
+
+
+class PreparedRRDBNet(_Prepared):
+    """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  ``first``, ``conv_body``, ``up1``, ``up2``, ``hr``
+    and per block three dense blocks of five convolutions, all as three-way split slabs with their biases; ``conv5`` of a dense block carries the block's
+    ``* 0.2`` in weight and bias (folded in float64), so that ``x5 * 0.2 + x`` is the convolution's residual epilogue; ``last`` conv_last's float32 weight
+    and bias for the exact kernel; ``slope64`` / ``slope32`` the LeakyReLU as a PReLU slope vector."""
+
+    __slots__ = ()
+
+    def get(self, weights, checked=None):
+        sd, num_block, ts = checked if checked is not None else _rrdb_validated("realesr_forward", weights)
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k in rrdbnet_state_dict_shapes(num_block)}
+        dev = ts[0].device
+
+        def conv(name, scale=None):
+            w, b = sd[name + ".weight"], sd[name + ".bias"]
+            if scale is None:
+                return prep_fwd(w, None, b)
+            return prep_fwd(w, torch.full((w.shape[0],), scale, dtype=torch.float64, device=dev), b.double() * scale)
+
+        with torch.no_grad():
+            body = [[[conv(f"body.{i}.rdb{r}.conv{k}", 0.2 if k == 5 else None) for k in range(1, 6)] for r in (1, 2, 3)] for i in range(num_block)]
+            P = dict(num_block=num_block, first=conv("conv_first"), body=body, conv_body=conv("conv_body"), up1=conv("conv_up1"), up2=conv("conv_up2"),
+                     hr=conv("conv_hr"), last=(sd["conv_last.weight"].contiguous(), sd["conv_last.bias"].contiguous()),
+                     slope64=torch.full((RRDB_FEAT,), RRDB_SLOPE, dtype=torch.float32, device=dev),
+                     slope32=torch.full((RRDB_GROW,), RRDB_SLOPE, dtype=torch.float32, device=dev))
+        return self._publish(key, P)
+
+
+def _conv3_into(out, x, prepared, cin, h, w, slope=None, residual=None):
+    """``e4s_conv2d_sb3`` (3x3, stride 1, zero pad 1) of ONE sample: the first ``cin`` planes of ``x`` into ``out``, both ``[planes, h, w]`` views of larger
+    buffers; LeakyReLU as the PReLU epilogue with ``slope``; ``residual`` added before it."""
+    slabs, bias = prepared
+    cout = slabs[0].shape[3]
+    lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, *[_p(s) for s in slabs], _p(bias), None, None, _p(slope), _p(residual),
+               2 if slope is not None else 0, 1, cin, cout, h, w, 3, 1, 1, _stream())
+
+
+def _rrdb_sample(P, x, out_f, out_u8, slabs, feat0, ups):
+    """The network on one sample ``x [3, h, w]``.  ``slabs``: three ``[192, h, w]`` buffers; a dense block reads the head of one (x, x1 ..) and each of its
+    first four convolutions writes its 32 planes right behind what it read, so no concatenation is formed; conv5 writes the head of the NEXT slab with this
+    slab's head as its residual.  An RRDB's input (the head of slab 0) outlives its three dense blocks: block 1 goes 0 -> 1, block 2 goes 1 -> 2, block 3
+    goes 2 -> 1, and ``e4s_esr_scale_add`` puts ``head(1) * 0.2 + head(0)`` back into the head of slab 0.  ``ups``: per upsampling the pair (nearest x2,
+    convolution output) of ``[64, 2h, 2w]`` and ``[64, 4h, 4w]`` buffers; conv_hr writes over conv_up2's input, which is free by then."""
+    _, h, w = x.shape
+    hw = h * w
+    st = _stream()
+    _conv3_into(feat0, x, P["first"], 3, h, w)
+    slabs[0][:RRDB_FEAT].copy_(feat0)
+    for block in P["body"]:
+        for rdb, (src, dst) in zip(block, ((0, 1), (1, 2), (2, 1))):
+            S = slabs[src]
+            for k in range(4):
+                cin = RRDB_FEAT + k * RRDB_GROW
+                _conv3_into(S[cin:cin + RRDB_GROW], S, rdb[k], cin, h, w, slope=P["slope32"])
+            _conv3_into(slabs[dst][:RRDB_FEAT], S, rdb[4], RRDB_SLAB, h, w, residual=S)
+        lib().call("e4s_esr_scale_add", _p(slabs[0]), _p(slabs[1]), _p(slabs[0]), RRDB_FEAT, hw, st)
+    feat = slabs[1][:RRDB_FEAT]
+    _conv3_into(feat, slabs[0], P["conv_body"], RRDB_FEAT, h, w, residual=feat0)               # feat + conv_body(body(feat))
+    for name, (up, out) in zip(("up1", "up2"), ups):
+        lib().call("e4s_esr_up2", _p(up), _p(feat), RRDB_FEAT, h, w, st)
+        h, w = 2 * h, 2 * w
+        _conv3_into(out, up, P[name], RRDB_FEAT, h, w, slope=P["slope64"])
+        feat = out
+    hr = ups[1][0]
+    _conv3_into(hr, feat, P["hr"], RRDB_FEAT, h, w, slope=P["slope64"])
+    lib().call("e4s_esr_tail", _p(out_u8), _p(out_f), _p(hr), _p(P["last"][0]), _p(P["last"][1]), 1, h, w, st)
+
+
+def _rrdb_run(x, P, want_float, want_u8):
+    """(float32 [bs, 3, 4h, 4w] or None, uint8 [bs, 4h, 4w, 3] or None) of ``x [bs, 3, h, w]``, sample after sample on one sample's scratch, made once."""
+    bs, _, h, w = x.shape
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)             # noqa: E731
+    out_f = new(bs, 3, 4 * h, 4 * w) if want_float else None
+    # the tail kernel always writes its uint8 image; a caller that wants the float output alone gets one sample's worth of it as scratch
+    out_u8 = torch.empty((bs if want_u8 else 1, 4 * h, 4 * w, 3), dtype=torch.uint8, device=x.device)
+    slabs = [new(RRDB_SLAB, h, w) for _ in range(3)]
+    feat0 = new(RRDB_FEAT, h, w)
+    ups = [(new(RRDB_FEAT, 2 * h, 2 * w), new(RRDB_FEAT, 2 * h, 2 * w)), (new(RRDB_FEAT, 4 * h, 4 * w), new(RRDB_FEAT, 4 * h, 4 * w))]
+    for b in range(bs):
+        _rrdb_sample(P, x[b], out_f[b] if want_float else None, out_u8[b if want_u8 else 0], slabs, feat0, ups)
+    return out_f, (out_u8 if want_u8 else None)
+
+
+def _rrdb_checked_all(name, x, weights):
+    checked = _rrdb_validated(name, weights)
+    _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, h, w] image")
+    if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError(f"{name}: x: expected a float32 [bs, 3, h, w] image with h, w >= 1, got {tuple(x.shape)}")
+    if 4 * x.shape[2] > 16384 or 4 * x.shape[3] > 16384:
+        raise ValueError(f"{name}: x is {x.shape[2]} x {x.shape[3]}: the x4 output may be 16384 x 16384 at the most")
+    if any(t.device != x.device for t in checked[2]):
+        raise RuntimeError(f"{name}: device mismatch: x on {x.device}, the weights on {sorted({str(t.device) for t in checked[2]})}")
+    _cuda_checked(name, x=x)
+    return checked
+
+
+def realesr_forward(x: torch.Tensor, weights) -> torch.Tensor:
+    """``RRDBNet.forward`` at scale 4 (basicsr's rrdbnet_arch, as ``RealESRBatchInfer`` builds it) in eval mode on the device: float32 ``[bs, 3, 4h, 4w]`` from
+    a float32 ``[bs, 3, h, w]`` image, ``h, w >= 1``.  ``weights``: a module with the network's keys (``RRDBNet``) or a mapping, bare or the checkpoint with
+    ``params_ema`` / ``params``; the block count is read off the keys.  A module's prepared weights are cached per parameter version; a mapping is prepared
+    on every call.  The 351 convolutions run on the three-way split-bf16 kernel except conv_last, which is exact float32 (``e4s_esr_tail``).  The samples of
+    a batch run one after another on scratch that does not grow with ``bs``, each exactly as a batch-of-one call.  Forward only, no gradient.  Every argument
+    is checked before any launch; no host synchronisation, the same inputs give the same bits, and after one eager call (which prepares the weights) the
+    call captures in a graph."""
+    name = "realesr_forward"
+    checked = _rrdb_checked_all(name, x, weights)
+    bs, _, h, w = x.shape
+    if bs == 0:
+        return torch.empty((0, 3, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
+    with torch.no_grad():
+        return _rrdb_run(x.detach().contiguous(), lossnet.prepare(PreparedRRDBNet, weights, checked), True, False)[0]
+
+
+def realesr_input(img_u8: torch.Tensor, out_hw, name: str = "realesr_input") -> torch.Tensor:
+    """The head of ``RealESRBatchInfer.infer_image`` and ``infer_batch`` (image_infer.py:64-65, :73-76) in one pass (``e4s_esr_input``): uint8
+    ``[bs, H, W, 3]`` to float32 ``[bs, 3, *out_hw]`` = the ``align_corners=True`` bilinear resize of ``clamp((v / 127.5 - 1) * 0.5 + 0.5, 0, 1)``."""
+    _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, "a uint8 [bs, H, W, 3] image")
+    bs, H, W, c3 = img_u8.shape
+    if c3 != 3 or H < 1 or W < 1 or H > 16384 or W > 16384:
+        raise ValueError(f"{name}: img_u8: expected a uint8 [bs, H, W, 3] image with 1 <= H, W <= 16384, got {tuple(img_u8.shape)}")
+    oh, ow = out_hw
+    for v in (oh, ow):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4096:
+            raise ValueError(f"{name}: the network's input size is a pair of ints in 1..4096, got {out_hw!r}")
+    _cuda_checked(name, img_u8=img_u8)
+    x = torch.empty((bs, 3, oh, ow), dtype=torch.float32, device=img_u8.device)
+    lib().call("e4s_esr_input", _p(x), _p(img_u8.contiguous()), bs, H, W, oh, ow, _stream())
+    return x
+
+
+def realesr_image(img_u8: torch.Tensor, weights, in_size: int = 256) -> torch.Tensor:
+    """``RealESRBatchInfer.infer_image`` (image_infer.py:71-80) for a batch on the device, as three fused steps: ``realesr_input`` (``/ 127.5 - 1``,
+    ``* 0.5 + 0.5``, the clamp and the ``align_corners=True`` bilinear resize to ``in_size``), the network, and ``e4s_esr_tail`` (conv_last, ``* 2 - 1``, the
+    clamp, ``* 127.5 + 127.5``, the clamp and the truncation).  uint8 ``[bs, H, W, 3]`` to uint8 ``[bs, 4 in_size, 4 in_size, 3]``."""
+    name = "realesr_image"
+    checked = _rrdb_validated(name, weights)
+    if isinstance(img_u8, torch.Tensor) and any(t.device != img_u8.device for t in checked[2]):
+        raise RuntimeError(f"{name}: device mismatch: img_u8 on {img_u8.device}, the weights on {sorted({str(t.device) for t in checked[2]})}")
+    with torch.no_grad():
+        x = realesr_input(img_u8, (in_size, in_size), name)
+        if x.shape[0] == 0:
+            return torch.empty((0, 4 * in_size, 4 * in_size, 3), dtype=torch.uint8, device=x.device)
+        return _rrdb_run(x, lossnet.prepare(PreparedRRDBNet, weights, checked), False, True)[1]
+
+
 __all__ = ["BLENDER_PARTS", "BLENDER_PART_IDS", "COLORREF_CHANNELS", "COLORREF_MAX_PIXELS", "blender_part_masks", "color_reference", "blender_packages",
            "RESUNET_WIDTHS", "ResUNet", "PreparedResUNet", "resunet_state_dict_shapes", "resunet_weight_tensors", "blender_unet", "blender_recolor",
            "FPN_CHANNELS", "BlenderFPN", "SmallFPN", "BlenderNet", "PreparedFPN", "fpn_state_dict_shapes", "fpn_weight_tensors", "fpn_output_size",
-           "flip_choice", "blender_fpn", "blender_features", "blender_forward"]
+           "flip_choice", "blender_fpn", "blender_features", "blender_forward",
+           "RRDBNet", "PreparedRRDBNet", "rrdbnet_state_dict_shapes", "rrdbnet_weight_tensors", "realesr_forward", "realesr_input", "realesr_image"]

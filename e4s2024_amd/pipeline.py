@@ -342,9 +342,25 @@ def color_transfer(swapped_u8: torch.Tensor, target_u8: torch.Tensor, swapped_la
     return ops.blending(d, composed, border).permute(0, 2, 3, 1).contiguous()
 
 
+def _recolor_nets_checked(ct_mode, recolor_fn, recolor_nets):
+    """``(blender, esr)`` for ``ct_mode='blender'``, their layouts and keys checked, or None; ``TypeError`` where ``recolor_nets`` does not belong."""
+    if recolor_nets is None:
+        return None
+    if recolor_fn is not None:
+        raise TypeError("swap_images: recolor_nets and recolor_fn are two ways to do step 2, the colour transfer: pass one of them")
+    if ct_mode != "blender":
+        raise TypeError(f"swap_images: recolor_nets goes with ct_mode='blender' (the other modes are arithmetic), got ct_mode={ct_mode!r}")
+    if not isinstance(recolor_nets, (tuple, list)) or len(recolor_nets) != 2:
+        raise TypeError("swap_images: recolor_nets is the pair (blender, esr): the recolouring network's weights and the Real-ESRGAN network's")
+    blender, esr = recolor_nets
+    ops_recolor._blender_weights("swap_images", blender)                # both fail here, before the crop and the swap are launched
+    ops_recolor._rrdb_validated("swap_images", esr)
+    return blender, esr
+
+
 @torch.no_grad()
 def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tensor, plan, recolor_fn=None, ct_mode: Optional[str] = None,
-                **swap_batch_kwargs) -> torch.Tensor:
+                recolor_nets=None, **swap_batch_kwargs) -> torch.Tensor:
     """The two-image caller's chain (``FaceSwap.face_swap_pipeline``, Face_swap_with_two_imgs.py:796-963, without its inpainting / Blender / GPEN
     networks) for a batch of target images, all on the device:
 
@@ -357,13 +373,20 @@ def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tenso
     ``driven``: ``[n, 3, 1024, 1024]`` in [-1, 1]; ``target_images_u8``: uint8 ``[n, H, W, 3]`` on the device; ``plan``: their ``align.CropPlan``;
     ``ct_mode`` 'lct' / 'mkl': step 2 on the device, ``recolored = color_transfer(swapped, crops, swapped map, target map, ct_mode)``;
     ``recolor_fn(swapped_u8, crops_u8) -> uint8 [n, 1024, 1024, 3]``: a colour transfer of the caller's own instead (the reference's other modes need cv2
-    or a network); passing both raises ``TypeError``.  Returns uint8 ``[n, H, W, 3]``, every pixel outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch``, with the guard and stream behaviour of ``swap_frames``."""
+    or a network); passing both raises ``TypeError``.  ``ct_mode='blender'`` with ``recolor_nets=(blender, esr)``: the reference's default mode,
+    ``recolored = color_transfer_blender(swapped, crops, parser, blender, esr)`` (the recolouring network and the Real-ESRGAN step, rows f8 - f11, with the
+    weights as ``ops.blender_forward`` and ``ops.realesr_forward`` take them); without ``recolor_nets`` that mode raises ``ValueError``, and ``recolor_nets``
+    with any other mode or with ``recolor_fn`` raises ``TypeError``.  Returns uint8 ``[n, H, W, 3]``, every pixel outside the faces' quads untouched.  Further keyword arguments go to ``swap_batch``, with the guard and stream behaviour of ``swap_frames``."""
     for k in ("mask_surgery", "to_uint8", "ear_interpolation", "comp_indices"):
         if k in swap_batch_kwargs:
             raise TypeError(f"swap_images: {k} is fixed (the image caller's style mix, and the paste needs the uint8 face and the mask-surgery hole)")
     if ct_mode is not None and recolor_fn is not None:
         raise TypeError("swap_images: ct_mode and recolor_fn are two ways to do step 2, the colour transfer: pass one of them")
-    if ct_mode is not None:
+    blender_nets = _recolor_nets_checked(ct_mode, recolor_fn, recolor_nets)
+    if ct_mode is not None and blender_nets is None:
+        if ct_mode == "blender":
+            raise ValueError(f"swap_images: ct_mode 'blender' needs recolor_nets=(blender, esr), the recolouring network and the Real-ESRGAN network; "
+                             f"without them the modes are {list(ops_post.CT_MODES)}")
         ops_post._ct_mode_checked(ct_mode, "swap_images")
     recolor = ct_mode is not None or recolor_fn is not None
     crops = ops.crop_align(target_images_u8, plan)
@@ -372,7 +395,9 @@ def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tenso
     # < 0.1 ms, accepted rather than giving swap_batch another switch)
     swapped, lab, extra = swap_batch(net, parser, driven, target, mask_surgery=True, ear_interpolation=False,
                                      comp_indices=IMAGE_COMP_INDICES_CT if recolor else IMAGE_COMP_INDICES, **swap_batch_kwargs)
-    if ct_mode is not None:
+    if blender_nets is not None:
+        swapped = color_blend(swapped, color_transfer_blender(swapped, crops, parser, *blender_nets), lab)
+    elif ct_mode is not None:
         swapped = color_blend(swapped, color_transfer(swapped, crops, lab, extra["target_labels"], ct_mode), lab)
     elif recolor_fn is not None:
         swapped = color_blend(swapped, recolor_fn(swapped, crops), lab)
@@ -422,3 +447,90 @@ def blender_infer_image(weights, img_a_u8: torch.Tensor, img_t_u8: torch.Tensor,
     img_a, img_t, labels_a, labels_t = blender_infer_inputs(img_a_u8, img_t_u8, labels_a_u8, labels_t_u8)
     pred, _, _ = ops.blender_forward(img_a, img_t, labels_a, labels_t, weights, flip_target)
     return (pred * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+# ------------------------------------------------------------------------------------ f11: the Real-ESRGAN step and ct_mode 'blender'
+ESR_IN = 256                            # RealESRBatchInfer.infer_batch resizes its input to 256 x 256 (image_infer.py:65)
+ESR_OUT = 1024                          # infer_image asks for 1024 x 1024 (:77), which is what the x4 network gives
+
+
+def _esr_size_checked(name, nm, v):
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
+        raise ValueError(f"{name}: {nm} is an int in 1..16384, got {v!r}")
+    return v
+
+
+@torch.no_grad()
+def realesr_infer_batch(weights, x: torch.Tensor, out_hw=None, in_size: int = ESR_IN) -> torch.Tensor:
+    """``RealESRBatchInfer.infer_batch`` (swap_face_fine/realesr/image_infer.py:60-69) on the device: float32 ``[bs, 3, H, W]`` in [-1, 1] to
+    ``[bs, 3, *out_hw]`` in [-1, 1] (``out_hw`` defaults to ``(H, W)``):
+
+        clamp(x * 0.5 + 0.5, 0, 1) -> bilinear to 256 x 256 (align_corners=True) -> RRDBNet (ops.realesr_forward) -> bilinear to out_hw -> clamp(r * 2 - 1, -1, 1)
+
+    The second resize is skipped when ``out_hw`` is the network's output size, where it is the identity.  ``weights`` as ``ops.realesr_forward`` takes them;
+    ``in_size`` is the reference's 256."""
+    name = "realesr_infer_batch"
+    ops_recolor._rrdb_validated(name, weights)
+    ops_recolor._tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image in [-1, 1]")
+    if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError(f"{name}: x: expected a float32 [bs, 3, H, W] image in [-1, 1], got {tuple(x.shape)}")
+    in_size = _esr_size_checked(name, "in_size", in_size)
+    out_hw = tuple(x.shape[2:]) if out_hw is None else tuple(out_hw)
+    if len(out_hw) != 2:
+        raise ValueError(f"{name}: out_hw is (height, width), got {out_hw!r}")
+    out_hw = (_esr_size_checked(name, "out_hw[0]", out_hw[0]), _esr_size_checked(name, "out_hw[1]", out_hw[1]))
+    ops_recolor._cuda_checked(name, x=x)
+    small = ops.bilinear_resize((x * 0.5 + 0.5).clamp(0, 1).contiguous(), (in_size, in_size), align_corners=True)
+    r = ops.realesr_forward(small, weights)
+    if tuple(r.shape[2:]) != out_hw:
+        r = ops.bilinear_resize(r, out_hw, align_corners=True)
+    return (r * 2. - 1.).clamp(-1, 1)
+
+
+@torch.no_grad()
+def realesr_infer_image(weights, img_u8: torch.Tensor, in_size: int = ESR_IN, out_size: int = ESR_OUT) -> torch.Tensor:
+    """``RealESRBatchInfer.infer_image`` (image_infer.py:71-80) for a batch on the device: uint8 ``[bs, H, W, 3]`` to uint8 ``[bs, 1024, 1024, 3]``,
+
+        v / 127.5 - 1 -> infer_batch(out_hw=(1024, 1024)) -> clamp(r * 127.5 + 127.5, 0, 255) -> uint8 (truncating)
+
+    With ``out_size == 4 * in_size`` (the reference's sizes) everything around the network's convolutions is two kernels (``ops.realesr_image``); otherwise
+    the x4 output goes through ``ops.bilinear_resize`` first.  ``in_size`` / ``out_size`` are the reference's 256 / 1024."""
+    name = "realesr_infer_image"
+    in_size, out_size = _esr_size_checked(name, "in_size", in_size), _esr_size_checked(name, "out_size", out_size)
+    if out_size == 4 * in_size:
+        return ops.realesr_image(img_u8, weights, in_size)
+    ops_recolor._rrdb_validated(name, weights)
+    x = ops.realesr_input(img_u8, (in_size, in_size))
+    if x.shape[0] == 0:
+        return torch.empty((0, out_size, out_size, 3), dtype=torch.uint8, device=x.device)
+    r = ops.bilinear_resize(ops.realesr_forward(x, weights), (out_size, out_size), align_corners=True)
+    r = (r * 2. - 1.).clamp(-1, 1)
+    return (r * 127.5 + 127.5).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+@torch.no_grad()
+def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, parser, blender, esr, flip_target=None) -> torch.Tensor:
+    """The ``'blender'`` branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:525-536), the reference's default mode, for a batch on
+    the device:
+
+        la, lt = the 19-class maps of the swapped face and of the target crop (:526, :595)
+        small  = BlenderInfer.infer_image(swapped, target, la, lt)             (:529-531; blender_infer_image, uint8 [bs, 256, 256, 3])
+        face   = small.resize(swapped.size)                                    (:533; Pillow's BICUBIC, ops.pil_resize)
+        out    = RealESRBatchInfer.infer_image(face)                           (:534; realesr_infer_image, uint8 [bs, 1024, 1024, 3])
+
+    ``swapped_u8`` / ``target_u8``: uint8 ``[bs, S, S, 3]`` crops (1024 in the pipeline); ``parser``: the ``FaceParser``; ``blender`` as
+    ``ops.blender_forward`` takes its weights, ``esr`` as ``ops.realesr_forward``; ``flip_target`` as ``ops.blender_features``."""
+    name = "color_transfer_blender"
+    _crops_checked(name, swapped_u8, target_u8)
+    if not swapped_u8.is_cuda:
+        raise RuntimeError(f"{name}: the frames must be CUDA tensors")
+    ops_recolor._rrdb_validated(name, esr)
+    ops_recolor._blender_weights(name, blender)
+    bs, h, w, _ = swapped_u8.shape
+    if bs == 0:
+        return torch.empty((0, ESR_OUT, ESR_OUT, 3), dtype=torch.uint8, device=swapped_u8.device)
+    to01 = lambda u8: u8.permute(0, 3, 1, 2).float() / 255                    # noqa: E731  (parse_batch takes [bs, 3, S, S] in [0, 1])
+    la = parser.parse_batch(to01(swapped_u8), seg12=False)
+    lt = parser.parse_batch(to01(target_u8), seg12=False)
+    small = blender_infer_image(blender, swapped_u8, target_u8, la, lt, flip_target)
+    return realesr_infer_image(esr, ops.pil_resize(small, (w, h)))

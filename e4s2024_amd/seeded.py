@@ -30,6 +30,7 @@ __all__ = [
     "seeded_resunet_state_dict",
     "seeded_fpn_state_dict",
     "seeded_small_fpn_state_dict",
+    "seeded_rrdbnet_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -261,9 +262,31 @@ def seeded_small_fpn_state_dict(seed: int) -> Dict[str, torch.Tensor]:
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in fpn_state_dict_shapes(True).items()}, seed, "fpn")
 
 
+# RRDBNet of the Real-ESRGAN step (basicsr's rrdbnet_arch, 351 convolutions): normal weights at a gain of 0.7 over the fan-in and biases over +-0.1.  With 23
+# blocks that keeps the body's activations below about a hundred and the output alive: at a gain of 1 nearly every output pixel saturates behind the
+# wrappers' clamps, and basicsr's own 0.1-scaled initialisation gives a flat image.  A test rescales conv_last to its case (tests/rrdb_model.py).
+RRDB_GAIN = 0.7
+
+
+def _rrdb_weight(seed, key, shape):
+    return seeded_array(seed, key, shape, 0.0, RRDB_GAIN / np.sqrt(int(np.prod(shape[1:]))), dist="normal")
+
+
+_RULES_RRDB = [
+    (r"\.bias$", (0.0, 0.1 / _SQRT3)),                                # U(-0.1, 0.1)
+    (r"\.weight$", _rrdb_weight),
+]
+
+
+def seeded_rrdbnet_state_dict(seed: int, num_block: int = 23) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.RRDBNet(num_block)`` (the keys of ``RealESRGAN_x4plus.pth``'s ``params_ema``)."""
+    from .ops_recolor import rrdbnet_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in rrdbnet_state_dict_shapes(num_block).items()}, seed, "rrdb")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
-             "fpn": _RULES_FPN}.get(family, _RULES_BISENET)
+             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -811,6 +811,23 @@ E4S_API int e4s_spade_shared(float* actv, const float* img, const float* weight,
 E4S_API int e4s_spade_modulate(float* out, const float* x, const float* mean, const float* rstd, const float* gamma_beta, int bs, int C, int h, int w, int leaky,
                                int padded, void* stream);
 
+/* f11: the Real-ESRGAN step of the recolouring (swap_face_fine/realesr/image_infer.py: RealESRBatchInfer around RRDBNet(3, 3, 64, 23, 32, scale=4); csrc/rrdb.hip),
+ * the glue between the network's convolutions, which run on e4s_conv2d_sb3.
+ *   e4s_esr_input     : uint8 img [bs][H][W][3] -> out [bs][3][oh][ow]: u = clamp((v / 127.5 - 1) * 0.5 + 0.5, 0, 1) per colour value, every operation rounded on
+ *                       its own ("/ 127.5" as PyTorch divides by a host scalar on the device: times the float32 reciprocal), then the align_corners=True bilinear
+ *                       pick with e4s_bilinear_resize's coordinates and blend.
+ *   e4s_esr_scale_add : y [planes][hw] = t * 0.2 + x, the product rounded, then the sum (PyTorch's t * 0.2 + x bit for bit).  y may be x or t.
+ *   e4s_esr_up2       : out [planes][2h][2w] = in [planes][h][w] at (y >> 1, x >> 1): F.interpolate(scale_factor=2, mode='nearest').
+ *   e4s_esr_tail      : r = conv3x3(x [bs][64][H][W], weight [3][64][3][3], zero pad 1) + bias [3] in exact float32: each sum is bias, then 576 fused
+ *                       multiply-adds in (input channel, row, column) order.  out_u8 [bs][H][W][3] = uint8(clamp(clamp(r * 2 - 1, -1, 1) * 127.5 + 127.5, 0, 255)),
+ *                       every operation rounded on its own, truncating; out_f [bs][3][H][W] = r when out_f is not NULL.
+ * 16-byte accesses along a row where the pointers and the row length allow, single elements otherwise: the same bits.  No atomics, no host synchronisation,
+ * grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.  bs == 0 (planes == 0) returns at once. */
+E4S_API int e4s_esr_input(float* out, const uint8_t* img, int bs, int H, int W, int oh, int ow, void* stream);
+E4S_API int e4s_esr_scale_add(float* y, const float* t, const float* x, int planes, int hw, void* stream);
+E4S_API int e4s_esr_up2(float* out, const float* in, int planes, int h, int w, void* stream);
+E4S_API int e4s_esr_tail(uint8_t* out_u8, float* out_f, const float* x, const float* weight, const float* bias, int bs, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
