@@ -1,4 +1,4 @@
-// The targets of the multi-target loss heads (lpips.hip, idloss.hip, fploss.hip, pixloss.hip): one reconstruction read against k <= 4 targets, target j
+// The targets of the multi-target loss heads (lpips.hip, idloss.hip, fploss.hip, pixloss.hip): one reconstruction read against k <= E4S_MAX_TARGETS targets, target j
 // weighted by w[j].  Target j of sample b starts at y[j] + frame * fstride + b * (per-sample size), frame = *frame_idx when frame_idx is given (a device
 // int32: a captured step selects the frame of a clip-wide cache by writing it before the replay; clamped to [0, nframes) so that a bad index cannot
 // read past the cache) and 0 otherwise.
@@ -7,7 +7,7 @@
 
 namespace e4s {
 
-constexpr int MAX_TARGETS = 4;
+constexpr int MAX_TARGETS = E4S_MAX_TARGETS;
 
 struct Targets {
     const float* y[MAX_TARGETS];

@@ -20,7 +20,7 @@ from .ops import _c, _p, _stream
 
 BN_EPS = 1e-5
 HEAD_BLOCK = 8192                            # e4s_id_head_partial: elements per partial sum
-MULTI_STATS = 9                              # e4s_id_head_*_multi: |x|^2 (|x|), then (|y_j|^2, x.y_j) ((|y_j|, cos_j)) for 4 targets
+MULTI_STATS = 1 + 2 * MAX_TARGETS            # e4s_id_head_*_multi: |x|^2 (|x|), then (|y_j|^2, x.y_j) ((|y_j|, cos_j)) per target
 
 
 # ------------------------------------------------------------------------------------------------ weights
@@ -88,15 +88,18 @@ def prep_dgrad(w, out_scale=None, in_scale=None):
 
 
 # ------------------------------------------------------------------------------------------------ convolution
-def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, residual=None):
-    """Split-bf16 convolution of csrc/conv.hip on prepared ``slabs``: three-way (``prep_fwd``) or two-way (``prep_dgrad``); ``pad`` defaults to k // 2."""
-    bs, cin, h, w = x.shape
+def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, residual=None, x1=None, slope=None, out=None):
+    """Split-bf16 convolution of csrc/conv.hip on prepared ``slabs``: three-way (``prep_fwd``) or two-way (``prep_dgrad``); ``pad`` defaults to k // 2.
+    Input channels come from ``x`` and then ``x1`` (a concatenation that is never formed); ``slope [cout]`` makes the activation a PReLU; ``residual`` is
+    added before it; ``out``: the ``[bs, cout, ho, wo]`` tensor (or view of a larger buffer) to write into."""
+    bs, c0, h, w = x.shape
+    cin = c0 if x1 is None else c0 + x1.shape[1]
     cout = slabs[0].shape[3]
     pad = k // 2 if pad is None else pad
-    out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
-    name = {3: "e4s_conv2d_sb3", 2: "e4s_conv2d_sb"}[len(slabs)]
-    lib().call(name, _p(out), _p(x), None, cin, *[_p(s) for s in slabs], _p(bias), None, None, None, _p(residual), 1 if relu else 0,
-               bs, cin, cout, h, w, k, stride, pad, _stream())
+    if out is None:
+        out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv2d_sb3" if len(slabs) == 3 else "e4s_conv2d_sb", _p(out), _p(x), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, _p(slope),
+               _p(residual), 2 if slope is not None else 1 if relu else 0, bs, cin, cout, h, w, k, stride, pad, _stream())
     return out
 
 

@@ -25,11 +25,9 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import lib
+from ._lib import LABEL_NONE, MAX_REGIONS, MAX_STYLE_JOBS, OUT_NHWC, OUT_SP, X_NHWC, X_SP, ChainLayer, StyleJob, lib  # noqa: F401  (include/e4s_hip.h's values)
 
 SQRT2 = 2.0 ** 0.5
-MAX_REGIONS = 16
-LABEL_NONE = 255
 
 
 # ----------------------------------------------------------------------------- helpers
@@ -824,7 +822,7 @@ def modconv_up_single(x, wt, s, d, blur, noise, noise_weight, act_bias, act: boo
         else:
             ev = _timed("modconv_up_fused_sb")
             lib().call("e4s_modconv_up_fused_sb", _p(out), _p(x), _p(wt[0]), _p(wt[1]), _p(s), _p(d), _p(_c(blur, "blur kernel")), _p(nz), nbs or 0,
-                       _p(noise_weight) if nz is not None else None, _p(act_bias), (1 if act else 0) | 8 | 16, bs, cin, cout, h, w, _p(sn), _stream())
+                       _p(noise_weight) if nz is not None else None, _p(act_bias), (1 if act else 0) | X_SP | OUT_SP, bs, cin, cout, h, w, _p(sn), _stream())
         if ev is not None:
             ev.record()
         return out
@@ -846,7 +844,7 @@ def modconv_up_single(x, wt, s, d, blur, noise, noise_weight, act_bias, act: boo
     if UP_FUSED:
         ev = _timed("modconv_up_fused_sb")
         lib().call("e4s_modconv_up_fused_sb", _p(out), _p(x), _p(wt[0]), _p(wt[1]), _p(s), _p(d), _p(_c(blur, "blur kernel")), _p(nz), nbs or 0,
-                   _p(noise_weight) if nz is not None else None, _p(act_bias), (1 if act else 0) | (2 if x_nhwc else 0) | (4 if out_nhwc else 0),
+                   _p(noise_weight) if nz is not None else None, _p(act_bias), (1 if act else 0) | (X_NHWC if x_nhwc else 0) | (OUT_NHWC if out_nhwc else 0),
                    bs, cin, cout, h, w, None, _stream())
         if ev is not None:
             ev.record()
@@ -868,7 +866,6 @@ def modconv_up_single(x, wt, s, d, blur, noise, noise_weight, act_bias, act: boo
 def style_demod_plan(jobs):
     """jobs: list of (key, styles [bs,nreg,sdim], mod_weight, mod_bias, wsq or None, cout).  Computes every layer's (s, d) in two
     launches and remembers them under ``key`` for the ``style_demod`` calls of the same forward pass."""
-    from ._lib import StyleJob
     _table_plan = _ctx().table_plan
     _table_plan.clear()
     if not jobs:
@@ -898,8 +895,8 @@ def style_demod_plan(jobs):
         arr[i] = StyleJob(s_t.data_ptr(), None if d_t is None else d_t.data_ptr(), styles.data_ptr(), styles.stride(0), styles.stride(1),
                           mwc.data_ptr(), mbc.data_ptr(), None if wsq is None else wsq.data_ptr(), nreg, cin, cout, 0)
         _table_plan[key] = ((styles.data_ptr(), tuple(styles.shape), styles.stride(), styles._version), s_t, d_t)
-    for i0 in range(0, len(jobs), 32):
-        n = min(32, len(jobs) - i0)
+    for i0 in range(0, len(jobs), MAX_STYLE_JOBS):
+        n = min(MAX_STYLE_JOBS, len(jobs) - i0)
         lib().call("e4s_style_demod_batched", ctypes.byref(arr, i0 * ctypes.sizeof(StyleJob)), n, bs, sdim, _stream())
     del keep
 
@@ -1104,12 +1101,12 @@ def region_modconv3x3(x, wt, s, d, labels, noise, noise_weight, act_bias, act: b
         else:
             lib().call("e4s_region_modconv3x3_mx", _p(out), _p(x), _p(wmx), arith, _p(mx_flags(x.device)) if arith else None, _p(s), _p(d), _p(labels), lh, lw,
                        _p(nz), nbs or 0, _p(noise_weight) if nz is not None else None, _p(act_bias), 1 if act else 0, bs, cin, cout, h, w, nreg,
-                       (1 if up else 0) | (16 if sn is not None else 0), _p(ws), wsn, *rgb_args, _p(sn),
+                       (1 if up else 0) | (OUT_SP if sn is not None else 0), _p(ws), wsn, *rgb_args, _p(sn),
                        _p(blocks), _p(bctrl) if blocks is not None else None, _stream())
     elif sb:
         lib().call("e4s_region_modconv3x3_sb", _p(out), _p(x), _p(wt[0]), _p(wt[1]), _p(s), _p(d), _p(labels), lh, lw, _p(nz), nbs or 0,
                    _p(noise_weight) if nz is not None else None, _p(act_bias), 1 if act else 0, bs, cin, cout, h, w, nreg,
-                   (1 if up else 0) | (2 if x_nhwc else 0) | (4 if out_nhwc else 0) | (16 if sn is not None else 0), _p(ws), wsn, *rgb_args, _p(sn),
+                   (1 if up else 0) | (X_NHWC if x_nhwc else 0) | (OUT_NHWC if out_nhwc else 0) | (OUT_SP if sn is not None else 0), _p(ws), wsn, *rgb_args, _p(sn),
                    _p(blocks), _p(bctrl) if blocks is not None else None, _stream())
     else:
         lib().call("e4s_region_modconv3x3", _p(out), _p(x), _p(wt), _p(s), _p(d), _p(labels), lh, lw, _p(nz), nbs or 0,
@@ -1168,7 +1165,6 @@ def chain_conv3x3(x_sp: torch.Tensor, wt, d, noise, noise_weight, act_bias, act:
     """Single-region ``StyledConv`` (same resolution) on split planes.  ``s_next [bs, 1, cout]``: also write the activation as split planes
     modulated for the next layer; ``rgb = (wt_rgb, s_rgb, bias, skip or None, up_kernel)``: the following ToRGB fused (as in
     ``region_modconv3x3``).  Returns ``(out_sp or None, rgb image or None)``."""
-    from ._lib import ChainLayer
     _req(x_sp, "x_sp", torch.int16)
     if x_sp.dim() != 6 or x_sp.shape[0] != 2 or x_sp.shape[-1] != 8 or not x_sp.is_contiguous():
         raise ValueError("chain_conv3x3: x_sp must be contiguous split planes [2, bs, C/8, H, W, 8]")

@@ -1,4 +1,8 @@
-"""Rows f8, f9 and f10: Blender recolouring.  Stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
+"""Rows f8 to f11: Blender recolouring (``ct_mode='blender'``), four stages: f8 the semantic colour reference, f9 the Res-U-Net that consumes its packages,
+f10 the SPADE feature network that feeds it, f11 the Real-ESRGAN step behind them.  The three networks share one weights path (``_validated``: keys, shapes
+and dtypes checked once per public call and handed on to ``lossnet.prepare``) and one convolution call (``lossnet.conv_sb``).
+
+Row f8, stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
 
 ``color_reference`` is ``get_color_refer`` (swap_face_fine/Blender/model_center/semantic_tools.py:50-167): per facial part a masked cross-attention from the
 animated image's pixels A to the target's pixels T, ``ref_p[:, a] = sum_t softmax_t(tau cos(x_a, y_t)) rgb_T[:, t]``, and its inverse.  ``blender_part_masks`` and
@@ -42,11 +46,16 @@ by reflection, so the glue WRITES reflection-padded planes and the convolution r
     block              out = conv_1(...) + bias + x_s in one epilogue (the convolution's residual pointer); norm_0 and norm_s share the statistics of x
 
 Spectral norm in eval mode makes no power iteration: ``weight_orig / (u . W v)`` is folded on the host in float64 when the weights are prepared.
+
+Row f11, stage 4 — the Real-ESRGAN step, ``RRDBNet(3, 3, 64, num_block, 32, scale=4)`` between the two wrappers of ``RealESRBatchInfer``
+(swap_face_fine/realesr/image_infer.py), forward only (``realesr_forward``, ``realesr_input``, ``realesr_image``); the glue on csrc/rrdb.hip.  A dense block's
+concatenations are never formed: its convolutions read the head of a 192-plane slab and write their 32 planes right behind it (``_rrdb_sample``).
 """
 from __future__ import annotations
 
 import ctypes
 import functools
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -54,7 +63,7 @@ import torch.nn.functional as F
 
 from . import lossnet
 from ._lib import lib
-from .lossnet import bn_fold, prep_fwd, weights_key
+from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
 from .ops import _Prepared, _c, _p, _stream
 from .ops_post import GREY_MORPH_MAX_RADIUS, grey_dilate
 
@@ -258,6 +267,62 @@ def blender_packages(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.T
     return packages, (inv, inv_target)
 
 
+# ------------------------------------------------------------------------------------------------ the networks' weights
+# What ``_validated`` needs to know of a network: ``cls`` its name in messages; ``shapes(variant)`` the public ``{key: shape}`` function; ``prefixes`` the key
+# prefixes a checkpoint may carry (``nested``: or a mapping of that name inside it); ``variant(name, sd)`` reads the width / small or full / block count off
+# the bare keys and raises for a missing probe key; ``training``: why a module in training mode is refused (None: it makes no difference); ``skip``: the key
+# suffixes that are not float weights.
+_Net = namedtuple("_Net", "cls shapes prefixes nested probes variant training skip")
+
+
+@functools.lru_cache(maxsize=8)
+def _keys_shapes(cls, *args):
+    with torch.device("meta"):
+        return tuple((k, tuple(v.shape)) for k, v in cls(*args).state_dict().items())
+
+
+@functools.lru_cache(maxsize=8)
+def _float_keys(net, variant):
+    return tuple((k, shape) for k, shape in net.shapes(variant).items() if not k.endswith(net.skip))
+
+
+def _validated(name, weights, net):
+    """(mapping with bare keys, variant, float tensors in key order) of ``weights``: a module with the network's keys or a mapping, bare or prefixed.  Made
+    once per public call (one ``state_dict()``) and handed on.  Refused, in this order: a module in training mode, anything without keys, a missing probe key,
+    a missing key, a wrong shape or dtype."""
+    if isinstance(weights, nn.Module):
+        if weights.training and net.training:
+            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; {net.training}: call .eval()")
+        sd = weights.state_dict()
+    elif hasattr(weights, "keys"):
+        sd = weights
+    else:
+        raise TypeError(f"{name}: weights must be a module or a mapping with the keys of {net.cls}, got {type(weights).__name__}")
+    if not any(p in sd for p in net.probes):
+        for prefix in net.prefixes:
+            if net.nested and isinstance(sd.get(prefix[:-1]), dict):          # the checkpoint file as torch.load gives it
+                sd = sd[prefix[:-1]]
+                break
+            if any(prefix + p in sd for p in net.probes):
+                sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+                break
+    variant = net.variant(name, sd)
+    out = []
+    for k, shape in _float_keys(net, variant):
+        t = sd.get(k)
+        if t is None:
+            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {net.cls} (ops.{net.shapes.__name__}({variant!r}))")
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"{name}: '{k}' is {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}, expected float32 {shape}")
+        out.append(t)
+    return sd, variant, out
+
+
+def _devices_checked(name, nm, t, ts):
+    if any(w.device != t.device for w in ts):
+        raise RuntimeError(f"{name}: device mismatch: {nm} on {t.device}, the weights on {sorted({str(w.device) for w in ts})}")
+
+
 # ------------------------------------------------------------------------------------------------ row f9: the Res-U-Net
 RESUNET_WIDTHS = (64, 16)                    # ResUNet(args): 64, or 16 with args.small_FPN
 RESUNET_IN_CHANNELS = 12
@@ -319,49 +384,28 @@ class ResUNet(nn.Module):
         return self.output_decoder_layer(x)
 
 
-@functools.lru_cache(maxsize=2)
-def _keys_shapes(width):
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in ResUNet(width).state_dict().items())
-
-
 def resunet_state_dict_shapes(width: int = 64):
     """``{key: shape}`` of ``ResUNet(width).state_dict()``, in its order."""
-    return dict(_keys_shapes(width))
+    return dict(_keys_shapes(ResUNet, width))
 
 
-def _resunet_mapping(weights):
-    if isinstance(weights, nn.Module):
-        return weights.state_dict()
-    if "input_encoder_layer.conv1.weight" not in weights and "unet.input_encoder_layer.conv1.weight" in weights:
-        return {k[len("unet."):]: v for k, v in weights.items() if k.startswith("unet.")}
-    return weights
-
-
-def _resunet_checked(name, weights):
-    """(mapping, width) of ``weights``: a module with the network's keys (``ResUNet``, the drop-in) in eval mode, or a mapping."""
-    if isinstance(weights, nn.Module):
-        if weights.training:
-            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; batch statistics are not offered: call .eval()")
-    elif not hasattr(weights, "keys"):
-        raise TypeError(f"{name}: weights must be a module or a mapping with the Res-U-Net's keys, got {type(weights).__name__}")
-    sd = _resunet_mapping(weights)
+def _resunet_width(name, sd):
     first = sd.get("input_encoder_layer.conv1.weight")
     if first is None:
         raise KeyError(f"{name}: the weights lack 'input_encoder_layer.conv1.weight': expected the keys of ResUNet (ops.resunet_state_dict_shapes())")
     width = int(first.shape[0])
     if width not in RESUNET_WIDTHS or tuple(first.shape[1:]) != (RESUNET_IN_CHANNELS, 3, 3):
         raise ValueError(f"{name}: the first convolution is {tuple(first.shape)}: the network's width must be one of {RESUNET_WIDTHS}")
-    return sd, width
+    return width
+
+
+_RESUNET_NET = _Net("ResUNet", resunet_state_dict_shapes, ("unet.",), False, ("input_encoder_layer.conv1.weight",), _resunet_width,
+                "batch statistics are not offered", ("num_batches_tracked",))
 
 
 def resunet_weight_tensors(weights):
-    """The float tensors of the network (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
-    sd, width = _resunet_checked("blender_unet", weights)
-    try:
-        return [sd[k] for k in resunet_state_dict_shapes(width) if not k.endswith("num_batches_tracked")]
-    except KeyError as e:
-        raise KeyError(f"blender_unet: the weights lack {e}: expected the keys of ResUNet({width})") from None
+    """The float tensors of the network (``num_batches_tracked`` aside), in key order, their shapes checked: what ``weights_key`` watches."""
+    return _validated("blender_unet", weights, _RESUNET_NET)[2]
 
 
 class PreparedResUNet(_Prepared):
@@ -371,13 +415,12 @@ class PreparedResUNet(_Prepared):
 
     __slots__ = ()
 
-    def get(self, weights):
-        ts = resunet_weight_tensors(weights)
+    def get(self, weights, checked=None):
+        sd, width, ts = checked if checked is not None else _validated("blender_unet", weights, _RESUNET_NET)
         key = weights_key(ts) + (ts[0].device,)
         hit = self._lookup(key)
         if hit is not None:
             return hit
-        sd, width = _resunet_checked("blender_unet", weights)
         sd = {k: _c(sd[k].detach(), k) for k in resunet_state_dict_shapes(width) if not k.endswith("num_batches_tracked")}
         blocks = {}
         with torch.no_grad():
@@ -396,24 +439,11 @@ class PreparedResUNet(_Prepared):
         return self._publish(key, dict(width=width, blocks=blocks, head=head))
 
 
-def _conv3(x0, prepared, *, k, stride=1, relu=False, residual=None, x1=None, pad=None):
-    """``e4s_conv2d_sb3`` on prepared ``(slabs, bias)``; input channels from ``x0`` then ``x1`` (a concatenation that is never formed).  Zero padding
-    ``k // 2`` unless ``pad`` says otherwise (0 for an input that carries its reflection padding)."""
-    slabs, bias = prepared
-    bs, c0, h, w = x0.shape
-    cin = c0 + (x1.shape[1] if x1 is not None else 0)
-    cout, pad = slabs[0].shape[3], k // 2 if pad is None else pad
-    out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x0.device)
-    lib().call("e4s_conv2d_sb3", _p(out), _p(x0), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, None, _p(residual), 1 if relu else 0,
-               bs, cin, cout, h, w, k, stride, pad, _stream())
-    return out
-
-
 def _block(B, x, act, x1=None):
     """conv1 (+ folded BatchNorm, ReLU) on ``act``, the 1x1 shortcut on the raw input (``x``, or ``x`` and ``x1``), conv2 + bias + shortcut."""
-    c1 = _conv3(act, B["conv1"], k=3, stride=B["stride"], relu=True)
-    shortcut = _conv3(x, B["sqz"], k=1, stride=B["stride"], x1=x1)
-    return _conv3(c1, B["conv2"], k=3, residual=shortcut)
+    c1 = conv_sb(act, *B["conv1"], k=3, stride=B["stride"], relu=True)
+    shortcut = conv_sb(x, *B["sqz"], k=1, stride=B["stride"], x1=x1)
+    return conv_sb(c1, *B["conv2"], k=3, residual=shortcut)
 
 
 def _unet_forward(P, x):
@@ -440,17 +470,22 @@ def _unet_forward(P, x):
     return out
 
 
-def _unet_checked(name, packages, weights):
+def _unet(name, packages, weights, checked=None):
+    """``blender_unet`` under the caller's name; ``checked``: the caller's own ``_validated`` weights."""
     _tensor_checked(name, "packages", packages, torch.float32, 4, f"float32 [bs, {RESUNET_IN_CHANNELS}, H, W] packages")
     bs, c, H, W = packages.shape
     if c != RESUNET_IN_CHANNELS:
         raise ValueError(f"{name}: packages: expected float32 [bs, {RESUNET_IN_CHANNELS}, H, W] packages, got {tuple(packages.shape)}")
     if H < 8 or W < 8 or H % 8 or W % 8:
         raise ValueError(f"{name}: packages are {H} x {W}: both sizes must be multiples of 8 (three stride-2 blocks), at least 8")
-    ts = resunet_weight_tensors(weights)
-    if any(t.device != packages.device for t in ts):
-        raise RuntimeError(f"{name}: device mismatch: packages on {packages.device}, the weights on {sorted({str(t.device) for t in ts})}")
+    if checked is None:
+        checked = _validated(name, weights, _RESUNET_NET)
+    _devices_checked(name, "packages", packages, checked[2])
     _cuda_checked(name, packages=packages)
+    if bs == 0:
+        return torch.empty((0, 3, H, W), dtype=torch.float32, device=packages.device)
+    with torch.no_grad():
+        return _unet_forward(lossnet.prepare(PreparedResUNet, weights, checked), packages.detach().contiguous())
 
 
 def blender_unet(packages: torch.Tensor, weights) -> torch.Tensor:
@@ -458,13 +493,14 @@ def blender_unet(packages: torch.Tensor, weights) -> torch.Tensor:
     ``packages`` of ``blender_packages``; ``H`` and ``W`` multiples of 8.  ``weights``: a module with the network's keys (``ResUNet``, the drop-in
     ``res_u_net.ResUNet``) or a mapping; the width is read off them.  Forward only, no gradient.  Every argument is checked before any launch; no host
     synchronisation, the same inputs give the same bits, and after one eager call (which prepares the weights) the call captures in a graph."""
-    name = "blender_unet"
-    _unet_checked(name, packages, weights)
-    bs, _, H, W = packages.shape
-    if bs == 0:
-        return torch.empty((0, 3, H, W), dtype=torch.float32, device=packages.device)
-    with torch.no_grad():
-        return _unet_forward(lossnet.prepare(PreparedResUNet, weights), packages.detach().contiguous())
+    return _unet("blender_unet", packages, weights)
+
+
+def _recolor(name, img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau, weights, checked):
+    if isinstance(img_t, torch.Tensor) and img_t.dim() == 4 and (img_t.shape[2] % 8 or img_t.shape[3] % 8):
+        raise ValueError(f"{name}: images are {img_t.shape[2]} x {img_t.shape[3]}: both sizes must be multiples of 8")
+    packages, pair = blender_packages(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau)
+    return _unet(name, packages, weights, checked), packages, pair
 
 
 def blender_recolor(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Tensor, labels_t: torch.Tensor, feats_a: torch.Tensor, feats_t: torch.Tensor,
@@ -472,11 +508,7 @@ def blender_recolor(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
     """``Blender.forward`` after its FPN calls: ``(pred, packages, (inv, inv_target))`` with ``packages`` and the pair from ``blender_packages`` and
     ``pred = blender_unet(packages, weights)``.  ``H`` and ``W`` multiples of 8."""
     name = "blender_recolor"
-    _resunet_checked(name, weights)
-    if isinstance(img_t, torch.Tensor) and img_t.dim() == 4 and (img_t.shape[2] % 8 or img_t.shape[3] % 8):
-        raise ValueError(f"{name}: images are {img_t.shape[2]} x {img_t.shape[3]}: both sizes must be multiples of 8")
-    packages, pair = blender_packages(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau)
-    return blender_unet(packages, weights), packages, pair
+    return _recolor(name, img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau, weights, _validated(name, weights, _RESUNET_NET))
 
 
 # ------------------------------------------------------------------------------------------------ row f10: the feature network
@@ -582,60 +614,27 @@ class BlenderNet(nn.Module):
         self.unet = ResUNet(16 if small_FPN else 64)
 
 
-@functools.lru_cache(maxsize=2)
-def _fpn_keys_shapes(small):
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in (SmallFPN() if small else BlenderFPN()).state_dict().items())
-
-
 def fpn_state_dict_shapes(small: bool = False):
     """``{key: shape}`` of ``BlenderFPN().state_dict()`` (``SmallFPN()`` with ``small``), in its order."""
-    return dict(_fpn_keys_shapes(bool(small)))
+    return dict(_keys_shapes(SmallFPN if small else BlenderFPN))
 
 
-def _fpn_mapping(weights):
-    sd = weights.state_dict() if isinstance(weights, nn.Module) else weights
-    if "layer1.0.weight_orig" in sd or "conv1.weight" in sd:
-        return sd
-    for prefix in _FPN_PREFIXES:
-        if prefix + "layer1.0.weight_orig" in sd or prefix + "conv1.weight" in sd:
-            return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    return sd
-
-
-def _fpn_checked(name, weights):
-    """(mapping, small) of ``weights``: a module with a feature network's keys (``BlenderFPN``, ``SmallFPN``, the drop-ins) in eval mode, or a mapping."""
-    if isinstance(weights, nn.Module):
-        if weights.training:
-            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; spectral norm's power iteration is not offered: call .eval()")
-    elif not hasattr(weights, "keys"):
-        raise TypeError(f"{name}: weights must be a module or a mapping with the feature network's keys, got {type(weights).__name__}")
-    sd = _fpn_mapping(weights)
+def _fpn_small(name, sd):
     if "layer1.0.weight_orig" in sd:
-        return sd, False
+        return False
     if "conv1.weight" in sd:
-        return sd, True
+        return True
     raise KeyError(f"{name}: the weights have neither 'layer1.0.weight_orig' (BlenderFPN) nor 'conv1.weight' (SmallFPN): expected the keys of "
                    f"ops.fpn_state_dict_shapes(), bare or prefixed with one of {_FPN_PREFIXES}")
 
 
-def _fpn_validated(name, weights):
-    """(mapping, small, tensors in key order) of ``weights``, keys, shapes and dtypes checked: made once per call and handed on."""
-    sd, small = _fpn_checked(name, weights)
-    out = []
-    for k, shape in fpn_state_dict_shapes(small).items():
-        t = sd.get(k)
-        if t is None:
-            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {'SmallFPN' if small else 'BlenderFPN'}")
-        if tuple(t.shape) != shape or t.dtype != torch.float32:
-            raise ValueError(f"{name}: '{k}' is {t.dtype} {tuple(t.shape)}, expected float32 {shape}")
-        out.append(t)
-    return sd, small, out
+_FPN_NET = _Net("BlenderFPN / SmallFPN", fpn_state_dict_shapes, _FPN_PREFIXES, False, ("layer1.0.weight_orig", "conv1.weight"), _fpn_small,
+            "spectral norm's power iteration is not offered", ())
 
 
 def fpn_weight_tensors(weights, name: str = "blender_fpn"):
     """The tensors of the feature network in key order, their shapes checked: what ``weights_key`` watches."""
-    return _fpn_validated(name, weights)[2]
+    return _validated(name, weights, _FPN_NET)[2]
 
 
 def _sigma_folded(sd, prefix):
@@ -654,7 +653,7 @@ class PreparedFPN(_Prepared):
     __slots__ = ()
 
     def get(self, weights, checked=None):
-        sd, small, ts = checked if checked is not None else _fpn_validated("blender_fpn", weights)
+        sd, small, ts = checked if checked is not None else _validated("blender_fpn", weights, _FPN_NET)
         key = weights_key(ts) + (ts[0].device,)
         hit = self._lookup(key)
         if hit is not None:
@@ -697,10 +696,10 @@ def _modulate(x, stats, gamma_beta, leaky, padded):
 
 def _fpn_forward(P, img):
     if P["small"]:
-        return _conv3(_conv3(img, P["convs"][0], k=1, stride=2), P["convs"][1], k=1, stride=2)
+        return conv_sb(conv_sb(img, *P["convs"][0], k=1, stride=2), *P["convs"][1], k=1, stride=2)
     x = img
     for i, L in enumerate(P["layers"]):                                 # conv -> InstanceNorm -> LeakyReLU; layer5 ends with its InstanceNorm
-        y = _conv3(x, L["conv"], k=3, stride=L["stride"])
+        y = conv_sb(x, *L["conv"], k=3, stride=L["stride"])
         x = _modulate(y, _plane_stats(y), None, leaky=i + 1 < len(P["layers"]), padded=False)
     bs, _, h, w = x.shape
     # gamma and beta depend on the image alone: the first layers of all seven norms in one launch, each norm's slice a contiguous padded batch
@@ -709,14 +708,14 @@ def _fpn_forward(P, img):
 
     def spade(norm, src, stats, leaky, padded):
         idx, gb = norm
-        return _modulate(src, stats, _conv3(actv[idx], gb, k=3, pad=0), leaky, padded)
+        return _modulate(src, stats, conv_sb(actv[idx], *gb, k=3, pad=0), leaky, padded)
 
     for B in P["blocks"]:
         stats = _plane_stats(x)                                         # norm_0 and norm_s normalise the same x
-        dx = _conv3(spade(B["norm_0"], x, stats, True, True), B["conv_0"], k=3, pad=0)
+        dx = conv_sb(spade(B["norm_0"], x, stats, True, True), *B["conv_0"], k=3, pad=0)
         a1 = spade(B["norm_1"], dx, _plane_stats(dx), True, True)
-        shortcut = _conv3(spade(B["norm_s"], x, stats, False, False), B["conv_s"], k=1) if B["conv_s"] is not None else x
-        x = _conv3(a1, B["conv_1"], k=3, pad=0, residual=shortcut)
+        shortcut = conv_sb(spade(B["norm_s"], x, stats, False, False), *B["conv_s"], k=1) if B["conv_s"] is not None else x
+        x = conv_sb(a1, *B["conv_1"], k=3, pad=0, residual=shortcut)
     return x
 
 
@@ -737,16 +736,14 @@ def _fpn_image_checked(name, nm, img):
 
 def _fpn_checked_all(name, weights, **images):
     """Every check of a feature-network call, once; returns the validated weights for ``_fpn_prepared``."""
-    checked = _fpn_validated(name, weights)
-    ts = checked[2]
+    checked = _validated(name, weights, _FPN_NET)
     for nm, img in images.items():
         _fpn_image_checked(name, nm, img)
     shapes = {tuple(img.shape) for img in images.values()}
     if len(shapes) != 1:
         raise ValueError(f"{name}: the images differ in shape: {sorted(shapes)}")
     for nm, img in images.items():
-        if any(t.device != img.device for t in ts):
-            raise RuntimeError(f"{name}: device mismatch: {nm} on {img.device}, the weights on {sorted({str(t.device) for t in ts})}")
+        _devices_checked(name, nm, img, checked[2])
     _cuda_checked(name, **images)
     return checked
 
@@ -831,7 +828,7 @@ def blender_forward(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
     fpn, tau, unet = _blender_weights(name, weights)
     if flip_target is not None and not isinstance(flip_target, bool):
         raise TypeError(f"{name}: flip_target is True, False or None, got {type(flip_target).__name__}")
-    _resunet_checked(name, unet)
+    unet_checked = _validated(name, unet, _RESUNET_NET)
     for nm, t in (("img_a", img_a), ("img_t", img_t)):
         _fpn_image_checked(name, nm, t)
     if img_t.shape[2] % 8 or img_t.shape[3] % 8:
@@ -842,7 +839,7 @@ def blender_forward(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
     if tau.numel() != 1 or tau.dtype != torch.float32 or tau.device != img_t.device:
         raise ValueError(f"{name}: referencer.trainable_tao is one float32 element on the images' device, got {tau.dtype} {tuple(tau.shape)} on {tau.device}")
     feats_a, feats_t = _features_run(img_a, img_t, fpn, checked, flip_target)
-    return blender_recolor(img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau.reshape(1), unet)
+    return _recolor(name, img_a, img_t, labels_a, labels_t, feats_a, feats_t, tau.reshape(1), unet, unet_checked)
 
 
 # ------------------------------------------------------------------------------------------------ row f11: the Real-ESRGAN step
@@ -903,55 +900,28 @@ class RRDBNet(nn.Module):
         return self.conv_last(F.leaky_relu(self.conv_hr(feat), RRDB_SLOPE))
 
 
-@functools.lru_cache(maxsize=4)
-def _rrdb_keys_shapes(num_block):
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in RRDBNet(num_block).state_dict().items())
-
-
 def rrdbnet_state_dict_shapes(num_block: int = 23):
     """``{key: shape}`` of ``RRDBNet(num_block).state_dict()``, in its order."""
-    return dict(_rrdb_keys_shapes(num_block))
+    return dict(_keys_shapes(RRDBNet, num_block))
 
 
-def _rrdb_validated(name, weights):
-    """(mapping, block count, tensors in key order) of ``weights``: a module with the network's keys (``RRDBNet``) or a mapping, bare or a checkpoint with
-    ``params_ema`` / ``params``; keys, shapes and dtypes checked.  The block count is read off the keys."""
-    if isinstance(weights, nn.Module):
-        sd = weights.state_dict()
-    elif hasattr(weights, "keys"):
-        sd = weights
-        if "conv_first.weight" not in sd:
-            for prefix in _RRDB_PREFIXES:
-                if isinstance(sd.get(prefix[:-1]), dict):                  # the checkpoint file as torch.load gives it
-                    sd = sd[prefix[:-1]]
-                    break
-                if prefix + "conv_first.weight" in sd:
-                    sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-                    break
-    else:
-        raise TypeError(f"{name}: weights must be a module or a mapping with RRDBNet's keys, got {type(weights).__name__}")
-    if "conv_first.weight" not in sd:
-        raise KeyError(f"{name}: the weights lack 'conv_first.weight': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
+def _rrdb_blocks(name, sd):
     num_block = 0
     while f"body.{num_block}.rdb1.conv1.weight" in sd:
         num_block += 1
-    if num_block < 1:
-        raise KeyError(f"{name}: the weights lack 'body.0.rdb1.conv1.weight': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
-    out = []
-    for k, shape in rrdbnet_state_dict_shapes(num_block).items():
-        t = sd.get(k)
-        if t is None:
-            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of RRDBNet({num_block})")
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
-            raise ValueError(f"{name}: '{k}' is {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}, expected float32 {shape}")
-        out.append(t)
-    return sd, num_block, out
+    for probe in ("conv_first.weight", "body.0.rdb1.conv1.weight"):
+        if probe not in sd:
+            raise KeyError(f"{name}: the weights lack '{probe}': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
+    return num_block
+
+
+# a mapping may be the checkpoint itself, with the network under ``params_ema`` or ``params``
+_RRDB_NET = _Net("RRDBNet", rrdbnet_state_dict_shapes, _RRDB_PREFIXES, True, ("conv_first.weight",), _rrdb_blocks, None, ())
 
 
 def rrdbnet_weight_tensors(weights, name: str = "realesr_forward"):
     """The tensors of the network in key order, their shapes checked: what ``weights_key`` watches."""
-    return _rrdb_validated(name, weights)[2]
+    return _validated(name, weights, _RRDB_NET)[2]
 
 
 class PreparedRRDBNet(_Prepared):
@@ -963,7 +933,7 @@ class PreparedRRDBNet(_Prepared):
     __slots__ = ()
 
     def get(self, weights, checked=None):
-        sd, num_block, ts = checked if checked is not None else _rrdb_validated("realesr_forward", weights)
+        sd, num_block, ts = checked if checked is not None else _validated("realesr_forward", weights, _RRDB_NET)
         key = weights_key(ts) + (ts[0].device,)
         hit = self._lookup(key)
         if hit is not None:
@@ -986,43 +956,31 @@ class PreparedRRDBNet(_Prepared):
         return self._publish(key, P)
 
 
-def _conv3_into(out, x, prepared, cin, h, w, slope=None, residual=None):
-    """``e4s_conv2d_sb3`` (3x3, stride 1, zero pad 1) of ONE sample: the first ``cin`` planes of ``x`` into ``out``, both ``[planes, h, w]`` views of larger
-    buffers; LeakyReLU as the PReLU epilogue with ``slope``; ``residual`` added before it."""
-    slabs, bias = prepared
-    cout = slabs[0].shape[3]
-    lib().call("e4s_conv2d_sb3", _p(out), _p(x), None, cin, *[_p(s) for s in slabs], _p(bias), None, None, _p(slope), _p(residual),
-               2 if slope is not None else 0, 1, cin, cout, h, w, 3, 1, 1, _stream())
-
-
-def _rrdb_sample(P, x, out_f, out_u8, slabs, feat0, ups):
-    """The network on one sample ``x [3, h, w]``.  ``slabs``: three ``[192, h, w]`` buffers; a dense block reads the head of one (x, x1 ..) and each of its
-    first four convolutions writes its 32 planes right behind what it read, so no concatenation is formed; conv5 writes the head of the NEXT slab with this
-    slab's head as its residual.  An RRDB's input (the head of slab 0) outlives its three dense blocks: block 1 goes 0 -> 1, block 2 goes 1 -> 2, block 3
-    goes 2 -> 1, and ``e4s_esr_scale_add`` puts ``head(1) * 0.2 + head(0)`` back into the head of slab 0.  ``ups``: per upsampling the pair (nearest x2,
-    convolution output) of ``[64, 2h, 2w]`` and ``[64, 4h, 4w]`` buffers; conv_hr writes over conv_up2's input, which is free by then."""
-    _, h, w = x.shape
-    hw = h * w
+def _rrdb_sample(P, x, out_f, out_u8, reads, writes, feat0, ups):
+    """The network on one sample ``x [1, 3, h, w]``.  ``reads`` / ``writes``: the views of three ``[1, 192, h, w]`` slabs (``_rrdb_run``); a dense block reads
+    the head of one (x, x1 ..) and each of its first four convolutions writes its 32 planes right behind what it read, so no concatenation is formed; conv5
+    writes the head of the NEXT slab with this slab's head as its residual.  An RRDB's input (the head of slab 0) outlives its three dense blocks: block 1
+    goes 0 -> 1, block 2 goes 1 -> 2, block 3 goes 2 -> 1, and ``e4s_esr_scale_add`` puts ``head(1) * 0.2 + head(0)`` back into the head of slab 0.
+    ``ups``: per upsampling the pair (nearest x2, convolution output) of ``[1, 64, 2h, 2w]`` and ``[1, 64, 4h, 4w]`` buffers; conv_hr writes over conv_up2's
+    input, which is free by then."""
+    _, _, h, w = x.shape
     st = _stream()
-    _conv3_into(feat0, x, P["first"], 3, h, w)
-    slabs[0][:RRDB_FEAT].copy_(feat0)
+    head0, head1 = reads[0][0], reads[1][0]
+    conv_sb(x, *P["first"], k=3, out=feat0)
+    head0.copy_(feat0)
     for block in P["body"]:
         for rdb, (src, dst) in zip(block, ((0, 1), (1, 2), (2, 1))):
-            S = slabs[src]
+            R, W = reads[src], writes[src]
             for k in range(4):
-                cin = RRDB_FEAT + k * RRDB_GROW
-                _conv3_into(S[cin:cin + RRDB_GROW], S, rdb[k], cin, h, w, slope=P["slope32"])
-            _conv3_into(slabs[dst][:RRDB_FEAT], S, rdb[4], RRDB_SLAB, h, w, residual=S)
-        lib().call("e4s_esr_scale_add", _p(slabs[0]), _p(slabs[1]), _p(slabs[0]), RRDB_FEAT, hw, st)
-    feat = slabs[1][:RRDB_FEAT]
-    _conv3_into(feat, slabs[0], P["conv_body"], RRDB_FEAT, h, w, residual=feat0)               # feat + conv_body(body(feat))
+                conv_sb(R[k], *rdb[k], k=3, slope=P["slope32"], out=W[k])
+            conv_sb(R[4], *rdb[4], k=3, residual=R[0], out=reads[dst][0])
+        lib().call("e4s_esr_scale_add", _p(head0), _p(head1), _p(head0), RRDB_FEAT, h * w, st)
+    feat = conv_sb(head0, *P["conv_body"], k=3, residual=feat0, out=head1)                    # feat + conv_body(body(feat))
     for name, (up, out) in zip(("up1", "up2"), ups):
         lib().call("e4s_esr_up2", _p(up), _p(feat), RRDB_FEAT, h, w, st)
         h, w = 2 * h, 2 * w
-        _conv3_into(out, up, P[name], RRDB_FEAT, h, w, slope=P["slope64"])
-        feat = out
-    hr = ups[1][0]
-    _conv3_into(hr, feat, P["hr"], RRDB_FEAT, h, w, slope=P["slope64"])
+        feat = conv_sb(up, *P[name], k=3, slope=P["slope64"], out=out)
+    hr = conv_sb(feat, *P["hr"], k=3, slope=P["slope64"], out=ups[1][0])
     lib().call("e4s_esr_tail", _p(out_u8), _p(out_f), _p(hr), _p(P["last"][0]), _p(P["last"][1]), 1, h, w, st)
 
 
@@ -1033,23 +991,26 @@ def _rrdb_run(x, P, want_float, want_u8):
     out_f = new(bs, 3, 4 * h, 4 * w) if want_float else None
     # the tail kernel always writes its uint8 image; a caller that wants the float output alone gets one sample's worth of it as scratch
     out_u8 = torch.empty((bs if want_u8 else 1, 4 * h, 4 * w, 3), dtype=torch.uint8, device=x.device)
-    slabs = [new(RRDB_SLAB, h, w) for _ in range(3)]
-    feat0 = new(RRDB_FEAT, h, w)
-    ups = [(new(RRDB_FEAT, 2 * h, 2 * w), new(RRDB_FEAT, 2 * h, 2 * w)), (new(RRDB_FEAT, 4 * h, 4 * w), new(RRDB_FEAT, 4 * h, 4 * w))]
+    slabs = [new(1, RRDB_SLAB, h, w) for _ in range(3)]
+    # the views the 15 convolutions of an RRDB go through, made here once: convolution k of a dense block reads the slab's first 64 + 32 k planes ...
+    reads = [[S[:, :RRDB_FEAT + k * RRDB_GROW] for k in range(5)] for S in slabs]
+    # ... and (k < 4) writes the 32 planes behind them
+    writes = [[S[:, RRDB_FEAT + k * RRDB_GROW:RRDB_FEAT + (k + 1) * RRDB_GROW] for k in range(4)] for S in slabs]
+    feat0 = new(1, RRDB_FEAT, h, w)
+    ups = [(new(1, RRDB_FEAT, 2 * h, 2 * w), new(1, RRDB_FEAT, 2 * h, 2 * w)), (new(1, RRDB_FEAT, 4 * h, 4 * w), new(1, RRDB_FEAT, 4 * h, 4 * w))]
     for b in range(bs):
-        _rrdb_sample(P, x[b], out_f[b] if want_float else None, out_u8[b if want_u8 else 0], slabs, feat0, ups)
+        _rrdb_sample(P, x[b:b + 1], out_f[b] if want_float else None, out_u8[b if want_u8 else 0], reads, writes, feat0, ups)
     return out_f, (out_u8 if want_u8 else None)
 
 
 def _rrdb_checked_all(name, x, weights):
-    checked = _rrdb_validated(name, weights)
+    checked = _validated(name, weights, _RRDB_NET)
     _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, h, w] image")
     if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
         raise ValueError(f"{name}: x: expected a float32 [bs, 3, h, w] image with h, w >= 1, got {tuple(x.shape)}")
     if 4 * x.shape[2] > 16384 or 4 * x.shape[3] > 16384:
         raise ValueError(f"{name}: x is {x.shape[2]} x {x.shape[3]}: the x4 output may be 16384 x 16384 at the most")
-    if any(t.device != x.device for t in checked[2]):
-        raise RuntimeError(f"{name}: device mismatch: x on {x.device}, the weights on {sorted({str(t.device) for t in checked[2]})}")
+    _devices_checked(name, "x", x, checked[2])
     _cuda_checked(name, x=x)
     return checked
 
@@ -1093,9 +1054,9 @@ def realesr_image(img_u8: torch.Tensor, weights, in_size: int = 256) -> torch.Te
     ``* 0.5 + 0.5``, the clamp and the ``align_corners=True`` bilinear resize to ``in_size``), the network, and ``e4s_esr_tail`` (conv_last, ``* 2 - 1``, the
     clamp, ``* 127.5 + 127.5``, the clamp and the truncation).  uint8 ``[bs, H, W, 3]`` to uint8 ``[bs, 4 in_size, 4 in_size, 3]``."""
     name = "realesr_image"
-    checked = _rrdb_validated(name, weights)
-    if isinstance(img_u8, torch.Tensor) and any(t.device != img_u8.device for t in checked[2]):
-        raise RuntimeError(f"{name}: device mismatch: img_u8 on {img_u8.device}, the weights on {sorted({str(t.device) for t in checked[2]})}")
+    checked = _validated(name, weights, _RRDB_NET)
+    if isinstance(img_u8, torch.Tensor):
+        _devices_checked(name, "img_u8", img_u8, checked[2])
     with torch.no_grad():
         x = realesr_input(img_u8, (in_size, in_size), name)
         if x.shape[0] == 0:

@@ -354,7 +354,7 @@ def _recolor_nets_checked(ct_mode, recolor_fn, recolor_nets):
         raise TypeError("swap_images: recolor_nets is the pair (blender, esr): the recolouring network's weights and the Real-ESRGAN network's")
     blender, esr = recolor_nets
     ops_recolor._blender_weights("swap_images", blender)                # both fail here, before the crop and the swap are launched
-    ops_recolor._rrdb_validated("swap_images", esr)
+    ops_recolor.rrdbnet_weight_tensors(esr, "swap_images")
     return blender, esr
 
 
@@ -470,7 +470,7 @@ def realesr_infer_batch(weights, x: torch.Tensor, out_hw=None, in_size: int = ES
     The second resize is skipped when ``out_hw`` is the network's output size, where it is the identity.  ``weights`` as ``ops.realesr_forward`` takes them;
     ``in_size`` is the reference's 256."""
     name = "realesr_infer_batch"
-    ops_recolor._rrdb_validated(name, weights)
+    ops_recolor.rrdbnet_weight_tensors(weights, name)
     ops_recolor._tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image in [-1, 1]")
     if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
         raise ValueError(f"{name}: x: expected a float32 [bs, 3, H, W] image in [-1, 1], got {tuple(x.shape)}")
@@ -499,7 +499,7 @@ def realesr_infer_image(weights, img_u8: torch.Tensor, in_size: int = ESR_IN, ou
     in_size, out_size = _esr_size_checked(name, "in_size", in_size), _esr_size_checked(name, "out_size", out_size)
     if out_size == 4 * in_size:
         return ops.realesr_image(img_u8, weights, in_size)
-    ops_recolor._rrdb_validated(name, weights)
+    ops_recolor.rrdbnet_weight_tensors(weights, name)
     x = ops.realesr_input(img_u8, (in_size, in_size))
     if x.shape[0] == 0:
         return torch.empty((0, out_size, out_size, 3), dtype=torch.uint8, device=x.device)
@@ -524,7 +524,7 @@ def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, pa
     _crops_checked(name, swapped_u8, target_u8)
     if not swapped_u8.is_cuda:
         raise RuntimeError(f"{name}: the frames must be CUDA tensors")
-    ops_recolor._rrdb_validated(name, esr)
+    ops_recolor.rrdbnet_weight_tensors(esr, name)
     ops_recolor._blender_weights(name, blender)
     bs, h, w, _ = swapped_u8.shape
     if bs == 0:

@@ -703,7 +703,7 @@ E4S_API int e4s_fp_maxpool2(float* out, const float* a, int planes, int h, int w
 E4S_API int e4s_fp_tap_bwd(float* g, const float* fx, const float* fy, const float* stats, const float* gout, const float* gpool, int bs, int C, int h,
                            int w, float scale, void* stream);
 
-/* Multi-target loss heads (csrc/lpips.hip, idloss.hip, fploss.hip, pixloss.hip): one reconstruction against k (1 .. 4) targets, target j weighted by tw[j]
+/* Multi-target loss heads (csrc/lpips.hip, idloss.hip, fploss.hip, pixloss.hip): one reconstruction against k (1 .. E4S_MAX_TARGETS) targets, target j weighted by tw[j]
  * — the driven and the recoloured frame of the PTI objective share the reconstruction's forward pass and input gradient.  ys [k] and tw [k] are HOST
  * arrays (device pointers, weights), read at the call.  Target j of sample b starts at ys[j] + f * fstride + b * (per-sample size) with f = *frame (a
  * device int32, e.g. written before a graph replay to pick a frame of a clip-wide feature cache, clamped to [0, nframes)), or f = 0 when frame is NULL.
@@ -717,6 +717,7 @@ E4S_API int e4s_fp_tap_bwd(float* g, const float* fx, const float* fy, const flo
  *                               targets already weighted (y fg), fg [bs][1][hw] or NULL (1); bs C <= 65535
  *   e4s_pix_mse_multi_bwd     : gx [bs][C][hw] = gout[0] 2 / (bs C hw) sum_j tw[j] (x fg - y_j) fg
  * No float atomics: the same inputs give the same bits; k = 1 with weight 1 gives the single-target heads' values. */
+#define E4S_MAX_TARGETS 4
 E4S_API int e4s_lpips_head_multi(float* partial, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,
                                  const float* lin, int bs, int c, int hw, float scale, void* stream);
 E4S_API int e4s_lpips_head_multi_bwd(float* gx, const float* fx, const float* const* ys, const float* tw, int k, const int* frame, int64_t fstride, int nframes,

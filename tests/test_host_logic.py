@@ -29,6 +29,91 @@ def test_library_exports_every_declared_symbol():
     assert {s for s in exported if s.startswith("e4s_")} == set(declared)          # nothing undeclared leaks out either
 
 
+def test_prototypes_are_derived_from_the_header():
+    """A handful of entry points that exercise every rule of ``_lib.parse_header``, written out: pointers of any kind, int, int64_t, float, unsigned."""
+    from e4s2024_amd import _lib
+    I, L, F, P, U = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint
+    want = {
+        "e4s_fused_bias_act": [P, P, P, P, I, I, F, F, L, L, L, P],
+        "e4s_gemm_sb": [P, P, P, I, I, I, I, I, I, I, L, L, L, I, P, L, P],
+        "e4s_erode_labels": [P, P, I, I, I, I, U, P],
+        "e4s_style_demod_batched": [P, I, I, I, P],                              # const E4sStyleJob*
+        "e4s_id_head_partial_multi": [P, P, P, P, I, P, L, I, I, L, P],           # const float* const*
+        "e4s_mconv_dgrad_tiles": [I, I],                                         # no pointer, no stream
+        "e4s_conv2d_sb3": [P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+        "e4s_abi_version": [],
+        "e4s_last_error": [],
+    }
+    for name, args in want.items():
+        assert _lib._PROTOS[name] == args, name
+    assert all(isinstance(a, list) for a in _lib._PROTOS.values())
+    fns = _lib.lib().cdll
+    assert fns.e4s_last_error.restype is ctypes.c_char_p and fns.e4s_abi_version.restype is I and fns.e4s_conv2d_sb3.restype is I
+    assert list(fns.e4s_erode_labels.argtypes) == want["e4s_erode_labels"]
+
+
+def test_host_structs_are_derived_from_the_header():
+    from e4s2024_amd import _lib
+    assert ctypes.sizeof(_lib.StyleJob) == 80 and ctypes.sizeof(_lib.ChainLayer) == 152
+    assert [n for n, _ in _lib.StyleJob._fields_] == ["s", "d", "styles", "stride_b", "stride_r", "mod_weight", "mod_bias", "wsq", "nreg", "cin", "cout", "_pad"]
+    assert [t for _, t in _lib.StyleJob._fields_] == [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 2 + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4
+    assert [n for n, _ in _lib.ChainLayer._fields_] == ["x_sp", "whi", "wlo", "d", "noise", "noise_weight", "act_bias", "out_sp", "s_next", "rgb_out", "rgb_wt", "rgb_s",
+                                                        "rgb_bias", "rgb_skip", "rgb_up_kernel", "noise_bs", "act", "bs", "cin", "cout", "h", "w", "_pad"]
+    assert [t for _, t in _lib.ChainLayer._fields_] == [ctypes.c_void_p] * 15 + [ctypes.c_int] * 8
+    job = _lib.StyleJob(1, None, 3, 4, 5, 6, 7, None, 9, 10, 11, 0)               # ops.style_demod_plan fills it by position
+    assert (job.s, job.d, job.stride_r, job.cout) == (1, None, 5, 11)
+
+
+@pytest.mark.parametrize("decl, names", [
+    ("E4S_API int e4s_bad(float* out, double x, void* stream);", ("e4s_bad", "double x")),
+    ("E4S_API int e4s_bad(float* out, size_t n);", ("e4s_bad", "size_t n")),
+    ("E4S_API int e4s_bad(E4sStyleJob job, void* stream);", ("e4s_bad", "E4sStyleJob job")),                  # a struct by value
+    ("E4S_API int e4s_bad(const int n);", ("e4s_bad", "const int n")),
+    ("E4S_API float e4s_bad(int n);", ("e4s_bad", "float")),                                                   # a return type without a rule
+    ("E4S_API int e4s_bad(void (*callback)(int), void* stream);", ("E4S_API",)),                               # a declaration it cannot read at all
+    ("typedef struct E4sBad { float* p; double x; } E4sBad;", ("E4sBad", "double x")),
+    ("typedef struct E4sBad { float *p, *q; } E4sBad;", ("E4sBad", "p, *q")),
+])
+def test_header_parser_refuses_what_it_has_no_rule_for(decl, names):
+    from e4s2024_amd import _lib
+    good = "/* E4S_API int e4s_in_a_comment(double x); */\n#define E4S_N (-3)\nE4S_API int e4s_good(const float* const* ys, int64_t n, unsigned bits); // double y\n"
+    protos, restypes, structs, defines = _lib.parse_header(good)
+    assert protos == {"e4s_good": [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint]} and defines == {"E4S_N": -3} and not structs
+    with pytest.raises(TypeError) as e:
+        _lib.parse_header(good + decl)
+    assert all(n in str(e.value) for n in names), str(e.value)
+
+
+def test_call_checks_the_argument_count_before_the_foreign_call():
+    """ctypes accepts extra arguments to a cdecl function, so ``call`` counts them itself.  A call that got through would fail differently: the arguments
+    below are rejected by the library (kh = 40) with a RuntimeError."""
+    from e4s2024_amd._lib import lib
+    one = ctypes.c_void_p(16)
+    args = (one, one, one, 1, 4, 4, 40, 4, 1, 1, 1, 1, 0, 0, 0, 0, None)
+    with pytest.raises(RuntimeError, match="e4s_upfirdn2d failed"):
+        lib().call("e4s_upfirdn2d", *args)
+    with pytest.raises(TypeError, match=r"e4s_upfirdn2d takes 17 arguments, 18 given"):
+        lib().call("e4s_upfirdn2d", *args, 7)
+    with pytest.raises(TypeError, match=r"e4s_upfirdn2d takes 17 arguments, 16 given"):
+        lib().call("e4s_upfirdn2d", *args[:-1])
+    with pytest.raises(TypeError, match=r"e4s_conv2d_sb3 takes 22 arguments, 23 given"):
+        lib().call("e4s_conv2d_sb3", *([None] * 23))
+
+
+def test_constants_come_from_the_header():
+    import re
+    from e4s2024_amd import _lib, lossnet, ops
+    src = open(_lib.HEADER).read()
+    define = lambda n: int(re.search(rf"^#define {n} \(?(-?\d+)\)?", src, re.M).group(1))   # noqa: E731
+    assert ops.MAX_REGIONS == define("E4S_MAX_REGIONS") == 16 and ops.LABEL_NONE == define("E4S_LABEL_NONE") == 255
+    assert _lib.MAX_TARGETS == lossnet.MAX_TARGETS == define("E4S_MAX_TARGETS") == 4
+    assert (ops.X_NHWC, ops.OUT_NHWC, ops.X_SP, ops.OUT_SP) == tuple(define(n) for n in ("E4S_X_NHWC", "E4S_OUT_NHWC", "E4S_X_SP", "E4S_OUT_SP")) == (2, 4, 8, 16)
+    assert ops.MAX_STYLE_JOBS == define("E4S_MAX_STYLE_JOBS") == 32 and _lib.ERR_ARG == define("E4S_ERR_ARG") == -1
+    assert _lib.ABI_VERSION == define("E4S_ABI_VERSION") == _lib.lib().cdll.e4s_abi_version()
+    targets_h = open(os.path.join(ROOT, "e4s2024_amd", "csrc", "targets.h")).read()
+    assert "MAX_TARGETS = E4S_MAX_TARGETS;" in targets_h and re.search(r"(?<![\w.])4(?![\w.])", targets_h) is None      # no literal 4 left
+
+
 def test_abi_signatures_carry_no_torch_types():
     import re
     src = open(os.path.join(ROOT, "include", "e4s_hip.h")).read()

@@ -169,3 +169,22 @@ def test_argument_errors_before_any_launch():
         ops.blender_recolor(img, img, lab, lab, feats, feats, 7.0, net)
     with pytest.raises(TypeError):
         ops.blender_recolor(img, img, lab, lab, feats, None, 7.0, net)
+
+
+def test_inner_weights_are_refused_by_name_before_any_launch():
+    """Every key, shape and dtype of a Res-U-Net is checked on the host, not the first convolution's alone; CPU tensors are refused after that."""
+    from e4s2024_amd import ops
+    good, sd, key = T(RM.case_inputs("8x8.w16")), RM.state_dict(16), "res_en_layer3.conv2.weight"
+    assert tuple(sd[key].shape) == (64, 64, 3, 3)
+    for call in (lambda w: ops.blender_unet(good, w), lambda w: ops.resunet_weight_tensors(w),
+                 lambda w: ops.blender_recolor(None, None, None, None, None, None, 7.0, w)):
+        with pytest.raises(KeyError, match=key):
+            call({k: v for k, v in sd.items() if k != key})
+        with pytest.raises(ValueError, match=key):
+            call({**sd, key: torch.zeros(64, 32, 3, 3)})                                      # the wrong cin
+        with pytest.raises(ValueError, match=f"{key}.*float64"):
+            call({**sd, key: sd[key].double()})
+        with pytest.raises(KeyError, match=key):
+            call({"unet." + k: v for k, v in sd.items() if k != key})
+    with pytest.raises(RuntimeError, match="must be a CUDA tensor"):                           # num_batches_tracked is no float weight: not asked for
+        ops.blender_unet(good, {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")})
