@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from ._lib import lib
-from .ops import _Prepared, _c, _p, _stream, _timed, _volatile, mx_arith, mx_exact_active, mx_flags
+from .ops import _Prepared, _c, _p, _req, _stream, _timed, _volatile, mx_arith, mx_exact_active, mx_flags
 
 # --------------------------------------------------------------------------- a8 / a9 (conv.hip, norm.hip, parser.hip)
 class PreparedConv(_Prepared):
@@ -455,6 +455,21 @@ def conv2d_winograd(x: torch.Tensor, U: torch.Tensor, *, in_norm=None, prelu: Op
     return out
 
 
+def _vec(t: Optional[torch.Tensor], n: int, name: str) -> Optional[torch.Tensor]:
+    """A per-plane / per-channel vector that a kernel reads through a bare pointer (gate, mean, rstd, PReLU slopes, ``add_vec``): ``None``, or a contiguous
+    float32 CUDA tensor of exactly ``n`` elements, whatever its shape.  Raises before anything is launched: a host pointer, another dtype, a strided view or
+    a wrong length would be read as garbage."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be torch.float32, got {t.dtype} (the MI355X path computes in fp32)")
+    if not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"{name} must be a contiguous tensor of {n} elements, got shape {tuple(t.shape)} with strides {tuple(t.stride())}")
+    return _req(t, name)                  # (the device last, so that every other rule can be exercised on host tensors)
+
+
 def plane_stats(x: torch.Tensor, eps: Optional[float] = None, want_nmean: bool = False):
     """Per-(b, c) mean [bs, C] (``eps=None``: mean only = global average pooling), or (mean, rstd[, nmean])."""
     x = _c(x, "input")
@@ -479,6 +494,8 @@ def vec_fc(x: torch.Tensor, weight: torch.Tensor, bn=None, act: int = ACT_NONE) 
     w = _c(weight.detach(), "weight")
     cout, cin = w.shape[0], w.shape[1]
     bs = x.shape[0]
+    if tuple(x.shape) != (bs, cin) or w.numel() != cout * cin:
+        raise ValueError(f"vec_fc: input {tuple(x.shape)} does not fit the weight {tuple(w.shape)} (expected [bs, {cin}])")
     y = torch.empty((bs, cout), dtype=torch.float32, device=x.device)
     if bn is not None:
         if bn.training:
@@ -496,6 +513,8 @@ def se_gate(pooled: torch.Tensor, fc1_weight: torch.Tensor, fc2_weight: torch.Te
     """``sigmoid(fc2 . relu(fc1 . pooled))`` for ``pooled [bs, C]`` and the two bias-free 1x1 conv weights of an SEModule, one launch
     (``e4s_se_gate``); value for value the two ``vec_fc`` calls."""
     x = _c(pooled, "pooled")
+    if x.ndim != 2:
+        raise ValueError(f"se_gate: pooled must be [bs, C], got {tuple(x.shape)}")
     w1, w2 = _c(fc1_weight.detach(), "fc1.weight"), _c(fc2_weight.detach(), "fc2.weight")
     bs, C = x.shape
     H = w1.shape[0]
@@ -543,21 +562,25 @@ def norm_gate_add(x, mean=None, rstd=None, gate=None, shortcut=None, sc_stats=No
     with ``stats_eps``): the statistics of ``x`` itself are computed in that launch too (``e4s_norm_self_gate_add_stats``; ``plane_stats`` first where the plane does not fit)."""
     x = _c(x, "input")
     bs, C, h, w = x.shape
+    mean, rstd, gate = _vec(mean, bs * C, "mean"), _vec(rstd, bs * C, "rstd"), _vec(gate, bs * C, "gate")
+    if (mean is None) != (rstd is None):
+        raise ValueError("norm_gate_add: mean and rstd go together")
     if self_eps is not None:
         if mean is not None or rstd is not None or stats_eps is None:
             raise ValueError("norm_gate_add: self_eps replaces mean / rstd and goes with stats_eps")
-        if not ((h * w) % 4 == 0 and (h * w <= ops.NGA_STATS_MAX_PIXELS or (h * w <= 4 * ops.NGA_STATS_MAX_PIXELS and shortcut is None))):
-            mean, rstd = plane_stats(x, self_eps)
-            self_eps = None
-    out = torch.empty_like(x)
     sc = scm = scr = None
     if shortcut is not None:
         sc = _c(shortcut, "shortcut")
         if tuple(sc.shape) != (bs, C, h * sc_stride, w * sc_stride):
             raise ValueError(f"shortcut shape {tuple(sc.shape)} != {(bs, C, h * sc_stride, w * sc_stride)}")
         if sc_stats is not None:
-            scm, scr = _c(sc_stats[0], "sc_mean"), _c(sc_stats[1], "sc_rstd")
-    pr = _p(_c(prelu.detach(), "prelu")) if prelu is not None else None
+            scm, scr = _vec(sc_stats[0], bs * C, "sc_mean"), _vec(sc_stats[1], bs * C, "sc_rstd")
+    pr = _p(_vec(prelu, C, "prelu").detach()) if prelu is not None else None
+    # (every argument is checked by here: nothing above launches)
+    if self_eps is not None and not ((h * w) % 4 == 0 and (h * w <= ops.NGA_STATS_MAX_PIXELS or (h * w <= 4 * ops.NGA_STATS_MAX_PIXELS and shortcut is None))):
+        mean, rstd = plane_stats(x, self_eps)
+        self_eps = None
+    out = torch.empty_like(x)
     if self_eps is not None:
         om = torch.empty((bs, C), dtype=torch.float32, device=x.device)
         orr = torch.empty_like(om)
@@ -580,6 +603,8 @@ def masked_avg_pool(feats: torch.Tensor, labels: torch.Tensor, nreg: int) -> tor
     feats = _c(feats, "features")
     labels = _c(labels, "labels", torch.uint8)
     bs, C, h, w = feats.shape
+    if labels.ndim != 3 or labels.shape[0] != bs:
+        raise ValueError(f"masked_avg_pool: labels {tuple(labels.shape)} do not fit {bs} images (expected [bs, H, W])")
     out = torch.empty((bs, nreg, C), dtype=torch.float32, device=feats.device)
     lib().call("e4s_masked_avg_pool", _p(out), _p(feats), _p(labels), labels.shape[1], labels.shape[2], bs, C, h, w, nreg, _stream())
     return out
@@ -617,6 +642,7 @@ def gate_add_upsample(feat, gate=None, add_map=None, add_vec=None, up: int = 1) 
     am = _c(add_map, "add_map") if add_map is not None else None
     if am is not None and tuple(am.shape) != tuple(feat.shape):
         raise ValueError("add_map must have the shape of feat")
+    gate, add_vec = _vec(gate, bs * C, "gate"), _vec(add_vec, bs * C, "add_vec")
     lib().call("e4s_gate_add_upsample", _p(out), _p(feat), _p(gate), _p(am), _p(add_vec), bs * C, h, w, up, _stream())
     return out
 
@@ -651,4 +677,4 @@ def tensor2im_u8(img: torch.Tensor) -> torch.Tensor:
     return out
 
 
-__all__ = ['MxOperandMap', 'conv3x3_s1_c4_pair', 'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'PreparedConv', '_is_f16x3', 'conv2d', 'PreparedWinograd', 'winograd_route', 'mx4_eligible', 'mx_conv_eligible', 'conv3x3_mx', 'conv3x3_s2_mx', 'conv3x3_s2_takes_mx', '_ShapeOnly', 'conv3x3_s2', 'conv3x3_s1_takes_mx3', 'conv3x3_s1', 'conv2d_winograd', 'plane_stats', 'vec_fc', 'se_gate', '_half_gates', 'half_gate', 'norm_gate_add', 'masked_avg_pool', '_out_like', 'bilinear_resize', 'maxpool3x3s2', 'gate_add_upsample', 'bilinear_argmax', 'bicubic_down_normalize', 'tensor2im_u8']
+__all__ = ['MxOperandMap', '_vec', 'conv3x3_s1_c4_pair', 'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'PreparedConv', '_is_f16x3', 'conv2d', 'PreparedWinograd', 'winograd_route', 'mx4_eligible', 'mx_conv_eligible', 'conv3x3_mx', 'conv3x3_s2_mx', 'conv3x3_s2_takes_mx', '_ShapeOnly', 'conv3x3_s2', 'conv3x3_s1_takes_mx3', 'conv3x3_s1', 'conv2d_winograd', 'plane_stats', 'vec_fc', 'se_gate', '_half_gates', 'half_gate', 'norm_gate_add', 'masked_avg_pool', '_out_like', 'bilinear_resize', 'maxpool3x3s2', 'gate_add_upsample', 'bilinear_argmax', 'bicubic_down_normalize', 'tensor2im_u8']

@@ -163,6 +163,37 @@ def test_ops_refuse_cpu_tensors_and_wrong_dtype():
         ops.plane_stats(torch.zeros(1, 4, 8, 8), 1e-5)
 
 
+def test_vector_arguments_of_the_glue_wrappers_are_checked_on_the_host():
+    """``ops_encode._vec``: gate / mean / rstd / shortcut statistics / PReLU slopes / add_vec reach their kernels as bare pointers, so the wrapper accepts only a
+    contiguous float32 CUDA tensor of exactly the expected length.  Pure host code: called here with host tensors, nothing can be launched."""
+    from e4s2024_amd.ops_encode import _vec
+    assert _vec(None, 6, "gate") is None
+    with pytest.raises(TypeError, match="torch.Tensor"):
+        _vec([0.5] * 6, 6, "gate")
+    with pytest.raises(TypeError, match="float32"):
+        _vec(torch.zeros(2, 3, dtype=torch.float64), 6, "gate")
+    with pytest.raises(TypeError, match="float32"):
+        _vec(torch.zeros(2, 3, dtype=torch.float16), 6, "rstd")
+    with pytest.raises(ValueError, match="contiguous tensor of 6 elements"):
+        _vec(torch.zeros(2, 6)[:, ::2], 6, "mean")                             # the right count behind a stride
+    with pytest.raises(ValueError, match="contiguous tensor of 6 elements"):
+        _vec(torch.zeros(3, 2).t(), 6, "sc_mean")
+    for n in (5, 7, 0):
+        with pytest.raises(ValueError, match="contiguous tensor of 6 elements"):
+            _vec(torch.zeros(n), 6, "prelu")
+    with pytest.raises(ValueError, match="contiguous tensor of 6 elements"):
+        _vec(torch.zeros(2, 3, 2), 6, "add_vec")
+    for good in (torch.zeros(6), torch.zeros(2, 3), torch.zeros(2, 3, 1, 1), torch.zeros(4, 6)[1]):
+        with pytest.raises(RuntimeError, match="CUDA tensor"):                  # everything else in order: only the device is left to object to
+            _vec(good, 6, "gate")
+    from e4s2024_amd import ops
+    for call in (lambda: ops.vec_fc(torch.zeros(2, 5), torch.zeros(3, 4)), lambda: ops.se_gate(torch.zeros(2, 8, 1, 1), torch.zeros(2, 8), torch.zeros(8, 2)),
+                 lambda: ops.masked_avg_pool(torch.zeros(2, 4, 8, 8), torch.zeros(1, 8, 8, dtype=torch.uint8), 12),
+                 lambda: ops.norm_gate_add(torch.zeros(1, 2, 4, 4), gate=torch.zeros(2)), lambda: ops.gate_add_upsample(torch.zeros(1, 2, 4, 4), gate=torch.zeros(2))):
+        with pytest.raises(RuntimeError, match="CUDA tensor"):                  # the wrappers themselves never get as far as a launch with host tensors
+            call()
+
+
 # ------------------------------------------------------------------------------------------------ drop-in trees
 def _meta(fn):
     with torch.device("meta"):
