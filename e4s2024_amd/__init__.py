@@ -8,13 +8,14 @@ Layout
                  ``models/stylegan2/op/``, ``models/encoders/psp_encoders.py``, ``swap_face_fine/face_parsing/*.py``, ``criteria/lpips/*.py``,
                  ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
                  ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``,
-                 ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``)
+                 ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``,
+                 ``swap_face_fine/gpen/face_model/gpen_model.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
 
 ``install()`` redirects exactly those module names to the drop-in files, leaving every other module of the reference
-tree (``utils.*``, ``models.encoders.model_irse``, ``swap_face_fine.gpen`` …) to resolve as before::
+tree (``utils.*``, ``models.encoders.model_irse``, the rest of ``swap_face_fine.gpen`` …) to resolve as before::
 
     import e4s2024_amd; e4s2024_amd.install()
     from models.networks import Net3                      # the MI355X implementation
@@ -75,9 +76,15 @@ ENHANCE_OVERRIDES = {
     "swap_face_fine.realesr.image_infer": "swap_face_fine/realesr/image_infer.py",
 }
 
+# row f12: GPEN face enhancement, stage 1: the generator behind FaceGAN (face_gan.py:14 imports FullGenerator and FullGenerator_SR from it).  The sibling ``op``
+# package is not redirected: the drop-in does not import it
+GPEN_OVERRIDES = {
+    "swap_face_fine.gpen.face_model.gpen_model": "swap_face_fine/gpen/face_model/gpen_model.py",
+}
+
 
 def _redirected():
-    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES}
+    return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -95,7 +102,8 @@ _finder = None
 
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
-    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``) and the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``) to the drop-in files.
+    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``) and GPEN's generator (``GPEN_OVERRIDES``) to the
+    drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -1,0 +1,620 @@
+"""Row f12: GPEN face enhancement, stage 1 — the GAN-prior generator, ``FullGenerator`` of swap_face_fine/gpen/face_model/gpen_model.py:628-690, in eval mode
+between the tensor ends of ``FaceGAN`` (face_gan.py:49-62): ``gpen_forward``, ``gpen_image``.  Everything else of ``FaceEnhancement.process`` (the RetinaFace
+detector, the 5-point warps, ParseNet, the RealESRNet pass, the paste mask, ``cv2.resize``) stays with the caller.
+
+The network is a StyleGAN2 synthesis network behind a strided-convolution encoder, with one style per sample; its contractions run on kernels the library
+has for the regional generator, in their single-region form (``nreg = 1``, no label map), the rest on csrc/gpen.hip:
+
+    ecd0               e4s_gpen_stem: 1 x 1 convolution 3 -> C0, bias, leaky-relu * sqrt(2) in exact float32; from uint8 it applies img2tensor's roundings too
+    ecd1 ..            e4s_upfirdn2d (4 x 4 FIR, pad (2, 2)), then e4s_conv2d_sb (3 x 3, stride 2, pad 0): sqrt(2) of the fused activation is folded into weight
+                       and bias in float64 (leaky-relu is positively homogeneous), the PReLU epilogue with a 0.2 slope vector is then FusedLeakyReLU exactly
+    final_linear, MLP  e4s_grouped_linear (groups = 1, act = 2) with EqualLinear's scale and lr_mul; PixelNorm between them is three stock tensor operations
+    tables             every layer's style and demodulation tables in one e4s_style_demod_batched call: the one latent is known before the first layer runs
+    StyledConv         the modulated convolution writes planes [0, C) of the layer's [2C, h, w] buffer with the first C entries of the activation bias and no
+                       additive noise; e4s_gpen_noise_half writes lrelu(noise.weight * f_r + bias[C:]) * sqrt(2) into planes [C, 2C), one launch for both layers
+                       of a resolution.  The concatenation is never copied.
+    ToRGB              e4s_region_torgb, which chains the skips through the FIR upsampling
+
+Up layers.  Three entries compute a single-region up layer: the parity-composed form (``e4s_region_modconv3x3_sb(up = 1)``: 4 x the transposed convolution's
+multiply-adds, but split-K over the input channels, so it fills the chip on a 4 x 4 map), the pair ``e4s_modconv_tconv_sb`` + ``e4s_blur_epilogue`` (1 x, no
+split-K, a [cout, 2h + 1, 2w + 1] round trip) and ``e4s_modconv_up_fused_sb`` (1 x, one launch, no split-K: its grid is tiles x cout / 32).  A layer whose
+input is at most ``UP_COMPOSED_MAX_WIDTH`` (32) wide takes the composed form: one sample at a time the 1 x entries run such a layer on 16 - 64 workgroups.
+Measured on an MI355X at GPEN-BFR-512's shapes, batch 1 (tools/time_gpen.py --layers; the table is profiles/f12_time_gpen.txt, quoted in DESIGN.md row
+f12): the composed form is 6 x faster at 4 x 4 and still ahead at 32 x 32, from 64 x 64 on the fused entry wins.  The two-launch pair is not used: it has
+the fused entry's grid and a round trip more.  ``ARITH = "f32"`` takes the
+composed exact-fp32 entry for every up layer.
+
+``ARITH`` (module attribute): ``"sb"``, the default, runs the convolutions on the two-way split-bf16 entries, the synthesis path's arithmetic (bar: 1e-3 on
+generated pixels); ``"f32"`` on the exact-fp32 entries ``e4s_region_modconv3x3`` / ``e4s_conv2d``.  The stem, the linear layers, the tables, ToRGB and the
+glue are float32 in both.
+
+The existing kernels write dense ``[bs, cout, h, w]`` outputs, so the samples of a batch run one after another on one sample's scratch, each exactly as a
+batch-of-one call.  Forward only; no host synchronisation; the same inputs give the same bits; after one eager call (which prepares the weights) a call
+captures in a graph."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import lossnet
+from ._lib import MAX_STYLE_JOBS, StyleJob, lib
+from .lossnet import weights_key
+from .ops import _Prepared, _c, _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
+from .ops_recolor import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+
+ARITH = "sb"                                 # "sb" | "f32" (module attribute, no environment variable: tests and tools set it)
+UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form (measured: see the module text)
+LR_MLP = 0.01
+SQRT2 = math.sqrt(2.0)
+_FIR = (1.0, 3.0, 3.0, 1.0)
+
+
+def gpen_channels(channel_multiplier: int = 2, narrow: float = 1):
+    """Channels per resolution (gpen_model.py:642-653)."""
+    c = {r: int(512 * narrow) for r in (4, 8, 16, 32)}
+    c.update({64: int(256 * channel_multiplier * narrow), 128: int(128 * channel_multiplier * narrow), 256: int(64 * channel_multiplier * narrow),
+              512: int(32 * channel_multiplier * narrow), 1024: int(16 * channel_multiplier * narrow), 2048: int(8 * channel_multiplier * narrow)})
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ the module: the reference's keys, a stock-PyTorch forward
+class _Fir(nn.Module):
+    """``Blur`` / ``Upsample``: the FIR buffer ``kernel``."""
+
+    def __init__(self, gain: float = 1.0):
+        super().__init__()
+        k = torch.tensor(_FIR, dtype=torch.float32)
+        k = k[None, :] * k[:, None]
+        k = k / k.sum()
+        self.register_buffer("kernel", k * gain if gain != 1.0 else k)
+
+
+class _EqualLinear(nn.Module):
+    def __init__(self, in_dim, out_dim, bias_init=0.0, lr_mul=1.0):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn(out_dim, in_dim).div_(lr_mul))
+        self.bias = nn.Parameter(torch.zeros(out_dim).fill_(bias_init))
+        self.lr_mul = lr_mul
+        self.scale = (1 / math.sqrt(in_dim)) * lr_mul
+
+
+class _EqualConv(nn.Module):
+    def __init__(self, cin, cout, k):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn(cout, cin, k, k))
+
+
+class _Bias(nn.Module):
+    """``FusedLeakyReLU``: its bias."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.bias = nn.Parameter(torch.zeros(c))
+
+
+class _ModConv(nn.Module):
+    def __init__(self, cin, cout, k, style_dim, up=False):
+        super().__init__()
+        if up:
+            self.blur = _Fir(4.0)
+        self.weight = nn.Parameter(torch.randn(1, cout, cin, k, k))
+        self.modulation = _EqualLinear(style_dim, cin, bias_init=1.0)
+
+
+class _Noise(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(1))
+
+
+class _StyledConv(nn.Module):
+    def __init__(self, cin, cout, style_dim, up=False):
+        super().__init__()
+        self.conv = _ModConv(cin, cout, 3, style_dim, up)
+        self.noise = _Noise()
+        self.activate = _Bias(2 * cout)
+
+
+class _ToRGB(nn.Module):
+    def __init__(self, cin, style_dim, up=True):
+        super().__init__()
+        if up:
+            self.upsample = _Fir(4.0)
+        self.conv = _ModConv(cin, 3, 1, style_dim)
+        self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
+
+
+class _Input(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.input = nn.Parameter(torch.randn(1, c, 4, 4))
+
+
+class _Generator(nn.Module):
+    def __init__(self, size, style_dim, n_mlp, ch):
+        super().__init__()
+        self.style = nn.Sequential(nn.Identity(), *[_EqualLinear(style_dim, style_dim, lr_mul=LR_MLP) for _ in range(n_mlp)])    # (0: PixelNorm)
+        self.input = _Input(ch[4])
+        self.conv1 = _StyledConv(ch[4], ch[4], style_dim)
+        self.to_rgb1 = _ToRGB(2 * ch[4], style_dim, up=False)
+        self.convs, self.upsamples, self.to_rgbs = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        cin = ch[4]
+        for i in range(3, int(math.log2(size)) + 1):
+            cout = ch[2 ** i]
+            self.convs.append(_StyledConv(2 * cin, cout, style_dim, up=True))
+            self.convs.append(_StyledConv(2 * cout, cout, style_dim))
+            self.to_rgbs.append(_ToRGB(2 * cout, style_dim))
+            cin = cout
+
+
+def _config_checked(size, style_dim, n_mlp, channel_multiplier, narrow):
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)      # noqa: E731
+    if not ok_int(size) or size < 8 or size > 2048 or size & (size - 1):
+        raise ValueError(f"GPEN: size is a power of two in 8..2048, got {size!r}")
+    if not ok_int(style_dim) or style_dim < 1 or not ok_int(n_mlp) or n_mlp < 1 or not ok_int(channel_multiplier) or channel_multiplier < 1:
+        raise ValueError(f"GPEN: style_dim, n_mlp and channel_multiplier are positive ints, got {style_dim!r}, {n_mlp!r}, {channel_multiplier!r}")
+    ch = gpen_channels(channel_multiplier, narrow)
+    if min(ch[2 ** i] for i in range(2, int(math.log2(size)) + 1)) < 1:
+        raise ValueError(f"GPEN: narrow = {narrow!r} leaves a level without channels")
+    return ch
+
+
+class GPEN(nn.Module):
+    """``FullGenerator(size, style_dim, n_mlp, channel_multiplier, narrow=narrow)`` of swap_face_fine/gpen/face_model/gpen_model.py with its ``state_dict`` keys,
+    shapes and order (163 tensors at the default, the FIR buffers and ``generator.input.input`` included; ``GPEN-BFR-512.pth`` loads with ``strict=True``).
+    ``forward`` is the plain PyTorch composition in eval mode — what the tests and the timing compare ``gpen_forward`` with; ``gpen_forward(x, module)`` runs
+    the same weights on the HIP kernels.  It starts with random weights and ``gpen_forward`` refuses it until ``load_state_dict`` has filled it."""
+
+    def __init__(self, size: int = 512, style_dim: int = 512, n_mlp: int = 8, channel_multiplier: int = 2, narrow: float = 1):
+        super().__init__()
+        ch = _config_checked(size, style_dim, n_mlp, channel_multiplier, narrow)
+        self.size, self.style_dim, self.n_mlp, self.channel_multiplier, self.narrow = size, style_dim, n_mlp, channel_multiplier, narrow
+        self.log_size = int(math.log2(size))
+        self.n_latent = 2 * self.log_size - 2
+        self.generator = _Generator(size, style_dim, n_mlp, ch)
+        self.ecd0 = nn.Sequential(nn.Sequential(_EqualConv(3, ch[size], 1), _Bias(ch[size])))          # (a ConvLayer inside a Sequential)
+        cin = ch[size]
+        for i in range(self.log_size, 2, -1):
+            cout = ch[2 ** (i - 1)]
+            setattr(self, f"ecd{self.log_size - i + 1}", nn.Sequential(nn.Sequential(_Fir(), _EqualConv(cin, cout, 3), _Bias(cout))))
+            cin = cout
+        self.final_linear = nn.Sequential(_EqualLinear(16 * ch[4], style_dim))
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        if "ecd0.0.0.weight" in state_dict and "generator.input.input" in state_dict:
+            self._loaded = True
+        return out
+
+    def forward(self, x, return_latents: bool = False):
+        if self.training:
+            raise NotImplementedError("GPEN: training mode is not implemented; call .eval()")
+        with torch.no_grad():
+            image, latent = _torch_forward(dict(self.state_dict()), x, self.log_size)
+        return image, (latent if return_latents else None)
+
+
+def _flrelu(x, bias):
+    return F.leaky_relu(x + bias.view((1, -1) + (1,) * (x.dim() - 2)), 0.2) * SQRT2
+
+
+def _upfirdn(x, k, up, pad):
+    bs, c, h, w = x.shape
+    if up > 1:
+        z = x.new_zeros(bs, c, h, up, w, up)
+        z[:, :, :, 0, :, 0] = x
+        x = z.reshape(bs, c, h * up, w * up)
+    x = F.pad(x, (pad[0], pad[1], pad[0], pad[1]))
+    out = F.conv2d(x.reshape(bs * c, 1, x.shape[2], x.shape[3]), torch.flip(k, [0, 1])[None, None])
+    return out.reshape(bs, c, out.shape[2], out.shape[3])
+
+
+def _torch_modconv(sd, p, x, w, up=False, demodulate=True):
+    W = sd[p + ".weight"][0]
+    cout, cin, k, _ = W.shape
+    s = F.linear(w, sd[p + ".modulation.weight"] * (1 / math.sqrt(w.shape[1])), sd[p + ".modulation.bias"])
+    Wm = (1 / math.sqrt(cin * k * k)) * W[None] * s[:, None, :, None, None]
+    if demodulate:
+        Wm = Wm * torch.rsqrt(Wm.pow(2).sum([2, 3, 4]) + 1e-8)[:, :, None, None, None]
+    bs, _, h, wd = x.shape
+    xg = x.reshape(1, bs * cin, h, wd)
+    if up:
+        out = F.conv_transpose2d(xg, Wm.transpose(1, 2).reshape(bs * cin, cout, k, k), stride=2, groups=bs)
+        return _upfirdn(out.reshape(bs, cout, out.shape[2], out.shape[3]), sd[p + ".blur.kernel"], 1, (1, 1))
+    return F.conv2d(xg, Wm.reshape(bs * cout, cin, k, k), padding=k // 2, groups=bs).reshape(bs, cout, h, wd)
+
+
+def _torch_styled(sd, p, x, w, noise, up=False):
+    y = _torch_modconv(sd, p + ".conv", x, w, up)
+    return _flrelu(torch.cat((y, sd[p + ".noise.weight"] * noise), 1), sd[p + ".activate.bias"])
+
+
+def _torch_forward(sd, x, log_size):
+    feats = []
+    W = sd["ecd0.0.0.weight"]
+    x = _flrelu(F.conv2d(x, W * (1 / math.sqrt(W.shape[1]))), sd["ecd0.0.1.bias"])
+    feats.append(x)
+    for i in range(1, log_size - 1):
+        W = sd[f"ecd{i}.0.1.weight"]
+        x = _flrelu(F.conv2d(_upfirdn(x, sd[f"ecd{i}.0.0.kernel"], 1, (2, 2)), W * (1 / math.sqrt(W.shape[1] * 9)), stride=2), sd[f"ecd{i}.0.2.bias"])
+        feats.append(x)
+    W = sd["final_linear.0.weight"]
+    z = _flrelu(F.linear(x.reshape(x.shape[0], -1), W * (1 / math.sqrt(W.shape[1]))), sd["final_linear.0.bias"])
+    z = z * torch.rsqrt(torch.mean(z ** 2, dim=1, keepdim=True) + 1e-8)
+    i = 1
+    while f"generator.style.{i}.weight" in sd:
+        W = sd[f"generator.style.{i}.weight"]
+        z = _flrelu(F.linear(z, W * ((1 / math.sqrt(W.shape[1])) * LR_MLP)), sd[f"generator.style.{i}.bias"] * LR_MLP)
+        i += 1
+    noise = [f for f in feats[::-1] for _ in (0, 1)][1:]
+    g = "generator."
+    out = sd[g + "input.input"].repeat(x.shape[0], 1, 1, 1)
+    out = _torch_styled(sd, g + "conv1", out, z, noise[0])
+    skip = _torch_modconv(sd, g + "to_rgb1.conv", out, z, demodulate=False) + sd[g + "to_rgb1.bias"]
+    for j in range(log_size - 2):
+        out = _torch_styled(sd, f"{g}convs.{2 * j}", out, z, noise[1 + 2 * j], up=True)
+        out = _torch_styled(sd, f"{g}convs.{2 * j + 1}", out, z, noise[2 + 2 * j])
+        p = f"{g}to_rgbs.{j}"
+        skip = _torch_modconv(sd, p + ".conv", out, z, demodulate=False) + sd[p + ".bias"] + _upfirdn(skip, sd[p + ".upsample.kernel"], 2, (2, 1))
+    return skip, z[:, None].repeat(1, 2 * log_size - 2, 1)
+
+
+# ------------------------------------------------------------------------------------------------ weights
+def gpen_state_dict_shapes(size: int = 512, style_dim: int = 512, n_mlp: int = 8, channel_multiplier: int = 2, narrow: float = 1):
+    """``{key: shape}`` of ``GPEN(size, style_dim, n_mlp, channel_multiplier, narrow).state_dict()``, in its order."""
+    return dict(_keys_shapes(GPEN, size, style_dim, n_mlp, channel_multiplier, narrow))
+
+
+def _gpen_variant(name, sd):
+    """(size, style_dim, n_mlp, channel_multiplier, narrow) read off the keys and shapes of ``sd``."""
+    for probe in ("ecd0.0.0.weight", "generator.input.input", "final_linear.0.weight"):
+        t = sd.get(probe)
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise KeyError(f"{name}: the weights lack '{probe}': expected the keys of FullGenerator (ops.gpen_state_dict_shapes())")
+    levels = 0
+    while f"ecd{levels}.0.{0 if levels == 0 else 1}.weight" in sd:
+        levels += 1
+    n_mlp = 0
+    while f"generator.style.{n_mlp + 1}.weight" in sd:
+        n_mlp += 1
+    size = 2 ** (levels + 1)
+    c4, c_size = int(sd["generator.input.input"].shape[1]), int(sd["ecd0.0.0.weight"].shape[0])
+    narrow = c4 / 512
+    base = {64: 256, 128: 128, 256: 64, 512: 32, 1024: 16, 2048: 8}.get(size)
+    cm = max(1, round(c_size / (base * narrow))) if base and narrow > 0 else 2
+    if levels < 2 or n_mlp < 1 or c4 < 1:
+        raise KeyError(f"{name}: the weights do not describe a FullGenerator ({levels} encoder levels, {n_mlp} style layers)")
+    return size, int(sd["final_linear.0.weight"].shape[0]), n_mlp, cm, narrow
+
+
+def _gpen_shapes(variant):
+    return gpen_state_dict_shapes(*variant)
+
+
+_MODULE_NETS = {}
+
+
+def _net_of(weights):
+    """The description ``_validated`` checks ``weights`` against.  A ``GPEN`` module hands over the configuration it was built with; only a mapping has it
+    read off its keys and shapes (``_gpen_variant``), which recovers ``narrow`` and ``channel_multiplier`` up to what ``int()`` left of them."""
+    if not isinstance(weights, GPEN):
+        return _GPEN_NET
+    cfg = (weights.size, weights.style_dim, weights.n_mlp, weights.channel_multiplier, weights.narrow)
+    net = _MODULE_NETS.get(cfg)
+    if net is None:
+        net = _MODULE_NETS[cfg] = _GPEN_NET._replace(variant=lambda name, sd, cfg=cfg: cfg)
+    return net
+
+
+_GPEN_NET = _Net("FullGenerator", _gpen_shapes, ("module.",), False, ("ecd0.0.0.weight",), _gpen_variant,
+                 "the native path is the eval-mode forward", ())
+
+
+def gpen_weight_tensors(weights, name: str = "gpen_forward"):
+    """The tensors of the network in key order, their shapes checked: what ``weights_key`` watches."""
+    return _validated(name, weights, _net_of(weights))[2]
+
+
+def check_loaded(weights):
+    """``weights`` itself; raises if it is a module whose weights were never loaded (an enhancement from initial parameters would be silently wrong)."""
+    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
+        raise RuntimeError(f"{type(weights).__name__}: the GPEN weights were never loaded (nothing is downloaded here); call load_state_dict first")
+    return weights
+
+
+def _use_composed(w_in: int) -> bool:
+    return ARITH != "sb" or w_in <= UP_COMPOSED_MAX_WIDTH
+
+
+class PreparedGPEN(_Prepared):
+    """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage or the arithmetic changes.  ``stem``: ecd0's weight with
+    its scale, ``[C0, 3]``, and bias; ``enc``: per level (FIR, slabs or K-major fp32 weight, bias, slope vector) with sqrt(2) folded into weight and bias in
+    float64; ``final`` and ``mlp``: the EqualLinear weights as they are (scale and lr_mul are call arguments); per modulated convolution its split-bf16 slabs
+    (or K-major fp32 weight), ``wsq`` table, modulation weights, noise weight and activation bias; per ToRGB its ``k = 1`` weight."""
+
+    __slots__ = ()
+
+    def get(self, weights, checked=None):
+        sd, variant, ts = checked if checked is not None else _validated("gpen_forward", weights, _net_of(weights))
+        key = weights_key(ts) + (ts[0].device, ARITH, UP_COMPOSED_MAX_WIDTH)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k in gpen_state_dict_shapes(*variant)}
+        size, sdim, n_mlp, _, _ = variant
+        log_size = int(math.log2(size))
+        dev = ts[0].device
+        sb = ARITH == "sb"
+        st = _stream()
+        new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+
+        def enc_level(i):
+            W, b = sd[f"ecd{i}.0.1.weight"], sd[f"ecd{i}.0.2.bias"]
+            cout, cin = W.shape[:2]
+            w = (W.double() * (SQRT2 / math.sqrt(cin * 9))).float().contiguous()
+            bias = (b.double() * SQRT2).float().contiguous()
+            if sb:
+                wt = tuple(new(((cin + 15) // 16, 9, 2, cout, 8), torch.int16) for _ in range(2))
+                lib().call("e4s_conv_prep_weights_sb", _p(wt[0]), _p(wt[1]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
+            else:
+                wt = new((cin, 9, cout))
+                lib().call("e4s_conv_prep_weights", _p(wt), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
+            return dict(fir=sd[f"ecd{i}.0.0.kernel"], wt=wt, bias=bias, slope=torch.full((cout,), 0.2, dtype=torch.float32, device=dev), cin=cin, cout=cout)
+
+        def styled(p, up, w_in):
+            W = sd[p + ".conv.weight"]
+            _, cout, cin, _, _ = W.shape
+            composed = up and _use_composed(w_in)
+            blur = sd[p + ".conv.blur.kernel"] if up else None
+            wsq = new((cin, cout))
+            if sb:
+                shape = (4 if composed else 1, (cin + 15) // 16, 9, 2, cout, 8)
+                wt = (new(shape, torch.int16), new(shape, torch.int16))
+                lib().call("e4s_modconv_prep_weights_sb", _p(wt[0]), _p(wt[1]), _p(wsq), _p(W), _p(blur) if composed else None, cout, cin, 1 if composed else 0, st)
+            else:
+                wt = new((4 if composed else 1, cin, 9, cout))
+                lib().call("e4s_modconv_prep_weights", _p(wt), _p(wsq), _p(W), _p(blur) if composed else None, cout, cin, 3, 1 if composed else 0, st)
+            return dict(wt=wt, wsq=wsq, mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], nw=sd[p + ".noise.weight"],
+                        bias=sd[p + ".activate.bias"], blur=blur, up=up, composed=composed, cin=cin, cout=cout)
+
+        def rgb(p, up):
+            W = sd[p + ".conv.weight"]
+            cin = W.shape[2]
+            wt = new((1, cin, 1, 3))
+            lib().call("e4s_modconv_prep_weights", _p(wt), None, _p(W), None, 3, cin, 1, 0, st)
+            return dict(wt=wt, mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], bias=sd[p + ".bias"].reshape(3).contiguous(),
+                        upk=sd[p + ".upsample.kernel"] if up else None, cin=cin)
+
+        with torch.no_grad():
+            W0 = sd["ecd0.0.0.weight"]
+            g = "generator."
+            convs, rgbs = [styled(g + "conv1", False, 4)], [rgb(g + "to_rgb1", False)]
+            for j in range(log_size - 2):
+                convs += [styled(f"{g}convs.{2 * j}", True, 4 << j), styled(f"{g}convs.{2 * j + 1}", False, 8 << j)]
+                rgbs.append(rgb(f"{g}to_rgbs.{j}", True))
+            P = dict(size=size, sdim=sdim, log_size=log_size, sb=sb,
+                     stem=((W0 * (1 / math.sqrt(3))).reshape(W0.shape[0], 3).contiguous(), sd["ecd0.0.1.bias"]),
+                     enc=[enc_level(i) for i in range(1, log_size - 1)],
+                     final=(sd["final_linear.0.weight"], sd["final_linear.0.bias"]),
+                     mlp=[(sd[f"{g}style.{i}.weight"], sd[f"{g}style.{i}.bias"]) for i in range(1, n_mlp + 1)],
+                     const=sd[g + "input.input"], convs=convs, rgbs=rgbs)
+        return self._publish(key, P)
+
+
+# ------------------------------------------------------------------------------------------------ the forward pass
+def _scratch(P, dev):
+    """One sample's buffers, made once per call: the encoder's features (the decoder's noise), one blurred map sized for the largest level, every decoder
+    layer's [2C, h, w] output, the ToRGB chain, the style / demodulation tables and the two style vectors the linear layers alternate between."""
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)               # noqa: E731
+    size = P["size"]
+    C0 = P["stem"][0].shape[0]
+    feats = [new(1, C0, size, size)]
+    r = size
+    blur_floats = 1
+    for L in P["enc"]:
+        blur_floats = max(blur_floats, L["cin"] * (r + 1) * (r + 1))
+        r //= 2
+        feats.append(new(1, L["cout"], r, r))
+    outs = []
+    r = 4
+    for L in P["convs"]:
+        if L["up"]:
+            r *= 2
+        outs.append(new(1, 2 * L["cout"], r, r))
+    n_s = sum(L["cin"] for L in P["convs"]) + sum(L["cin"] for L in P["rgbs"])
+    n_d = sum(L["cout"] for L in P["convs"])
+    return dict(feats=feats, blur=new(blur_floats), outs=outs, rgb=[new(1, 3, 4 << j, 4 << j) for j in range(len(P["rgbs"]))], s=new(n_s), d=new(n_d),
+                z=[new(1, 1, P["sdim"]), new(1, 1, P["sdim"])])
+
+
+def _tables(P, S, latent):
+    """Every layer's (s, d) from ``latent [1, 1, sdim]`` in one batched call; returns [(s, d)] for the convolutions and [s] for the ToRGBs."""
+    layers = P["convs"] + P["rgbs"]
+    arr = (StyleJob * len(layers))()
+    so = do = 0
+    conv_t, rgb_t = [], []
+    for i, L in enumerate(layers):
+        s_t = S["s"][so:so + L["cin"]]
+        so += L["cin"]
+        d_t = None
+        if "wsq" in L:
+            d_t = S["d"][do:do + L["cout"]]
+            do += L["cout"]
+            conv_t.append((s_t, d_t))
+        else:
+            rgb_t.append(s_t)
+        arr[i] = StyleJob(s_t.data_ptr(), None if d_t is None else d_t.data_ptr(), latent.data_ptr(), latent.stride(0), latent.stride(1), L["mw"].data_ptr(),
+                          L["mb"].data_ptr(), None if d_t is None else L["wsq"].data_ptr(), 1, L["cin"], L.get("cout", 3), 0)
+    for i0 in range(0, len(layers), MAX_STYLE_JOBS):
+        lib().call("e4s_style_demod_batched", ctypes.byref(arr, i0 * ctypes.sizeof(StyleJob)), min(MAX_STYLE_JOBS, len(layers) - i0), 1, P["sdim"], _stream())
+    return conv_t, rgb_t
+
+
+def _modconv(P, L, x, out, s, d, h, w):
+    """The layer's modulated convolution on one sample into ``out`` (planes [0, C) of its buffer) with the first C activation-bias entries, leaky-relu * sqrt(2)."""
+    cin, cout = L["cin"], L["cout"]
+    st = _stream()
+    up = L["up"]
+    if up and not L["composed"]:
+        lib().call("e4s_modconv_up_fused_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), _p(L["blur"]), None, 0, None, _p(L["bias"]), 1,
+                   1, cin, cout, h, w, None, st)
+        return
+    ho, wo = (2 * h, 2 * w) if up else (h, w)
+    ws, wsn = None, 0
+    if cout * ho * wo <= SPLITK_MAX_OUT_FLOATS:
+        wsn = 16 * cout * ho * wo
+        ws = _workspace(x.device, wsn)
+    if P["sb"]:
+        lib().call("e4s_region_modconv3x3_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), None, 0, 0, None, 0, None, _p(L["bias"]), 1,
+                   1, cin, cout, h, w, 1, 1 if up else 0, _p(ws), wsn, None, None, None, None, None, None, None, None, None, st)
+    else:
+        lib().call("e4s_region_modconv3x3", _p(out), _p(x), _p(L["wt"]), _p(s), _p(d), None, 0, 0, None, 0, None, _p(L["bias"]), 1,
+                   1, cin, cout, h, w, 1, 1 if up else 0, _p(ws), wsn, st)
+
+
+def _noise_half(f, layers, outs):
+    """planes [C, 2C) of one or two layers' buffers from the encoder feature ``f [1, C, h, w]``."""
+    C, h, w = f.shape[1:]
+    hw = h * w
+    a, b = layers[0], (layers[1] if len(layers) > 1 else None)
+    lib().call("e4s_gpen_noise_half", _p(outs[0][:, C:]), _p(outs[1][:, C:]) if b else None, _p(f), _p(a["nw"]), _p(b["nw"]) if b else None, _p(a["bias"][C:]),
+               _p(b["bias"][C:]) if b else None, 1, C, hw, 2 * C * hw, _stream())
+
+
+def _gpen_sample(P, S, x, x_u8, out_f, latent_row):
+    """The network on one sample: ``x [1, 3, size, size]`` float32 or ``x_u8 [1, size, size, 3]``; the image goes to ``out_f [1, 3, size, size]``, the style
+    vector to ``latent_row [1, 1, sdim]``."""
+    st = _stream()
+    size, sdim = P["size"], P["sdim"]
+    feats = S["feats"]
+    lib().call("e4s_gpen_stem", _p(feats[0]), _p(x), _p(x_u8), _p(P["stem"][0]), _p(P["stem"][1]), 1, feats[0].shape[1], size, size, st)
+    r = size
+    for L, src, dst in zip(P["enc"], feats[:-1], feats[1:]):
+        lib().call("e4s_upfirdn2d", _p(S["blur"]), _p(src), _p(L["fir"]), L["cin"], r, r, 4, 4, 1, 1, 1, 1, 2, 2, 2, 2, st)
+        if P["sb"]:
+            lib().call("e4s_conv2d_sb", _p(dst), _p(S["blur"]), None, L["cin"], _p(L["wt"][0]), _p(L["wt"][1]), _p(L["bias"]), None, None, _p(L["slope"]), None, 2,
+                       1, L["cin"], L["cout"], r + 1, r + 1, 3, 2, 0, st)
+        else:
+            lib().call("e4s_conv2d", _p(dst), _p(S["blur"]), None, L["cin"], _p(L["wt"]), _p(L["bias"]), None, None, _p(L["slope"]), None, 2,
+                       1, L["cin"], L["cout"], r + 1, r + 1, 3, 2, 0, st)
+        r //= 2
+    f4 = feats[-1]
+    za, zb = S["z"]
+    W, b = P["final"]
+    grouped_linear(f4.view(1, 1, -1), [W], [b], scale=1 / math.sqrt(W.shape[1]), bias_mul=1.0, act=2, out=za)
+    torch.mul(za, torch.rsqrt(torch.mean(za * za, dim=2, keepdim=True) + 1e-8), out=zb)                 # PixelNorm
+    cur, nxt = zb, za
+    for i, (W, b) in enumerate(P["mlp"]):
+        dst = latent_row if i == len(P["mlp"]) - 1 else nxt
+        grouped_linear(cur, [W], [b], scale=(1 / math.sqrt(W.shape[1])) * LR_MLP, bias_mul=LR_MLP, act=2, out=dst)
+        cur, nxt = dst, cur
+    conv_t, rgb_t = _tables(P, S, latent_row)
+    convs, outs, rgbs = P["convs"], S["outs"], P["rgbs"]
+    noise = feats[::-1]                                                                                 # f4, f8, ..., f_size
+    _modconv(P, convs[0], P["const"], outs[0][:, :convs[0]["cout"]], *conv_t[0], 4, 4)
+    _noise_half(noise[0], convs[:1], outs[:1])
+    n_rgb = len(rgbs)
+
+    def torgb(j, x, skip, h):
+        dst = out_f if j == n_rgb - 1 else S["rgb"][j]
+        R = rgbs[j]
+        lib().call("e4s_region_torgb", _p(dst), _p(x), _p(R["wt"]), _p(rgb_t[j]), None, 0, 0, _p(R["bias"]), _p(skip), _p(R["upk"]) if skip is not None else None,
+                   1, R["cin"], h, h, 1, st)
+        return dst
+
+    skip = torgb(0, outs[0], None, 4)
+    h = 4
+    for j in range(1, n_rgb):
+        a, b = 2 * j - 1, 2 * j
+        _modconv(P, convs[a], outs[a - 1], outs[a][:, :convs[a]["cout"]], *conv_t[a], h, h)
+        h *= 2
+        _noise_half(noise[j], convs[a:b + 1], outs[a:b + 1])
+        _modconv(P, convs[b], outs[a], outs[b][:, :convs[b]["cout"]], *conv_t[b], h, h)
+        skip = torgb(j, outs[b], skip, h)
+
+
+def _gpen_run(P, x, x_u8, want_latent):
+    src = x if x is not None else x_u8
+    bs, dev = src.shape[0], src.device
+    size, sdim, n_latent = P["size"], P["sdim"], 2 * P["log_size"] - 2
+    out = torch.empty((bs, 3, size, size), dtype=torch.float32, device=dev)
+    lat = torch.empty((bs, 1, sdim), dtype=torch.float32, device=dev)
+    S = _scratch(P, dev)
+    for b in range(bs):
+        _gpen_sample(P, S, None if x is None else x[b:b + 1], None if x_u8 is None else x_u8[b:b + 1], out[b:b + 1], lat[b:b + 1])
+    return out, (lat.repeat(1, n_latent, 1) if want_latent else None)
+
+
+def _gpen_checked_all(name, weights, x=None, img_u8=None):
+    check_loaded(weights)
+    checked = _validated(name, weights, _net_of(weights))
+    size = checked[1][0]
+    if x is not None:
+        _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, size, size] image")
+        if tuple(x.shape[1:]) != (3, size, size):
+            raise ValueError(f"{name}: x is {tuple(x.shape)}: the network's size is {size}, expected [bs, 3, {size}, {size}]")
+        t, nm = x, "x"
+    else:
+        _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, "a uint8 [bs, size, size, 3] RGB image")
+        if tuple(img_u8.shape[1:]) != (size, size, 3):
+            raise ValueError(f"{name}: img_u8 is {tuple(img_u8.shape)}: the network's size is {size}, expected [bs, {size}, {size}, 3] "
+                             "(resizing to the network's size is the caller's)")
+        t, nm = img_u8, "img_u8"
+    _cuda_checked(name, **{nm: t})
+    _devices_checked(name, nm, t, checked[2])
+    if ARITH not in ("sb", "f32"):
+        raise ValueError(f"{name}: ops_gpen.ARITH is 'sb' or 'f32', got {ARITH!r}")
+    return checked
+
+
+def gpen_forward(x: torch.Tensor, weights, return_latents: bool = False):
+    """``FullGenerator.forward(x)`` (gpen_model.py:671-690) in eval mode on the device: ``(image, latent or None)`` with the float32 image
+    ``[bs, 3, size, size]`` and the latent ``[bs, n_latent, style_dim]``, from a float32 ``x [bs, 3, size, size]``.  ``weights``: a module with the network's
+    keys (``GPEN``, the drop-in ``FullGenerator``) or a mapping such as ``torch.load('GPEN-BFR-512.pth')``; the configuration is read off the keys and shapes.
+    A module's prepared weights are cached per parameter version; a mapping is prepared on every call.  Refused: a CPU tensor, another dtype, a module in
+    training mode, a module that never loaded weights, an image of another size.  Every argument is checked before any launch."""
+    name = "gpen_forward"
+    checked = _gpen_checked_all(name, weights, x=x)
+    if x.shape[0] == 0:
+        size, sdim = checked[1][0], checked[1][1]
+        n_latent = 2 * int(math.log2(size)) - 2
+        return x.new_empty((0, 3, size, size)), (x.new_empty((0, n_latent, sdim)) if return_latents else None)
+    with torch.no_grad():
+        return _gpen_run(lossnet.prepare(PreparedGPEN, weights, checked), x.detach().contiguous(), None, return_latents)
+
+
+def gpen_image(img_u8: torch.Tensor, weights) -> torch.Tensor:
+    """``FaceGAN.process`` behind its ``cv2.resize`` and without its BGR flips: uint8 ``[bs, size, size, 3]`` RGB to uint8 of the same shape, as three fused
+    steps: the stem kernel applies ``img2tensor`` (``/ 255``, ``(x - 0.5) / 0.5``), the network, and ``e4s_gpen_to_u8`` (``* 0.5 + 0.5``, the clip, ``* 255``,
+    the truncation).  An image of another size raises ``ValueError``: the resize is the caller's (the reference's is cv2's fixed-point bilinear)."""
+    name = "gpen_image"
+    checked = _gpen_checked_all(name, weights, img_u8=img_u8)
+    bs, size = img_u8.shape[0], checked[1][0]
+    out = torch.empty((bs, size, size, 3), dtype=torch.uint8, device=img_u8.device)
+    if bs == 0:
+        return out
+    with torch.no_grad():
+        r, _ = _gpen_run(lossnet.prepare(PreparedGPEN, weights, checked), None, img_u8.contiguous(), False)
+        lib().call("e4s_gpen_to_u8", _p(out), _p(r), bs, size, size, _stream())
+    return out
+
+
+def gpen_to_u8(x: torch.Tensor) -> torch.Tensor:
+    """``FaceGAN.tensor2img`` without its flip (``e4s_gpen_to_u8``): float32 ``[bs, 3, H, W]`` to uint8 ``[bs, H, W, 3]``."""
+    _tensor_checked("gpen_to_u8", "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image")
+    if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError(f"gpen_to_u8: expected a float32 [bs, 3, H, W] image, got {tuple(x.shape)}")
+    _cuda_checked("gpen_to_u8", x=x)
+    x = x.contiguous()
+    out = torch.empty((x.shape[0], x.shape[2], x.shape[3], 3), dtype=torch.uint8, device=x.device)
+    lib().call("e4s_gpen_to_u8", _p(out), _p(x), x.shape[0], x.shape[2], x.shape[3], _stream())
+    return out
+
+
+__all__ = ["GPEN", "PreparedGPEN", "gpen_channels", "gpen_state_dict_shapes", "gpen_weight_tensors", "gpen_forward", "gpen_image", "gpen_to_u8"]

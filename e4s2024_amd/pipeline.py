@@ -508,6 +508,13 @@ def realesr_infer_image(weights, img_u8: torch.Tensor, in_size: int = ESR_IN, ou
     return (r * 127.5 + 127.5).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
+def gpen_enhance(weights, img_u8: torch.Tensor) -> torch.Tensor:
+    """``FaceGAN.process`` (swap_face_fine/gpen/face_model/face_gan.py:36-47) behind its ``cv2.resize`` and without its BGR flips, on the device: uint8
+    ``[bs, size, size, 3]`` RGB faces, already at the network's size, to the enhanced uint8 faces of the same shape (``ops.gpen_image``).  ``weights`` as
+    ``ops.gpen_forward`` takes them.  The detector, the warps, the parsing mask and the paste of ``FaceEnhancement.process`` stay with the caller."""
+    return ops.gpen_image(img_u8, weights)
+
+
 @torch.no_grad()
 def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, parser, blender, esr, flip_target=None) -> torch.Tensor:
     """The ``'blender'`` branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:525-536), the reference's default mode, for a batch on

@@ -31,6 +31,7 @@ __all__ = [
     "seeded_fpn_state_dict",
     "seeded_small_fpn_state_dict",
     "seeded_rrdbnet_state_dict",
+    "seeded_gpen_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -284,9 +285,51 @@ def seeded_rrdbnet_state_dict(seed: int, num_block: int = 23) -> Dict[str, torch
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in rrdbnet_state_dict_shapes(num_block).items()}, seed, "rrdb")
 
 
+# GPEN's generator (swap_face_fine/gpen/face_model/gpen_model.py FullGenerator): the equalised-lr layers scale themselves, so weights are unit-variance (the
+# style MLP's are randn / lr_mul with lr_mul = 0.01).  noise.weight, every activation bias and every ToRGB bias are zero in the reference's initialisation; here
+# they are NOT: a zero noise weight hides the whole concatenated half of every StyledConv.  GPEN_RGB_GAIN scales the ToRGB weights so that the sum of the skip
+# chain stays in the image range (output standard deviation 0.3 - 0.5, at most 5 % of the values outside (-1, 1), on the tests' cases).
+GPEN_RGB_GAIN = 0.35
+
+
+def _fir_kernel(gain):
+    def rule(seed, key, shape):
+        assert tuple(shape) == (4, 4), shape
+        k = np.outer([1.0, 3.0, 3.0, 1.0], [1.0, 3.0, 3.0, 1.0])
+        return (k / k.sum() * gain).astype(np.float32)
+    return rule
+
+
+def _gpen_noise_weight(seed, key, shape):
+    a = seeded_array(seed, key, shape, 0.0, 0.3)
+    return np.where(a < 0, a - np.float32(0.3), a + np.float32(0.3))          # magnitude in [0.3, 0.82), either sign
+
+
+_RULES_GPEN = [
+    (r"^ecd\d+\.0\.0\.kernel$", _fir_kernel(1.0)),
+    (r"\.blur\.kernel$|\.upsample\.kernel$", _fir_kernel(4.0)),
+    (r"\.noise\.weight$", _gpen_noise_weight),
+    (r"\.activate\.bias$|^ecd\d+\.0\.\d\.bias$|^final_linear\.0\.bias$", (0.0, 0.1)),
+    (r"\.modulation\.bias$", (1.0, 0.1)),
+    (r"\.modulation\.weight$", (0.0, 1.0)),
+    (r"^generator\.style\.\d+\.weight$", (0.0, 100.0)),
+    (r"^generator\.style\.\d+\.bias$", (0.0, 10.0)),                          # times lr_mul: +-0.17
+    (r"^generator\.to_rgb.*\.conv\.weight$", (0.0, GPEN_RGB_GAIN)),
+    (r"^generator\.to_rgb.*\.bias$", (0.0, 0.05)),
+    (r"\.weight$|^generator\.input\.input$", (0.0, 1.0)),
+]
+
+
+def seeded_gpen_state_dict(seed: int, size: int = 512, style_dim: int = 512, n_mlp: int = 8, channel_multiplier: int = 2, narrow: float = 1) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.GPEN(size, style_dim, n_mlp, channel_multiplier, narrow)`` (the keys of ``GPEN-BFR-512.pth`` at the default)."""
+    from .ops_gpen import gpen_state_dict_shapes
+    shapes = gpen_state_dict_shapes(size, style_dim, n_mlp, channel_multiplier, narrow)
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "gpen")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
-             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB}.get(family, _RULES_BISENET)
+             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -829,6 +829,26 @@ E4S_API int e4s_esr_scale_add(float* y, const float* t, const float* x, int plan
 E4S_API int e4s_esr_up2(float* out, const float* in, int planes, int h, int w, void* stream);
 E4S_API int e4s_esr_tail(uint8_t* out_u8, float* out_f, const float* x, const float* weight, const float* bias, int bs, int H, int W, void* stream);
 
+/* f12: GPEN face enhancement, stage 1 — what the GAN-prior generator (swap_face_fine/gpen/face_model/gpen_model.py:628-690 FullGenerator, between the tensor ends of
+ * face_gan.py:49-62; csrc/gpen.hip) needs beside e4s_upfirdn2d, e4s_conv2d(_sb), e4s_grouped_linear, e4s_style_demod_batched, the single-region modulated
+ * convolutions and e4s_region_torgb.
+ *   e4s_gpen_stem       : ecd0 (gpen_model.py:658, ConvLayer(3, C0, 1)): out [bs][C0][H][W] = lrelu(bias[co] + sum_c weight[co][c] x[c]) * sqrt(2) in exact float32:
+ *                         bias, then one fused multiply-add per input channel in channel order, then v > 0 ? v : 0.2 v, then the scale.  weight [C0][3] carries the
+ *                         equalised-lr scale.  Exactly one input: x float [bs][3][H][W], or x_u8 uint8 [bs][H][W][3] (RGB) taken through FaceGAN.img2tensor first
+ *                         (v / 255 as a true division, - 0.5, / 0.5, each rounded on its own).
+ *   e4s_gpen_noise_half : the concatenated half of a StyledConv (gpen_model.py:294-302, 350-356): out_k[b * out_stride_b + c * hw + p] =
+ *                         lrelu(fl(w_k[0] * f[b][c][p]) + bias_k[c]) * sqrt(2) for k = 0 and, when out1 is not NULL, k = 1: f [bs][C][hw] is read once for both
+ *                         layers of a resolution.  out_k aims at plane C of a [bs][2C][hw] buffer (out_stride_b = 2 C hw), bias_k at entry C of the activation bias,
+ *                         w_k at the device scalar noise.weight.  The bits of scale * F.leaky_relu(cat(out, w * noise) + bias, 0.2).
+ *   e4s_gpen_to_u8      : FaceGAN.tensor2img without its channel flip: out uint8 [bs][H][W][3] = uint8(clip(x * 0.5 + 0.5, 0, 1) * 255) of x [bs][3][H][W], every
+ *                         operation rounded on its own, truncating.
+ * 16-byte accesses along a row (12 bytes of uint8 pixels) where the pointers and the row length allow, single elements otherwise: the same bits.  No atomics, no
+ * host synchronisation, grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_gpen_stem(float* out, const float* x, const uint8_t* x_u8, const float* weight, const float* bias, int bs, int C0, int H, int W, void* stream);
+E4S_API int e4s_gpen_noise_half(float* out0, float* out1, const float* f, const float* w0, const float* w1, const float* bias0, const float* bias1,
+                                int bs, int C, int hw, int64_t out_stride_b, void* stream);
+E4S_API int e4s_gpen_to_u8(uint8_t* out, const float* x, int bs, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
