@@ -14,6 +14,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_grad``    row f1: the native gradients of the synthesis path
 * ``ops_recolor`` rows f8 - f11: Blender recolouring — the semantic colour reference, the Res-U-Net, the SPADE feature network and the Real-ESRGAN step (resolved on first use, like any name a stage module defines late)
 * ``ops_gpen``    row f12: GPEN face enhancement, stage 1 — the GAN-prior generator (resolved on first use too)
+* ``ops_parsenet`` row f13: GPEN face enhancement, stage 2 — the ParseNet face mask (resolved on first use too)
 """
 from __future__ import annotations
 
@@ -1401,7 +1402,7 @@ def __getattr__(name):        # PEP 562
     import importlib
     import sys
     if not name.startswith("__"):
-        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen"):
+        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

@@ -515,6 +515,14 @@ def gpen_enhance(weights, img_u8: torch.Tensor) -> torch.Tensor:
     return ops.gpen_image(img_u8, weights)
 
 
+def gpen_face_mask(parsenet, faces_u8: torch.Tensor) -> torch.Tensor:
+    """``FaceParse.process`` (swap_face_fine/gpen/face_parse/face_parsing.py:39-45) behind its ``cv2.resize``, on the device: uint8 ``[bs, S, S, 3]`` RGB faces
+    at the network's ``in_size`` — what ``gpen_enhance`` returns — to the uint8 paste masks ``[bs, S', S']`` of 0 / 255 (``ops.parsenet_mask`` with
+    ``bgr=False``: the reference's BGR flip and this caller's RGB cancel).  ``parsenet`` as ``ops.parsenet_forward`` takes weights.  The Gaussian blurs of
+    ``mask_postprocess`` and the paste stay with the caller."""
+    return ops.parsenet_mask(faces_u8, parsenet, bgr=False)
+
+
 @torch.no_grad()
 def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, parser, blender, esr, flip_target=None) -> torch.Tensor:
     """The ``'blender'`` branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:525-536), the reference's default mode, for a batch on

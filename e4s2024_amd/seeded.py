@@ -32,6 +32,7 @@ __all__ = [
     "seeded_small_fpn_state_dict",
     "seeded_rrdbnet_state_dict",
     "seeded_gpen_state_dict",
+    "seeded_parsenet_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -327,9 +328,43 @@ def seeded_gpen_state_dict(seed: int, size: int = 512, style_dim: int = 512, n_m
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "gpen")
 
 
+# GPEN's ParseNet (swap_face_fine/gpen/face_parse/parse_model.py): fan-in-scaled convolutions; BatchNorm scales over +-1.5, about half of them negative
+# and one per layer exactly zero (a fold that took |gamma|, or divided by it, shows), running statistics and biases away from the identity.  A residual
+# block's second convolution has the smaller gain PARSENET_RES_GAIN, so that the sum over the blocks keeps the activations O(1) through the depth, and
+# PARSENET_MASK_GAIN puts the standard deviation of the 19 logits between 1 and 10 on the tests' cases (tests/parsenet_model.py checks both): logits in the
+# hundreds would widen every bar.
+PARSENET_RES_GAIN = 0.7
+PARSENET_MASK_GAIN = 2.0
+
+
+def _parsenet_bn_scale(seed, key, shape):
+    a = seeded_array(seed, key, shape, 0.0, 1.5 / _SQRT3)                       # U(-1.5, 1.5)
+    a[zlib.crc32(key.encode("utf-8")) % a.size] = 0.0
+    return a
+
+
+_RULES_PARSENET = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"running_var$", (1.0, 0.5 / _SQRT3)),                                     # U(0.5, 1.5)
+    (r"running_mean$", (0.0, 0.2)),
+    (r"\.norm\.norm\.weight$", _parsenet_bn_scale),
+    (r"\.norm\.norm\.bias$", (0.0, 0.2)),
+    (r"\.conv2d\.bias$", (0.0, 0.1)),
+    (r"\.conv2\.conv2d\.weight$", _fan_in_std(PARSENET_RES_GAIN)),
+    (r"^out_mask_conv\.conv2d\.weight$", _fan_in_std(PARSENET_MASK_GAIN)),
+    (r"\.conv2d\.weight$", _fan_in_std(1.0)),
+]
+
+
+def seeded_parsenet_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for a network with the keys of GPEN's ``ParseNet``: ``template`` is its ``state_dict()`` (meta tensors will do; ``ops.ParseNet(...)``
+    or the reference's class give the same keys), ``num_batches_tracked`` included."""
+    return seeded_state_dict(template, seed, "parsenet")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
-             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN}.get(family, _RULES_BISENET)
+             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

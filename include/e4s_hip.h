@@ -849,6 +849,30 @@ E4S_API int e4s_gpen_noise_half(float* out0, float* out1, const float* f, const 
                                 int bs, int C, int hw, int64_t out_stride_b, void* stream);
 E4S_API int e4s_gpen_to_u8(uint8_t* out, const float* x, int bs, int H, int W, void* stream);
 
+/* f13: GPEN face enhancement, stage 2 — what the face mask's network (swap_face_fine/gpen/face_parse/parse_model.py:21-75 ParseNet, blocks.py:72-125 ConvLayer and
+ * ResidualBlock, between the tensor ends of face_parsing.py:39-79; csrc/parsenet.hip) needs around its 3 x 3 convolutions, which run on e4s_conv2d_sb3 with
+ * pad = 0 on planes that e4s_parsenet_pad wrote: that kernel pads with zeros only, every ConvLayer pads by reflection (index -1 is 1, index n is n - 2) and the
+ * decoder's put a nearest x 2 in front.
+ *   e4s_parsenet_stem : encoder.0 = ConvLayer(3, C0, 3) (parse_model.py:46; reflection pad 1, bias, no norm, no activation): out [bs][C0][H][W] in exact float32,
+ *                       each output bias[co], then 27 fused multiply-adds in (input channel, row, column) order over weight [C0][3][3][3]; the reflection is index
+ *                       arithmetic.  Exactly one input: x float [bs][3][H][W], or x_u8 uint8 [bs][H][W][3] taken through FaceParse.img2tensor first
+ *                       (face_parsing.py:59-63): with bgr = 1 colour c is byte 2 - c (the [..., ::-1] flip), with bgr = 0 byte c, and the value is lut[byte] with
+ *                       lut [256] the float32 of numpy's float64 v / 255. * 2 - 1, made on the host with that expression.  H, W >= 2.
+ *   e4s_parsenet_pad  : the input of a reflection-padded convolution in one pass: out [planes][u h + 2][u w + 2] = reflection pad 1 of the nearest x u of
+ *                       v = x + add, x and add [planes][h][w], the sum rounded once (add may be NULL: v = x); u = 1, or 2 with the source at (y >> 1, x >> 1)
+ *                       (F.interpolate(scale_factor=2, mode='nearest'), blocks.py:84).  add carries feat + body(feat) (parse_model.py:71), which is never a pass
+ *                       of its own.  Every output cell is computed from the one source element its index names, so a border cell holds the bits of the
+ *                       interior cell it mirrors.  h, w >= 2 when u = 1, h, w >= 1 when u = 2.
+ * The mask (face_parsing.py:65-79: argmax over the 19 classes, then MASK_COLORMAP) is e4s_bilinear_argmax at equal size with the colour map as its table: at
+ * ih == oh, iw == ow the scale (ih - 1) / (oh - 1) is exactly 1, the coordinates are integers and the blend is 1 * q + 0 * q', which is q for finite logits, so the
+ * call is argmax + table (first maximum wins, as torch.argmax).
+ * 16-byte accesses where the pointers and the row length allow (the stem along a row when W % 4 == 0, 12 bytes of uint8 pixels; the pad kernel over the flat
+ * output, whose rows are not 16-byte aligned one by one), single elements otherwise: the same bits.  No atomics, no host synchronisation, grids depend on the
+ * shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.  bs == 0 (planes == 0) returns at once. */
+E4S_API int e4s_parsenet_stem(float* out, const float* x, const uint8_t* x_u8, const float* lut, int bgr, const float* weight, const float* bias, int bs, int C0,
+                              int H, int W, void* stream);
+E4S_API int e4s_parsenet_pad(float* out, const float* x, const float* add, int planes, int h, int w, int u, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
