@@ -9,7 +9,8 @@ Layout
                  ``criteria/id_loss.py``, ``criteria/face_parsing/face_parsing_loss.py``,
                  ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``,
                  ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``,
-                 ``swap_face_fine/gpen/face_model/gpen_model.py``, ``swap_face_fine/gpen/face_parse/parse_model.py``)
+                 ``swap_face_fine/gpen/face_model/gpen_model.py``, ``swap_face_fine/gpen/face_parse/parse_model.py``,
+                 ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -89,9 +90,17 @@ GPEN_PARSE_OVERRIDES = {
 }
 
 
+# row f14: GPEN face enhancement, stage 3: the detector behind FaceEnhancement (face_enhancement.py imports RetinaFaceDetection, which imports RetinaFace).  The
+# siblings (``facemodels.net``, ``data``, ``layers``, ``utils``) are not redirected: the drop-ins do not import them
+GPEN_DETECT_OVERRIDES = {
+    "swap_face_fine.gpen.face_detect.facemodels.retinaface": "swap_face_fine/gpen/face_detect/facemodels/retinaface.py",
+    "swap_face_fine.gpen.face_detect.retinaface_detection": "swap_face_fine/gpen/face_detect/retinaface_detection.py",
+}
+
+
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
-            **GPEN_PARSE_OVERRIDES}
+            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -109,8 +118,8 @@ _finder = None
 
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
-    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``) and GPEN's
-    face-mask network (``GPEN_PARSE_OVERRIDES``) to the drop-in files.
+    ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
+    face-mask network (``GPEN_PARSE_OVERRIDES``) and GPEN's face detector (``GPEN_DETECT_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

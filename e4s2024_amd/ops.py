@@ -15,6 +15,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_recolor`` rows f8 - f11: Blender recolouring — the semantic colour reference, the Res-U-Net, the SPADE feature network and the Real-ESRGAN step (resolved on first use, like any name a stage module defines late)
 * ``ops_gpen``    row f12: GPEN face enhancement, stage 1 — the GAN-prior generator (resolved on first use too)
 * ``ops_parsenet`` row f13: GPEN face enhancement, stage 2 — the ParseNet face mask (resolved on first use too)
+* ``ops_retinaface`` row f14: GPEN face enhancement, stage 3 — the RetinaFace detector (resolved on first use too)
 """
 from __future__ import annotations
 
@@ -1402,7 +1403,7 @@ def __getattr__(name):        # PEP 562
     import importlib
     import sys
     if not name.startswith("__"):
-        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet"):
+        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

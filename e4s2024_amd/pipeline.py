@@ -523,6 +523,14 @@ def gpen_face_mask(parsenet, faces_u8: torch.Tensor) -> torch.Tensor:
     return ops.parsenet_mask(faces_u8, parsenet, bgr=False)
 
 
+def gpen_detect_faces(net, frames_u8: torch.Tensor, bgr: bool = True):
+    """``RetinaFaceDetection.detect`` (swap_face_fine/gpen/face_detect/retinaface_detection.py:61-131) as ``FaceEnhancement.process`` calls it, for a batch of
+    frames on the device: uint8 ``[bs, H, W, 3]`` (BGR as the reference takes them, RGB with ``bgr=False``) to a list of ``(dets [n, 5], landms [n, 10])`` per
+    frame (``ops.retinaface_detect`` at the reference's thresholds).  ``net`` as ``ops.retinaface_forward`` takes weights.  The 5-point ``warpAffine`` pair
+    around the enhancement stays with the caller."""
+    return ops.retinaface_detect(frames_u8, net, bgr=bgr)
+
+
 @torch.no_grad()
 def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, parser, blender, esr, flip_target=None) -> torch.Tensor:
     """The ``'blender'`` branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:525-536), the reference's default mode, for a batch on

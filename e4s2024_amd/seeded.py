@@ -33,6 +33,7 @@ __all__ = [
     "seeded_rrdbnet_state_dict",
     "seeded_gpen_state_dict",
     "seeded_parsenet_state_dict",
+    "seeded_retinaface_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -362,9 +363,52 @@ def seeded_parsenet_state_dict(template: Mapping[str, torch.Tensor], seed: int) 
     return seeded_state_dict(template, seed, "parsenet")
 
 
+# GPEN's RetinaFace detector (swap_face_fine/gpen/face_detect/facemodels/retinaface.py, cfg_re50): He-scaled convolutions (gain sqrt 2 in front of the ReLUs;
+# body.conv1 a hundred times smaller, its input being pixels minus a mean); BatchNorm scales of magnitude 0.5 .. 1.5 and either sign — none near zero, so every
+# channel and every Bottleneck's residual branch stays alive — running variances over 0.5 .. 1.5 and running means and biases away from zero, so that a fold that
+# drops the mean, the bias or the square root shows.  A Bottleneck's last BatchNorm has half that magnitude, which keeps the sum over a stage's blocks O(1).
+# The head gains put 5 % .. 40 % of the anchors above the 0.9 score, spread the candidates' scores, and make neighbouring boxes overlap enough for NMS to
+# remove at least a fifth of them (tests/golden/make_golden_retinaface.py asserts the conditions on the tests' cases).
+RETINA_CONV1_GAIN = 0.014
+RETINA_CLASS_GAIN = 0.07
+RETINA_BBOX_GAIN = 0.03
+RETINA_LANDMARK_GAIN = 0.05
+
+
+def _retina_bn_scale(mag):
+    def rule(seed, key, shape):
+        a = seeded_array(seed, key, shape, 0.0, 1.0 / _SQRT3)                   # U(-1, 1)
+        return (np.sign(a) + (a == 0)) * (np.float32(0.5) + np.abs(a)) * np.float32(mag)
+    return rule
+
+
+_RULES_RETINAFACE = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"running_var$", (1.0, 0.5 / _SQRT3)),                                     # U(0.5, 1.5)
+    (r"running_mean$", (0.0, 0.2)),
+    (r"\.bn3\.weight$", _retina_bn_scale(0.5)),
+    (r"\.bn\d\.weight$|\.downsample\.1\.weight$|^(fpn|ssh\d)\.\w+\.1\.weight$", _retina_bn_scale(1.0)),
+    (r"\.bn\d\.bias$|\.downsample\.1\.bias$|^(fpn|ssh\d)\.\w+\.1\.bias$", (0.0, 0.2)),
+    (r"conv1x1\.bias$", (0.0, 0.1)),
+    (r"^body\.conv1\.weight$", _fan_in_std(RETINA_CONV1_GAIN)),
+    (r"^ClassHead\.\d\.conv1x1\.weight$", _fan_in_std(RETINA_CLASS_GAIN)),
+    (r"^BboxHead\.\d\.conv1x1\.weight$", _fan_in_std(RETINA_BBOX_GAIN)),
+    (r"^LandmarkHead\.\d\.conv1x1\.weight$", _fan_in_std(RETINA_LANDMARK_GAIN)),
+    (r"\.weight$", _fan_in_std(1.4)),
+]
+
+
+def seeded_retinaface_state_dict(seed: int, out_channel: int = 256) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.RetinaFace`` at ``cfg_re50`` with that ``out_channel`` (the keys of ``RetinaFace-R50.pth`` at the default)."""
+    from .ops_retinaface import retinaface_state_dict_shapes
+    shapes = retinaface_state_dict_shapes(out_channel)
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "retinaface")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
-             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET}.get(family, _RULES_BISENET)
+             "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
+             "retinaface": _RULES_RETINAFACE}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

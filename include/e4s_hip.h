@@ -873,6 +873,38 @@ E4S_API int e4s_parsenet_stem(float* out, const float* x, const uint8_t* x_u8, c
                               int H, int W, void* stream);
 E4S_API int e4s_parsenet_pad(float* out, const float* x, const float* add, int planes, int h, int w, int u, void* stream);
 
+/* f14: GPEN face enhancement, stage 3 — the RetinaFace detector (swap_face_fine/gpen/face_detect/retinaface_detection.py:61-131 detect, facemodels/retinaface.py,
+ * facemodels/net.py, layers/functions/prior_box.py, utils/box_utils.py decode and decode_landm, utils/nms/py_cpu_nms.py; csrc/retinaface.hip): the glue between the
+ * network's convolutions (conv.hip, stem and pooling as the face parser's ResNet) and the detection tail on the device.
+ *   e4s_retina_input   : out [bs][3][H][W] = pixel - (104, 117, 123) in BGR plane order from img_u8 [bs][H][W][3] (bgr = 1: byte c is plane c; bgr = 0: byte 2 - c).
+ *                        Exact; the mean cannot go into the stem's bias, because the zero padding comes behind the subtraction.
+ *   e4s_retina_up_add  : out [planes][h][w] = a + b[min(floor(y * (float)hb / h), hb - 1)][min(floor(x * (float)wb / w), wb - 1)], b [planes][hb][wb]:
+ *                        F.interpolate(size=..., mode="nearest") + add of FPN.forward (net.py:89-94) in one pass, ATen's legacy index rule, any size pair.
+ *   e4s_retina_cat_relu: out [bs][ca + cb + cc][hw] = relu(cat(a, b, c)) of SSH.forward (net.py:64-65) for any batch.
+ *   e4s_retina_decode  : head_l [bs][32][ceil(H / s)][ceil(W / s)], s = 8, 16, 32: channels 0-7 BboxHead (anchor, coordinate), 8-11 ClassHead (anchor, class), 12-31
+ *                        LandmarkHead (anchor, value) of level l.  Anchor (y w + x) 2 + a, levels concatenated, N in all.  Writes, each group optional as a whole,
+ *                        the dense loc [bs][N][4], conf [bs][N][2] (softmax) and landms [bs][N][10] of RetinaFace.forward, and score [bs][N] (class 1),
+ *                        boxes [bs][N][4] and lmk [bs][N][10]: decode / decode_landm with variances (0.1, 0.2) on priors from index arithmetic (a correctly rounded
+ *                        float32 division of the exact numerator: PriorBox.forward's values), times (W, H, ...), every operation rounded on its own.
+ *   e4s_retina_priors  : out [N][4] = those priors (cx, cy, s_kx, s_ky).
+ *   e4s_retina_compact : keys [bs][cap] (int64) = (score bits << 32) | (0xFFFFFFFF - anchor) of every anchor with score > threshold in anchor order, -1 behind them;
+ *                        counts [bs][2] = (anchors above the threshold, candidates kept).  With more than cap the cap highest scores are kept (ties at the cut: the
+ *                        lower anchors).  Sorting the keys descending orders the candidates by score, equal scores by anchor.  cap <= 16384.
+ *   e4s_retina_nms     : py_cpu_nms on keys sorted descending: (x2 - x1 + 1)(y2 - y1 + 1) areas, ovr = inter / (a_i + a_j - inter) in float32, greedy, ovr <= thresh
+ *                        stays; dets [bs][keep_top_k][5] (box, score), landms_out [bs][keep_top_k][10] as (x0..x4, y0..y4), keep [bs][keep_top_k] (positions in the
+ *                        sorted list), nkeep [bs], all cut to keep_top_k; rows behind nkeep are not written.  cbox [bs][cap][4] is workspace.
+ * 16-byte accesses where pointers and lengths allow, single elements otherwise: the same bits.  No float atomics, no host synchronisation, grids from shapes and
+ * capacities alone: the same inputs give the same bits, and the calls can be captured in a graph.  bs == 0 (planes == 0) returns at once. */
+E4S_API int e4s_retina_input(float* out, const uint8_t* img_u8, int bgr, int bs, int H, int W, void* stream);
+E4S_API int e4s_retina_up_add(float* out, const float* a, const float* b, int planes, int h, int w, int hb, int wb, void* stream);
+E4S_API int e4s_retina_cat_relu(float* out, const float* a, const float* b, const float* c, int bs, int ca, int cb, int cc, int hw, void* stream);
+E4S_API int e4s_retina_priors(float* out, int H, int W, void* stream);
+E4S_API int e4s_retina_decode(float* loc, float* conf, float* landms, float* score, float* boxes, float* lmk, const float* head0, const float* head1,
+                              const float* head2, int bs, int H, int W, void* stream);
+E4S_API int e4s_retina_compact(int64_t* keys, int* counts, const float* score, int bs, int N, int cap, float threshold, void* stream);
+E4S_API int e4s_retina_nms(float* dets, float* landms_out, int* keep, int* nkeep, float* cbox, int64_t* sorted_keys, const int* counts, const float* boxes,
+                           const float* lmk, int bs, int N, int cap, int keep_top_k, float nms_threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
