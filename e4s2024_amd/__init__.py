@@ -10,7 +10,8 @@ Layout
                  ``swap_face_fine/Blender/model_center/semantic_tools.py``, ``swap_face_fine/Blender/model_center/res_u_net.py``,
                  ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``,
                  ``swap_face_fine/gpen/face_model/gpen_model.py``, ``swap_face_fine/gpen/face_parse/parse_model.py``,
-                 ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``)
+                 ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``,
+                 ``swap_face_fine/gpen/align_faces.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -97,10 +98,16 @@ GPEN_DETECT_OVERRIDES = {
     "swap_face_fine.gpen.face_detect.retinaface_detection": "swap_face_fine/gpen/face_detect/retinaface_detection.py",
 }
 
+# row f15: GPEN face enhancement, stage 4: the 5-point alignment (face_enhancement.py imports warp_and_crop_face and get_reference_facial_points from it),
+# without cv2 and skimage
+GPEN_ALIGN_OVERRIDES = {
+    "swap_face_fine.gpen.align_faces": "swap_face_fine/gpen/align_faces.py",
+}
+
 
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
-            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES}
+            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -119,7 +126,8 @@ _finder = None
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
     ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
-    face-mask network (``GPEN_PARSE_OVERRIDES``) and GPEN's face detector (``GPEN_DETECT_OVERRIDES``) to the drop-in files.
+    face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``) and GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) to the
+    drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

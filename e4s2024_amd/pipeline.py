@@ -532,6 +532,64 @@ def gpen_detect_faces(net, frames_u8: torch.Tensor, bgr: bool = True):
 
 
 @torch.no_grad()
+def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_u8: Optional[torch.Tensor] = None, return_faces: bool = False):
+    """``FaceEnhancement.process(img, aligned=False)`` (swap_face_fine/gpen/face_enhancement.py:68-110) behind its ``use_sr`` branch, for a batch of frames on
+    the device: RGB uint8 ``[bs, H, W, 3]`` to the enhanced uint8 frames of the same shape,
+
+        dets, landms   = gpen_detect_faces(detector, frames, bgr=False)          (:68; every frame's faces concatenated in detector order)
+        T, flags       = ops.gpen_face_transforms(...)                           (:75-80, :93; warp_and_crop_face's similarity pair, score and size flags)
+        of             = ops.gpen_warp_crop(frames, frame_of_face, T, S)         (:80; cv2.warpAffine to the S x S crop, S the generator's size)
+        ef             = gpen_enhance(gpen, of)                                  (:83)
+        mask           = ops.gpen_mask_feather(gpen_face_mask(parsenet, ef))     (:89; mask_postprocess)
+        out            = ops.gpen_paste(base, ops.gpen_smooth_small(ef, flags), mask, T, flags, face_begin)     (:91-108)
+
+    at the reference's constants (``ops.GPEN_PASTE_DEFAULTS``).  ``base_u8`` is what the faces are pasted over: the frames themselves, or — the reference's
+    ``use_sr`` — a super-resolved frame of the same shape (its RealESRNet pass and the resize of the frame to its size are not done here).  With
+    ``return_faces`` the result is ``(out, orig_faces, enhanced_faces)``: per frame the uint8 ``[n_b, S, S, 3]`` crops and enhanced faces of the faces above the
+    score threshold, the reference's second and third results.  A frame without a face comes back as ``base``.  The one device-to-host read is the detector's, of
+    its kept counts (with ``return_faces`` the flags are read too, to drop the skipped faces).  Refused: a ParseNet whose mask is not S x S (the reference
+    resizes it with cv2), frames that are not uint8 ``[bs, H, W, 3]`` on the device, a ``base_u8`` of another shape.  A non-contiguous view is accepted and
+    copied."""
+    name = "gpen_enhance_frames"
+    from . import ops_gpen, ops_parsenet
+    ops_recolor._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
+    if frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError(f"{name}: frames_u8: expected uint8 [bs, H, W, 3] RGB frames with bs >= 1, got {tuple(frames_u8.shape)}")
+    ops_recolor._cuda_checked(name, frames_u8=frames_u8)
+    if base_u8 is not None:
+        ops_recolor._tensor_checked(name, "base_u8", base_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] frames")
+        if base_u8.shape != frames_u8.shape or base_u8.device != frames_u8.device:
+            raise ValueError(f"{name}: base_u8 is {tuple(base_u8.shape)} on {base_u8.device}: expected the frames' {tuple(frames_u8.shape)} on {frames_u8.device} "
+                             "(resizing the frame to a super-resolved size is the caller's)")
+    ops_gpen.check_loaded(gpen)
+    S = int(ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+    structure = ops_recolor._validated(name, parsenet, ops_parsenet._net_of(parsenet))[1]
+    if ops_parsenet.parsenet_output_size(structure, S, S) != (S, S):
+        raise ValueError(f"{name}: the ParseNet turns a {S} x {S} face into a {ops_parsenet.parsenet_output_size(structure, S, S)} mask: expected {S} x {S} "
+                         "(the reference resizes the mask with cv2, which is not done here)")
+    D = ops.GPEN_PASTE_DEFAULTS
+    frames = frames_u8.contiguous()
+    bs, dev = frames.shape[0], frames.device
+    per_frame = gpen_detect_faces(detector, frames, bgr=False)
+    counts = [int(d.shape[0]) for d, _ in per_frame]
+    dets, landms = torch.cat([d for d, _ in per_frame]), torch.cat([l for _, l in per_frame])
+    begin = [0]
+    for c in counts:
+        begin.append(begin[-1] + c)
+    face_begin = torch.tensor(begin, dtype=torch.int32, device=dev)
+    frame_of_face = torch.tensor([b for b, c in enumerate(counts) for _ in range(c)], dtype=torch.int32, device=dev)
+    T, flags = ops.gpen_face_transforms(dets, landms, ops.gpen_reference_points(S), D["threshold"], D["small_face"])
+    of = ops.gpen_warp_crop(frames, frame_of_face, T, S)
+    ef = gpen_enhance(gpen, of)
+    masks = ops.gpen_mask_feather(gpen_face_mask(parsenet, ef), D["ksize"], D["sigma"], D["thres"])
+    out = ops.gpen_paste(frames if base_u8 is None else base_u8, ops.gpen_smooth_small(ef, flags), masks, T, flags, face_begin)
+    if not return_faces:
+        return out
+    kept = ((flags & ops.GPEN_FACE_SKIP) == 0).cpu()
+    return out, [of[a:b][kept[a:b]] for a, b in zip(begin, begin[1:])], [ef[a:b][kept[a:b]] for a, b in zip(begin, begin[1:])]
+
+
+@torch.no_grad()
 def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, parser, blender, esr, flip_target=None) -> torch.Tensor:
     """The ``'blender'`` branch of the image caller's ``_color_transfer`` (Face_swap_with_two_imgs.py:525-536), the reference's default mode, for a batch on
     the device:

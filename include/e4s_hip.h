@@ -905,6 +905,39 @@ E4S_API int e4s_retina_compact(int64_t* keys, int* counts, const float* score, i
 E4S_API int e4s_retina_nms(float* dets, float* landms_out, int* keep, int* nkeep, float* cbox, int64_t* sorted_keys, const int* counts, const float* boxes,
                            const float* lmk, int bs, int N, int cap, int keep_top_k, float nms_threshold, void* stream);
 
+/* f15: GPEN face enhancement, stage 4 — what FaceEnhancement.process(aligned=False) (swap_face_fine/gpen/face_enhancement.py:68-108, align_faces.py:25-93, 210-266;
+ * csrc/gpen_paste.hip) does between its three networks, in OpenCV's arithmetic as tests/gpen_paste_model.py restates it.  Float64 arrays travel as void pointers.
+ *   transforms [n][2][2][3] (float64): per face the 2 x 3 forward matrix (frame -> crop) and the 2 x 3 inverse (crop -> frame).  flags [n]: bit 0 = skip the face,
+ *   bit 1 = a small face.  "warpAffine(src, M, (w, h))" below is cv2's with flags=3: M inverted in float64, the map in fixed point (10 fractional bits, sampled on
+ *   its 1/32 grid after + 16), bilinear, constant-0 border; uint8 with the integer weights (32 - ax)(32 - ay) ... and (sum + 512) >> 10.
+ *   e4s_gpen_face_transforms : dets [n][5] (x1, y1, x2, y2, score), landms [n][10] (x0..x4, y0..y4), ref_points [5][2] (float64, cast to float32 first as the
+ *                              reference does): the least-squares similarity pair of warp_and_crop_face in float64 closed form (no SVD), and the flags: skip if
+ *                              score < threshold, if a landmark is not finite or if the landmarks coincide (the matrices are then zero); small if
+ *                              min(y2 - y1, x2 - x1) < small_face, in float32.  One lane per face.
+ *   e4s_gpen_warp_crop_u8    : out [n][S][S][3] = warpAffine(frames[frame_of_face[i]] [H][W][3], forward_i, (S, S)); a frame index outside 0 .. bs - 1 gives zeros.
+ *   e4s_gpen_smooth3_u8      : out [n][S][S][3] = cv2.filter2D(face, -1, [[1,2,1],[2,4,2],[1,2,1]] / 16) (BORDER_REFLECT_101, the sum / 16 rounded half to even) of
+ *                              the faces whose small flag is set, a copy of the others.  out must not be faces.
+ *   e4s_gpen_mask_feather    : out [n][S][S] (float32) = mask_postprocess(masks / 255): `thres` rows and columns at each edge zeroed, then twice the separable
+ *                              k-tap blur (rows, then columns, BORDER_REFLECT_101) with the float64 taps [k], float64 sums and intermediates in scratch
+ *                              (e4s_gpen_mask_feather_scratch_bytes).  k odd, k / 2 < S, k <= 129, thres >= 1.
+ *   e4s_gpen_paste_u8        : per frame b and its faces face_begin[b] .. face_begin[b + 1] - 1 in order, skipped ones left out: m_i = warpAffine(masks_i,
+ *                              inverse_i, (W, H)) in float32 (weights (1 - fx)(1 - fy) ..., ((v00 w0 + v01 w1) + v10 w2) + v11 w3), p_i the uint8 warpAffine of
+ *                              faces_i; where m_i - full_mask > 0: full_mask = m_i, full_img = p_i; out [bs][H][W][3] = convertScaleAbs(base (1 - full_mask) +
+ *                              full_img full_mask) in float32, every operation rounded on its own.  One pass, no full-frame intermediate; full_mask [bs][H][W]
+ *                              is optional output.  out may be base itself (each lane reads its own pixels before it writes them), no other overlap.  n == 0
+ *                              copies base to out.
+ * No host synchronisation, no atomics, grids from shapes and counts alone: the same inputs give the same bits, and the calls can be captured in a graph.  n == 0
+ * returns without a launch. */
+E4S_API int e4s_gpen_face_transforms(void* transforms, int* flags, const float* dets, const float* landms, const void* ref_points, float threshold,
+                                     float small_face, int n, void* stream);
+E4S_API int e4s_gpen_warp_crop_u8(uint8_t* out, const uint8_t* frames, const int* frame_of_face, const void* transforms, int n, int bs, int H, int W, int S,
+                                  void* stream);
+E4S_API int e4s_gpen_smooth3_u8(uint8_t* out, const uint8_t* faces, const int* flags, int n, int S, void* stream);
+E4S_API int e4s_gpen_mask_feather_scratch_bytes(int n, int S, int64_t* bytes);
+E4S_API int e4s_gpen_mask_feather(float* out, const uint8_t* masks, const void* taps, void* scratch, int n, int S, int k, int thres, void* stream);
+E4S_API int e4s_gpen_paste_u8(uint8_t* out, float* full_mask, const uint8_t* base, const uint8_t* faces, const float* masks, const void* transforms,
+                              const int* flags, const int* face_begin, int n, int bs, int H, int W, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
