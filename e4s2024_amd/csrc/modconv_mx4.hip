@@ -179,9 +179,8 @@ __device__ __forceinline__ void q_tile_body(const SbParams& p, unsigned char* ld
         if (more) load_x(chunk + 1, 0);
         const float4* xf4 = reinterpret_cast<const float4*>(lds_raw + Q_PATCH0 + cur * Q_PATCHB);
         const float* ss = reinterpret_cast<const float*>(lds_raw + Q_SS0 + cur * Q_SSB);
-        float sv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sv[e] = cls >= 0 ? ss[cls * CKS + khalf * 8 + e] : 0.f;
+        f32x2 sv[4];
+        mx_load_sv(ss, cls, khalf, sv);
 
 #pragma unroll
         for (int row = 0; row < 3; ++row) {
@@ -198,16 +197,12 @@ __device__ __forceinline__ void q_tile_body(const SbParams& p, unsigned char* ld
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 const int e = xoff + row * CQ::PW + t;
-                const float4 xa = xf4[(2 * khalf) * Q_PSTRIDE + e], xq = xf4[(2 * khalf + 1) * Q_PSTRIDE + e];
-                const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xq.x, xq.y, xq.z, xq.w};
+                const f32x4* xv4 = reinterpret_cast<const f32x4*>(xf4);
+                const f32x4 xa = xv4[(2 * khalf) * Q_PSTRIDE + e], xq = xv4[(2 * khalf + 1) * Q_PSTRIDE + e];
+                const f32x2 xp[4] = {__builtin_shufflevector(xa, xa, 0, 1), __builtin_shufflevector(xa, xa, 2, 3),
+                                     __builtin_shufflevector(xq, xq, 0, 1), __builtin_shufflevector(xq, xq, 2, 3)};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float a = xv[2 * j] * sv[2 * j], bq = xv[2 * j + 1] * sv[2 * j + 1];
-                    const f16x2 a1 = __builtin_convertvector((f32x2){a, bq}, f16x2);
-                    v1[t * 4 + j] = __builtin_bit_cast(unsigned, a1);
-                    v2[t * 4 + j] = resid_pair_f16(xv[2 * j], sv[2 * j], xv[2 * j + 1], sv[2 * j + 1], v1[t * 4 + j]);
-                    amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(bq)));
-                }
+                for (int j = 0; j < 4; ++j) { unsigned q1, q2; mx_prep_pair(xp[j], sv[j], q1, q2, amax); v1[t * 4 + j] = q1; v2[t * 4 + j] = q2; }    // (five instructions per pair: modconv_mx_tile.h)
             }
             Q_FENCE();
 #pragma unroll
@@ -248,15 +243,11 @@ __device__ __forceinline__ void q_tile_body(const SbParams& p, unsigned char* ld
                 for (int i = 0; i < 2; ++i) sc[i] = (int)wsc[i * 32];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {      // fp6(w - w1) x fp6(a1)     (operands read right in front of their MFMA, as modconv_mx.hip does: 6 registers each)
-                    const uint4 lo = f6lo[2 * Q_TN + i * 32];
-                    const uint2 hi = f6hi[2 * Q_TN + i * 32];
-                    acc[a][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(lo, hi), bx1, acc[a][i], 2, 2, 1, sc[i], 0, (int)e1);
+                    acc[a][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6_lds(f6lo + 2 * Q_TN + i * 32, f6hi + 2 * Q_TN + i * 32), bx1, acc[a][i], 2, 2, 1, sc[i], 0, (int)e1);
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {      // fp6(w1) x fp6(a - a1)
-                    const uint4 lo = f6lo[i * 32];
-                    const uint2 hi = f6hi[i * 32];
-                    acc[a][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(lo, hi), bx2, acc[a][i], 2, 2, 0, sc[i], 0, (int)e2);
+                    acc[a][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6_lds(f6lo + i * 32, f6hi + i * 32), bx2, acc[a][i], 2, 2, 0, sc[i], 0, (int)e2);
                 }
                 Q_FENCE();
             }

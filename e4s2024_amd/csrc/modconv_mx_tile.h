@@ -56,6 +56,30 @@ __device__ __forceinline__ unsigned resid_pair_f16(float xa, float sa, float xb,
     return r;
 }
 
+// One PAIR of a masked row's 24 values in the five instructions it needs (tools/loop_mix.py counts them; profiles/mxvalu_loop_mix.txt): a = x * s as one packed
+// fp32 multiply, a1 = f16(a) RNE as one packed conversion, the residual pair (two mix-fmas) and ONE three-operand maximum for the range — amax = max(amax, |a.x|, |a.y|),
+// the value the nested fmaxf(fabsf()) form gives (a maximum does not depend on its order), which hipcc built from one |x| instruction per VALUE plus combining ones.
+// x and s as register pairs: written with scalar operands hipcc paired 26 of a chunk's 36 products and multiplied the other 20 values one by one.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void mx_prep_pair(f32x2 x, f32x2 s, unsigned& v1, unsigned& v2, float& amax) {
+    f32x2 a;
+    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(a) : "v"(x), "v"(s));
+    v1 = __builtin_bit_cast(unsigned, __builtin_convertvector(a, f16x2));                    // v_cvt_pk_f16_f32
+    v2 = resid_pair_f16(x[0], s[0], x[1], s[1], v1);
+    asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a[0]), "v"(a[1]));
+}
+// This lane's eight modulation values of a chunk (its region's row of the table, channels 8 khalf .. + 7; zeros for a pixel without a region) as four register pairs:
+// two 16-byte reads from a clamped row and eight selects — the per-value `cls >= 0 ? ss[..] : 0` form became eight 4-byte reads, each under its own exec mask.
+__device__ __forceinline__ void mx_load_sv(const float* ss, int cls, int khalf, f32x2 (&sv)[4]) {
+    const f32x4* row = reinterpret_cast<const f32x4*>(ss + (cls >= 0 ? cls : 0) * CKS + khalf * 8);
+    const f32x4 lo = row[0], hi = row[1];
+    const bool on = cls >= 0;
+    sv[0] = (f32x2){on ? lo[0] : 0.f, on ? lo[1] : 0.f};
+    sv[1] = (f32x2){on ? lo[2] : 0.f, on ? lo[3] : 0.f};
+    sv[2] = (f32x2){on ? hi[0] : 0.f, on ? hi[1] : 0.f};
+    sv[3] = (f32x2){on ? hi[2] : 0.f, on ? hi[3] : 0.f};
+}
+
 // "This value exists HERE": an empty asm that claims to rewrite the register(s).  The two-phase loop needs it — LLVM sinks pure conversions to their first
 // use, i.e. across the barrier into the phase that must hold nothing but MFMAs (and keeps their 32 source registers alive across it).
 template <typename T>
@@ -72,6 +96,16 @@ __device__ __forceinline__ i32x8 mx_op6(u32x6 c) {
 __device__ __forceinline__ i32x8 mx_op6(uint4 lo, uint2 hi) {
     const i32x4v a = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w};
     const i32x2v b2 = {(int)hi.x, (int)hi.y};
+    const i32x4v b = __builtin_shufflevector(b2, b2, 0, 1, -1, -1);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, -1, -1);
+}
+
+// An fp6 weight operand straight from the row slot: 16 bytes + the 8-byte tail.  The tail is a VOLATILE read: hipcc pairs two ordinary 8-byte reads of neighbouring
+// fragments into one ds_read2_b64, whose halves then reach registers 4-5 of their operand tuples through two v_mov_b32 each (24 moves per chunk between the
+// MFMAs); a volatile read is not paired and lands in its tuple.  (Still a compiler-tracked LDS read: its lgkmcnt wait is hipcc's.)
+__device__ __forceinline__ i32x8 mx_op6_lds(const uint4* lo, const uint2* hi) {
+    const i32x4v a = *reinterpret_cast<const i32x4v*>(lo);
+    const i32x2v b2 = *(const volatile __attribute__((address_space(3))) i32x2v*)hi;       // (named as LDS: a volatile access keeps hipcc from inferring it)
     const i32x4v b = __builtin_shufflevector(b2, b2, 0, 1, -1, -1);
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, -1, -1);
 }
@@ -287,9 +321,15 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
 
         const float4* xf4 = reinterpret_cast<const float4*>(lds_raw + L::PATCH0 + cur * MX_PATCHB);
         const float* ss = reinterpret_cast<const float*>(lds_raw + L::SS0 + cur * MX_SSB);
+        constexpr bool MASKED1 = ARITH == 1 && !ENC;      // the masked f16 + fp6 loop: modulation values as register pairs (mx_prep_pair)
         float sv[8];
+        f32x2 sv2[4];
+        if constexpr (MASKED1) {
+            mx_load_sv(ss, cls[0], khalf, sv2);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) sv[e] = ENC ? 1.f : (cls[0] >= 0 ? ss[cls[0] * CKS + khalf * 8 + e] : 0.f);
+            for (int e = 0; e < 8; ++e) sv[e] = ENC ? 1.f : (cls[0] >= 0 ? ss[cls[0] * CKS + khalf * 8 + e] : 0.f);
+        }
 
 #pragma unroll
         for (int row = 0; row < 3; ++row) {
@@ -398,13 +438,14 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
                 } else {
                 // as in the plain-convolution mode: the row's activation and f16 weight fragments are requested together, ahead of the first conversion
                 float amax = 0.f;
-                float4 xa[3], xb[3];
+                f32x4 xa[3], xb[3];
                 uint4 wv[3][4];
+                const f32x4* xv4 = reinterpret_cast<const f32x4*>(xf4);
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
                     const int e = xoff + row * C::PW + t;
-                    xa[t] = xf4[(2 * khalf) * MX_PSTRIDE + e];
-                    xb[t] = xf4[(2 * khalf + 1) * MX_PSTRIDE + e];
+                    xa[t] = xv4[(2 * khalf) * MX_PSTRIDE + e];
+                    xb[t] = xv4[(2 * khalf + 1) * MX_PSTRIDE + e];
                 }
 #pragma unroll
                 for (int t = 0; t < 3; ++t)
@@ -416,20 +457,15 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
-                    const float xv[8] = {xa[t].x, xa[t].y, xa[t].z, xa[t].w, xb[t].x, xb[t].y, xb[t].z, xb[t].w};
+                    const f32x2 xp[4] = {__builtin_shufflevector(xa[t], xa[t], 0, 1), __builtin_shufflevector(xa[t], xa[t], 2, 3),
+                                         __builtin_shufflevector(xb[t], xb[t], 0, 1), __builtin_shufflevector(xb[t], xb[t], 2, 3)};
                     if constexpr (MX_ABL & 8) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { v1[t * 4 + j] = __builtin_bit_cast(unsigned, xv[2 * j]); v2[t * 4 + j] = __builtin_bit_cast(unsigned, xv[2 * j + 1]); }
+                        for (int j = 0; j < 4; ++j) { v1[t * 4 + j] = __builtin_bit_cast(unsigned, xp[j][0]); v2[t * 4 + j] = __builtin_bit_cast(unsigned, xp[j][1]); }
                         amax = 1.0f;
                     } else {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float a = xv[2 * j] * sv[2 * j], bq = xv[2 * j + 1] * sv[2 * j + 1];
-                        const f16x2 a1 = __builtin_convertvector((f32x2){a, bq}, f16x2);
-                        v1[t * 4 + j] = __builtin_bit_cast(unsigned, a1);
-                        v2[t * 4 + j] = resid_pair_f16(xv[2 * j], sv[2 * j], xv[2 * j + 1], sv[2 * j + 1], v1[t * 4 + j]);
-                        amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(bq)));
-                    }
+                        for (int j = 0; j < 4; ++j) { unsigned q1, q2; mx_prep_pair(xp[j], sv2[j], q1, q2, amax); v1[t * 4 + j] = q1; v2[t * 4 + j] = q2; }
                     }
                     const uint4 b1 = make_uint4(v1[t * 4], v1[t * 4 + 1], v1[t * 4 + 2], v1[t * 4 + 3]);
 #pragma unroll
@@ -453,21 +489,15 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
                 const i32x8 bx1 = mx_op6(p1), bx2 = mx_op6(p2);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {       // fp6(w - w1) x fp6(a1)
-                    uint4 lo; uint2 hi; int sc;
-                    if constexpr (ENC && (MX_ABL & 2)) { lo = make_uint4(tid, i, row, 1); hi = make_uint2(tid, i); sc = 127 << 8; }
-                    else { lo = f6lo[2 * MX_TN + i * 32]; hi = f6hi[2 * MX_TN + i * 32]; sc = (int)wsc[i * 32]; }
-                    const i32x8 aw = mx_op6(lo, hi);
-                    if constexpr (ENC && (MX_ABL & 1)) { asm volatile("" :: "v"(lo.x), "v"(hi.x), "v"(sc), "v"(bx1[0])); }
-                    else acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aw, bx1, acc[i][0], 2, 2, 1, sc, 0, (int)e1);
+                    const int sc = (int)wsc[i * 32];
+                    const i32x8 aw = mx_op6_lds(f6lo + 2 * MX_TN + i * 32, f6hi + 2 * MX_TN + i * 32);
+                    acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aw, bx1, acc[i][0], 2, 2, 1, sc, 0, (int)e1);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {       // fp6(w1) x fp6(a - a1)
-                    uint4 lo; uint2 hi; int sc;
-                    if constexpr (ENC && (MX_ABL & 2)) { lo = make_uint4(tid, i, row, 2); hi = make_uint2(i, tid); sc = 127; }
-                    else { lo = f6lo[i * 32]; hi = f6hi[i * 32]; sc = (int)wsc[i * 32]; }
-                    const i32x8 aw = mx_op6(lo, hi);
-                    if constexpr (ENC && (MX_ABL & 1)) { asm volatile("" :: "v"(lo.x), "v"(hi.x), "v"(sc), "v"(bx2[0])); }
-                    else acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aw, bx2, acc[i][0], 2, 2, 0, sc, 0, (int)e2);
+                    const int sc = (int)wsc[i * 32];
+                    const i32x8 aw = mx_op6_lds(f6lo + i * 32, f6hi + i * 32);
+                    acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aw, bx2, acc[i][0], 2, 2, 0, sc, 0, (int)e2);
                 }
                 }
             }
