@@ -11,7 +11,8 @@ Layout
                  ``swap_face_fine/Blender/model_center/backbone.py``, ``swap_face_fine/realesr/image_infer.py``,
                  ``swap_face_fine/gpen/face_model/gpen_model.py``, ``swap_face_fine/gpen/face_parse/parse_model.py``,
                  ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``,
-                 ``swap_face_fine/gpen/align_faces.py``)
+                 ``swap_face_fine/gpen/align_faces.py``, ``swap_face_fine/gpen/sr_model/rrdbnet_arch.py``,
+                 ``swap_face_fine/gpen/sr_model/real_esrnet.py``, ``swap_face_fine/gpen/face_enhancement.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -104,10 +105,18 @@ GPEN_ALIGN_OVERRIDES = {
     "swap_face_fine.gpen.align_faces": "swap_face_fine/gpen/align_faces.py",
 }
 
+# row f16: GPEN face enhancement, stage 5: the RealESRNet pass (real_esrnet.py imports RRDBNet from rrdbnet_arch.py) and FaceEnhancement itself, without cv2,
+# skimage and basicsr.  ``sr_model.arch_util`` is not redirected: the drop-ins do not import it
+GPEN_SR_OVERRIDES = {
+    "swap_face_fine.gpen.sr_model.rrdbnet_arch": "swap_face_fine/gpen/sr_model/rrdbnet_arch.py",
+    "swap_face_fine.gpen.sr_model.real_esrnet": "swap_face_fine/gpen/sr_model/real_esrnet.py",
+    "swap_face_fine.gpen.face_enhancement": "swap_face_fine/gpen/face_enhancement.py",
+}
+
 
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
-            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES}
+            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -126,8 +135,8 @@ _finder = None
 def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
     ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
-    face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``) and GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) to the
-    drop-in files.
+    face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``), GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) and
+    GPEN's RealESRNet pass with ``FaceEnhancement`` itself (``GPEN_SR_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -1,6 +1,6 @@
 """Row f12: GPEN face enhancement, stage 1 — the GAN-prior generator, ``FullGenerator`` of swap_face_fine/gpen/face_model/gpen_model.py:628-690, in eval mode
 between the tensor ends of ``FaceGAN`` (face_gan.py:49-62): ``gpen_forward``, ``gpen_image``.  Everything else of ``FaceEnhancement.process`` (the RetinaFace
-detector, the 5-point warps, ParseNet, the RealESRNet pass, the paste mask, ``cv2.resize``) stays with the caller.
+detector, the 5-point warps, ParseNet, the RealESRNet pass, the paste mask, ``cv2.resize``) is rows f13 - f16; ``pipeline.gpen_face_enhancement`` chains them.
 
 The network is a StyleGAN2 synthesis network behind a strided-convolution encoder, with one style per sample; its contractions run on kernels the library
 has for the regional generator, in their single-region form (``nreg = 1``, no label map), the rest on csrc/gpen.hip:

@@ -544,7 +544,7 @@ def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_
         out            = ops.gpen_paste(base, ops.gpen_smooth_small(ef, flags), mask, T, flags, face_begin)     (:91-108)
 
     at the reference's constants (``ops.GPEN_PASTE_DEFAULTS``).  ``base_u8`` is what the faces are pasted over: the frames themselves, or — the reference's
-    ``use_sr`` — a super-resolved frame of the same shape (its RealESRNet pass and the resize of the frame to its size are not done here).  With
+    ``use_sr`` — a super-resolved frame of the same shape (its RealESRNet pass and the resize of the frame to its size are ``gpen_face_enhancement``'s).  With
     ``return_faces`` the result is ``(out, orig_faces, enhanced_faces)``: per frame the uint8 ``[n_b, S, S, 3]`` crops and enhanced faces of the faces above the
     score threshold, the reference's second and third results.  A frame without a face comes back as ``base``.  The one device-to-host read is the detector's, of
     its kept counts (with ``return_faces`` the flags are read too, to drop the skipped faces).  Refused: a ParseNet whose mask is not S x S (the reference
@@ -587,6 +587,55 @@ def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_
         return out
     kept = ((flags & ops.GPEN_FACE_SKIP) == 0).cpu()
     return out, [of[a:b][kept[a:b]] for a, b in zip(begin, begin[1:])], [ef[a:b][kept[a:b]] for a, b in zip(begin, begin[1:])]
+
+
+def gpen_super_resolve(sr, frames_u8: torch.Tensor, bgr: bool = False) -> torch.Tensor:
+    """``RealESRNet.process`` (swap_face_fine/gpen/sr_model/real_esrnet.py:26-60) for a batch on the device under this module's RGB convention
+    (``ops.gpen_sr_image``; ``bgr=True``: BGR in and out, as the reference takes it): uint8 ``[bs, H, W, 3]`` to the super-resolved uint8
+    ``[bs, Ho, Wo, 3]``, ``(Ho, Wo) = ops.gpen_sr_output_size(H, W, scale)[0]``.  ``sr`` as ``ops.gpen_sr_forward`` takes weights."""
+    return ops.gpen_sr_image(frames_u8, sr, bgr=bgr)
+
+
+@torch.no_grad()
+def gpen_face_enhancement(detector, gpen, parsenet, sr, frames_u8: torch.Tensor, aligned: bool = False, return_faces: bool = False):
+    """The whole of ``FaceEnhancement.process(img, aligned)`` (swap_face_fine/gpen/face_enhancement.py:51-110) for a batch of RGB uint8 frames on the device;
+    ``sr`` None is the reference's ``use_sr=False``.
+
+    ``aligned=True`` (:53-61): the frames are faces at the generator's size; ``ef = gpen_enhance(gpen, frames)`` and, with ``sr``, ``out =
+    gpen_super_resolve(sr, ef)``, otherwise ``out = ef``.  ``detector`` and ``parsenet`` are not used and may be None.
+
+    ``aligned=False`` with ``sr`` (:63-66, :105-106): ``img_sr = gpen_super_resolve(sr, frames)``, the frames resized to its size
+    (``ops.cv_resize_linear``), and ``gpen_enhance_frames`` on the resized frames with ``img_sr`` as the base the faces are pasted over.  Without ``sr``
+    exactly ``gpen_enhance_frames``.
+
+    Returns ``out``, or with ``return_faces`` the reference's triple ``(out, orig_faces, enhanced_faces)``: aligned, ``[frames]`` and ``[ef]``; otherwise as
+    ``gpen_enhance_frames`` gives them.  Every argument is checked before any launch."""
+    name = "gpen_face_enhancement"
+    from . import ops_gpen, ops_gpen_sr
+    ops_recolor._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
+    if frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError(f"{name}: frames_u8: expected uint8 [bs, H, W, 3] RGB frames with bs >= 1, got {tuple(frames_u8.shape)}")
+    if sr is not None:
+        ops_recolor._devices_checked(name, "frames_u8", frames_u8, ops_gpen_sr.gpen_sr_weight_tensors(sr, name))
+    ops_recolor._cuda_checked(name, frames_u8=frames_u8)
+    if aligned:
+        ops_gpen.check_loaded(gpen)
+        S = int(ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+        if tuple(frames_u8.shape[1:3]) != (S, S):
+            raise ValueError(f"{name}: aligned faces are {S} x {S}, the generator's size (the reference resizes them with cv2, which is not done here), "
+                             f"got {tuple(frames_u8.shape)}")
+        ef = gpen_enhance(gpen, frames_u8)
+        out = ef if sr is None else gpen_super_resolve(sr, ef)
+        return (out, [frames_u8], [ef]) if return_faces else out
+    if sr is None:
+        return gpen_enhance_frames(detector, gpen, parsenet, frames_u8, return_faces=return_faces)
+    from . import ops_parsenet
+    ops_gpen.check_loaded(gpen)                                               # what gpen_enhance_frames refuses, before the RealESRNet pass runs
+    ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))
+    ops_recolor._validated(name, parsenet, ops_parsenet._net_of(parsenet))
+    img_sr = gpen_super_resolve(sr, frames_u8)
+    resized = ops.cv_resize_linear(frames_u8, (img_sr.shape[2], img_sr.shape[1]))
+    return gpen_enhance_frames(detector, gpen, parsenet, resized, base_u8=img_sr, return_faces=return_faces)
 
 
 @torch.no_grad()

@@ -31,6 +31,7 @@ __all__ = [
     "seeded_fpn_state_dict",
     "seeded_small_fpn_state_dict",
     "seeded_rrdbnet_state_dict",
+    "seeded_gpen_sr_state_dict",
     "seeded_gpen_state_dict",
     "seeded_parsenet_state_dict",
     "seeded_retinaface_state_dict",
@@ -285,6 +286,13 @@ def seeded_rrdbnet_state_dict(seed: int, num_block: int = 23) -> Dict[str, torch
     """Seed-only weights for ``ops.RRDBNet(num_block)`` (the keys of ``RealESRGAN_x4plus.pth``'s ``params_ema``)."""
     from .ops_recolor import rrdbnet_state_dict_shapes
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in rrdbnet_state_dict_shapes(num_block).items()}, seed, "rrdb")
+
+
+def seeded_gpen_sr_state_dict(seed: int, num_block: int = 23, num_feat: int = 32, scale: int = 2) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.GpenSRNet(num_block, num_feat, scale)`` (the keys of a ``realesrnet_x2.pth``'s ``params_ema``), in
+    ``seeded_rrdbnet_state_dict``'s distribution."""
+    from .ops_gpen_sr import gpen_sr_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in gpen_sr_state_dict_shapes(num_block, num_feat, scale).items()}, seed, "rrdb")
 
 
 # GPEN's generator (swap_face_fine/gpen/face_model/gpen_model.py FullGenerator): the equalised-lr layers scale themselves, so weights are unit-variance (the

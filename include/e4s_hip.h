@@ -938,6 +938,30 @@ E4S_API int e4s_gpen_mask_feather(float* out, const uint8_t* masks, const void* 
 E4S_API int e4s_gpen_paste_u8(uint8_t* out, float* full_mask, const uint8_t* base, const uint8_t* faces, const float* masks, const void* transforms,
                               const int* flags, const int* face_begin, int n, int bs, int H, int W, int S, void* stream);
 
+/* f16: GPEN face enhancement, stage 5 — the ends of the RealESRNet pass (swap_face_fine/gpen/sr_model/real_esrnet.py:26-60 RealESRNet.process around
+ * rrdbnet_arch.py:64-116 RRDBNet; csrc/gpen_sr.hip) and the resize of the frame to the super-resolved size (face_enhancement.py:66).  The network's convolutions run
+ * on e4s_conv2d_sb3, its glue on e4s_esr_scale_add and e4s_esr_up2.
+ *   e4s_gsr_input           : uint8 img [bs][H][W][3] -> out [bs][3 r r][(H + ph) / r][(W + pw) / r], r = 1, 2 or 4: v / 255 as a correctly rounded float32 division,
+ *                             colour c from byte 2 - c with bgr (byte c without), the reflect pad of ph = (-H) mod r rows and pw = (-W) mod r columns at the
+ *                             bottom / right (F.pad(..., 'reflect'): index n + i is n - 2 - i; needs H > ph, W > pw) and pixel_unshuffle by r (arch_util.py:109-125:
+ *                             channel c r r + dy r + dx) in one pass.  r = 1: no pad, no unshuffle.
+ *   e4s_gsr_tail            : q = conv3x3(x [bs][C][H][W], weight [3][C][3][3], zero pad 1) + bias [3] in exact float32 as e4s_esr_tail forms it: bias, then C * 9 fused
+ *                             multiply-adds in (input channel, row, column) order; C a multiple of 8 up to 64.  out_u8 [bs][Ho][Wo][3] = uint8(rint(clamp(q, 0, 1) *
+ *                             255.0f)) of the first Ho x Wo pixels, the product rounded on its own, rint to even (numpy's .round()), channel o at byte 2 - o with bgr;
+ *                             out_f [bs][3][H][W] = q, uncropped, when out_f is not NULL.
+ *   e4s_cv_resize_linear_u8 : out [bs][Ho][Wo][3] = cv2.resize(img [bs][H][W][3], (Wo, Ho)) at INTER_LINEAR in OpenCV's portable fixed-point arithmetic: per axis
+ *                             scale = src / dst (double), f = float((d + 0.5) scale - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= src - 1: s = src - 1,
+ *                             f = 0; coefficients short(rint((1 - f) 2048)), short(rint(f 2048)) (1 - f in float32); h = S[s] a0 + S[s + 1] a1 in int32 per row, then
+ *                             (((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2.  H == 2 Ho with W == 2 Wo (cv2 takes INTER_AREA there) is refused.  Not run
+ *                             against OpenCV by anyone: tests/gpen_sr_model.py restates it and is the pin.
+ * 16-byte accesses along a row (12 bytes of uint8 pixels) where the pointers and the row length allow, single elements otherwise: the same bits; the resize is a
+ * byte gather.  No atomics, no host synchronisation, grids depend on the shapes alone: the same inputs give the same bits, and the calls can be captured in a graph.
+ * bs == 0 returns at once. */
+E4S_API int e4s_gsr_input(float* out, const uint8_t* img, int bs, int H, int W, int r, int bgr, void* stream);
+E4S_API int e4s_gsr_tail(uint8_t* out_u8, float* out_f, const float* x, const float* weight, const float* bias, int bs, int C, int H, int W, int Ho, int Wo, int bgr,
+                         void* stream);
+E4S_API int e4s_cv_resize_linear_u8(uint8_t* out, const uint8_t* img, int bs, int H, int W, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
