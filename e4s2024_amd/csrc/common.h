@@ -40,6 +40,11 @@ static inline unsigned coprime_stride(unsigned n) {
     return s % n ? s % n : 1u;
 }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the grid of a grid-stride kernel over n items in 256-lane blocks: at least 1, at most 16384
+static inline int grid_1d(int64_t n) {
+    const int64_t b = cdiv64(n, 256);
+    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
+}
 
 // wave64 butterfly reductions: v[l] (op) v[l ^ 32], then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 — every lane ends with the result.  The partner values come over the VALU's own
 // lane-permute paths (v_permlane32_swap / v_permlane16_swap for the two row exchanges, DPP row_ror:8, row_half_mirror + quad_perm[3,2,1,0] = l ^ 4, quad_perm for ^ 2 and

@@ -20,10 +20,6 @@ namespace e4s {
 constexpr int GPEN_CPB = 16;                     // output channels of the stem per workgroup row (blockIdx.y)
 constexpr float GPEN_SQRT2 = 1.41421356237309515f;
 
-static inline int gpen_grid(int64_t n) {
-    const int64_t b = cdiv64(n, 256);
-    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
 static inline bool gpen_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
 }
@@ -181,14 +177,14 @@ extern "C" int e4s_gpen_stem(float* out, const float* x, const uint8_t* x_u8, co
     hipStream_t st = (hipStream_t)stream;
     if (x) {
         if (W % 4 == 0 && gpen_aligned16(out, x))
-            hipLaunchKernelGGL((gpen_stem_kernel<4, false>), dim3(gpen_grid(n / 4), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n / 4, hw, C0);
+            hipLaunchKernelGGL((gpen_stem_kernel<4, false>), dim3(grid_1d(n / 4), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n / 4, hw, C0);
         else
-            hipLaunchKernelGGL((gpen_stem_kernel<1, false>), dim3(gpen_grid(n), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n, hw, C0);
+            hipLaunchKernelGGL((gpen_stem_kernel<1, false>), dim3(grid_1d(n), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n, hw, C0);
     } else {
         if (W % 4 == 0 && gpen_aligned16(out) && (((uintptr_t)x_u8) & 3) == 0)
-            hipLaunchKernelGGL((gpen_stem_kernel<4, true>), dim3(gpen_grid(n / 4), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n / 4, hw, C0);
+            hipLaunchKernelGGL((gpen_stem_kernel<4, true>), dim3(grid_1d(n / 4), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n / 4, hw, C0);
         else
-            hipLaunchKernelGGL((gpen_stem_kernel<1, true>), dim3(gpen_grid(n), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n, hw, C0);
+            hipLaunchKernelGGL((gpen_stem_kernel<1, true>), dim3(grid_1d(n), gy), dim3(256), 0, st, out, x, x_u8, weight, bias, n, hw, C0);
     }
     return check_launch("gpen_stem");
 }
@@ -201,9 +197,9 @@ extern "C" int e4s_gpen_noise_half(float* out0, float* out1, const float* f, con
     const int64_t n = (int64_t)bs * C * hw;
     hipStream_t st = (hipStream_t)stream;
     if (hw % 4 == 0 && out_stride_b % 4 == 0 && gpen_aligned16(out0, out1, f))
-        hipLaunchKernelGGL(gpen_noise_half_kernel<4>, dim3(gpen_grid(n / 4)), dim3(256), 0, st, out0, out1, f, w0, w1, bias0, bias1, n / 4, C, (int64_t)hw, out_stride_b);
+        hipLaunchKernelGGL(gpen_noise_half_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, st, out0, out1, f, w0, w1, bias0, bias1, n / 4, C, (int64_t)hw, out_stride_b);
     else
-        hipLaunchKernelGGL(gpen_noise_half_kernel<1>, dim3(gpen_grid(n)), dim3(256), 0, st, out0, out1, f, w0, w1, bias0, bias1, n, C, (int64_t)hw, out_stride_b);
+        hipLaunchKernelGGL(gpen_noise_half_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, st, out0, out1, f, w0, w1, bias0, bias1, n, C, (int64_t)hw, out_stride_b);
     return check_launch("gpen_noise_half");
 }
 
@@ -213,8 +209,8 @@ extern "C" int e4s_gpen_to_u8(uint8_t* out, const float* x, int bs, int H, int W
     E4S_REQUIRE(out && x, "gpen_to_u8: null tensor");
     const int64_t hw = (int64_t)H * W, n = (int64_t)bs * hw;
     if (W % 4 == 0 && gpen_aligned16(x) && (((uintptr_t)out) & 3) == 0)
-        hipLaunchKernelGGL(gpen_to_u8_kernel<4>, dim3(gpen_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, out, x, n / 4, hw);
+        hipLaunchKernelGGL(gpen_to_u8_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, (hipStream_t)stream, out, x, n / 4, hw);
     else
-        hipLaunchKernelGGL(gpen_to_u8_kernel<1>, dim3(gpen_grid(n)), dim3(256), 0, (hipStream_t)stream, out, x, n, hw);
+        hipLaunchKernelGGL(gpen_to_u8_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, out, x, n, hw);
     return check_launch("gpen_to_u8");
 }

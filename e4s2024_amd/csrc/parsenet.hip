@@ -19,10 +19,6 @@ namespace e4s {
 
 constexpr int PN_CPB = 16;                       // output channels of the stem per workgroup row (blockIdx.y)
 
-static inline int pn_grid(int64_t n) {
-    const int64_t b = cdiv64(n, 256);
-    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
 static inline bool pn_aligned16(const void* a, const void* b = nullptr) { return ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0; }
 
 // ReflectionPad2d(1): index -1 is 1, index n is n - 2 (n >= 2; with n == 2 the two sides read 1 and 0)
@@ -158,14 +154,14 @@ extern "C" int e4s_parsenet_stem(float* out, const float* x, const uint8_t* x_u8
     hipStream_t st = (hipStream_t)stream;
     if (x) {
         if (W % 4 == 0 && pn_aligned16(out, x))
-            hipLaunchKernelGGL((parsenet_stem_kernel<4, false>), dim3(pn_grid(n / 4), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n / 4, H, W, C0);
+            hipLaunchKernelGGL((parsenet_stem_kernel<4, false>), dim3(grid_1d(n / 4), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n / 4, H, W, C0);
         else
-            hipLaunchKernelGGL((parsenet_stem_kernel<1, false>), dim3(pn_grid(n), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n, H, W, C0);
+            hipLaunchKernelGGL((parsenet_stem_kernel<1, false>), dim3(grid_1d(n), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n, H, W, C0);
     } else {
         if (W % 4 == 0 && pn_aligned16(out) && (((uintptr_t)x_u8) & 3) == 0)
-            hipLaunchKernelGGL((parsenet_stem_kernel<4, true>), dim3(pn_grid(n / 4), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n / 4, H, W, C0);
+            hipLaunchKernelGGL((parsenet_stem_kernel<4, true>), dim3(grid_1d(n / 4), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n / 4, H, W, C0);
         else
-            hipLaunchKernelGGL((parsenet_stem_kernel<1, true>), dim3(pn_grid(n), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n, H, W, C0);
+            hipLaunchKernelGGL((parsenet_stem_kernel<1, true>), dim3(grid_1d(n), gy), dim3(256), 0, st, out, x, x_u8, lut, bgr, weight, bias, n, H, W, C0);
     }
     return check_launch("parsenet_stem");
 }
@@ -180,9 +176,9 @@ extern "C" int e4s_parsenet_pad(float* out, const float* x, const float* add, in
     hipStream_t st = (hipStream_t)stream;
     if (pn_aligned16(out)) {
         const int64_t n = cdiv64(total, 4);
-        hipLaunchKernelGGL(parsenet_pad_kernel<4>, dim3(pn_grid(n)), dim3(256), 0, st, out, x, add, n, total, h, w, u - 1);
+        hipLaunchKernelGGL(parsenet_pad_kernel<4>, dim3(grid_1d(n)), dim3(256), 0, st, out, x, add, n, total, h, w, u - 1);
     } else {
-        hipLaunchKernelGGL(parsenet_pad_kernel<1>, dim3(pn_grid(total)), dim3(256), 0, st, out, x, add, total, total, h, w, u - 1);
+        hipLaunchKernelGGL(parsenet_pad_kernel<1>, dim3(grid_1d(total)), dim3(256), 0, st, out, x, add, total, total, h, w, u - 1);
     }
     return check_launch("parsenet_pad");
 }

@@ -10,10 +10,6 @@
 
 namespace e4s {
 
-static inline int stream_grid(int64_t n) {
-    const int64_t b = cdiv64(n, 256);
-    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
 static inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
@@ -142,9 +138,9 @@ extern "C" int e4s_resunet_preact(float* act, const float* x, const float* scale
     E4S_REQUIRE(act && x && scale && shift, "resunet_preact: null tensor");
     const int64_t n = (int64_t)bs * C * hw;
     if (hw % 4 == 0 && aligned16(act, x))
-        hipLaunchKernelGGL(resunet_preact_kernel<4>, dim3(stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, act, x, scale, shift, n / 4, C, hw / 4);
+        hipLaunchKernelGGL(resunet_preact_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, (hipStream_t)stream, act, x, scale, shift, n / 4, C, hw / 4);
     else
-        hipLaunchKernelGGL(resunet_preact_kernel<1>, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)stream, act, x, scale, shift, n, C, hw);
+        hipLaunchKernelGGL(resunet_preact_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, act, x, scale, shift, n, C, hw);
     return check_launch("resunet_preact");
 }
 
@@ -157,10 +153,10 @@ extern "C" int e4s_resunet_up_cat_preact(float* act, float* up, const float* low
     const float sy = (float)(h - 1) / (float)(2 * h - 1), sx = (float)(w - 1) / (float)(2 * w - 1);
     const int64_t n = (int64_t)bs * (c_low + c_skip) * 4 * h * w;
     if (aligned16(act, up, skip))
-        hipLaunchKernelGGL(resunet_up_cat_preact_kernel<4>, dim3(stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, act, up, low, skip, scale, shift,
+        hipLaunchKernelGGL(resunet_up_cat_preact_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, (hipStream_t)stream, act, up, low, skip, scale, shift,
                            n / 4, c_low, c_skip, h, w, sy, sx);
     else
-        hipLaunchKernelGGL(resunet_up_cat_preact_kernel<1>, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)stream, act, up, low, skip, scale, shift, n,
+        hipLaunchKernelGGL(resunet_up_cat_preact_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, act, up, low, skip, scale, shift, n,
                            c_low, c_skip, h, w, sy, sx);
     return check_launch("resunet_up_cat_preact");
 }
@@ -172,8 +168,8 @@ extern "C" int e4s_resunet_head(float* out, const float* x, const float* w, cons
     E4S_REQUIRE(out && x && w && b, "resunet_head: null tensor");
     const int64_t n = (int64_t)bs * hw;
     if (hw % 4 == 0 && aligned16(out, x))
-        hipLaunchKernelGGL(resunet_head_kernel<4>, dim3(stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, out, x, w, b, n / 4, C, hw / 4);
+        hipLaunchKernelGGL(resunet_head_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, (hipStream_t)stream, out, x, w, b, n / 4, C, hw / 4);
     else
-        hipLaunchKernelGGL(resunet_head_kernel<1>, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)stream, out, x, w, b, n, C, hw);
+        hipLaunchKernelGGL(resunet_head_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, out, x, w, b, n, C, hw);
     return check_launch("resunet_head");
 }

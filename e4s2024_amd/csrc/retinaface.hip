@@ -24,10 +24,6 @@ constexpr int RF_HEAD = 32;                      // channels of a level's head m
 constexpr int RF_MAX_CAP = 16384;                // candidates per image the NMS holds flags for
 constexpr int RF_CT = 1024;                      // threads of the one-workgroup-per-image kernels
 
-static inline int rf_grid(int64_t n) {
-    const int64_t b = cdiv64(n, 256);
-    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
 static inline bool rf_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
@@ -388,9 +384,9 @@ extern "C" int e4s_retina_input(float* out, const uint8_t* img_u8, int bgr, int 
     const int64_t hw = (int64_t)H * W, n = bs * hw;
     hipStream_t st = (hipStream_t)stream;
     if (hw % 4 == 0 && rf_al16(out) && (((uintptr_t)img_u8) & 3) == 0)
-        hipLaunchKernelGGL(retina_input_kernel<4>, dim3(rf_grid(n / 4)), dim3(256), 0, st, out, img_u8, bgr, n / 4, hw);
+        hipLaunchKernelGGL(retina_input_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, st, out, img_u8, bgr, n / 4, hw);
     else
-        hipLaunchKernelGGL(retina_input_kernel<1>, dim3(rf_grid(n)), dim3(256), 0, st, out, img_u8, bgr, n, hw);
+        hipLaunchKernelGGL(retina_input_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, st, out, img_u8, bgr, n, hw);
     return check_launch("retina_input");
 }
 
@@ -402,9 +398,9 @@ extern "C" int e4s_retina_up_add(float* out, const float* a, const float* b, int
     const int64_t n = (int64_t)planes * h * w;
     hipStream_t st = (hipStream_t)stream;
     if (w % 4 == 0 && rf_al16(out, a))
-        hipLaunchKernelGGL(retina_up_add_kernel<4>, dim3(rf_grid(n / 4)), dim3(256), 0, st, out, a, b, n / 4, h, w, hb, wb, sy, sx);
+        hipLaunchKernelGGL(retina_up_add_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, st, out, a, b, n / 4, h, w, hb, wb, sy, sx);
     else
-        hipLaunchKernelGGL(retina_up_add_kernel<1>, dim3(rf_grid(n)), dim3(256), 0, st, out, a, b, n, h, w, hb, wb, sy, sx);
+        hipLaunchKernelGGL(retina_up_add_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, st, out, a, b, n, h, w, hb, wb, sy, sx);
     return check_launch("retina_up_add");
 }
 
@@ -415,9 +411,9 @@ extern "C" int e4s_retina_cat_relu(float* out, const float* a, const float* b, c
     const int64_t n = (int64_t)bs * (ca + cb + cc) * hw;
     hipStream_t st = (hipStream_t)stream;
     if (hw % 4 == 0 && rf_al16(out, a, b, c))
-        hipLaunchKernelGGL(retina_cat_relu_kernel<4>, dim3(rf_grid(n / 4)), dim3(256), 0, st, out, a, b, c, n / 4, ca, cb, cc, hw);
+        hipLaunchKernelGGL(retina_cat_relu_kernel<4>, dim3(grid_1d(n / 4)), dim3(256), 0, st, out, a, b, c, n / 4, ca, cb, cc, hw);
     else
-        hipLaunchKernelGGL(retina_cat_relu_kernel<1>, dim3(rf_grid(n)), dim3(256), 0, st, out, a, b, c, n, ca, cb, cc, hw);
+        hipLaunchKernelGGL(retina_cat_relu_kernel<1>, dim3(grid_1d(n)), dim3(256), 0, st, out, a, b, c, n, ca, cb, cc, hw);
     return check_launch("retina_cat_relu");
 }
 
@@ -425,7 +421,7 @@ extern "C" int e4s_retina_priors(float* out, int H, int W, void* stream) {
     E4S_REQUIRE(out && H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "retina_priors: null tensor or bad size");
     RetinaDecodeParams p;
     rf_levels(p, 1, H, W);
-    hipLaunchKernelGGL(retina_priors_kernel, dim3(rf_grid(p.N)), dim3(256), 0, (hipStream_t)stream, out, p);
+    hipLaunchKernelGGL(retina_priors_kernel, dim3(grid_1d(p.N)), dim3(256), 0, (hipStream_t)stream, out, p);
     return check_launch("retina_priors");
 }
 
@@ -445,9 +441,9 @@ extern "C" int e4s_retina_decode(float* loc, float* conf, float* landms, float* 
     hipStream_t st = (hipStream_t)stream;
     // a position's rows start at multiples of 32, 16 and 80 bytes: aligned whenever the tensors are
     if (rf_al16(loc, conf, landms) && rf_al16(boxes, lmk))
-        hipLaunchKernelGGL(retina_decode_kernel<true>, dim3(rf_grid(n)), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(retina_decode_kernel<true>, dim3(grid_1d(n)), dim3(256), 0, st, p);
     else
-        hipLaunchKernelGGL(retina_decode_kernel<false>, dim3(rf_grid(n)), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(retina_decode_kernel<false>, dim3(grid_1d(n)), dim3(256), 0, st, p);
     return check_launch("retina_decode");
 }
 
@@ -470,7 +466,7 @@ extern "C" int e4s_retina_nms(float* dets, float* landms_out, int* keep, int* nk
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)bs * cap;
     const long long* kp = reinterpret_cast<const long long*>(sorted_keys);
-    hipLaunchKernelGGL(retina_gather_kernel, dim3(rf_grid(n)), dim3(256), 0, st, cbox, kp, counts, boxes, n, N, cap);
+    hipLaunchKernelGGL(retina_gather_kernel, dim3(grid_1d(n)), dim3(256), 0, st, cbox, kp, counts, boxes, n, N, cap);
     hipLaunchKernelGGL(retina_nms_kernel, dim3(bs), dim3(RF_CT), 0, st, dets, landms_out, keep, nkeep, cbox, kp, counts, lmk, N, cap, keep_top_k, nms_threshold);
     return check_launch("retina_nms");
 }

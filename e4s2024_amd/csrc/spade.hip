@@ -15,10 +15,6 @@
 
 namespace e4s {
 
-static inline int spade_grid(int64_t n) {
-    const int64_t b = cdiv64(n, 256);
-    return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
 static inline bool spade_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
 }
@@ -136,8 +132,8 @@ __global__ __launch_bounds__(256) void spade_modulate_kernel(float* __restrict__
 template <int V>
 static void launch_modulate(bool pad, hipStream_t st, float* out, const float* x, const float* mean, const float* rstd, const float* gb, int64_t n, int C, int h,
                             int w, float slope) {
-    if (pad) hipLaunchKernelGGL((spade_modulate_kernel<V, true>), dim3(spade_grid(n)), dim3(256), 0, st, out, x, mean, rstd, gb, n, C, h, w, slope);
-    else hipLaunchKernelGGL((spade_modulate_kernel<V, false>), dim3(spade_grid(n)), dim3(256), 0, st, out, x, mean, rstd, gb, n, C, h, w, slope);
+    if (pad) hipLaunchKernelGGL((spade_modulate_kernel<V, true>), dim3(grid_1d(n)), dim3(256), 0, st, out, x, mean, rstd, gb, n, C, h, w, slope);
+    else hipLaunchKernelGGL((spade_modulate_kernel<V, false>), dim3(grid_1d(n)), dim3(256), 0, st, out, x, mean, rstd, gb, n, C, h, w, slope);
 }
 
 }  // namespace e4s

@@ -44,7 +44,7 @@ from . import lossnet
 from ._lib import MAX_STYLE_JOBS, StyleJob, lib
 from .lossnet import weights_key
 from .ops import _Prepared, _c, _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
-from .ops_recolor import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
 
 ARITH = "sb"                                 # "sb" | "f32" (module attribute, no environment variable: tests and tools set it)
 UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form (measured: see the module text)

@@ -20,7 +20,7 @@ import torch
 
 from ._lib import lib
 from .ops import _p, _stream
-from .ops_recolor import _cuda_checked, _tensor_checked
+from .netweights import _cuda_checked, _tensor_checked
 
 GPEN_PASTE_DEFAULTS = {"ksize": 101, "sigma": 11, "thres": 20, "threshold": 0.9, "small_face": 100}        # face_enhancement.py:24, 44-48, 75, 93
 GPEN_FACE_SKIP, GPEN_FACE_SMALL = 1, 2

@@ -30,7 +30,7 @@ from . import lossnet
 from ._lib import lib
 from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
 from .ops import _Prepared, _c, _p, _stream
-from .ops_recolor import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
 
 SLOPE = 0.2                                  # ReluLayer's LeakyReLU (blocks.py:58)
 # FaceParse.MASK_COLORMAP (face_parsing.py:30): background, hat (14) and cloth (18) are 0, every other class 255

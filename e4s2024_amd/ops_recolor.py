@@ -1,6 +1,6 @@
 """Rows f8 to f11: Blender recolouring (``ct_mode='blender'``), four stages: f8 the semantic colour reference, f9 the Res-U-Net that consumes its packages,
-f10 the SPADE feature network that feeds it, f11 the Real-ESRGAN step behind them.  The three networks share one weights path (``_validated``: keys, shapes
-and dtypes checked once per public call and handed on to ``lossnet.prepare``) and one convolution call (``lossnet.conv_sb``).
+f10 the SPADE feature network that feeds it, f11 the Real-ESRGAN step behind them.  The three networks share one weights path (``netweights._validated``:
+keys, shapes and dtypes checked once per public call and handed on to ``lossnet.prepare``) and one convolution call (``lossnet.conv_sb``).
 
 Row f8, stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
 
@@ -48,24 +48,25 @@ by reflection, so the glue WRITES reflection-padded planes and the convolution r
 Spectral norm in eval mode makes no power iteration: ``weight_orig / (u . W v)`` is folded on the host in float64 when the weights are prepared.
 
 Row f11, stage 4 — the Real-ESRGAN step, ``RRDBNet(3, 3, 64, num_block, 32, scale=4)`` between the two wrappers of ``RealESRBatchInfer``
-(swap_face_fine/realesr/image_infer.py), forward only (``realesr_forward``, ``realesr_input``, ``realesr_image``); the glue on csrc/rrdb.hip.  A dense block's
-concatenations are never formed: its convolutions read the head of a 192-plane slab and write their 32 planes right behind it (``_rrdb_sample``).
+(swap_face_fine/realesr/image_infer.py), forward only (``realesr_forward``, ``realesr_input``, ``realesr_image``).  The network is ``ops_rrdb``'s, shared with row f16, at width 64 and scale 4; the two ends of
+``RealESRBatchInfer`` around it are here, on csrc/rrdb.hip (``e4s_esr_input``, ``e4s_esr_tail``).
 """
 from __future__ import annotations
 
 import ctypes
 import functools
-from collections import namedtuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet
+from . import lossnet, ops_rrdb
 from ._lib import lib
 from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
+from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
 from .ops import _Prepared, _c, _p, _stream
 from .ops_post import GREY_MORPH_MAX_RADIUS, grey_dilate
+from .ops_rrdb import GpenSRNet
 
 BLENDER_PARTS = ("skin", "hair", "eye", "nose", "lip", "tooth", "ear", "brow", "inpainting")
 # the 19-class parser ids of the eight head parts (semantic_tools.py:170-179)
@@ -90,19 +91,6 @@ def _consts(device):
         c = _CONSTS[device] = (lut.to(device), torch.arange(_NPARTS - 1, device=device).view(1, -1, 1, 1),
                                torch.tensor(_IMAGENET_MEAN, device=device).view(1, 3, 1, 1), torch.tensor(_IMAGENET_STD, device=device).view(1, 3, 1, 1))
     return c
-
-
-def _tensor_checked(name, nm, t, dtype, ndim, what):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: {nm} must be a torch.Tensor")
-    if t.dtype != dtype or t.dim() != ndim:
-        raise ValueError(f"{name}: {nm}: expected {what}, got {t.dtype} {tuple(t.shape)}")
-
-
-def _cuda_checked(name, **tensors):
-    for nm, t in tensors.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"{name}: {nm} must be a CUDA tensor")
 
 
 def _labels_checked(name, labels_a, labels_t):
@@ -265,62 +253,6 @@ def blender_packages(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.T
     packages[:, 8:9] = grey
     packages[:, 9:12] = img_t * (1 - e_at)
     return packages, (inv, inv_target)
-
-
-# ------------------------------------------------------------------------------------------------ the networks' weights
-# What ``_validated`` needs to know of a network: ``cls`` its name in messages; ``shapes(variant)`` the public ``{key: shape}`` function; ``prefixes`` the key
-# prefixes a checkpoint may carry (``nested``: or a mapping of that name inside it); ``variant(name, sd)`` reads the width / small or full / block count off
-# the bare keys and raises for a missing probe key; ``training``: why a module in training mode is refused (None: it makes no difference); ``skip``: the key
-# suffixes that are not float weights.
-_Net = namedtuple("_Net", "cls shapes prefixes nested probes variant training skip")
-
-
-@functools.lru_cache(maxsize=8)
-def _keys_shapes(cls, *args):
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in cls(*args).state_dict().items())
-
-
-@functools.lru_cache(maxsize=8)
-def _float_keys(net, variant):
-    return tuple((k, shape) for k, shape in net.shapes(variant).items() if not k.endswith(net.skip))
-
-
-def _validated(name, weights, net):
-    """(mapping with bare keys, variant, float tensors in key order) of ``weights``: a module with the network's keys or a mapping, bare or prefixed.  Made
-    once per public call (one ``state_dict()``) and handed on.  Refused, in this order: a module in training mode, anything without keys, a missing probe key,
-    a missing key, a wrong shape or dtype."""
-    if isinstance(weights, nn.Module):
-        if weights.training and net.training:
-            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; {net.training}: call .eval()")
-        sd = weights.state_dict()
-    elif hasattr(weights, "keys"):
-        sd = weights
-    else:
-        raise TypeError(f"{name}: weights must be a module or a mapping with the keys of {net.cls}, got {type(weights).__name__}")
-    if not any(p in sd for p in net.probes):
-        for prefix in net.prefixes:
-            if net.nested and isinstance(sd.get(prefix[:-1]), dict):          # the checkpoint file as torch.load gives it
-                sd = sd[prefix[:-1]]
-                break
-            if any(prefix + p in sd for p in net.probes):
-                sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-                break
-    variant = net.variant(name, sd)
-    out = []
-    for k, shape in _float_keys(net, variant):
-        t = sd.get(k)
-        if t is None:
-            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {net.cls} (ops.{net.shapes.__name__}({variant!r}))")
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
-            raise ValueError(f"{name}: '{k}' is {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}, expected float32 {shape}")
-        out.append(t)
-    return sd, variant, out
-
-
-def _devices_checked(name, nm, t, ts):
-    if any(w.device != t.device for w in ts):
-        raise RuntimeError(f"{name}: device mismatch: {nm} on {t.device}, the weights on {sorted({str(w.device) for w in ts})}")
 
 
 # ------------------------------------------------------------------------------------------------ row f9: the Res-U-Net
@@ -843,61 +775,15 @@ def blender_forward(img_a: torch.Tensor, img_t: torch.Tensor, labels_a: torch.Te
 
 
 # ------------------------------------------------------------------------------------------------ row f11: the Real-ESRGAN step
-RRDB_FEAT = 64                               # RRDBNet(num_feat=64, num_grow_ch=32, scale=4): the only configuration the reference builds
-RRDB_GROW = 32
-RRDB_SLAB = RRDB_FEAT + 4 * RRDB_GROW        # planes of a dense block's slab: x, x1 .. x4
-RRDB_SLOPE = 0.2
-_RRDB_PREFIXES = ("params_ema.", "params.")
-
-
-class _RDB(nn.Module):
-    """``ResidualDenseBlock(64, 32)`` of basicsr's rrdbnet_arch under its parameter names."""
-
-    def __init__(self):
-        super().__init__()
-        for k in range(1, 6):
-            setattr(self, f"conv{k}", nn.Conv2d(RRDB_FEAT + (k - 1) * RRDB_GROW, RRDB_GROW if k < 5 else RRDB_FEAT, 3, 1, 1))
-
-    def forward(self, x):
-        xs = [x]
-        for k in range(1, 5):
-            xs.append(F.leaky_relu(getattr(self, f"conv{k}")(torch.cat(xs, 1)), RRDB_SLOPE))
-        return self.conv5(torch.cat(xs, 1)) * 0.2 + x
-
-
-class _RRDB(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.rdb1, self.rdb2, self.rdb3 = _RDB(), _RDB(), _RDB()
-
-    def forward(self, x):
-        return self.rdb3(self.rdb2(self.rdb1(x))) * 0.2 + x
-
-
-class RRDBNet(nn.Module):
-    """``RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4)`` of basicsr's rrdbnet_arch with its ``state_dict`` keys and shapes
-    (``RealESRGAN_x4plus.pth``'s ``params_ema``, load with ``strict=True``): 702 tensors at 23 blocks.  ``forward`` is the plain PyTorch composition — what the
-    tests and the timing compare ``realesr_forward`` with; ``realesr_forward(x, module)`` runs the same weights on the HIP kernels."""
+class RRDBNet(GpenSRNet):
+    """``RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4)`` of basicsr's rrdbnet_arch, the only configuration the reference builds, with its
+    ``state_dict`` keys and shapes (``RealESRGAN_x4plus.pth``'s ``params_ema``, load with ``strict=True``): 702 tensors at 23 blocks.  ``ops_rrdb``'s mirror
+    module at width 64 and scale 4; ``forward`` is the plain PyTorch composition — what the tests and the timing compare ``realesr_forward`` with;
+    ``realesr_forward(x, module)`` runs the same weights on the HIP kernels."""
 
     def __init__(self, num_block: int = 23):
-        super().__init__()
-        if isinstance(num_block, bool) or not isinstance(num_block, int) or num_block < 1:
-            raise ValueError(f"RRDBNet: num_block is a positive int, got {num_block!r}")
-        self.num_block = num_block
-        self.conv_first = nn.Conv2d(3, RRDB_FEAT, 3, 1, 1)
-        self.body = nn.Sequential(*[_RRDB() for _ in range(num_block)])
-        self.conv_body = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
-        self.conv_up1 = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
-        self.conv_up2 = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
-        self.conv_hr = nn.Conv2d(RRDB_FEAT, RRDB_FEAT, 3, 1, 1)
-        self.conv_last = nn.Conv2d(RRDB_FEAT, 3, 3, 1, 1)
-
-    def forward(self, x):
-        feat = self.conv_first(x)
-        feat = feat + self.conv_body(self.body(feat))
-        feat = F.leaky_relu(self.conv_up1(F.interpolate(feat, scale_factor=2, mode="nearest")), RRDB_SLOPE)
-        feat = F.leaky_relu(self.conv_up2(F.interpolate(feat, scale_factor=2, mode="nearest")), RRDB_SLOPE)
-        return self.conv_last(F.leaky_relu(self.conv_hr(feat), RRDB_SLOPE))
+        ops_rrdb._config_checked("RRDBNet", num_block, 64, 4)
+        super().__init__(num_block, 64, 4)
 
 
 def rrdbnet_state_dict_shapes(num_block: int = 23):
@@ -905,18 +791,9 @@ def rrdbnet_state_dict_shapes(num_block: int = 23):
     return dict(_keys_shapes(RRDBNet, num_block))
 
 
-def _rrdb_blocks(name, sd):
-    num_block = 0
-    while f"body.{num_block}.rdb1.conv1.weight" in sd:
-        num_block += 1
-    for probe in ("conv_first.weight", "body.0.rdb1.conv1.weight"):
-        if probe not in sd:
-            raise KeyError(f"{name}: the weights lack '{probe}': expected the keys of RRDBNet (ops.rrdbnet_state_dict_shapes())")
-    return num_block
-
-
-# a mapping may be the checkpoint itself, with the network under ``params_ema`` or ``params``
-_RRDB_NET = _Net("RRDBNet", rrdbnet_state_dict_shapes, _RRDB_PREFIXES, True, ("conv_first.weight",), _rrdb_blocks, None, ())
+# the block count is the whole variant: any other width or scale fails the shapes of ``rrdbnet_state_dict_shapes``
+_RRDB_NET = _Net("RRDBNet", rrdbnet_state_dict_shapes, ops_rrdb._PREFIXES, True, ("conv_first.weight",),
+                 functools.partial(ops_rrdb._blocks, shapes="rrdbnet_state_dict_shapes"), None, ())
 
 
 def rrdbnet_weight_tensors(weights, name: str = "realesr_forward"):
@@ -924,83 +801,16 @@ def rrdbnet_weight_tensors(weights, name: str = "realesr_forward"):
     return _validated(name, weights, _RRDB_NET)[2]
 
 
-class PreparedRRDBNet(_Prepared):
-    """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  ``first``, ``conv_body``, ``up1``, ``up2``, ``hr``
-    and per block three dense blocks of five convolutions, all as three-way split slabs with their biases; ``conv5`` of a dense block carries the block's
-    ``* 0.2`` in weight and bias (folded in float64), so that ``x5 * 0.2 + x`` is the convolution's residual epilogue; ``last`` conv_last's float32 weight
-    and bias for the exact kernel; ``slope64`` / ``slope32`` the LeakyReLU as a PReLU slope vector."""
+class PreparedRRDBNet(ops_rrdb._PreparedRRDB):
+    """``ops_rrdb._PreparedRRDB`` for the network at width 64 and scale 4."""
 
     __slots__ = ()
-
-    def get(self, weights, checked=None):
-        sd, num_block, ts = checked if checked is not None else _validated("realesr_forward", weights, _RRDB_NET)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in rrdbnet_state_dict_shapes(num_block)}
-        dev = ts[0].device
-
-        def conv(name, scale=None):
-            w, b = sd[name + ".weight"], sd[name + ".bias"]
-            if scale is None:
-                return prep_fwd(w, None, b)
-            return prep_fwd(w, torch.full((w.shape[0],), scale, dtype=torch.float64, device=dev), b.double() * scale)
-
-        with torch.no_grad():
-            body = [[[conv(f"body.{i}.rdb{r}.conv{k}", 0.2 if k == 5 else None) for k in range(1, 6)] for r in (1, 2, 3)] for i in range(num_block)]
-            P = dict(num_block=num_block, first=conv("conv_first"), body=body, conv_body=conv("conv_body"), up1=conv("conv_up1"), up2=conv("conv_up2"),
-                     hr=conv("conv_hr"), last=(sd["conv_last.weight"].contiguous(), sd["conv_last.bias"].contiguous()),
-                     slope64=torch.full((RRDB_FEAT,), RRDB_SLOPE, dtype=torch.float32, device=dev),
-                     slope32=torch.full((RRDB_GROW,), RRDB_SLOPE, dtype=torch.float32, device=dev))
-        return self._publish(key, P)
-
-
-def _rrdb_sample(P, x, out_f, out_u8, reads, writes, feat0, ups):
-    """The network on one sample ``x [1, 3, h, w]``.  ``reads`` / ``writes``: the views of three ``[1, 192, h, w]`` slabs (``_rrdb_run``); a dense block reads
-    the head of one (x, x1 ..) and each of its first four convolutions writes its 32 planes right behind what it read, so no concatenation is formed; conv5
-    writes the head of the NEXT slab with this slab's head as its residual.  An RRDB's input (the head of slab 0) outlives its three dense blocks: block 1
-    goes 0 -> 1, block 2 goes 1 -> 2, block 3 goes 2 -> 1, and ``e4s_esr_scale_add`` puts ``head(1) * 0.2 + head(0)`` back into the head of slab 0.
-    ``ups``: per upsampling the pair (nearest x2, convolution output) of ``[1, 64, 2h, 2w]`` and ``[1, 64, 4h, 4w]`` buffers; conv_hr writes over conv_up2's
-    input, which is free by then."""
-    _, _, h, w = x.shape
-    st = _stream()
-    head0, head1 = reads[0][0], reads[1][0]
-    conv_sb(x, *P["first"], k=3, out=feat0)
-    head0.copy_(feat0)
-    for block in P["body"]:
-        for rdb, (src, dst) in zip(block, ((0, 1), (1, 2), (2, 1))):
-            R, W = reads[src], writes[src]
-            for k in range(4):
-                conv_sb(R[k], *rdb[k], k=3, slope=P["slope32"], out=W[k])
-            conv_sb(R[4], *rdb[4], k=3, residual=R[0], out=reads[dst][0])
-        lib().call("e4s_esr_scale_add", _p(head0), _p(head1), _p(head0), RRDB_FEAT, h * w, st)
-    feat = conv_sb(head0, *P["conv_body"], k=3, residual=feat0, out=head1)                    # feat + conv_body(body(feat))
-    for name, (up, out) in zip(("up1", "up2"), ups):
-        lib().call("e4s_esr_up2", _p(up), _p(feat), RRDB_FEAT, h, w, st)
-        h, w = 2 * h, 2 * w
-        feat = conv_sb(up, *P[name], k=3, slope=P["slope64"], out=out)
-    hr = conv_sb(feat, *P["hr"], k=3, slope=P["slope64"], out=ups[1][0])
-    lib().call("e4s_esr_tail", _p(out_u8), _p(out_f), _p(hr), _p(P["last"][0]), _p(P["last"][1]), 1, h, w, st)
+    _entry, _net = "realesr_forward", _RRDB_NET
 
 
 def _rrdb_run(x, P, want_float, want_u8):
-    """(float32 [bs, 3, 4h, 4w] or None, uint8 [bs, 4h, 4w, 3] or None) of ``x [bs, 3, h, w]``, sample after sample on one sample's scratch, made once."""
-    bs, _, h, w = x.shape
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)             # noqa: E731
-    out_f = new(bs, 3, 4 * h, 4 * w) if want_float else None
-    # the tail kernel always writes its uint8 image; a caller that wants the float output alone gets one sample's worth of it as scratch
-    out_u8 = torch.empty((bs if want_u8 else 1, 4 * h, 4 * w, 3), dtype=torch.uint8, device=x.device)
-    slabs = [new(1, RRDB_SLAB, h, w) for _ in range(3)]
-    # the views the 15 convolutions of an RRDB go through, made here once: convolution k of a dense block reads the slab's first 64 + 32 k planes ...
-    reads = [[S[:, :RRDB_FEAT + k * RRDB_GROW] for k in range(5)] for S in slabs]
-    # ... and (k < 4) writes the 32 planes behind them
-    writes = [[S[:, RRDB_FEAT + k * RRDB_GROW:RRDB_FEAT + (k + 1) * RRDB_GROW] for k in range(4)] for S in slabs]
-    feat0 = new(1, RRDB_FEAT, h, w)
-    ups = [(new(1, RRDB_FEAT, 2 * h, 2 * w), new(1, RRDB_FEAT, 2 * h, 2 * w)), (new(1, RRDB_FEAT, 4 * h, 4 * w), new(1, RRDB_FEAT, 4 * h, 4 * w))]
-    for b in range(bs):
-        _rrdb_sample(P, x[b:b + 1], out_f[b] if want_float else None, out_u8[b if want_u8 else 0], reads, writes, feat0, ups)
-    return out_f, (out_u8 if want_u8 else None)
+    """``ops_rrdb._run`` with ``e4s_esr_tail`` at its end: (float32 [bs, 3, 4h, 4w] or None, uint8 [bs, 4h, 4w, 3] or None) of ``x [bs, 3, h, w]``."""
+    return ops_rrdb._run(x, P, want_float, (4 * x.shape[2], 4 * x.shape[3]) if want_u8 else None, ("e4s_esr_tail", (), ()))
 
 
 def _rrdb_checked_all(name, x, weights):

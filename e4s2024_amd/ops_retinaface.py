@@ -28,7 +28,7 @@ from . import lossnet
 from ._lib import lib
 from .lossnet import bn_fold, conv_sb, weights_key
 from .ops import _Prepared, _c, _p, _stream
-from .ops_recolor import _Net, _cuda_checked, _devices_checked, _tensor_checked, _validated
+from .netweights import _Net, _cuda_checked, _devices_checked, _tensor_checked, _validated
 
 ARITH = "sb3"                                # "sb3": e4s_conv2d_sb3 (fp32-class); "sb": e4s_conv2d_sb (two-way split bf16)
 RETINAFACE_MAX_SIDE = 1500                              # detect resizes a larger image with cv2 first (retinaface_detection.py:67-70): out of scope

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import ops, ops_post, ops_recolor
+from . import netweights, ops, ops_post, ops_recolor
 
 DEFAULT_COMP_INDICES = tuple(sorted(set(range(12)) - {0, 4, 11}))      # face_swap_video_pipeline.py:436: keep target background, hair, ear-rings
 # the two-image caller (Face_swap_with_two_imgs.py:469-472): it also keeps the target's eye glasses (10) and, with colour transfer, its neck and ears
@@ -471,7 +471,7 @@ def realesr_infer_batch(weights, x: torch.Tensor, out_hw=None, in_size: int = ES
     ``in_size`` is the reference's 256."""
     name = "realesr_infer_batch"
     ops_recolor.rrdbnet_weight_tensors(weights, name)
-    ops_recolor._tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image in [-1, 1]")
+    netweights._tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image in [-1, 1]")
     if x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
         raise ValueError(f"{name}: x: expected a float32 [bs, 3, H, W] image in [-1, 1], got {tuple(x.shape)}")
     in_size = _esr_size_checked(name, "in_size", in_size)
@@ -479,7 +479,7 @@ def realesr_infer_batch(weights, x: torch.Tensor, out_hw=None, in_size: int = ES
     if len(out_hw) != 2:
         raise ValueError(f"{name}: out_hw is (height, width), got {out_hw!r}")
     out_hw = (_esr_size_checked(name, "out_hw[0]", out_hw[0]), _esr_size_checked(name, "out_hw[1]", out_hw[1]))
-    ops_recolor._cuda_checked(name, x=x)
+    netweights._cuda_checked(name, x=x)
     small = ops.bilinear_resize((x * 0.5 + 0.5).clamp(0, 1).contiguous(), (in_size, in_size), align_corners=True)
     r = ops.realesr_forward(small, weights)
     if tuple(r.shape[2:]) != out_hw:
@@ -552,18 +552,18 @@ def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_
     copied."""
     name = "gpen_enhance_frames"
     from . import ops_gpen, ops_parsenet
-    ops_recolor._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
+    netweights._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
     if frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
         raise ValueError(f"{name}: frames_u8: expected uint8 [bs, H, W, 3] RGB frames with bs >= 1, got {tuple(frames_u8.shape)}")
-    ops_recolor._cuda_checked(name, frames_u8=frames_u8)
+    netweights._cuda_checked(name, frames_u8=frames_u8)
     if base_u8 is not None:
-        ops_recolor._tensor_checked(name, "base_u8", base_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] frames")
+        netweights._tensor_checked(name, "base_u8", base_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] frames")
         if base_u8.shape != frames_u8.shape or base_u8.device != frames_u8.device:
             raise ValueError(f"{name}: base_u8 is {tuple(base_u8.shape)} on {base_u8.device}: expected the frames' {tuple(frames_u8.shape)} on {frames_u8.device} "
                              "(resizing the frame to a super-resolved size is the caller's)")
     ops_gpen.check_loaded(gpen)
-    S = int(ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
-    structure = ops_recolor._validated(name, parsenet, ops_parsenet._net_of(parsenet))[1]
+    S = int(netweights._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+    structure = netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))[1]
     if ops_parsenet.parsenet_output_size(structure, S, S) != (S, S):
         raise ValueError(f"{name}: the ParseNet turns a {S} x {S} face into a {ops_parsenet.parsenet_output_size(structure, S, S)} mask: expected {S} x {S} "
                          "(the reference resizes the mask with cv2, which is not done here)")
@@ -612,15 +612,15 @@ def gpen_face_enhancement(detector, gpen, parsenet, sr, frames_u8: torch.Tensor,
     ``gpen_enhance_frames`` gives them.  Every argument is checked before any launch."""
     name = "gpen_face_enhancement"
     from . import ops_gpen, ops_gpen_sr
-    ops_recolor._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
+    netweights._tensor_checked(name, "frames_u8", frames_u8, torch.uint8, 4, "uint8 [bs, H, W, 3] RGB frames")
     if frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
         raise ValueError(f"{name}: frames_u8: expected uint8 [bs, H, W, 3] RGB frames with bs >= 1, got {tuple(frames_u8.shape)}")
     if sr is not None:
-        ops_recolor._devices_checked(name, "frames_u8", frames_u8, ops_gpen_sr.gpen_sr_weight_tensors(sr, name))
-    ops_recolor._cuda_checked(name, frames_u8=frames_u8)
+        netweights._devices_checked(name, "frames_u8", frames_u8, ops_gpen_sr.gpen_sr_weight_tensors(sr, name))
+    netweights._cuda_checked(name, frames_u8=frames_u8)
     if aligned:
         ops_gpen.check_loaded(gpen)
-        S = int(ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+        S = int(netweights._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
         if tuple(frames_u8.shape[1:3]) != (S, S):
             raise ValueError(f"{name}: aligned faces are {S} x {S}, the generator's size (the reference resizes them with cv2, which is not done here), "
                              f"got {tuple(frames_u8.shape)}")
@@ -631,8 +631,8 @@ def gpen_face_enhancement(detector, gpen, parsenet, sr, frames_u8: torch.Tensor,
         return gpen_enhance_frames(detector, gpen, parsenet, frames_u8, return_faces=return_faces)
     from . import ops_parsenet
     ops_gpen.check_loaded(gpen)                                               # what gpen_enhance_frames refuses, before the RealESRNet pass runs
-    ops_recolor._validated(name, gpen, ops_gpen._net_of(gpen))
-    ops_recolor._validated(name, parsenet, ops_parsenet._net_of(parsenet))
+    netweights._validated(name, gpen, ops_gpen._net_of(gpen))
+    netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))
     img_sr = gpen_super_resolve(sr, frames_u8)
     resized = ops.cv_resize_linear(frames_u8, (img_sr.shape[2], img_sr.shape[1]))
     return gpen_enhance_frames(detector, gpen, parsenet, resized, base_u8=img_sr, return_faces=return_faces)

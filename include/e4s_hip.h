@@ -939,7 +939,7 @@ E4S_API int e4s_gpen_paste_u8(uint8_t* out, float* full_mask, const uint8_t* bas
                               const int* flags, const int* face_begin, int n, int bs, int H, int W, int S, void* stream);
 
 /* f16: GPEN face enhancement, stage 5 — the ends of the RealESRNet pass (swap_face_fine/gpen/sr_model/real_esrnet.py:26-60 RealESRNet.process around
- * rrdbnet_arch.py:64-116 RRDBNet; csrc/gpen_sr.hip) and the resize of the frame to the super-resolved size (face_enhancement.py:66).  The network's convolutions run
+ * rrdbnet_arch.py:64-116 RRDBNet; csrc/gpen_sr.hip, the tail on csrc/rrdb.hip) and the resize of the frame to the super-resolved size (face_enhancement.py:66).  The network's convolutions run
  * on e4s_conv2d_sb3, its glue on e4s_esr_scale_add and e4s_esr_up2.
  *   e4s_gsr_input           : uint8 img [bs][H][W][3] -> out [bs][3 r r][(H + ph) / r][(W + pw) / r], r = 1, 2 or 4: v / 255 as a correctly rounded float32 division,
  *                             colour c from byte 2 - c with bgr (byte c without), the reflect pad of ph = (-H) mod r rows and pw = (-W) mod r columns at the

@@ -1,4 +1,4 @@
-"""Row f16 on the device: the three kernels of csrc/gpen_sr.hip alone, ``ops.gpen_sr_forward`` / ``gpen_sr_image`` / ``cv_resize_linear`` against
+"""Row f16 on the device: its three kernels (csrc/gpen_sr.hip, the tail on csrc/rrdb.hip) alone, ``ops.gpen_sr_forward`` / ``gpen_sr_image`` / ``cv_resize_linear`` against
 tests/gpen_sr_model.py on the cases of g27_gpen_sr.npz, and ``pipeline.gpen_face_enhancement`` with the drop-in ``FaceEnhancement`` against the composition of
 their pieces and against what the reference's ``process`` gave.  Small shapes throughout: each test takes seconds.
 

@@ -119,16 +119,32 @@ def _tail(x, w, b, out_f=True, off=False):
     return u8, f
 
 
+def _tail_inputs(H, W, bs=2):
+    # (a 1 x 1 image fills one tap of nine: three times the input for the same spread of the output)
+    x = T(seeded.seeded_array(5, "esr.tail.x", (bs, 64, H, W), 0.0, 3.0 if H * W == 1 else 1.0, "normal")).to(DEV)
+    w = seeded.seeded_array(5, "esr.tail.w", (3, 64, 3, 3), 0.0, 0.25 / np.sqrt(576.0), "normal")
+    return x, w, np.array([0.5, 0.45, 0.55], dtype=np.float32)
+
+
+@pytest.mark.parametrize("H,W", [(5, 7), (16, 64), (20, 68), (67, 130)])
+def test_both_tails_run_one_tile(H, W):
+    """``e4s_esr_tail`` and ``e4s_gsr_tail`` at 64 channels without crop or flip: the same float output bit for bit (5 x 7 and 67 x 130 in the one-element form,
+    16 x 64 one whole tile, 20 x 68 the vector form with a ragged tile), and two uint8 images, since the two ends differ."""
+    x, w, b = _tail_inputs(H, W)
+    w, b = T(w).to(DEV), T(b).to(DEV)
+    esr_u8, esr_f = _tail(x, w, b)
+    gsr_u8, gsr_f = torch.empty_like(esr_u8), torch.empty_like(esr_f)
+    lib().call("e4s_gsr_tail", _p(gsr_u8), _p(gsr_f), _p(x), _p(w), _p(b), x.shape[0], 64, H, W, H, W, 0, _stream())
+    assert torch.equal(esr_f, gsr_f)
+    assert not torch.equal(esr_u8, gsr_u8)
+
+
 @pytest.mark.parametrize("H,W", [(1, 1), (5, 7), (67, 130), (16, 64), (20, 68)])
 def test_tail_against_float64(H, W):
     """The float output within (577 + 1) 2^-24 max(sum |w x| + |b|) of float64; the uint8 image by the uint8 rule, its ``e32`` the same sum in float32 in the
     kernel's documented order (``rrdb_model.tail_f32``); the form at a 4-byte offset and the call without the float output give the same bits.  67 x 130
     spans tiles in both directions, 16 x 64 is one whole tile, 20 x 68 has a multiple-of-four width that is no multiple of the tile."""
-    bs = 2
-    # (a 1 x 1 image fills one tap of nine: three times the input for the same spread of the output)
-    x = T(seeded.seeded_array(5, "esr.tail.x", (bs, 64, H, W), 0.0, 3.0 if H * W == 1 else 1.0, "normal")).to(DEV)
-    w = seeded.seeded_array(5, "esr.tail.w", (3, 64, 3, 3), 0.0, 0.25 / np.sqrt(576.0), "normal")
-    b = np.array([0.5, 0.45, 0.55], dtype=np.float32)
+    x, w, b = _tail_inputs(H, W)
     m = RM.tail(x.cpu().numpy(), w, b)
     u8, f = _tail(x, T(w).to(DEV), T(b).to(DEV))
     err = RM.max_err(f.cpu().numpy(), m["r"])
@@ -154,6 +170,16 @@ def test_network_against_the_float64_model(tag):
     print(f"{tag}: kernels against float64 {err:.3e} = {err / c['e32']:.2f} e32, e32 {c['e32']:.3e}, bound {bound:.3e}")
     record_parity("rrdb.worst_err_over_e32", _WORST["ratio"], RM.MARGIN, "realesr_forward against the float64 model, in units of the float32 model's own error")
     assert err <= bound
+
+
+@pytest.mark.parametrize("tag", ["b2.12x20", "b1.5x3"])
+def test_realesr_forward_is_gpen_sr_forward_at_width_64_and_scale_4(tag):
+    """Rows f11 and f16 run one network: on the same weights the two public calls give the same bits, for one sample and for a batch of two."""
+    c = RM.case(tag)
+    net = _net(c["sd"], tag)
+    for x in (T(c["x"]), T(RM.images01(12, 2, 6, 10))):
+        x = x.to(DEV)
+        assert torch.equal(ops.realesr_forward(x, net), ops.gpen_sr_forward(x, net))
 
 
 def test_batch_runs_mappings_and_empty_batches():

@@ -33,6 +33,15 @@ def test_mirror_has_the_keys_of_the_checkpoint():
         ops.RRDBNet(0)
 
 
+@pytest.mark.parametrize("nb", [1, 2])
+def test_mirror_is_the_gpen_sr_mirror_at_width_64_and_scale_4(nb):
+    """Rows f11 and f16 run one network: the same keys and shapes in the same order, and one module's weights load into the other."""
+    from e4s2024_amd import ops
+    assert list(ops.rrdbnet_state_dict_shapes(nb).items()) == list(ops.gpen_sr_state_dict_shapes(nb, 64, 4).items())
+    if nb == 1:
+        ops.GpenSRNet(1, 64, 4).load_state_dict(ops.RRDBNet(1).state_dict(), strict=True)
+
+
 def test_seeded_weights_depend_on_the_seed_alone():
     from e4s2024_amd import seeded
     assert "seeded_rrdbnet_state_dict" in seeded.__all__
