@@ -199,6 +199,8 @@ extern "C" int e4s_conv3x3_mx(float* out, const float* x, const void* wmx, int a
 }
 
 int e4s::launch_modconv_mx(SbParams& p, int arith, hipStream_t st, float* workspace, int64_t workspace_floats, bool plain_conv) {
+    if ((int64_t)p.h * p.w * 4 > MX_PLANE_MAX_BYTES)       // the patch loads' buffer descriptors (mx_plane_load)
+        return fail(E4S_ERR_ARG, "%s: a channel plane of %d x %d is more than 2^31 - 1 bytes", plain_conv ? "conv3x3_mx" : "region_modconv3x3_mx", p.h, p.w);
     p.tiles_x = cdiv(p.w, C::TW);
     p.tiles_y = cdiv(p.h, C::TH);
     const int npar = p.up ? 4 : 1;

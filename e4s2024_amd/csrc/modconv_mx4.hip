@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void prep_weights_mx4_kernel(unsigned char* __
 __device__ __forceinline__ void q_tile_body(const SbParams& p, unsigned char* lds_raw, const int tile, const int cotile, const int b, const int c_own) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 7;        // ("& 7": see mx_tile_body — of the 52 pieces of a row only the last four need a test)
     const int l5 = lane & 31, khalf = lane >> 5;
     const int y0 = (tile / p.tiles_x) * CQ::TH, x0 = (tile % p.tiles_x) * CQ::TW;
     const int co0 = cotile * Q_TN;
@@ -132,22 +132,22 @@ __device__ __forceinline__ void q_tile_body(const SbParams& p, unsigned char* ld
     const int ppy = tid / CQ::PW, ppx = tid - ppy * CQ::PW;
     const int pgy = y0 - 1 + ppy, pgx = x0 - 1 + ppx;
     const bool p_in = tid < CQ::PATCH && pgy >= 0 && pgy < p.h && pgx >= 0 && pgx < p.w;
-    const int goffs = p_in ? pgy * p.w + pgx : 0;
+    const unsigned voff = p_in ? (unsigned)(pgy * p.w + pgx) * 4u : MX_VOFF_NONE;      // (mx_plane_load, modconv_mx_tile.h: lanes without a patch pixel load zeros)
+    const float* xbu = mx_uniform_ptr(xb);
+    const int plane_bytes = __builtin_amdgcn_readfirstlane(hw * 4);
     const int s_r = tid / CKS < p.nreg ? tid / CKS : p.nreg - 1, s_c = tid % CKS;
-    auto load_x = [&](int chunk, int hf) __attribute__((always_inline)) {       // (unconditional loads from clamped addresses: see modconv_mx.hip)
-        const int ci0 = chunk * CKS;
-        const int cmax = p.cin - 1 - ci0;
+    auto load_x = [&](int chunk, int hf) __attribute__((always_inline)) {       // (unconditional loads through the planes' buffer descriptors: see modconv_mx_tile.h)
+        const int ci0 = chunk * CKS;                 // (cin % CKS == 0: the launcher requires it)
         if (wave < (CQ::PATCH + 63) / 64) {
+            const float* plane = xbu + (size_t)(ci0 + 8 * hf) * hw;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) xr[c] = xb[(size_t)(ci0 + (8 * hf + c < cmax ? 8 * hf + c : cmax)) * hw + goffs];
+            for (int c = 0; c < 8; ++c, plane += hw) xr[c] = mx_plane_load(plane, plane_bytes, voff);
         }
-        if (hf == 0) sr = sb[(size_t)s_r * p.cin + ci0 + (s_c < cmax ? s_c : cmax)];
+        if (hf == 0) sr = sb[(size_t)s_r * p.cin + ci0 + s_c];
     };
     auto store_x = [&](int buf, int chunk, int hf) __attribute__((always_inline)) {
         float4* xf4 = reinterpret_cast<float4*>(lds_raw + Q_PATCH0 + buf * Q_PATCHB);
         if (tid < CQ::PATCH) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) xr[c] = p_in ? xr[c] : 0.f;
 #pragma unroll
             for (int k = 0; k < 2; ++k) xf4[(2 * hf + k) * Q_PSTRIDE + tid] = make_float4(xr[4 * k], xr[4 * k + 1], xr[4 * k + 2], xr[4 * k + 3]);
         }
@@ -369,6 +369,7 @@ extern "C" int e4s_region_upconv_mx4(float* out, const float* x, const void* wmx
     E4S_REQUIRE(out && x && wmx4 && wmx && s && labels, "region_upconv_mx4: null tensor");
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= CKS && cin % CKS == 0 && cout >= 128 && cout % 128 == 0 && h >= 1 && w >= 32,
                 "region_upconv_mx4: bad size (cin %% 16 == 0, cout %% 128 == 0, width >= 32)");
+    E4S_REQUIRE((int64_t)h * w * 4 <= MX_PLANE_MAX_BYTES, "region_upconv_mx4: a channel plane of %d x %d is more than 2^31 - 1 bytes", h, w);      // (mx_plane_load)
     E4S_REQUIRE(nreg >= 1 && nreg <= E4S_MAX_REGIONS && lh >= 1 && lw >= 1, "region_upconv_mx4: bad region map");
     E4S_REQUIRE(!noise || (noise_weight && (noise_bs == 1 || noise_bs == bs)), "region_upconv_mx4: noise needs its weight and batch 1 or bs");
     E4S_REQUIRE((((uintptr_t)wmx4 | (uintptr_t)wmx | (uintptr_t)out) & 15) == 0 && (!noise || ((uintptr_t)noise & 7) == 0),

@@ -70,6 +70,8 @@ __device__ __forceinline__ void mx_prep_pair(f32x2 x, f32x2 s, unsigned& v1, uns
 }
 // This lane's eight modulation values of a chunk (its region's row of the table, channels 8 khalf .. + 7; zeros for a pixel without a region) as four register pairs:
 // two 16-byte reads from a clamped row and eight selects — the per-value `cls >= 0 ? ss[..] : 0` form became eight 4-byte reads, each under its own exec mask.
+// (A ZERO ROW behind the table for the pixels without a region — two reads and no select — was built and measured: the three masked kernels of a one-stream step
+// took 7 - 10 us MORE with it than with the selects, same box and session; profiles/mxstage_ab.txt.)
 __device__ __forceinline__ void mx_load_sv(const float* ss, int cls, int khalf, f32x2 (&sv)[4]) {
     const f32x4* row = reinterpret_cast<const f32x4*>(ss + (cls >= 0 ? cls : 0) * CKS + khalf * 8);
     const f32x4 lo = row[0], hi = row[1];
@@ -78,6 +80,24 @@ __device__ __forceinline__ void mx_load_sv(const float* ss, int cls, int khalf, 
     sv[1] = (f32x2){on ? lo[2] : 0.f, on ? lo[3] : 0.f};
     sv[2] = (f32x2){on ? hi[0] : 0.f, on ? hi[1] : 0.f};
     sv[3] = (f32x2){on ? hi[2] : 0.f, on ? hi[3] : 0.f};
+}
+
+// The activation patch is loaded through buffer descriptors, one per channel PLANE of the sample (base = the plane, num_records = its h * w * 4 bytes, built from
+// wave-uniform values only: the channel steps on the scalar side), with ONE per-lane 32-bit byte offset that does not change from chunk to chunk.  A lane that owns
+// no in-image patch pixel (outside the image, or a thread beyond the patch) carries MX_VOFF_NONE: beyond every plane's range, so the hardware's range check returns
+// 0 for it — the padding of the convolution — without reading memory.  (Before: a 64-bit address per channel and chunk, v_lshl_add_u64 each, a clamped valid address
+// for such lanes and a select per staged value to zero what they read.)  The range check compares offset + 4 with num_records: a plane of more than 2^31 - 1 bytes
+// cannot be addressed this way (MX_PLANE_MAX_BYTES: the launchers refuse it by name).
+constexpr unsigned MX_VOFF_NONE = 0x80000000u;
+constexpr long long MX_PLANE_MAX_BYTES = 0x7fffffffll;
+__device__ __forceinline__ const float* mx_uniform_ptr(const float* q) {          // a pointer the compiler may keep in SGPRs (the descriptor must be wave-uniform to it)
+    const unsigned long long a = reinterpret_cast<unsigned long long>(q);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ float mx_plane_load(const float* plane, int plane_bytes, unsigned voff) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(plane), 0, plane_bytes, 0x00020000);
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, 0, 0));
 }
 
 // "This value exists HERE": an empty asm that claims to rewrite the register(s).  The two-phase loop needs it — LLVM sinks pure conversions to their first
@@ -142,7 +162,9 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: DMA destinations (M0) and the piece loop stay in SGPRs
+    // scalar: DMA destinations (M0) and the piece loop stay in SGPRs.  "& 7" (512 threads: a no-op) lets hipcc see that only a row's LAST piece needs a test
+    // (dma_row): unbounded, every piece's `piece < NPIECE` was a wave-uniform condition kept as a lane mask and passed through a VGPR at each use in the K loop
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 7;
     const int l5 = lane & 31, khalf = lane >> 5;
 
     const int pa = par >> 1, pb_ = par & 1;
@@ -201,25 +223,26 @@ __device__ __forceinline__ void mx_tile_body(const SbParams& p, unsigned char* l
     const int ppy = tid / C::PW, ppx = tid - ppy * C::PW;
     const int pgy = y0 - 1 + ppy, pgx = x0 - 1 + ppx;
     const bool p_in = tid < C::PATCH && pgy >= 0 && pgy < p.h && pgx >= 0 && pgx < p.w;
-    const int goffs = p_in ? pgy * p.w + pgx : 0;
+    const unsigned voff = p_in ? (unsigned)(pgy * p.w + pgx) * 4u : MX_VOFF_NONE;      // (mx_plane_load)
+    const float* xbu = mx_uniform_ptr(xb);
+    const int plane_bytes = __builtin_amdgcn_readfirstlane(hw * 4);
     const int s_r = tid / CKS < p.nreg ? tid / CKS : p.nreg - 1, s_c = tid % CKS;
     auto load_x = [&](int chunk) __attribute__((always_inline)) {       // next chunk's patch pixel (16 channels) and modulation table entry
         // Unconditional, branch-free loads (as modconv_sb.hip learned): a load under a per-lane condition, or a register that is also written by a plain
-        // move (`sr = cond ? load : 0`), makes hipcc wait vmcnt(0) right behind the issue — the whole latency exposed once per chunk.  Out-of-range
-        // lanes read a clamped valid address and are zeroed when the chunk is written to LDS; waves 6 and 7 own no patch pixel (wave-uniform branch).
+        // move (`sr = cond ? load : 0`), makes hipcc wait vmcnt(0) right behind the issue — the whole latency exposed once per chunk.  Lanes without an
+        // in-image patch pixel get their zeros from the buffer range check (mx_plane_load); waves 6 and 7 own no patch pixel (wave-uniform branch).
+        // (every launcher of this tile requires cin % CKS == 0: a chunk's 16 channels all exist)
         const int ci0 = chunk * CKS;
-        const int cmax = p.cin - 1 - ci0;
         if (wave < (C::PATCH + 63) / 64) {
+            const float* plane = xbu + (size_t)ci0 * hw;
 #pragma unroll
-            for (int c = 0; c < CKS; ++c) xr[c] = xb[(size_t)(ci0 + (c < cmax ? c : cmax)) * hw + goffs];
+            for (int c = 0; c < CKS; ++c, plane += hw) xr[c] = mx_plane_load(plane, plane_bytes, voff);
         }
-        if constexpr (!ENC) sr = sb[(size_t)s_r * p.cin + ci0 + (s_c < cmax ? s_c : cmax)];
+        if constexpr (!ENC) sr = sb[(size_t)s_r * p.cin + ci0 + s_c];
     };
     auto store_x = [&](int buf, int chunk) __attribute__((always_inline)) {     // the staged chunk -> patch buffer `buf` in the K loop's operand form
         float4* xf4 = reinterpret_cast<float4*>(lds_raw + L::PATCH0 + buf * MX_PATCHB);
         if (tid < C::PATCH) {
-#pragma unroll
-            for (int c = 0; c < CKS; ++c) xr[c] = p_in ? xr[c] : 0.f;
             if constexpr (ENC) {  // instance norm on load: this sample's statistics from the table staged in LDS at kernel start (mean 0 / rstd 1 without),
                                   // read as wave-uniform float4s — as global loads they were 32 vector-memory requests per chunk inside the K loop
                 const float4* nm = reinterpret_cast<const float4*>(lds_raw + L::BYTES) + chunk * (CKS / 4);
