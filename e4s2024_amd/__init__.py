@@ -12,7 +12,8 @@ Layout
                  ``swap_face_fine/gpen/face_model/gpen_model.py``, ``swap_face_fine/gpen/face_parse/parse_model.py``,
                  ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``,
                  ``swap_face_fine/gpen/align_faces.py``, ``swap_face_fine/gpen/sr_model/rrdbnet_arch.py``,
-                 ``swap_face_fine/gpen/sr_model/real_esrnet.py``, ``swap_face_fine/gpen/face_enhancement.py``)
+                 ``swap_face_fine/gpen/sr_model/real_esrnet.py``, ``swap_face_fine/gpen/face_enhancement.py``,
+                 ``swap_face_fine/face_vid2vid/modules/keypoint_detector.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -113,10 +114,16 @@ GPEN_SR_OVERRIDES = {
     "swap_face_fine.gpen.face_enhancement": "swap_face_fine/gpen/face_enhancement.py",
 }
 
+# row f17: face-vid2vid reenactment, stage 1: KPDetector and HEEstimator (drive_demo.py imports them from it).  ``sync_batchnorm`` and ``modules.util`` are not
+# redirected: the drop-in imports neither
+REENACT_KP_OVERRIDES = {
+    "swap_face_fine.face_vid2vid.modules.keypoint_detector": "swap_face_fine/face_vid2vid/modules/keypoint_detector.py",
+}
+
 
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
-            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES}
+            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES, **REENACT_KP_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -136,7 +143,8 @@ def install(force: bool = False) -> str:
     """Redirect the hot-path module names (``OVERRIDES``), the loss networks' (``LOSS_OVERRIDES``) and the recolouring modules' (``RECOLOR_OVERRIDES``,
     ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
     face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``), GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) and
-    GPEN's RealESRNet pass with ``FaceEnhancement`` itself (``GPEN_SR_OVERRIDES``) to the drop-in files.
+    GPEN's RealESRNet pass with ``FaceEnhancement`` itself (``GPEN_SR_OVERRIDES``) and face-vid2vid's keypoint detector and head-pose estimator
+    (``REENACT_KP_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

@@ -18,6 +18,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_retinaface`` row f14: GPEN face enhancement, stage 3 — the RetinaFace detector (resolved on first use too)
 * ``ops_gpen_paste`` row f15: GPEN face enhancement, stage 4 — align, feather and paste around the three networks (resolved on first use too)
 * ``ops_gpen_sr`` row f16: GPEN face enhancement, stage 5 — the RealESRNet pass and cv2's linear resize (resolved on first use too)
+* ``ops_reenact`` row f17: face-vid2vid reenactment, stage 1 — KPDetector, HEEstimator and keypoint_transformation (resolved on first use too)
 """
 from __future__ import annotations
 
@@ -1405,7 +1406,7 @@ def __getattr__(name):        # PEP 562
     import importlib
     import sys
     if not name.startswith("__"):
-        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr"):
+        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr", "ops_reenact"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

@@ -1,0 +1,783 @@
+"""Row f17: face-vid2vid reenactment, stage 1 — everything that turns images into the two keypoint sets the generator consumes: ``KPDetector`` and
+``HEEstimator`` of swap_face_fine/face_vid2vid/modules/keypoint_detector.py (with the blocks of modules/util.py) in eval mode, and ``keypoint_transformation``
+with ``headpose_pred_to_degree`` and ``get_rotation_matrix`` of drive_demo.py:67-180.
+
+    KPDetector     e4s_v2v_antialias_down (pad, 13 x 13 Gaussian and [::4, ::4] in one pass, exact float32)
+                   DownBlock2d: conv 3 x 3 + folded BatchNorm + ReLU (the 3-channel first one on the exact e4s_conv2d, the others on e4s_conv2d_sb3), e4s_avgpool2x2
+                   the 1 x 1 convolution on e4s_conv2d_sb3; its output [bs, C D, h, w] IS the volume [bs, C, D, h, w]
+                   UpBlock3d: e4s_conv3d_sb3 with up_hw = 2 (the nearest (1, 2, 2) upsampling is in the gather), BatchNorm folded in float64, ReLU
+                   the kp (and jacobian) heads: e4s_conv3d_sb3 with bias; e4s_v2v_heatmap_kp: softmax(logit / temperature) over the volume and its expectations
+    HEEstimator    conv1 7 x 7 stride 2 on the exact e4s_conv2d + folded BatchNorm + ReLU, e4s_maxpool3x3s2, every 1 x 1 / 3 x 3 convolution on e4s_conv2d_sb3 with
+                   its bias and BatchNorm folded in float64, ReLU and the residual add fused; e4s_plane_stats as the global average pool; the five linear heads as
+                   one e4s_vec_fc (exact float32 products)
+    transformation e4s_v2v_kp_transform: degrees, rotation matrix, transformed keypoints and Jacobians in one launch per batch
+
+The reference's oddities are kept: ``yaw = fc_roll(out)`` and ``roll = fc_yaw(out)``, degrees ``sum(p idx) 3 - 99``, radians through 3.14, ``rot = pitch_mat
+yaw_mat roll_mat``.  One difference: the reference's ``keypoint_transformation`` reshapes the caller's ``he['t']`` in place to ``[bs, 1, 3]`` (``unsqueeze_``);
+here ``he`` is left as it was.
+
+Forward only; no host synchronisation; the same inputs give the same bits; after one eager call (which prepares the weights) a call captures in a graph."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import lossnet
+from ._lib import lib
+from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
+from .ops import _Prepared, _c, _p, _stream
+from .netweights import _Net, _cuda_checked, _devices_checked, _tensor_checked, _validated
+
+NUM_BINS = 66                                # headpose_pred_to_degree's idx_tensor is range(66) whatever the module's num_bins
+
+
+# ------------------------------------------------------------------------------------------------ configuration arithmetic
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def antialias_kernel(scale_factor) -> torch.Tensor:
+    """``AntiAliasInterpolation2d(channels, scale).weight[0, 0]``: sigma = (1 / scale - 1) / 2, k = 2 round(4 sigma) + 1, the normalised float32 Gaussian."""
+    sigma = (1 / scale_factor - 1) / 2
+    k = 2 * round(sigma * 4) + 1
+    ax = torch.arange(k, dtype=torch.float32)
+    g = torch.exp(-(ax - (k - 1) / 2) ** 2 / (2 * sigma ** 2))
+    kernel = g[:, None] * g[None, :]                 # the reference multiplies the two meshgrid factors into 1: rows first
+    return kernel / torch.sum(kernel)
+
+
+def kp_detector_structure(block_expansion=32, num_kp=15, image_channel=3, max_features=1024, reshape_channel=16384, reshape_depth=16, num_blocks=5,
+                          estimate_jacobian=False, scale_factor=0.25, single_jacobian_map=False):
+    """The constructor arithmetic of ``KPDetector`` / ``KPHourglass`` as ``(image_channel, down widths, reshape_depth, up widths, num_kp, jacobian maps,
+    anti-alias kernel size or 0, its stride)``; refuses what the native path does not implement."""
+    if not all(_is_int(v) for v in (block_expansion, num_kp, image_channel, max_features, reshape_channel, reshape_depth, num_blocks)):
+        raise ValueError("KPDetector: block_expansion, num_kp, image_channel, max_features, reshape_channel, reshape_depth and num_blocks are ints")
+    if min(block_expansion, num_kp, max_features, reshape_channel, reshape_depth, num_blocks) < 1:
+        raise ValueError("KPDetector: widths, depths and counts are positive")
+    if image_channel != 3:
+        raise ValueError(f"KPDetector: image_channel {image_channel} is not implemented: the native network takes three colour channels")
+    if single_jacobian_map:
+        raise ValueError("KPDetector: single_jacobian_map=True is not implemented: the native path keeps one Jacobian map per keypoint")
+    inv = 1.0 / float(scale_factor) if scale_factor and scale_factor > 0 else 0.0
+    if inv < 1 or abs(inv - round(inv)) > 1e-9:
+        raise ValueError(f"KPDetector: scale_factor {scale_factor!r} is not implemented: its inverse must be an integer (1, 0.5, 0.25, ...)")
+    width = lambda i: min(max_features, block_expansion * 2 ** i)      # noqa: E731
+    if reshape_channel != reshape_depth * width(num_blocks):
+        raise ValueError(f"KPDetector: reshape_channel {reshape_channel} breaks reshape_channel == reshape_depth * min(max_features, block_expansion * "
+                         f"2 ** num_blocks) = {reshape_depth} * {width(num_blocks)}: the 1 x 1 convolution's output is reshaped to that volume")
+    if reshape_depth < 2:
+        raise ValueError(f"KPDetector: reshape_depth {reshape_depth}: every extent of the final volume must be at least 2 (the coordinate grid divides by n - 1)")
+    down = tuple(width(i + 1) for i in range(num_blocks))
+    up = tuple(width(num_blocks - i - 1) for i in range(num_blocks))
+    s = int(round(inv))
+    k = 0 if s == 1 else 2 * round((s - 1) / 2 * 4) + 1
+    return int(image_channel), down, int(reshape_depth), up, int(num_kp), int(num_kp) if estimate_jacobian else 0, int(k), s
+
+
+def kp_volume_size(structure, H: int, W: int):
+    """(D, H', W') of the heatmap volume for an H x W input."""
+    _, down, depth, up, _, _, k, s = structure
+    if k:
+        H, W = -(-H // s), -(-W // s)
+    for _ in down:
+        H, W = H // 2, W // 2
+    return depth, H * 2 ** len(up), W * 2 ** len(up)
+
+
+# ------------------------------------------------------------------------------------------------ the modules: the reference's keys, a stock-PyTorch forward
+class _DownBlock2d(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, 3, padding=1)
+        self.norm = nn.BatchNorm2d(cout, affine=True)
+
+    def forward(self, x):
+        return F.avg_pool2d(F.relu(self.norm(self.conv(x))), 2)
+
+
+class _UpBlock3d(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = nn.Conv3d(cin, cout, 3, padding=1)
+        self.norm = nn.BatchNorm3d(cout, affine=True)
+
+    def forward(self, x):
+        return F.relu(self.norm(self.conv(F.interpolate(x, scale_factor=(1, 2, 2)))))
+
+
+class _KPHourglass(nn.Module):
+    def __init__(self, structure):
+        super().__init__()
+        cin, down, depth, up, _, _, _, _ = structure
+        self.down_blocks = nn.Sequential()
+        for i, c in enumerate(down):
+            self.down_blocks.add_module(f"down{i}", _DownBlock2d(cin if i == 0 else down[i - 1], c))
+        self.conv = nn.Conv2d(down[-1], depth * down[-1], 1)
+        self.up_blocks = nn.Sequential()
+        for i, c in enumerate(up):
+            self.up_blocks.add_module(f"up{i}", _UpBlock3d(down[-1] if i == 0 else up[i - 1], c))
+        self.reshape_depth, self.out_filters = depth, up[-1]
+
+    def forward(self, x):
+        out = self.conv(self.down_blocks(x))
+        bs, c, h, w = out.shape
+        return self.up_blocks(out.view(bs, c // self.reshape_depth, self.reshape_depth, h, w))
+
+
+class _AntiAlias(nn.Module):
+    """``AntiAliasInterpolation2d(channels, scale)``: its buffer ``weight [channels, 1, k, k]``."""
+
+    def __init__(self, channels, scale):
+        super().__init__()
+        kernel = antialias_kernel(scale)
+        self.register_buffer("weight", kernel.view(1, 1, *kernel.shape).repeat(channels, 1, 1, 1))
+        self.groups, self.stride, self.pad = channels, int(round(1 / scale)), kernel.shape[0] // 2
+
+    def forward(self, x):
+        out = F.conv2d(F.pad(x, (self.pad,) * 4), self.weight, groups=self.groups)
+        return out[:, :, ::self.stride, ::self.stride]
+
+
+class _Loadable(nn.Module):
+    """Random weights until ``load_state_dict`` has filled the module: the native entries refuse it before."""
+    _PROBE = ()
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        if all(k in state_dict for k in self._PROBE):
+            self._loaded = True
+        return out
+
+
+class KPDetector(_Loadable):
+    """``KPDetector(block_expansion, feature_channel, num_kp, image_channel, max_features, reshape_channel, reshape_depth, num_blocks, temperature,
+    estimate_jacobian, scale_factor, single_jacobian_map)`` of swap_face_fine/face_vid2vid/modules/keypoint_detector.py with its ``state_dict`` keys, shapes and
+    order; the defaults are the upstream ``vox-256.yaml`` (75 tensors, the buffer ``down.weight`` included; ``checkpoint['kp_detector']`` loads with
+    ``strict=True``).  ``forward`` is the plain PyTorch composition in eval mode, returning ``{'value'[, 'jacobian']}`` — what the tests compare
+    ``kp_detector_forward`` with; ``kp_detector_forward(x, module)`` runs the same weights on the HIP kernels.  Refused with ``ValueError``:
+    ``single_jacobian_map=True``, a ``scale_factor`` whose inverse is no integer, a ``reshape_channel`` other than ``reshape_depth * min(max_features,
+    block_expansion * 2 ** num_blocks)``, ``reshape_depth < 2``, ``image_channel != 3``."""
+    _PROBE = ("predictor.conv.weight", "kp.weight")
+
+    def __init__(self, block_expansion=32, feature_channel=32, num_kp=15, image_channel=3, max_features=1024, reshape_channel=16384, reshape_depth=16,
+                 num_blocks=5, temperature=0.1, estimate_jacobian=False, scale_factor=0.25, single_jacobian_map=False):
+        super().__init__()
+        self.structure = kp_detector_structure(block_expansion, num_kp, image_channel, max_features, reshape_channel, reshape_depth, num_blocks,
+                                               estimate_jacobian, scale_factor, single_jacobian_map)
+        if not float(temperature) > 0:
+            raise ValueError(f"KPDetector: temperature {temperature!r} must be positive")
+        self.predictor = _KPHourglass(self.structure)
+        self.kp = nn.Conv3d(self.predictor.out_filters, num_kp, 3, padding=1)
+        if estimate_jacobian:
+            self.num_jacobian_maps = num_kp
+            self.jacobian = nn.Conv3d(self.predictor.out_filters, 9 * num_kp, 3, padding=1)
+            self.jacobian.weight.data.zero_()
+            self.jacobian.bias.data.copy_(torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1] * num_kp, dtype=torch.float))
+        else:
+            self.jacobian = None
+        self.temperature, self.scale_factor = temperature, scale_factor
+        if self.structure[6]:
+            self.down = _AntiAlias(image_channel, scale_factor)
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("KPDetector: training mode is not implemented; call .eval()")
+        with torch.no_grad():
+            if self.structure[6]:
+                x = self.down(x)
+            feature_map = self.predictor(x)
+            prediction = self.kp(feature_map)
+            bs, K, D, H, W = prediction.shape
+            if min(D, H, W) < 2:
+                raise ValueError(f"KPDetector: the final volume is {D} x {H} x {W}: every extent must be at least 2")
+            heatmap = F.softmax(prediction.view(bs, K, -1) / self.temperature, dim=2).view(bs, K, D, H, W)
+            ax = lambda n: 2 * (torch.arange(n).type(heatmap.type()) / (n - 1)) - 1      # noqa: E731
+            grid = torch.stack((ax(W).view(1, 1, W).expand(D, H, W), ax(H).view(1, H, 1).expand(D, H, W), ax(D).view(D, 1, 1).expand(D, H, W)), 3)
+            out = {"value": (heatmap.unsqueeze(-1) * grid[None, None]).sum(dim=(2, 3, 4))}
+            if self.jacobian is not None:
+                jm = self.jacobian(feature_map).reshape(bs, K, 9, D, H, W)
+                out["jacobian"] = (heatmap.unsqueeze(2) * jm).view(bs, K, 9, -1).sum(dim=-1).view(bs, K, 3, 3)
+            return out
+
+
+class _ResBottleneck(nn.Module):
+    def __init__(self, c, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(c, c // 4, 1)
+        self.conv2 = nn.Conv2d(c // 4, c // 4, 3, padding=1, stride=stride)
+        self.conv3 = nn.Conv2d(c // 4, c, 1)
+        self.norm1 = nn.BatchNorm2d(c // 4, affine=True)
+        self.norm2 = nn.BatchNorm2d(c // 4, affine=True)
+        self.norm3 = nn.BatchNorm2d(c, affine=True)
+        self.stride = stride
+        if stride != 1:
+            self.skip = nn.Conv2d(c, c, 1, stride=stride)
+            self.norm4 = nn.BatchNorm2d(c, affine=True)
+
+    def forward(self, x):
+        out = F.relu(self.norm1(self.conv1(x)))
+        out = F.relu(self.norm2(self.conv2(out)))
+        out = self.norm3(self.conv3(out))
+        if self.stride != 1:
+            x = self.norm4(self.skip(x))
+        return F.relu(out + x)
+
+
+# the stages of HEEstimator in key order: (1 x 1 widening convolution + norm, its width), the strided block, the group of stride-1 blocks (name, letter, count)
+_HE_STAGES = ((("conv3", "norm3", 512), "block2", ("block3", "b3_", 3)), (("conv4", "norm4", 1024), "block4", ("block5", "b5_", 5)),
+              (("conv5", "norm5", 2048), "block6", ("block7", "b7_", 2)))
+_HE_HEADS = ("fc_roll", "fc_pitch", "fc_yaw", "fc_t", "fc_exp")
+
+
+class HEEstimator(_Loadable):
+    """``HEEstimator(block_expansion, feature_channel, num_kp, image_channel, max_features, num_bins, estimate_jacobian)`` of keypoint_detector.py:85-178 with
+    its keys (402 tensors at the upstream configuration); the widths 256 .. 2048 are the reference's constants, only ``conv1`` follows ``block_expansion``.
+    ``forward`` is the plain PyTorch composition in eval mode, returning ``{'yaw', 'pitch', 'roll', 't', 'exp'}`` with the reference's crossed heads
+    (``yaw = fc_roll(out)``, ``roll = fc_yaw(out)``)."""
+    _PROBE = ("conv1.weight", "fc_exp.weight")
+
+    def __init__(self, block_expansion=64, feature_channel=32, num_kp=15, image_channel=3, max_features=2048, num_bins=66, estimate_jacobian=False):
+        super().__init__()
+        if not all(_is_int(v) and v >= 1 for v in (block_expansion, num_kp, image_channel, num_bins)):
+            raise ValueError("HEEstimator: block_expansion, num_kp, image_channel and num_bins are positive ints")
+        if image_channel != 3:
+            raise ValueError(f"HEEstimator: image_channel {image_channel} is not implemented: the native network takes three colour channels")
+        self.structure = (int(image_channel), int(block_expansion), int(num_bins), int(num_kp))
+        self.conv1 = nn.Conv2d(image_channel, block_expansion, 7, padding=3, stride=2)
+        self.norm1 = nn.BatchNorm2d(block_expansion, affine=True)
+        self.conv2 = nn.Conv2d(block_expansion, 256, 1)
+        self.norm2 = nn.BatchNorm2d(256, affine=True)
+        self.block1 = nn.Sequential()
+        for i in range(3):
+            self.block1.add_module(f"b1_{i}", _ResBottleneck(256, 1))
+        for (conv, norm, c), strided, (group, letter, n) in _HE_STAGES:
+            setattr(self, conv, nn.Conv2d(c // 2, c, 1))
+            setattr(self, norm, nn.BatchNorm2d(c, affine=True))
+            setattr(self, strided, _ResBottleneck(c, 2))
+            seq = nn.Sequential()
+            for i in range(n):
+                seq.add_module(f"{letter}{i}", _ResBottleneck(c, 1))
+            setattr(self, group, seq)
+        self.fc_roll = nn.Linear(2048, num_bins)
+        self.fc_pitch = nn.Linear(2048, num_bins)
+        self.fc_yaw = nn.Linear(2048, num_bins)
+        self.fc_t = nn.Linear(2048, 3)
+        self.fc_exp = nn.Linear(2048, 3 * num_kp)
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("HEEstimator: training mode is not implemented; call .eval()")
+        with torch.no_grad():
+            out = F.max_pool2d(F.relu(self.norm1(self.conv1(x))), 3, 2, 1)
+            out = self.block1(F.relu(self.norm2(self.conv2(out))))
+            for (conv, norm, _), strided, (group, _, _) in _HE_STAGES:
+                out = getattr(self, group)(getattr(self, strided)(F.relu(getattr(self, norm)(getattr(self, conv)(out)))))
+            out = F.adaptive_avg_pool2d(out, 1).view(out.shape[0], -1)
+            return {"yaw": self.fc_roll(out), "pitch": self.fc_pitch(out), "roll": self.fc_yaw(out), "t": self.fc_t(out), "exp": self.fc_exp(out)}
+
+
+# ------------------------------------------------------------------------------------------------ weights: keys, shapes, validation
+def _bn_shapes(out, p, c):
+    for k in ("weight", "bias", "running_mean", "running_var"):
+        out[f"{p}.{k}"] = (c,)
+    out[p + ".num_batches_tracked"] = ()
+
+
+def kp_detector_structure_shapes(structure):
+    """``{key: shape}`` of the ``KPDetector`` with ``structure`` (``kp_detector_structure``), in ``state_dict`` order."""
+    cin, down, depth, up, K, jmaps, k, _ = structure
+    out = {}
+    for i, c in enumerate(down):
+        p = f"predictor.down_blocks.down{i}"
+        out[p + ".conv.weight"], out[p + ".conv.bias"] = (c, cin if i == 0 else down[i - 1], 3, 3), (c,)
+        _bn_shapes(out, p + ".norm", c)
+    out["predictor.conv.weight"], out["predictor.conv.bias"] = (depth * down[-1], down[-1], 1, 1), (depth * down[-1],)
+    for i, c in enumerate(up):
+        p = f"predictor.up_blocks.up{i}"
+        out[p + ".conv.weight"], out[p + ".conv.bias"] = (c, down[-1] if i == 0 else up[i - 1], 3, 3, 3), (c,)
+        _bn_shapes(out, p + ".norm", c)
+    out["kp.weight"], out["kp.bias"] = (K, up[-1], 3, 3, 3), (K,)
+    if jmaps:
+        out["jacobian.weight"], out["jacobian.bias"] = (9 * jmaps, up[-1], 3, 3, 3), (9 * jmaps,)
+    if k:
+        out["down.weight"] = (cin, 1, k, k)
+    return out
+
+
+def he_estimator_structure_shapes(structure):
+    """``{key: shape}`` of the ``HEEstimator`` with ``structure`` = (image_channel, block_expansion, num_bins, num_kp), in ``state_dict`` order."""
+    cin, be, nbins, K = structure
+    out = {}
+
+    def conv(p, co, ci, k):
+        out[p + ".weight"], out[p + ".bias"] = (co, ci, k, k), (co,)
+
+    def bottleneck(p, c, strided):
+        conv(p + ".conv1", c // 4, c, 1), conv(p + ".conv2", c // 4, c // 4, 3), conv(p + ".conv3", c, c // 4, 1)
+        _bn_shapes(out, p + ".norm1", c // 4), _bn_shapes(out, p + ".norm2", c // 4), _bn_shapes(out, p + ".norm3", c)
+        if strided:
+            conv(p + ".skip", c, c, 1), _bn_shapes(out, p + ".norm4", c)
+
+    conv("conv1", be, cin, 7), _bn_shapes(out, "norm1", be)
+    conv("conv2", 256, be, 1), _bn_shapes(out, "norm2", 256)
+    for i in range(3):
+        bottleneck(f"block1.b1_{i}", 256, False)
+    for (cv, norm, c), strided, (group, letter, n) in _HE_STAGES:
+        conv(cv, c, c // 2, 1), _bn_shapes(out, norm, c)
+        bottleneck(strided, c, True)
+        for i in range(n):
+            bottleneck(f"{group}.{letter}{i}", c, False)
+    for name, n in zip(_HE_HEADS, (nbins, nbins, nbins, 3, 3 * K)):
+        out[name + ".weight"], out[name + ".bias"] = (n, 2048), (n,)
+    return out
+
+
+def kp_detector_state_dict_shapes(**config):
+    """``{key: shape}`` of ``KPDetector(**config).state_dict()``, in its order (the upstream configuration by default)."""
+    config.pop("feature_channel", None), config.pop("temperature", None)
+    return kp_detector_structure_shapes(kp_detector_structure(**config))
+
+
+def he_estimator_state_dict_shapes(block_expansion=64, num_kp=15, image_channel=3, num_bins=66):
+    """``{key: shape}`` of ``HEEstimator(...).state_dict()``, in its order."""
+    return he_estimator_structure_shapes((image_channel, block_expansion, num_bins, num_kp))
+
+
+def _shape_of(name, sd, key, ndim, cls):
+    t = sd.get(key)
+    if not isinstance(t, torch.Tensor) or t.dim() != ndim:
+        raise KeyError(f"{name}: the weights lack '{key}': expected the keys of {cls}")
+    return tuple(int(d) for d in t.shape)
+
+
+def _kp_structure_of_keys(name, sd):
+    """The structure read off the keys and shapes of a mapping (a ``KPDetector`` module hands over its own)."""
+    down, i = [], 0
+    cin = _shape_of(name, sd, "predictor.down_blocks.down0.conv.weight", 4, "KPDetector")[1]
+    while f"predictor.down_blocks.down{i}.conv.weight" in sd:
+        down.append(_shape_of(name, sd, f"predictor.down_blocks.down{i}.conv.weight", 4, "KPDetector")[0])
+        i += 1
+    depth = _shape_of(name, sd, "predictor.conv.weight", 4, "KPDetector")[0] // down[-1]
+    up, i = [], 0
+    while f"predictor.up_blocks.up{i}.conv.weight" in sd:
+        up.append(_shape_of(name, sd, f"predictor.up_blocks.up{i}.conv.weight", 5, "KPDetector")[0])
+        i += 1
+    K = _shape_of(name, sd, "kp.weight", 5, "KPDetector")[0]
+    jmaps = _shape_of(name, sd, "jacobian.weight", 5, "KPDetector")[0] // 9 if "jacobian.weight" in sd else 0
+    k = _shape_of(name, sd, "down.weight", 4, "KPDetector")[2] if "down.weight" in sd else 0
+    s = (k + 3) // 4 if k else 1                                      # k = 2 round(2 (s - 1)) + 1 = 4 s - 3 for an integer s
+    if min(depth, len(up)) < 1 or (k and (k != 4 * s - 3)) or (jmaps and jmaps != K):
+        raise ValueError(f"{name}: the weights are not a KPDetector the native path implements (depth {depth}, {len(up)} up blocks, anti-alias kernel {k}, "
+                         f"{jmaps} Jacobian maps for {K} keypoints)")
+    return cin, tuple(down), depth, tuple(up), K, jmaps, k, s
+
+
+def _he_structure_of_keys(name, sd):
+    be, cin = _shape_of(name, sd, "conv1.weight", 4, "HEEstimator")[:2]
+    return cin, be, _shape_of(name, sd, "fc_roll.weight", 2, "HEEstimator")[0], _shape_of(name, sd, "fc_exp.weight", 2, "HEEstimator")[0] // 3
+
+
+_EVAL = "the native path is the eval-mode forward (BatchNorm's running statistics)"
+_KP_NET = _Net("KPDetector", kp_detector_structure_shapes, ("module.", "kp_detector."), True, ("predictor.conv.weight",), _kp_structure_of_keys, _EVAL,
+               ("num_batches_tracked",))
+_HE_NET = _Net("HEEstimator", he_estimator_structure_shapes, ("module.", "he_estimator."), True, ("conv1.weight",), _he_structure_of_keys, _EVAL,
+               ("num_batches_tracked",))
+_MODULE_NETS = {}
+
+
+def _net_of(weights, base):
+    """The description ``_validated`` checks ``weights`` against (``base``: ``_KP_NET`` or ``_HE_NET``): a mirror module is held to the structure it was built
+    with, anything else to the structure its keys and shapes spell."""
+    if not isinstance(weights, KPDetector if base is _KP_NET else HEEstimator):
+        return base
+    key = (base.cls, weights.structure)
+    if key not in _MODULE_NETS:
+        _MODULE_NETS[key] = base._replace(variant=lambda name, sd, s=weights.structure: s)
+    return _MODULE_NETS[key]
+
+
+def _check_loaded(name, weights):
+    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
+        raise RuntimeError(f"{name}: {type(weights).__name__}: the weights were never loaded (nothing is downloaded here); call load_state_dict first")
+
+
+def _slabs3d(cout, cin, device):
+    return tuple(torch.empty(((cin + 15) // 16, 27, 2, cout, 8), dtype=torch.int16, device=device) for _ in range(3))
+
+
+def prep_conv3d(w, scale=None, shift=None):
+    """(three-way split slabs of the Conv3d weight ``w [cout, cin, 3, 3, 3]`` times ``scale[co]``, the shift as fp32 bias or None) for ``conv3d_sb3``."""
+    cout, cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"prep_conv3d: expected a [cout, cin, 3, 3, 3] weight, got {tuple(w.shape)}")
+    if scale is not None:
+        w = (w.double() * scale[:, None, None, None, None]).float()
+    w = _c(w, "weight")
+    s3 = _slabs3d(cout, cin, w.device)
+    lib().call("e4s_conv3d_prep_weights_sb3", _p(s3[0]), _p(s3[1]), _p(s3[2]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, _stream())
+    return s3, (shift.float().contiguous() if shift is not None else None)
+
+
+def conv3d_sb3(x, slabs, bias=None, *, relu: bool = False, residual=None, up_hw: int = 1):
+    """``act(conv3d(up(x), W, stride 1, zero pad 1) + bias + residual)`` of csrc/conv3d.hip on prepared ``slabs`` (``prep_conv3d``): ``x [bs, cin, D, h, w]``
+    float32, ``up`` the nearest (1, ``up_hw``, ``up_hw``) upsampling folded into the gather; returns ``[bs, cout, D, up_hw h, up_hw w]``."""
+    x = _c(x, "x")
+    if x.dim() != 5 or up_hw not in (1, 2) or x.shape[1] > 16 * slabs[0].shape[0] or x.shape[1] <= 16 * (slabs[0].shape[0] - 1):
+        raise ValueError(f"conv3d_sb3: x is {tuple(x.shape)} with up_hw {up_hw}: expected [bs, cin, D, h, w] matching the slabs and up_hw 1 or 2")
+    bs, cin, D, h, w = x.shape
+    cout = slabs[0].shape[3]
+    out = torch.empty((bs, cout, D, up_hw * h, up_hw * w), dtype=torch.float32, device=x.device)
+    if residual is not None:
+        residual = _c(residual, "residual")
+        if residual.shape != out.shape:
+            raise ValueError(f"conv3d_sb3: residual shape {tuple(residual.shape)} != output {tuple(out.shape)}")
+    lib().call("e4s_conv3d_sb3", _p(out), _p(x), *[_p(s) for s in slabs], _p(bias), _p(residual), 1 if relu else 0, up_hw, bs, cin, cout, D, up_hw * h,
+               up_hw * w, _stream())
+    return out
+
+
+def _fold_bias(sd, conv, norm):
+    """(scale, shift) of ``norm(conv(x) + bias)`` in float64: the convolution's bias goes through the BatchNorm."""
+    s, b = bn_fold(sd, norm)
+    return s, b + sd[conv + ".bias"].double() * s
+
+
+def _exact2d(w, scale, shift):
+    """K-major fp32 weight ``[cin][k k][cout]`` of the exact kernel with ``scale`` folded in float64, and the bias."""
+    cout, cin, k, _ = w.shape
+    wt = (w.double() * scale[:, None, None, None]).float().permute(1, 2, 3, 0).reshape(cin, k * k, cout).contiguous()
+    return wt, shift.float().contiguous()
+
+
+def _conv_any(x, prepared, k, stride=1, relu=False, residual=None):
+    """A 2-D convolution on whichever kernel its weights were prepared for: the exact one (a K-major tensor: fewer than 16 input channels) or sb3 (slabs)."""
+    w, bias = prepared
+    if isinstance(w, tuple):
+        return conv_sb(x, w, bias, k=k, stride=stride, relu=relu, residual=residual)
+    bs, cin, h, wd = x.shape
+    cout, pad = w.shape[2], k // 2
+    out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv2d", _p(out), _p(x), None, 0, _p(w), _p(bias), None, None, None, _p(residual), 1 if relu else 0, bs, cin, cout, h, wd, k, stride, pad,
+               _stream())
+    return out
+
+
+def _prep2d(sd, conv, norm=None):
+    w = sd[conv + ".weight"]
+    scale, shift = _fold_bias(sd, conv, norm) if norm is not None else (torch.ones(w.shape[0], dtype=torch.float64, device=w.device), sd[conv + ".bias"].double())
+    if w.shape[1] < 16:
+        return _exact2d(w, scale, shift)
+    return prep_fwd(w, scale, shift)
+
+
+class PreparedKPDetector(_Prepared):
+    """The kernels' copies of a ``KPDetector``'s weights, rebuilt when a tensor changes version or storage: per DownBlock2d the convolution with its bias and
+    BatchNorm folded in float64 (K-major fp32 under 16 input channels, three-way split slabs otherwise), the 1 x 1 convolution's slabs, per UpBlock3d and for
+    the heads the 27-tap slabs, and the anti-alias kernel."""
+
+    __slots__ = ()
+
+    def get(self, weights, checked=None):
+        sd, structure, ts = checked if checked is not None else _validated("kp_detector_forward", weights, _net_of(weights, _KP_NET))
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k in kp_detector_structure_shapes(structure) if not k.endswith("num_batches_tracked")}
+        _, down, _, up, _, jmaps, k, _ = structure
+        with torch.no_grad():
+            P = dict(down=[_prep2d(sd, f"predictor.down_blocks.down{i}.conv", f"predictor.down_blocks.down{i}.norm") for i in range(len(down))],
+                     conv=_prep2d(sd, "predictor.conv"),
+                     up=[prep_conv3d(sd[f"predictor.up_blocks.up{i}.conv.weight"], *_fold_bias(sd, f"predictor.up_blocks.up{i}.conv", f"predictor.up_blocks.up{i}.norm"))
+                         for i in range(len(up))],
+                     kp=prep_conv3d(sd["kp.weight"], None, sd["kp.bias"].double()),
+                     jac=prep_conv3d(sd["jacobian.weight"], None, sd["jacobian.bias"].double()) if jmaps else None,
+                     taps=sd["down.weight"][0, 0].contiguous() if k else None)
+        return self._publish(key, P)
+
+
+class PreparedHEEstimator(_Prepared):
+    """The kernels' copies of an ``HEEstimator``'s weights: ``conv1`` K-major fp32 with ``norm1`` folded, every other convolution as three-way split slabs with
+    its bias and BatchNorm folded in float64, and the five heads as one ``[3 num_bins + 3 + 3 num_kp, 2048]`` matrix in key order with its bias."""
+
+    __slots__ = ()
+
+    def get(self, weights, checked=None):
+        sd, structure, ts = checked if checked is not None else _validated("he_estimator_forward", weights, _net_of(weights, _HE_NET))
+        key = weights_key(ts) + (ts[0].device,)
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k in he_estimator_structure_shapes(structure) if not k.endswith("num_batches_tracked")}
+        dev = ts[0].device
+
+        def bottleneck(p, strided):
+            return dict(c1=_prep2d(sd, p + ".conv1", p + ".norm1"), c2=_prep2d(sd, p + ".conv2", p + ".norm2"), c3=_prep2d(sd, p + ".conv3", p + ".norm3"),
+                        skip=_prep2d(sd, p + ".skip", p + ".norm4") if strided else None)
+
+        with torch.no_grad():
+            stages = [dict(widen=_prep2d(sd, "conv2", "norm2"), blocks=[bottleneck(f"block1.b1_{i}", False) for i in range(3)])]
+            for (cv, norm, _), strided, (group, letter, n) in _HE_STAGES:
+                stages.append(dict(widen=_prep2d(sd, cv, norm), blocks=[bottleneck(strided, True)] + [bottleneck(f"{group}.{letter}{i}", False) for i in range(n)]))
+            n = sum(sd[h + ".bias"].shape[0] for h in _HE_HEADS)
+            P = dict(stem=_exact2d(sd["conv1.weight"], *_fold_bias(sd, "conv1", "norm1")), stages=stages,
+                     fc_w=torch.cat([sd[h + ".weight"] for h in _HE_HEADS]).contiguous(), fc_b=torch.cat([sd[h + ".bias"] for h in _HE_HEADS]).contiguous(),
+                     ones=torch.ones(n, dtype=torch.float32, device=dev), zeros=torch.zeros(n, dtype=torch.float32, device=dev))
+        return self._publish(key, P)
+
+
+# ------------------------------------------------------------------------------------------------ the forward passes
+def _checked_image(name, x, weights, base):
+    """Everything that can be refused, before any launch; returns the checked weights."""
+    _check_loaded(name, weights)
+    checked = _validated(name, weights, _net_of(weights, base))
+    _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image")
+    if x.shape[1] != 3:
+        raise ValueError(f"{name}: x is {tuple(x.shape)}: expected three colour channels")
+    if min(x.shape[2:]) < 1 or max(x.shape[2:]) > 16384:
+        raise ValueError(f"{name}: x is {tuple(x.shape)}: sides of 1 .. 16384")
+    return checked
+
+
+def heatmap_keypoints(logits, jac_planes=None, temperature=0.1, want_heatmap=False):
+    """``e4s_v2v_heatmap_kp``: the softmax of ``logits [bs, K, D, H, W] / temperature`` over each volume and its expectation on the (x, y, z) grid in [-1, 1]:
+    ``value [bs, K, 3]``; with ``jac_planes [bs, 9 K, D, H, W]`` also ``jacobian [bs, K, 3, 3]``; the normalised ``heatmap`` when wanted.  Returns the three
+    (None where not asked for)."""
+    logits = _c(logits, "logits")
+    if logits.dim() != 5 or min(logits.shape[2:]) < 2:
+        raise ValueError(f"heatmap_keypoints: logits are {tuple(logits.shape)}: expected [bs, K, D, H, W] with every extent of the volume at least 2")
+    bs, K, D, H, W = logits.shape
+    if jac_planes is not None:
+        jac_planes = _c(jac_planes, "jac_planes")
+        if tuple(jac_planes.shape) != (bs, 9 * K, D, H, W):
+            raise ValueError(f"heatmap_keypoints: jac_planes are {tuple(jac_planes.shape)}, expected {(bs, 9 * K, D, H, W)}")
+    value = torch.empty((bs, K, 3), dtype=torch.float32, device=logits.device)
+    jac = torch.empty((bs, K, 3, 3), dtype=torch.float32, device=logits.device) if jac_planes is not None else None
+    heat = torch.empty_like(logits) if want_heatmap else None
+    lib().call("e4s_v2v_heatmap_kp", _p(value), _p(jac), _p(heat), _p(logits), _p(jac_planes), float(temperature), bs, K, D, H, W, _stream())
+    return value, jac, heat
+
+
+def antialias_down(x, taps, stride: int):
+    """``AntiAliasInterpolation2d.forward`` on ``x [bs, C, H, W]`` with the ``k x k`` kernel ``taps``: only the kept outputs are evaluated."""
+    x, taps = _c(x, "x"), _c(taps, "taps")
+    bs, c, h, w = x.shape
+    out = torch.empty((bs, c, -(-h // stride), -(-w // stride)), dtype=torch.float32, device=x.device)
+    lib().call("e4s_v2v_antialias_down", _p(out), _p(x), _p(taps), bs * c, h, w, taps.shape[0], int(stride), _stream())
+    return out
+
+
+def avgpool2x2(x):
+    """``nn.AvgPool2d(2)`` on ``[bs, C, H, W]`` (an odd last row or column is dropped)."""
+    x = _c(x, "x")
+    bs, c, h, w = x.shape
+    if min(h, w) < 2:
+        raise ValueError(f"avgpool2x2: x is {tuple(x.shape)}: the planes must be at least 2 x 2")
+    out = torch.empty((bs, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    lib().call("e4s_avgpool2x2", _p(out), _p(x), bs * c, h, w, _stream())
+    return out
+
+
+def kp_detector_forward(x: torch.Tensor, weights, temperature=None, want_heatmap: bool = False):
+    """``KPDetector.forward(x)`` (keypoint_detector.py:56-82) in eval mode on the device: ``{'value' [bs, num_kp, 3][, 'jacobian' [bs, num_kp, 3, 3]]}`` from a
+    float32 ``x [bs, 3, H, W]``; with ``want_heatmap`` also ``'prediction'`` (the logits) and ``'heatmap'``.  ``weights``: a module with the network's keys
+    (``KPDetector``, the drop-in) or the mapping ``torch.load`` returns (``checkpoint['kp_detector']`` or the checkpoint itself); a mapping's structure is read off
+    its keys and shapes, and its ``temperature`` — which no key holds — is the argument (default: the module's, 0.1 for a mapping).  A module's prepared weights
+    are cached per parameter version.  Refused before any launch: a CPU tensor, another dtype, other than three channels, a module in training mode or never
+    loaded, an input that leaves an extent of the final volume below 2."""
+    name = "kp_detector_forward"
+    checked = _checked_image(name, x, weights, _KP_NET)
+    structure = checked[1]
+    if temperature is None:
+        temperature = getattr(weights, "temperature", 0.1)
+    if not float(temperature) > 0:
+        raise ValueError(f"{name}: temperature {temperature!r} must be positive")
+    D, H, W = kp_volume_size(structure, int(x.shape[2]), int(x.shape[3]))
+    if min(D, H, W) < 2:
+        raise ValueError(f"{name}: x is {tuple(x.shape)}: the final volume would be {D} x {H} x {W}, every extent must be at least 2")
+    _cuda_checked(name, x=x)
+    _devices_checked(name, "x", x, checked[2])
+    K, jmaps = structure[4], structure[5]
+    bs = x.shape[0]
+    if bs == 0:
+        out = {"value": x.new_empty((0, K, 3))}
+        if jmaps:
+            out["jacobian"] = x.new_empty((0, K, 3, 3))
+        return out
+    with torch.no_grad():
+        P = lossnet.prepare(PreparedKPDetector, weights, checked)
+        cur = x.detach().contiguous()
+        if P["taps"] is not None:
+            cur = antialias_down(cur, P["taps"], structure[7])
+        for L in P["down"]:
+            cur = avgpool2x2(_conv_any(cur, L, 3, relu=True))
+        cur = _conv_any(cur, P["conv"], 1)
+        cur = cur.view(bs, cur.shape[1] // D, D, cur.shape[2], cur.shape[3])
+        for L in P["up"]:
+            cur = conv3d_sb3(cur, *L, relu=True, up_hw=2)
+        logits = conv3d_sb3(cur, *P["kp"])
+        planes = conv3d_sb3(cur, *P["jac"]) if jmaps else None
+        value, jac, heat = heatmap_keypoints(logits, planes, temperature, want_heatmap)
+    out = {"value": value}
+    if jmaps:
+        out["jacobian"] = jac
+    if want_heatmap:
+        out["prediction"], out["heatmap"] = logits, heat
+    return out
+
+
+def he_estimator_forward(x: torch.Tensor, weights):
+    """``HEEstimator.forward(x)`` (keypoint_detector.py:136-178) in eval mode on the device: ``{'yaw', 'pitch', 'roll' [bs, num_bins], 't' [bs, 3], 'exp' [bs, 3
+    num_kp]}`` from a float32 ``x [bs, 3, H, W]``, the head names crossed as the reference crosses them (``yaw`` comes from ``fc_roll``, ``roll`` from
+    ``fc_yaw``).  The five outputs are views of one ``[bs, 3 num_bins + 3 + 3 num_kp]`` tensor.  ``weights`` and the refusals: see ``kp_detector_forward``."""
+    name = "he_estimator_forward"
+    checked = _checked_image(name, x, weights, _HE_NET)
+    _, _, nbins, K = checked[1]
+    _cuda_checked(name, x=x)
+    _devices_checked(name, "x", x, checked[2])
+    bs, _, H, W = x.shape
+    n = 3 * nbins + 3 + 3 * K
+    y = torch.empty((bs, n), dtype=torch.float32, device=x.device)
+    if bs:
+        with torch.no_grad():
+            P = lossnet.prepare(PreparedHEEstimator, weights, checked)
+            cur = _conv_any(x.detach().contiguous(), P["stem"], 7, stride=2, relu=True)
+            pooled = torch.empty((bs, cur.shape[1], (cur.shape[2] - 1) // 2 + 1, (cur.shape[3] - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+            lib().call("e4s_maxpool3x3s2", _p(pooled), _p(cur), bs * cur.shape[1], cur.shape[2], cur.shape[3], _stream())
+            cur = pooled
+            for S in P["stages"]:
+                cur = _conv_any(cur, S["widen"], 1, relu=True)
+                for L in S["blocks"]:
+                    stride = 2 if L["skip"] is not None else 1
+                    o = _conv_any(cur, L["c1"], 1, relu=True)
+                    o = _conv_any(o, L["c2"], 3, stride=stride, relu=True)
+                    idn = _conv_any(cur, L["skip"], 1, stride=stride) if L["skip"] is not None else cur
+                    cur = _conv_any(o, L["c3"], 1, relu=True, residual=idn)
+            feat = torch.empty((bs, cur.shape[1]), dtype=torch.float32, device=x.device)
+            lib().call("e4s_plane_stats", _p(feat), None, None, _p(cur), bs * cur.shape[1], cur.shape[2] * cur.shape[3], 0.0, _stream())
+            # the bias rides on e4s_vec_fc's BatchNorm slot: (a - 0) * (1 / sqrt(1 + 0)) + bias
+            lib().call("e4s_vec_fc", _p(y), _p(feat), _p(P["fc_w"]), _p(P["ones"]), _p(P["fc_b"]), _p(P["zeros"]), _p(P["ones"]), 0.0, 0, bs, cur.shape[1], n,
+                       _stream())
+    roll_head, pitch_head, yaw_head, t, exp = torch.split(y, (nbins, nbins, nbins, 3, 3 * K), dim=1)
+    return {"yaw": roll_head, "pitch": pitch_head, "roll": yaw_head, "t": t, "exp": exp}
+
+
+# ------------------------------------------------------------------------------------------------ keypoint_transformation
+def _angles(name, he, yaw, pitch, roll, free_view):
+    """(the three logit rows or None, deg_in [bs, 3] or None) of drive_demo.py:137-157: without ``free_view`` the logits; with it a fixed angle where one is
+    given (a number, for every sample) and the logits' degrees where it is None."""
+    rows = [he["yaw"], he["pitch"], he["roll"]]
+    for nm, r in zip(("yaw", "pitch", "roll"), rows):
+        _tensor_checked(name, f"he['{nm}']", r, torch.float32, 2, "float32 [bs, 66] logits")
+        if r.shape != rows[0].shape or r.shape[1] != NUM_BINS:
+            raise ValueError(f"{name}: he['{nm}'] is {tuple(r.shape)}: expected [bs, {NUM_BINS}] (headpose_pred_to_degree weighs 66 bins)")
+    if not free_view:
+        return rows, None
+    fixed = (yaw, pitch, roll)
+    return [None if f is not None else r for f, r in zip(fixed, rows)], fixed
+
+
+def _transform(name, kp_canonical, he, estimate_jacobian, free_view, yaw, pitch, roll):
+    if not hasattr(kp_canonical, "keys") or "value" not in kp_canonical or not hasattr(he, "keys"):
+        raise TypeError(f"{name}: kp_canonical is KPDetector's output dict and he HEEstimator's")
+    kp, t, exp = kp_canonical["value"], he["t"], he["exp"]
+    _tensor_checked(name, "kp_canonical['value']", kp, torch.float32, 3, "float32 [bs, num_kp, 3]")
+    rows, fixed = _angles(name, he, yaw, pitch, roll, free_view)
+    bs, K = he["yaw"].shape[0], kp.shape[1]
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != bs * 3 or t.dim() not in (2, 3):
+        raise ValueError(f"{name}: he['t'] is {tuple(getattr(t, 'shape', ()))}: expected float32 [bs, 3] (or the [bs, 1, 3] the reference leaves behind)")
+    _tensor_checked(name, "he['exp']", exp, torch.float32, 2, "float32 [bs, 3 num_kp]")
+    if kp.shape[2] != 3 or kp.shape[0] not in (bs, 1) or tuple(exp.shape) != (bs, 3 * K):
+        raise ValueError(f"{name}: kp_canonical['value'] is {tuple(kp.shape)} and he['exp'] {tuple(exp.shape)} for a batch of {bs}: expected [bs or 1, K, 3] and [bs, 3 K]")
+    jac = None
+    if estimate_jacobian:
+        jac = kp_canonical.get("jacobian")
+        _tensor_checked(name, "kp_canonical['jacobian']", jac, torch.float32, 4, "float32 [bs, num_kp, 3, 3]")
+        if tuple(jac.shape) != (kp.shape[0], K, 3, 3):
+            raise ValueError(f"{name}: kp_canonical['jacobian'] is {tuple(jac.shape)}, expected {(kp.shape[0], K, 3, 3)}")
+    ts = {"kp_canonical['value']": kp, "he['yaw']": he["yaw"], "he['pitch']": he["pitch"], "he['roll']": he["roll"], "he['t']": t, "he['exp']": exp}
+    if jac is not None:
+        ts["kp_canonical['jacobian']"] = jac
+    for nm, v in ts.items():
+        if not v.is_cuda:
+            raise RuntimeError(f"{name}: {nm} must be a CUDA tensor")
+    dev = kp.device
+    if any(v.device != dev for v in ts.values()):
+        raise RuntimeError(f"{name}: device mismatch among the tensors")
+    deg_in = None
+    if fixed is not None:
+        deg_in = torch.tensor([[0.0 if f is None else float(f) for f in fixed]] * max(bs, 1), dtype=torch.float32).to(dev)[:bs].contiguous()
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
+    value, jout, deg, rot = new(bs, K, 3), (new(bs, K, 3, 3) if jac is not None else None), new(bs, 3), new(bs, 3, 3)
+    with torch.no_grad():
+        # contiguous copies (the heads are column slices of one tensor) stay alive in these names until the launch is queued
+        rows_c = [None if r is None else r.detach().contiguous() for r in rows]
+        t_c, exp_c, kp_c = t.detach().contiguous(), exp.detach().contiguous(), kp.detach().contiguous()
+        jac_c = None if jac is None else jac.detach().contiguous()
+        lib().call("e4s_v2v_kp_transform", _p(value), _p(jout), _p(deg), _p(rot), *[_p(r) for r in rows_c], _p(deg_in), _p(t_c), _p(exp_c), _p(kp_c), _p(jac_c),
+                   bs, kp.shape[0], K, NUM_BINS, _stream())
+    return value, jout, deg, rot
+
+
+def keypoint_transformation(kp_canonical, he, estimate_jacobian=True, free_view=False, yaw=0, pitch=0, roll=0):
+    """``keypoint_transformation`` of drive_demo.py:135-180 on the device in one launch: ``{'value': rot kp + t + exp, 'jacobian': rot jacobian or None}`` with
+    ``rot = pitch_mat yaw_mat roll_mat`` from the degrees of the three logit rows (radians through 3.14).  ``kp_canonical['value']`` may hold one sample for every
+    frame of ``he``.  With ``free_view`` an angle that is a number replaces that row's degrees for every sample, ``None`` keeps the row's.  Unlike the reference,
+    ``he['t']`` is not reshaped in place: the caller's dict is left as it was (a ``[bs, 1, 3]`` tensor the reference left behind is accepted)."""
+    value, jac, _, _ = _transform("keypoint_transformation", kp_canonical, he, estimate_jacobian, free_view, yaw, pitch, roll)
+    return {"value": value, "jacobian": jac}
+
+
+def headpose_degrees(he):
+    """``headpose_pred_to_degree`` of the three rows of ``he``: float32 ``[bs, 3]`` of (yaw, pitch, roll) degrees, ``sum(softmax(row) idx) 3 - 99``."""
+    return _pose("headpose_degrees", he)[0]
+
+
+def rotation_matrix(he):
+    """``get_rotation_matrix`` of those degrees: float32 ``[bs, 3, 3]``."""
+    return _pose("rotation_matrix", he)[1]
+
+
+def _pose(name, he):
+    if not hasattr(he, "keys"):
+        raise TypeError(f"{name}: he is HEEstimator's output dict")
+    bs = he["yaw"].shape[0] if isinstance(he["yaw"], torch.Tensor) and he["yaw"].dim() == 2 else 0
+    dev = he["yaw"].device if isinstance(he["yaw"], torch.Tensor) else "cpu"
+    zero = {"value": torch.zeros((1, 1, 3), dtype=torch.float32, device=dev)}
+    stub = dict(he, t=torch.zeros((bs, 3), dtype=torch.float32, device=dev), exp=torch.zeros((bs, 3), dtype=torch.float32, device=dev))
+    _, _, deg, rot = _transform(name, zero, stub, False, False, 0, 0, 0)
+    return deg, rot
+
+
+# ------------------------------------------------------------------------------------------------ the clip-level function
+def reenact_keypoints(source, driving, kp_detector, he_estimator, estimate_jacobian=None):
+    """What ``make_animation`` (drive_demo.py:182-) computes in front of the generator: ``kp_canonical = kp_detector(source)``, once per clip, and the transformed
+    keypoints of the source and of every driving frame.  ``source [1, 3, H, W]`` and ``driving [n, 3, H, W]`` are float32 in [0, 1] on the device.  ONE
+    ``HEEstimator`` pass runs over the n + 1 images.  Returns ``(kp_canonical, kp_source, kp_driving)``, ``kp_driving`` batched over the n frames.
+    ``estimate_jacobian``: default, whether the detector has a Jacobian head."""
+    name = "reenact_keypoints"
+    for nm, t in (("source", source), ("driving", driving)):
+        _tensor_checked(name, nm, t, torch.float32, 4, "a float32 [n, 3, H, W] image batch")
+    if source.shape[0] != 1 or driving.shape[1:] != source.shape[1:]:
+        raise ValueError(f"{name}: source is {tuple(source.shape)} and driving {tuple(driving.shape)}: expected [1, 3, H, W] and [n, 3, H, W] of one size")
+    _cuda_checked(name, source=source, driving=driving)
+    kp_canonical = kp_detector_forward(source, kp_detector)
+    if estimate_jacobian is None:
+        estimate_jacobian = "jacobian" in kp_canonical
+    he = he_estimator_forward(torch.cat((source, driving)), he_estimator)
+    part = lambda a, b: {k: v[a:b] for k, v in he.items()}      # noqa: E731
+    kp_source = keypoint_transformation(kp_canonical, part(0, 1), estimate_jacobian)
+    kp_driving = keypoint_transformation(kp_canonical, part(1, None), estimate_jacobian)
+    return kp_canonical, kp_source, kp_driving
+
+
+__all__ = ["KPDetector", "HEEstimator", "PreparedKPDetector", "PreparedHEEstimator", "NUM_BINS", "antialias_kernel", "kp_detector_structure", "kp_volume_size",
+           "kp_detector_structure_shapes", "he_estimator_structure_shapes", "kp_detector_state_dict_shapes", "he_estimator_state_dict_shapes", "prep_conv3d",
+           "conv3d_sb3", "heatmap_keypoints", "antialias_down", "avgpool2x2", "kp_detector_forward", "he_estimator_forward", "keypoint_transformation",
+           "headpose_degrees", "rotation_matrix", "reenact_keypoints"]

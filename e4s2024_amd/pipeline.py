@@ -531,6 +531,14 @@ def gpen_detect_faces(net, frames_u8: torch.Tensor, bgr: bool = True):
     return ops.retinaface_detect(frames_u8, net, bgr=bgr)
 
 
+def reenact_keypoints(kp_detector, he_estimator, source: torch.Tensor, driving: torch.Tensor, estimate_jacobian: Optional[bool] = None):
+    """What ``make_animation`` (swap_face_fine/face_vid2vid/drive_demo.py:182-) computes in front of the generator, for a clip on the device: float32 ``source
+    [1, 3, H, W]`` and ``driving [n, 3, H, W]`` in [0, 1] to ``(kp_canonical, kp_source, kp_driving)`` — the detector once on the source, ONE head-pose pass over
+    the n + 1 images, ``kp_driving`` batched over the frames (``ops.reenact_keypoints``).  The two networks as ``ops.kp_detector_forward`` and
+    ``ops.he_estimator_forward`` take weights.  The dense-motion network and the generator stay with the caller."""
+    return ops.reenact_keypoints(source, driving, kp_detector, he_estimator, estimate_jacobian)
+
+
 @torch.no_grad()
 def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_u8: Optional[torch.Tensor] = None, return_faces: bool = False):
     """``FaceEnhancement.process(img, aligned=False)`` (swap_face_fine/gpen/face_enhancement.py:68-110) behind its ``use_sr`` branch, for a batch of frames on

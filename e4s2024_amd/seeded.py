@@ -35,6 +35,8 @@ __all__ = [
     "seeded_gpen_state_dict",
     "seeded_parsenet_state_dict",
     "seeded_retinaface_state_dict",
+    "seeded_kp_detector_state_dict",
+    "seeded_he_estimator_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -413,10 +415,66 @@ def seeded_retinaface_state_dict(seed: int, out_channel: int = 256) -> Dict[str,
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "retinaface")
 
 
+# face-vid2vid's KPDetector and HEEstimator (swap_face_fine/face_vid2vid/modules/keypoint_detector.py): He-scaled convolutions in front of the ReLUs; BatchNorm
+# scales over -1.5 .. 1.5 with one exact zero per layer (a dead channel), running variances over 0.5 .. 1.5, and running means and biases away from zero, so that
+# a fold that drops the mean, a bias or the square root shows.  A ResBottleneck's last BatchNorm has half that magnitude, which keeps the sum over a stage's blocks
+# O(1).  ``down.weight`` is the architecture's constant Gaussian.  The ``kp`` head's gain is chosen so that every heatmap of the tests' cases has an effective
+# support 1 / sum p^2 between 8 positions and a quarter of its volume, neither a one-hot nor uniform (the logits are far from Gaussian: divided by the temperature
+# 0.1 a keypoint's have a standard deviation of 2 to 10, most of it in a few broad bumps).  The pose heads' gain spreads each 66-bin softmax over a handful of bins and the degrees over tens of degrees (tests/golden/make_golden_vid2vid_kp.py asserts the
+# conditions on the tests' cases).
+V2V_KP_HEAD_GAIN = 1.5
+V2V_JACOBIAN_GAIN = 1.0
+V2V_POSE_GAIN = 1.2
+
+
+def _v2v_bn_scale(mag):
+    def rule(seed, key, shape):
+        a = seeded_array(seed, key, shape, 0.0, 1.5 * mag / _SQRT3)             # U(-1.5, 1.5) * mag
+        a[zlib.crc32(key.encode("utf-8")) % a.size] = 0.0
+        return a
+    return rule
+
+
+def _v2v_antialias(seed, key, shape):
+    from .ops_reenact import antialias_kernel
+    s = (shape[-1] + 3) // 4                                                    # k = 4 s - 3 (AntiAliasInterpolation2d at scale 1 / s)
+    k = antialias_kernel(1.0 / s).numpy()
+    assert k.shape == tuple(shape[2:]), (k.shape, shape)
+    return np.broadcast_to(k, shape).copy()
+
+
+_RULES_V2V_KP = [
+    (r"num_batches_tracked$", "zero_long"),
+    (r"^down\.weight$", _v2v_antialias),
+    (r"running_var$", (1.0, 0.5 / _SQRT3)),                                     # U(0.5, 1.5)
+    (r"running_mean$", (0.0, 0.2)),
+    (r"\.norm3\.weight$", _v2v_bn_scale(0.5)),
+    (r"(^|\.)norm\d?\.weight$", _v2v_bn_scale(1.0)),
+    (r"(^|\.)norm\d?\.bias$", (0.0, 0.2)),
+    (r"\.bias$", (0.0, 0.1)),
+    (r"^kp\.weight$", _fan_in_std(V2V_KP_HEAD_GAIN)),
+    (r"^jacobian\.weight$", _fan_in_std(V2V_JACOBIAN_GAIN)),
+    (r"^fc_(roll|pitch|yaw)\.weight$", _fan_in_std(V2V_POSE_GAIN)),
+    (r"^fc_(t|exp)\.weight$", _fan_in_std(1.0)),
+    (r"\.weight$", _fan_in_std(1.4)),
+]
+
+
+def seeded_kp_detector_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for a network with the keys of face-vid2vid's ``KPDetector``: ``template`` is its ``state_dict()`` (meta tensors will do;
+    ``ops.KPDetector(...)`` or the reference's class give the same keys), ``num_batches_tracked`` and the buffer ``down.weight`` included."""
+    return seeded_state_dict(template, seed, "v2v_kp")
+
+
+def seeded_he_estimator_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for a network with the keys of face-vid2vid's ``HEEstimator`` (``template`` as above)."""
+    return seeded_state_dict(template, seed, "v2v_kp")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
              "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
-             "retinaface": _RULES_RETINAFACE}.get(family, _RULES_BISENET)
+             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -962,6 +962,42 @@ E4S_API int e4s_gsr_tail(uint8_t* out_u8, float* out_f, const float* x, const fl
                          void* stream);
 E4S_API int e4s_cv_resize_linear_u8(uint8_t* out, const uint8_t* img, int bs, int H, int W, int Ho, int Wo, void* stream);
 
+/* f17: face-vid2vid reenactment, stage 1 — keypoints and head pose (swap_face_fine/face_vid2vid/modules/keypoint_detector.py:9-178, modules/util.py:55-103, 175-213,
+ * 335-418, drive_demo.py:67-180; csrc/conv3d.hip, csrc/vid2vid.hip).  The 2-D convolutions of both networks run on e4s_conv2d / e4s_conv2d_sb3.
+ *   e4s_conv3d_prep_weights_sb3 : a Conv3d weight [cout][cin][3][3][3] (times the folded BatchNorm scale) as three bf16 slabs [ceil(cin / 16)][27][2][cout][8], the
+ *                                 chunk layout of e4s_conv_prep_weights_sb3 with the 27 taps in (kd, kh, kw) order; bias_out as there.
+ *   e4s_conv3d_sb3              : out [bs][cout][D][H][W] = act(conv3d(x', w, stride 1, zero pad 1) + bias + residual), x' [bs][cin][D][H][W] =
+ *                                 x [bs][cin][D][H / up_hw][W / up_hw] read at (d, y / up_hw, x / up_hw): the nearest (1, 2, 2) upsampling of UpBlock3d folded into
+ *                                 the gather (up_hw 1 or 2; H and W multiples of it).  D, H, W are the OUTPUT extents.  Implicit GEMM with K = 27 cin on the three-way
+ *                                 bf16 split (six v_mfma_f32_32x32x16_bf16 per 16-deep step, fp32 accumulation: fp32-class).  act: 0 none, 1 ReLU.  bias [cout] and
+ *                                 residual [bs][cout][D][H][W] optional.  Any cin and cout >= 1, no padding on the caller's side.  Scalar loads of x: any 4-byte alignment
+ *                                 gives the same bits.
+ *   e4s_v2v_antialias_down      : out [planes][ceil(h / s)][ceil(w / s)] = AntiAliasInterpolation2d: zero pad k / 2, the k x k kernel `taps` (k odd, <= 33; the
+ *                                 module's normalised Gaussian buffer), then [::s, ::s], only the kept outputs evaluated: k k fused multiply-adds in (row, column)
+ *                                 order from 0, exact float32.
+ *   e4s_avgpool2x2              : nn.AvgPool2d(2) on [planes][h][w] -> [planes][h / 2][w / 2] (an odd last row / column is dropped): (((a + b) + c) + d) * 0.25 in row order.
+ *   e4s_v2v_heatmap_kp          : per (sample, keypoint) one workgroup: m = max(logit / temperature) over the D H W positions (a float32 division, as the reference divides), e = exp(logit / temperature - m), then
+ *                                 value [bs][K][3] = (sum e x, sum e y, sum e z) / sum e on the grid 2 i / (n - 1) - 1 in (x, y, z) order (each extent >= 2);
+ *                                 with jac_planes [bs][9 K][D][H][W]: jacobian [bs][K][3][3] = sum e J_j / sum e; heatmap [bs][K][D][H][W] = e / sum e when wanted.
+ *                                 Each lane sums its strided positions in order, the 256 partial sums are added in a fixed tree: the same inputs give the same bits.
+ *   e4s_v2v_kp_transform        : per sample: degrees (yaw, pitch, roll) = sum softmax(row) idx * 3 - 99 of the three [bs][nbins] logit rows (summed in float64, rounded once), or deg_in [bs][3]
+ *                                 itself when logits are NULL (free_view); radians = deg / 180 * 3.14; rot = pitch_mat yaw_mat roll_mat (drive_demo.py:107-133);
+ *                                 value_out [bs][K][3] = rot kp + t + exp (kp [kp_bs][K][3] with kp_bs == bs or 1: one canonical set for every frame);
+ *                                 jac_out [bs][K][3][3] = rot jac (einsum 'bmp,bkps->bkms') when jac is given; deg_out [bs][3] and rot_out [bs][3][3] optional.
+ * No atomics, no host synchronisation, grids from shapes alone: the calls can be captured in a graph.  bs == 0 (planes == 0) returns at once. */
+E4S_API int e4s_conv3d_prep_weights_sb3(uint16_t* w0, uint16_t* w1, uint16_t* w2, float* bias_out, const float* weight, const float* bn_gamma,
+                                        const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, const float* conv_bias, int cout, int cin,
+                                        void* stream);
+E4S_API int e4s_conv3d_sb3(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias, const float* residual,
+                           int act, int up_hw, int bs, int cin, int cout, int D, int H, int W, void* stream);
+E4S_API int e4s_v2v_antialias_down(float* out, const float* x, const float* taps, int planes, int h, int w, int k, int s, void* stream);
+E4S_API int e4s_avgpool2x2(float* out, const float* x, int planes, int h, int w, void* stream);
+E4S_API int e4s_v2v_heatmap_kp(float* value, float* jacobian, float* heatmap, const float* logits, const float* jac_planes, float temperature, int bs, int K, int D,
+                               int H, int W, void* stream);
+E4S_API int e4s_v2v_kp_transform(float* value_out, float* jac_out, float* deg_out, float* rot_out, const float* yaw, const float* pitch, const float* roll,
+                                 const float* deg_in, const float* t, const float* exp, const float* kp, const float* jac, int bs, int kp_bs, int K, int nbins,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
