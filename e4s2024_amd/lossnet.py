@@ -1,7 +1,8 @@
-"""What the frozen loss networks of the PTI objective (``ops_lpips``, ``ops_id``, ``ops_fp``) have in common on the host side: the cache of prepared
-weights, split-bf16 weight preparation and the two convolution entry points of csrc/conv.hip, the banded resampler of csrc/idloss.hip and its
-adjoint, the cosine heads, two small kernels, and the checks and call arguments of the multi-target heads.  The library is resolved inside the
-calls only, so the module imports on a machine without it.
+"""What the frozen loss networks of the PTI objective (``ops_lpips``, ``ops_id``, ``ops_fp``) have in common on the host side, and what the stage networks
+(``ops_recolor``, ``ops_rrdb``, ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) take from it: the cache of prepared weights, BatchNorm
+folding, weight preparation for and the calls of the convolutions of csrc/conv.hip (split-bf16: ``prep_fwd`` / ``prep_dgrad`` / ``conv_sb``; exact float32:
+``prep_exact`` / ``conv_exact``), the banded resampler of csrc/idloss.hip and its adjoint, the cosine heads, two small kernels, and the checks and call
+arguments of the multi-target heads.  The library is resolved inside the calls only, so the module imports on a machine without it.
 
 Multi-target terms: PTI compares one reconstruction with the driven frame and with the recoloured driven frame (training/video_swap_ft_coach.py:274-287).
 Both terms see the same input, so each loss network runs its forward pass and input gradient once; only the heads read the k <= 4 targets' features.
@@ -61,15 +62,30 @@ def _slabs(n: int, cout: int, cin: int, k: int, device):
     return tuple(torch.empty(((cin + 15) // 16, k * k, 2, cout, 8), dtype=torch.int16, device=device) for _ in range(n))
 
 
-def prep_fwd(w, scale=None, shift=None):
-    """(three-way split slabs of ``w * scale[co]``, the shift as fp32 bias or None) for ``conv_sb``."""
+def fold_conv_bn(sd, conv, norm):
+    """Float64 (scale, shift) of ``norm(conv(x) + bias)``: the convolution's own bias goes through the eval-mode BatchNorm behind it."""
+    scale, shift = bn_fold(sd, norm)
+    return scale, shift + sd[conv + ".bias"].double() * scale
+
+
+def prep_fwd(w, scale=None, shift=None, terms=3):
+    """(split-bf16 slabs of ``w * scale[co]``: three-way, or two-way with ``terms=2``; the shift as fp32 bias or None) for ``conv_sb``."""
     cout, cin, k, _ = w.shape
     if scale is not None:
         w = (w.double() * scale[:, None, None, None]).float()
     w = w.contiguous()
-    s3 = _slabs(3, cout, cin, k, w.device)
-    lib().call("e4s_conv_prep_weights_sb3", _p(s3[0]), _p(s3[1]), _p(s3[2]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, k, k, _stream())
-    return s3, (shift.float().contiguous() if shift is not None else None)
+    slabs = _slabs(terms, cout, cin, k, w.device)
+    lib().call("e4s_conv_prep_weights_sb3" if terms == 3 else "e4s_conv_prep_weights_sb", *[_p(s) for s in slabs], None, _p(w), None, None, None, None, 0.0, None,
+               cout, cin, k, k, _stream())
+    return slabs, (shift.float().contiguous() if shift is not None else None)
+
+
+def prep_exact(w, scale=None, shift=None):
+    """(K-major fp32 weight ``[cin][k k][cout]`` of ``w * scale[co]``, folded in float64; the shift as fp32 bias or None) for ``conv_exact``.  Plain torch."""
+    cout, cin, k, _ = w.shape
+    if scale is not None:
+        w = (w.double() * scale[:, None, None, None]).float()
+    return w.permute(1, 2, 3, 0).reshape(cin, k * k, cout).contiguous(), (shift.float().contiguous() if shift is not None else None)
 
 
 def prep_dgrad(w, out_scale=None, in_scale=None):
@@ -100,6 +116,19 @@ def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] 
         out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
     lib().call("e4s_conv2d_sb3" if len(slabs) == 3 else "e4s_conv2d_sb", _p(out), _p(x), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, _p(slope),
                _p(residual), 2 if slope is not None else 1 if relu else 0, bs, cin, cout, h, w, k, stride, pad, _stream())
+    return out
+
+
+def conv_exact(x, wt, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, slope=None, residual=None, out=None):
+    """Exact-float32 convolution of csrc/conv.hip (``e4s_conv2d``) on a K-major weight (``prep_exact``, or ``e4s_conv_prep_weights``' copy of that layout);
+    ``pad``, ``slope``, ``residual`` and ``out`` as ``conv_sb`` takes them."""
+    bs, cin, h, w = x.shape
+    cout = wt.numel() // (cin * k * k)
+    pad = k // 2 if pad is None else pad
+    if out is None:
+        out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv2d", _p(out), _p(x), None, 0, _p(wt), _p(bias), None, None, _p(slope), _p(residual), 2 if slope is not None else 1 if relu else 0,
+               bs, cin, cout, h, w, k, stride, pad, _stream())
     return out
 
 

@@ -1,6 +1,8 @@
-"""What the stage modules (``ops_recolor``, ``ops_rrdb``, ``ops_gpen*``, ``ops_parsenet``, ``ops_retinaface``) and ``pipeline`` share when they take a network's
-weights and tensors from a caller: the description of a network (``_Net``), the one validation of a module or mapping against it (``_validated``: keys, shapes
-and dtypes checked once per public call and handed on to ``lossnet.prepare``), and the tensor checks every public call makes before any launch."""
+"""What the stage modules (``ops_recolor``, ``ops_rrdb``, ``ops_gpen*``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) and ``pipeline`` share when they take a
+network's weights and tensors from a caller: the description of a network (``_Net``; ``module_net`` pins it to the structure a mirror module was built with), the
+one validation of a module or mapping against it (``_validated``: keys, shapes and dtypes checked once per public call and handed on to ``lossnet.prepare``), the
+cache of the kernels' copies of the weights (``PreparedNet``: a network states its ``_Net`` and builds its payload, the key and the look-up are here), and the
+tensor checks every public call makes before any launch."""
 from __future__ import annotations
 
 import functools
@@ -8,6 +10,11 @@ from collections import namedtuple
 
 import torch
 import torch.nn as nn
+
+from .lossnet import weights_key
+from .ops import _Prepared, _c
+
+EVAL_ONLY = "the native path is the eval-mode forward (BatchNorm's running statistics)"       # a ``_Net.training`` most networks with a BatchNorm share
 
 
 def _tensor_checked(name, nm, t, dtype, ndim, what):
@@ -21,6 +28,22 @@ def _cuda_checked(name, **tensors):
     for nm, t in tensors.items():
         if not t.is_cuda:
             raise RuntimeError(f"{name}: {nm} must be a CUDA tensor")
+
+
+def _image_checked(name, x, img_u8, what_x, what_u8):
+    """The image argument of a public call, a float32 ``x [bs, C, H, W]`` or, without one, a uint8 ``img_u8 [bs, H, W, C]``: type, dtype and rank checked
+    (``what_*``: the expectation the message states).  Returns (the tensor, its argument name, H, W, C); the sizes a network allows are the caller's rules."""
+    if x is not None:
+        _tensor_checked(name, "x", x, torch.float32, 4, what_x)
+        return x, "x", x.shape[2], x.shape[3], x.shape[1]
+    _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, what_u8)
+    return img_u8, "img_u8", img_u8.shape[1], img_u8.shape[2], img_u8.shape[3]
+
+
+def _placed_checked(name, nm, t, ts):
+    """``t`` is on a GPU, and on the one the weight tensors ``ts`` are on: the last two refusals of a public call."""
+    _cuda_checked(name, **{nm: t})
+    _devices_checked(name, nm, t, ts)
 
 
 # What ``_validated`` needs to know of a network: ``cls`` its name in messages; ``shapes(variant)`` the public ``{key: shape}`` function; ``prefixes`` the key
@@ -76,3 +99,57 @@ def _validated(name, weights, net):
 def _devices_checked(name, nm, t, ts):
     if any(w.device != t.device for w in ts):
         raise RuntimeError(f"{name}: device mismatch: {nm} on {t.device}, the weights on {sorted({str(w.device) for w in ts})}")
+
+
+_MODULE_NETS = {}
+
+
+def module_net(base, structure):
+    """``base`` with its variant pinned to ``structure``: what a mirror module, which knows the configuration it was built with, is validated against (only a
+    mapping has its structure read off its keys and shapes).  One ``_Net`` object per (base, structure), so ``_float_keys`` caches on it."""
+    net = _MODULE_NETS.get((base, structure))
+    if net is None:
+        net = _MODULE_NETS[base, structure] = base._replace(variant=lambda name, sd: structure)
+    return net
+
+
+def check_loaded(name, weights, what):
+    """Raises for a mirror module that still has the random weights it was built with (``_loaded`` False: an output from them would be silently wrong).
+    ``what``: the weights as the message names them; ``name`` None: no entry in front."""
+    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
+        raise RuntimeError(f"{name + ': ' if name else ''}{type(weights).__name__}: {what} were never loaded (nothing is downloaded here); call load_state_dict first")
+
+
+def bn_shapes(out, prefix, c):
+    """The five ``state_dict`` entries of a BatchNorm over ``c`` channels, added to ``out`` in their order."""
+    for k in ("weight", "bias", "running_mean", "running_var"):
+        out[f"{prefix}.{k}"] = (c,)
+    out[prefix + ".num_batches_tracked"] = ()
+
+
+class PreparedNet(_Prepared):
+    """The kernels' copies of a stage network's weights, cached per storage and version of every tensor, the device and ``_settings()``.  A network states
+    ``_entry``, the public name its messages carry; ``_net``, its ``_Net``, or a method ``_net(weights)`` where a mirror module pins the structure; if its payload
+    depends on module knobs, ``_settings()``, read at call time; and ``_build(sd, variant, dev)``: the payload from the contiguous float tensors ``sd`` by bare
+    key, called under ``no_grad``."""
+
+    __slots__ = ()
+    _entry = _net = None
+
+    def _settings(self) -> tuple:
+        return ()
+
+    def _build(self, sd, variant, dev):
+        raise NotImplementedError
+
+    def get(self, weights, checked=None):
+        """The payload for ``weights``; ``checked``: what the caller's own ``_validated`` of them returned, so that it is not made twice."""
+        net = self._net if isinstance(self._net, _Net) else self._net(weights)
+        sd, variant, ts = checked if checked is not None else _validated(self._entry, weights, net)
+        key = weights_key(ts) + (ts[0].device,) + self._settings()
+        hit = self._lookup(key)
+        if hit is not None:
+            return hit
+        sd = {k: _c(sd[k].detach(), k) for k, _ in _float_keys(net, variant)}
+        with torch.no_grad():
+            return self._publish(key, self._build(sd, variant, ts[0].device))

@@ -32,8 +32,8 @@ from typing import Optional
 
 from . import lossnet
 from ._lib import lib
-from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_sb, cos_heads, cos_heads_multi, pool_matrix, prep_dgrad, prep_fwd,
-                      relu_mask, target_rows, weights_key)
+from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_exact, conv_sb, cos_heads, cos_heads_multi, pool_matrix, prep_dgrad,
+                      prep_fwd, relu_mask, target_rows, weights_key)
 from .ops import _Prepared, _c, _p, _stream
 
 SIDE = 512                                   # FaceParsingLoss.face_pool: AdaptiveAvgPool2d((512, 512)) unless x.shape[2] == 512
@@ -222,14 +222,8 @@ def _network_input(xs, R):
 
 # ------------------------------------------------------------------------------------------------ forward
 def _conv_relu(x, B, which):
-    if which == 1 and B["cin"] < 16:
-        n, cin, h, w = x.shape
-        cout = B["cout"]
-        out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
-        wt, bias = B["fwd1"]
-        lib().call("e4s_conv2d", _p(out), _p(x), None, cin, _p(wt), _p(bias), None, None, None, None, 1, n, cin, cout, h, w, 3, 1, 1, _stream())
-        return out
-    return conv_sb(x, *B["fwd1" if which == 1 else "fwd2"], k=3, relu=True)
+    conv = conv_exact if which == 1 and B["cin"] < 16 else conv_sb
+    return conv(x, *B["fwd1" if which == 1 else "fwd2"], k=3, relu=True)
 
 
 def _encoder(x, P):

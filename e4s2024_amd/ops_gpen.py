@@ -40,11 +40,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet
+from . import lossnet, netweights
 from ._lib import MAX_STYLE_JOBS, StyleJob, lib
-from .lossnet import weights_key
-from .ops import _Prepared, _c, _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
-from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .ops import _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
+from .netweights import PreparedNet, _Net, _cuda_checked, _image_checked, _keys_shapes, _placed_checked, _tensor_checked, _validated, module_net
 
 ARITH = "sb"                                 # "sb" | "f32" (module attribute, no environment variable: tests and tools set it)
 UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form (measured: see the module text)
@@ -297,19 +296,12 @@ def _gpen_shapes(variant):
     return gpen_state_dict_shapes(*variant)
 
 
-_MODULE_NETS = {}
-
-
 def _net_of(weights):
     """The description ``_validated`` checks ``weights`` against.  A ``GPEN`` module hands over the configuration it was built with; only a mapping has it
     read off its keys and shapes (``_gpen_variant``), which recovers ``narrow`` and ``channel_multiplier`` up to what ``int()`` left of them."""
     if not isinstance(weights, GPEN):
         return _GPEN_NET
-    cfg = (weights.size, weights.style_dim, weights.n_mlp, weights.channel_multiplier, weights.narrow)
-    net = _MODULE_NETS.get(cfg)
-    if net is None:
-        net = _MODULE_NETS[cfg] = _GPEN_NET._replace(variant=lambda name, sd, cfg=cfg: cfg)
-    return net
+    return module_net(_GPEN_NET, (weights.size, weights.style_dim, weights.n_mlp, weights.channel_multiplier, weights.narrow))
 
 
 _GPEN_NET = _Net("FullGenerator", _gpen_shapes, ("module.",), False, ("ecd0.0.0.weight",), _gpen_variant,
@@ -323,8 +315,7 @@ def gpen_weight_tensors(weights, name: str = "gpen_forward"):
 
 def check_loaded(weights):
     """``weights`` itself; raises if it is a module whose weights were never loaded (an enhancement from initial parameters would be silently wrong)."""
-    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
-        raise RuntimeError(f"{type(weights).__name__}: the GPEN weights were never loaded (nothing is downloaded here); call load_state_dict first")
+    netweights.check_loaded(None, weights, "the GPEN weights")
     return weights
 
 
@@ -332,24 +323,24 @@ def _use_composed(w_in: int) -> bool:
     return ARITH != "sb" or w_in <= UP_COMPOSED_MAX_WIDTH
 
 
-class PreparedGPEN(_Prepared):
+class PreparedGPEN(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage or the arithmetic changes.  ``stem``: ecd0's weight with
     its scale, ``[C0, 3]``, and bias; ``enc``: per level (FIR, slabs or K-major fp32 weight, bias, slope vector) with sqrt(2) folded into weight and bias in
     float64; ``final`` and ``mlp``: the EqualLinear weights as they are (scale and lr_mul are call arguments); per modulated convolution its split-bf16 slabs
     (or K-major fp32 weight), ``wsq`` table, modulation weights, noise weight and activation bias; per ToRGB its ``k = 1`` weight."""
 
     __slots__ = ()
+    _entry = "gpen_forward"
 
-    def get(self, weights, checked=None):
-        sd, variant, ts = checked if checked is not None else _validated("gpen_forward", weights, _net_of(weights))
-        key = weights_key(ts) + (ts[0].device, ARITH, UP_COMPOSED_MAX_WIDTH)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in gpen_state_dict_shapes(*variant)}
+    def _net(self, weights):
+        return _net_of(weights)
+
+    def _settings(self):
+        return ARITH, UP_COMPOSED_MAX_WIDTH
+
+    def _build(self, sd, variant, dev):
         size, sdim, n_mlp, _, _ = variant
         log_size = int(math.log2(size))
-        dev = ts[0].device
         sb = ARITH == "sb"
         st = _stream()
         new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
@@ -391,20 +382,18 @@ class PreparedGPEN(_Prepared):
             return dict(wt=wt, mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], bias=sd[p + ".bias"].reshape(3).contiguous(),
                         upk=sd[p + ".upsample.kernel"] if up else None, cin=cin)
 
-        with torch.no_grad():
-            W0 = sd["ecd0.0.0.weight"]
-            g = "generator."
-            convs, rgbs = [styled(g + "conv1", False, 4)], [rgb(g + "to_rgb1", False)]
-            for j in range(log_size - 2):
-                convs += [styled(f"{g}convs.{2 * j}", True, 4 << j), styled(f"{g}convs.{2 * j + 1}", False, 8 << j)]
-                rgbs.append(rgb(f"{g}to_rgbs.{j}", True))
-            P = dict(size=size, sdim=sdim, log_size=log_size, sb=sb,
-                     stem=((W0 * (1 / math.sqrt(3))).reshape(W0.shape[0], 3).contiguous(), sd["ecd0.0.1.bias"]),
-                     enc=[enc_level(i) for i in range(1, log_size - 1)],
-                     final=(sd["final_linear.0.weight"], sd["final_linear.0.bias"]),
-                     mlp=[(sd[f"{g}style.{i}.weight"], sd[f"{g}style.{i}.bias"]) for i in range(1, n_mlp + 1)],
-                     const=sd[g + "input.input"], convs=convs, rgbs=rgbs)
-        return self._publish(key, P)
+        W0 = sd["ecd0.0.0.weight"]
+        g = "generator."
+        convs, rgbs = [styled(g + "conv1", False, 4)], [rgb(g + "to_rgb1", False)]
+        for j in range(log_size - 2):
+            convs += [styled(f"{g}convs.{2 * j}", True, 4 << j), styled(f"{g}convs.{2 * j + 1}", False, 8 << j)]
+            rgbs.append(rgb(f"{g}to_rgbs.{j}", True))
+        return dict(size=size, sdim=sdim, log_size=log_size, sb=sb,
+                    stem=((W0 * (1 / math.sqrt(3))).reshape(W0.shape[0], 3).contiguous(), sd["ecd0.0.1.bias"]),
+                    enc=[enc_level(i) for i in range(1, log_size - 1)],
+                    final=(sd["final_linear.0.weight"], sd["final_linear.0.bias"]),
+                    mlp=[(sd[f"{g}style.{i}.weight"], sd[f"{g}style.{i}.bias"]) for i in range(1, n_mlp + 1)],
+                    const=sd[g + "input.input"], convs=convs, rgbs=rgbs)
 
 
 # ------------------------------------------------------------------------------------------------ the forward pass
@@ -555,19 +544,11 @@ def _gpen_checked_all(name, weights, x=None, img_u8=None):
     check_loaded(weights)
     checked = _validated(name, weights, _net_of(weights))
     size = checked[1][0]
-    if x is not None:
-        _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, size, size] image")
-        if tuple(x.shape[1:]) != (3, size, size):
-            raise ValueError(f"{name}: x is {tuple(x.shape)}: the network's size is {size}, expected [bs, 3, {size}, {size}]")
-        t, nm = x, "x"
-    else:
-        _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, "a uint8 [bs, size, size, 3] RGB image")
-        if tuple(img_u8.shape[1:]) != (size, size, 3):
-            raise ValueError(f"{name}: img_u8 is {tuple(img_u8.shape)}: the network's size is {size}, expected [bs, {size}, {size}, 3] "
-                             "(resizing to the network's size is the caller's)")
-        t, nm = img_u8, "img_u8"
-    _cuda_checked(name, **{nm: t})
-    _devices_checked(name, nm, t, checked[2])
+    t, nm, H, W, c = _image_checked(name, x, img_u8, "a float32 [bs, 3, size, size] image", "a uint8 [bs, size, size, 3] RGB image")
+    if (c, H, W) != (3, size, size):
+        expected = f"[bs, 3, {size}, {size}]" if x is not None else f"[bs, {size}, {size}, 3] (resizing to the network's size is the caller's)"
+        raise ValueError(f"{name}: {nm} is {tuple(t.shape)}: the network's size is {size}, expected {expected}")
+    _placed_checked(name, nm, t, checked[2])
     if ARITH not in ("sb", "f32"):
         raise ValueError(f"{name}: ops_gpen.ARITH is 'sb' or 'f32', got {ARITH!r}")
     return checked

@@ -28,9 +28,9 @@ import torch.nn.functional as F
 
 from . import lossnet
 from ._lib import lib
-from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
-from .ops import _Prepared, _c, _p, _stream
-from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .lossnet import bn_fold, conv_sb, prep_fwd
+from .ops import _p, _stream
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _keys_shapes, _placed_checked, _validated, bn_shapes, check_loaded, module_net
 
 SLOPE = 0.2                                  # ReluLayer's LeakyReLU (blocks.py:58)
 # FaceParse.MASK_COLORMAP (face_parsing.py:30): background, hat (14) and cloth (18) are 0, every other class 255
@@ -167,9 +167,7 @@ def _conv_shapes(out, p, cin, cout, bn):
     if not bn:
         out[p + ".conv2d.bias"] = (cout,)
         return
-    for k in ("weight", "bias", "running_mean", "running_var"):
-        out[f"{p}.norm.norm.{k}"] = (cout,)
-    out[p + ".norm.norm.num_batches_tracked"] = ()
+    bn_shapes(out, p + ".norm.norm", cout)
 
 
 def _block_prefixes(blocks):
@@ -221,19 +219,13 @@ def _structure_of_keys(name, sd):
     return c0, tuple(blocks), int(w[1]), int(w[0])
 
 
-_PARSENET_NET = _Net("ParseNet", parsenet_structure_shapes, ("module.",), False, ("encoder.0.conv2d.weight",), _structure_of_keys,
-                     "the native path is the eval-mode forward (BatchNorm's running statistics)", ("num_batches_tracked",))
-_MODULE_NETS = {}
+_PARSENET_NET = _Net("ParseNet", parsenet_structure_shapes, ("module.",), False, ("encoder.0.conv2d.weight",), _structure_of_keys, EVAL_ONLY,
+                     ("num_batches_tracked",))
 
 
 def _net_of(weights):
     """The description ``_validated`` checks ``weights`` against: a ``ParseNet`` module is held to the structure it was built with."""
-    if not isinstance(weights, ParseNet):
-        return _PARSENET_NET
-    net = _MODULE_NETS.get(weights.structure)
-    if net is None:
-        net = _MODULE_NETS[weights.structure] = _PARSENET_NET._replace(variant=lambda name, sd, s=weights.structure: s)
-    return net
+    return module_net(_PARSENET_NET, weights.structure) if isinstance(weights, ParseNet) else _PARSENET_NET
 
 
 def parsenet_weight_tensors(weights, name: str = "parsenet_forward"):
@@ -241,27 +233,19 @@ def parsenet_weight_tensors(weights, name: str = "parsenet_forward"):
     return _validated(name, weights, _net_of(weights))[2]
 
 
-def _check_loaded(name, weights):
-    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
-        raise RuntimeError(f"{name}: {type(weights).__name__}: the ParseNet weights were never loaded (nothing is downloaded here); call load_state_dict first")
-
-
-class PreparedParseNet(_Prepared):
+class PreparedParseNet(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  ``stem``: encoder.0's weight ``[C0, 27]`` and bias as
     they are; per block the three-way split slabs and float32 biases of ``conv1`` / ``conv2`` with the eval BatchNorm folded in float64 and of the shortcut
     convolution, and the 0.2 slope vector; ``head19`` / ``head22``: ``out_mask_conv`` alone and with ``out_img_conv`` behind it; ``lut``: img2tensor's 256
     values; ``cmap``: MASK_COLORMAP as uint8."""
 
     __slots__ = ()
+    _entry = "parsenet_forward"
 
-    def get(self, weights, checked=None):
-        sd, structure, ts = checked if checked is not None else _validated("parsenet_forward", weights, _net_of(weights))
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        dev = ts[0].device
-        sd = {k: _c(sd[k].detach(), k) for k in parsenet_structure_shapes(structure) if not k.endswith("num_batches_tracked")}
+    def _net(self, weights):
+        return _net_of(weights)
+
+    def _build(self, sd, structure, dev):
         c0, blocks, _, ncls = structure
 
         def plain(p):
@@ -270,17 +254,15 @@ class PreparedParseNet(_Prepared):
         def normed(p):
             return prep_fwd(sd[p + ".conv2d.weight"], *bn_fold(sd, p + ".norm.norm"))
 
-        with torch.no_grad():
-            layers = [dict(group=p.split(".")[0], scale=scale, cout=cout, sc=plain(p + ".shortcut_func") if shortcut else None, c1=normed(p + ".conv1"),
-                           c2=normed(p + ".conv2"), slope=torch.full((cout,), SLOPE, dtype=torch.float32, device=dev))
-                      for p, scale, _, cout, shortcut in _block_prefixes(blocks)]
-            wm, bm = sd["out_mask_conv.conv2d.weight"], sd["out_mask_conv.conv2d.bias"]
-            wi, bi = sd["out_img_conv.conv2d.weight"], sd["out_img_conv.conv2d.bias"]
-            P = dict(c0=c0, ncls=ncls, stem=(sd["encoder.0.conv2d.weight"].reshape(c0, 27).contiguous(), sd["encoder.0.conv2d.bias"]), blocks=layers,
-                     head19=prep_fwd(wm, None, bm.double()), head22=prep_fwd(torch.cat((wm, wi)), None, torch.cat((bm, bi)).double()),
-                     lut=torch.from_numpy(img2tensor_table()).to(dev),
-                     cmap=torch.tensor([MASK_COLORMAP[c] if c < len(MASK_COLORMAP) else 255 for c in range(ncls)], dtype=torch.uint8).to(dev))
-        return self._publish(key, P)
+        layers = [dict(group=p.split(".")[0], scale=scale, cout=cout, sc=plain(p + ".shortcut_func") if shortcut else None, c1=normed(p + ".conv1"),
+                       c2=normed(p + ".conv2"), slope=torch.full((cout,), SLOPE, dtype=torch.float32, device=dev))
+                  for p, scale, _, cout, shortcut in _block_prefixes(blocks)]
+        wm, bm = sd["out_mask_conv.conv2d.weight"], sd["out_mask_conv.conv2d.bias"]
+        wi, bi = sd["out_img_conv.conv2d.weight"], sd["out_img_conv.conv2d.bias"]
+        return dict(c0=c0, ncls=ncls, stem=(sd["encoder.0.conv2d.weight"].reshape(c0, 27).contiguous(), sd["encoder.0.conv2d.bias"]), blocks=layers,
+                    head19=prep_fwd(wm, None, bm.double()), head22=prep_fwd(torch.cat((wm, wi)), None, torch.cat((bm, bi)).double()),
+                    lut=torch.from_numpy(img2tensor_table()).to(dev),
+                    cmap=torch.tensor([MASK_COLORMAP[c] if c < len(MASK_COLORMAP) else 255 for c in range(ncls)], dtype=torch.uint8).to(dev))
 
 
 # ------------------------------------------------------------------------------------------------ the forward pass
@@ -337,14 +319,9 @@ def parsenet_output_size(structure, H: int, W: int):
 
 def _checked_all(name, weights, x=None, img_u8=None, sized=False):
     """Everything that can be refused, before any launch: (checked weights, output size)."""
-    _check_loaded(name, weights)
+    check_loaded(name, weights, "the ParseNet weights")
     checked = _validated(name, weights, _net_of(weights))
-    if x is not None:
-        _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image")
-        t, nm, (H, W), c = x, "x", x.shape[2:], x.shape[1]
-    else:
-        _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, "a uint8 [bs, S, S, 3] image")
-        t, nm, (H, W), c = img_u8, "img_u8", img_u8.shape[1:3], img_u8.shape[3]
+    t, nm, H, W, c = _image_checked(name, x, img_u8, "a float32 [bs, 3, H, W] image", "a uint8 [bs, S, S, 3] image")
     if c != 3:
         raise ValueError(f"{name}: {nm} is {tuple(t.shape)}: expected three colour channels")
     in_size = getattr(weights, "in_size", None)
@@ -354,8 +331,7 @@ def _checked_all(name, weights, x=None, img_u8=None, sized=False):
     out_hw = parsenet_output_size(checked[1], int(H), int(W))
     if out_hw is None or max(out_hw) > 16384 or max(H, W) > 16384:
         raise ValueError(f"{name}: {nm} is {H} x {W}: every feature map of the network must stay at least 2 x 2 (and no side above 16384)")
-    _cuda_checked(name, **{nm: t})
-    _devices_checked(name, nm, t, checked[2])
+    _placed_checked(name, nm, t, checked[2])
     return checked, out_hw
 
 

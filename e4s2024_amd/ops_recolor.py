@@ -62,9 +62,9 @@ import torch.nn.functional as F
 
 from . import lossnet, ops_rrdb
 from ._lib import lib
-from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
-from .netweights import _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
-from .ops import _Prepared, _c, _p, _stream
+from .lossnet import bn_fold, conv_sb, fold_conv_bn, prep_fwd
+from .netweights import PreparedNet, _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .ops import _p, _stream
 from .ops_post import GREY_MORPH_MAX_RADIUS, grey_dilate
 from .ops_rrdb import GpenSRNet
 
@@ -340,35 +340,28 @@ def resunet_weight_tensors(weights):
     return _validated("blender_unet", weights, _RESUNET_NET)[2]
 
 
-class PreparedResUNet(_Prepared):
+class PreparedResUNet(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  Per block: ``pre`` the float32 (scale, shift) of
     the pre-activation BatchNorm (None for the input block), ``conv1`` with the BatchNorm after it and its own bias folded in (float64), ``conv2`` and
     ``sqz`` with their biases, all as three-way split slabs; ``head`` the output convolution's weight [3, width] and bias."""
 
     __slots__ = ()
+    _entry, _net = "blender_unet", _RESUNET_NET
 
-    def get(self, weights, checked=None):
-        sd, width, ts = checked if checked is not None else _validated("blender_unet", weights, _RESUNET_NET)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in resunet_state_dict_shapes(width) if not k.endswith("num_batches_tracked")}
+    def _build(self, sd, width, dev):
         blocks = {}
-        with torch.no_grad():
-            for name in ("input_encoder_layer",) + _ENCODER + _DECODER:
-                first = name == "input_encoder_layer"
-                pre = None
-                if not first:
-                    s, t = bn_fold(sd, name + ".bn1")
-                    pre = (s.float().contiguous(), t.float().contiguous())
-                s, t = bn_fold(sd, name + (".bn1" if first else ".bn2"))
-                blocks[name] = dict(pre=pre, stride=2 if name in _ENCODER else 1,
-                                    conv1=prep_fwd(sd[name + ".conv1.weight"], s, t + sd[name + ".conv1.bias"].double() * s),
-                                    conv2=prep_fwd(sd[name + ".conv2.weight"], None, sd[name + ".conv2.bias"]),
-                                    sqz=prep_fwd(sd[name + ".sqz_layer.weight"], None, sd[name + ".sqz_layer.bias"]))
-            head = (sd["output_decoder_layer.0.weight"].reshape(3, width).contiguous(), sd["output_decoder_layer.0.bias"].contiguous())
-        return self._publish(key, dict(width=width, blocks=blocks, head=head))
+        for name in ("input_encoder_layer",) + _ENCODER + _DECODER:
+            first = name == "input_encoder_layer"
+            pre = None
+            if not first:
+                s, t = bn_fold(sd, name + ".bn1")
+                pre = (s.float().contiguous(), t.float().contiguous())
+            blocks[name] = dict(pre=pre, stride=2 if name in _ENCODER else 1,
+                                conv1=prep_fwd(sd[name + ".conv1.weight"], *fold_conv_bn(sd, name + ".conv1", name + (".bn1" if first else ".bn2"))),
+                                conv2=prep_fwd(sd[name + ".conv2.weight"], None, sd[name + ".conv2.bias"]),
+                                sqz=prep_fwd(sd[name + ".sqz_layer.weight"], None, sd[name + ".sqz_layer.bias"]))
+        head = (sd["output_decoder_layer.0.weight"].reshape(3, width).contiguous(), sd["output_decoder_layer.0.bias"].contiguous())
+        return dict(width=width, blocks=blocks, head=head)
 
 
 def _block(B, x, act, x1=None):
@@ -576,38 +569,32 @@ def _sigma_folded(sd, prefix):
     return (w / sigma).float()
 
 
-class PreparedFPN(_Prepared):
+class PreparedFPN(PreparedNet):
     """The kernels' copies of a feature network's weights, rebuilt when a tensor changes version or storage.  ``BlenderFPN``: ``layers`` the five
     convolutions with sigma folded in, per block ``conv_0`` / ``conv_1`` (with bias) and ``conv_s`` likewise and per norm the gamma and beta convolutions
     concatenated into one of ``2 C`` outputs, all as three-way split slabs; ``shared`` the first layers of the seven norms stacked ``[7 * 128, 3, 3, 3]``
     with their biases.  ``SmallFPN``: its two convolutions."""
 
     __slots__ = ()
+    _entry, _net = "blender_fpn", _FPN_NET
 
-    def get(self, weights, checked=None):
-        sd, small, ts = checked if checked is not None else _validated("blender_fpn", weights, _FPN_NET)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in fpn_state_dict_shapes(small)}
-        with torch.no_grad():
-            if small:
-                return self._publish(key, dict(small=True, convs=[prep_fwd(sd[f"{n}.weight"], None, sd[f"{n}.bias"]) for n in ("conv1", "conv2")]))
-            layers = [dict(conv=prep_fwd(_sigma_folded(sd, name + ".0")), stride=stride) for name, _, _, stride in _FPN_LAYERS]
-            norms = _fpn_norms()
-            blocks = []
-            for name, fin, fout in _FPN_BLOCKS:
-                B = dict(conv_0=prep_fwd(_sigma_folded(sd, name + ".conv_0"), None, sd[name + ".conv_0.bias"]),
-                         conv_1=prep_fwd(_sigma_folded(sd, name + ".conv_1"), None, sd[name + ".conv_1.bias"]),
-                         conv_s=prep_fwd(_sigma_folded(sd, name + ".conv_s")) if fin != fout else None)
-                for n in ("norm_0", "norm_1") + (("norm_s",) if fin != fout else ()):
-                    p = f"{name}.{n}"
-                    B[n] = (norms.index(p), prep_fwd(torch.cat([sd[p + ".mlp_gamma.weight"], sd[p + ".mlp_beta.weight"]]), None,
-                                                     torch.cat([sd[p + ".mlp_gamma.bias"], sd[p + ".mlp_beta.bias"]])))
-                blocks.append(B)
-            shared = (torch.cat([sd[p + ".mlp_shared.1.weight"] for p in norms]).contiguous(), torch.cat([sd[p + ".mlp_shared.1.bias"] for p in norms]).contiguous())
-        return self._publish(key, dict(small=False, layers=layers, blocks=blocks, shared=shared, nnorms=len(norms)))
+    def _build(self, sd, small, dev):
+        if small:
+            return dict(small=True, convs=[prep_fwd(sd[f"{n}.weight"], None, sd[f"{n}.bias"]) for n in ("conv1", "conv2")])
+        layers = [dict(conv=prep_fwd(_sigma_folded(sd, name + ".0")), stride=stride) for name, _, _, stride in _FPN_LAYERS]
+        norms = _fpn_norms()
+        blocks = []
+        for name, fin, fout in _FPN_BLOCKS:
+            B = dict(conv_0=prep_fwd(_sigma_folded(sd, name + ".conv_0"), None, sd[name + ".conv_0.bias"]),
+                     conv_1=prep_fwd(_sigma_folded(sd, name + ".conv_1"), None, sd[name + ".conv_1.bias"]),
+                     conv_s=prep_fwd(_sigma_folded(sd, name + ".conv_s")) if fin != fout else None)
+            for n in ("norm_0", "norm_1") + (("norm_s",) if fin != fout else ()):
+                p = f"{name}.{n}"
+                B[n] = (norms.index(p), prep_fwd(torch.cat([sd[p + ".mlp_gamma.weight"], sd[p + ".mlp_beta.weight"]]), None,
+                                                 torch.cat([sd[p + ".mlp_gamma.bias"], sd[p + ".mlp_beta.bias"]])))
+            blocks.append(B)
+        shared = (torch.cat([sd[p + ".mlp_shared.1.weight"] for p in norms]).contiguous(), torch.cat([sd[p + ".mlp_shared.1.bias"] for p in norms]).contiguous())
+        return dict(small=False, layers=layers, blocks=blocks, shared=shared, nnorms=len(norms))
 
 
 def _plane_stats(x):

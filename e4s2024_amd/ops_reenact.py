@@ -26,9 +26,9 @@ import torch.nn.functional as F
 
 from . import lossnet
 from ._lib import lib
-from .lossnet import bn_fold, conv_sb, prep_fwd, weights_key
-from .ops import _Prepared, _c, _p, _stream
-from .netweights import _Net, _cuda_checked, _devices_checked, _tensor_checked, _validated
+from .lossnet import conv_exact, conv_sb, fold_conv_bn, prep_exact, prep_fwd
+from .ops import _c, _p, _stream
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, bn_shapes, check_loaded, module_net
 
 NUM_BINS = 66                                # headpose_pred_to_degree's idx_tensor is range(66) whatever the module's num_bins
 
@@ -283,12 +283,6 @@ class HEEstimator(_Loadable):
 
 
 # ------------------------------------------------------------------------------------------------ weights: keys, shapes, validation
-def _bn_shapes(out, p, c):
-    for k in ("weight", "bias", "running_mean", "running_var"):
-        out[f"{p}.{k}"] = (c,)
-    out[p + ".num_batches_tracked"] = ()
-
-
 def kp_detector_structure_shapes(structure):
     """``{key: shape}`` of the ``KPDetector`` with ``structure`` (``kp_detector_structure``), in ``state_dict`` order."""
     cin, down, depth, up, K, jmaps, k, _ = structure
@@ -296,12 +290,12 @@ def kp_detector_structure_shapes(structure):
     for i, c in enumerate(down):
         p = f"predictor.down_blocks.down{i}"
         out[p + ".conv.weight"], out[p + ".conv.bias"] = (c, cin if i == 0 else down[i - 1], 3, 3), (c,)
-        _bn_shapes(out, p + ".norm", c)
+        bn_shapes(out, p + ".norm", c)
     out["predictor.conv.weight"], out["predictor.conv.bias"] = (depth * down[-1], down[-1], 1, 1), (depth * down[-1],)
     for i, c in enumerate(up):
         p = f"predictor.up_blocks.up{i}"
         out[p + ".conv.weight"], out[p + ".conv.bias"] = (c, down[-1] if i == 0 else up[i - 1], 3, 3, 3), (c,)
-        _bn_shapes(out, p + ".norm", c)
+        bn_shapes(out, p + ".norm", c)
     out["kp.weight"], out["kp.bias"] = (K, up[-1], 3, 3, 3), (K,)
     if jmaps:
         out["jacobian.weight"], out["jacobian.bias"] = (9 * jmaps, up[-1], 3, 3, 3), (9 * jmaps,)
@@ -320,16 +314,16 @@ def he_estimator_structure_shapes(structure):
 
     def bottleneck(p, c, strided):
         conv(p + ".conv1", c // 4, c, 1), conv(p + ".conv2", c // 4, c // 4, 3), conv(p + ".conv3", c, c // 4, 1)
-        _bn_shapes(out, p + ".norm1", c // 4), _bn_shapes(out, p + ".norm2", c // 4), _bn_shapes(out, p + ".norm3", c)
+        bn_shapes(out, p + ".norm1", c // 4), bn_shapes(out, p + ".norm2", c // 4), bn_shapes(out, p + ".norm3", c)
         if strided:
-            conv(p + ".skip", c, c, 1), _bn_shapes(out, p + ".norm4", c)
+            conv(p + ".skip", c, c, 1), bn_shapes(out, p + ".norm4", c)
 
-    conv("conv1", be, cin, 7), _bn_shapes(out, "norm1", be)
-    conv("conv2", 256, be, 1), _bn_shapes(out, "norm2", 256)
+    conv("conv1", be, cin, 7), bn_shapes(out, "norm1", be)
+    conv("conv2", 256, be, 1), bn_shapes(out, "norm2", 256)
     for i in range(3):
         bottleneck(f"block1.b1_{i}", 256, False)
     for (cv, norm, c), strided, (group, letter, n) in _HE_STAGES:
-        conv(cv, c, c // 2, 1), _bn_shapes(out, norm, c)
+        conv(cv, c, c // 2, 1), bn_shapes(out, norm, c)
         bottleneck(strided, c, True)
         for i in range(n):
             bottleneck(f"{group}.{letter}{i}", c, False)
@@ -383,28 +377,16 @@ def _he_structure_of_keys(name, sd):
     return cin, be, _shape_of(name, sd, "fc_roll.weight", 2, "HEEstimator")[0], _shape_of(name, sd, "fc_exp.weight", 2, "HEEstimator")[0] // 3
 
 
-_EVAL = "the native path is the eval-mode forward (BatchNorm's running statistics)"
-_KP_NET = _Net("KPDetector", kp_detector_structure_shapes, ("module.", "kp_detector."), True, ("predictor.conv.weight",), _kp_structure_of_keys, _EVAL,
+_KP_NET = _Net("KPDetector", kp_detector_structure_shapes, ("module.", "kp_detector."), True, ("predictor.conv.weight",), _kp_structure_of_keys, EVAL_ONLY,
                ("num_batches_tracked",))
-_HE_NET = _Net("HEEstimator", he_estimator_structure_shapes, ("module.", "he_estimator."), True, ("conv1.weight",), _he_structure_of_keys, _EVAL,
+_HE_NET = _Net("HEEstimator", he_estimator_structure_shapes, ("module.", "he_estimator."), True, ("conv1.weight",), _he_structure_of_keys, EVAL_ONLY,
                ("num_batches_tracked",))
-_MODULE_NETS = {}
 
 
 def _net_of(weights, base):
     """The description ``_validated`` checks ``weights`` against (``base``: ``_KP_NET`` or ``_HE_NET``): a mirror module is held to the structure it was built
     with, anything else to the structure its keys and shapes spell."""
-    if not isinstance(weights, KPDetector if base is _KP_NET else HEEstimator):
-        return base
-    key = (base.cls, weights.structure)
-    if key not in _MODULE_NETS:
-        _MODULE_NETS[key] = base._replace(variant=lambda name, sd, s=weights.structure: s)
-    return _MODULE_NETS[key]
-
-
-def _check_loaded(name, weights):
-    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
-        raise RuntimeError(f"{name}: {type(weights).__name__}: the weights were never loaded (nothing is downloaded here); call load_state_dict first")
+    return module_net(base, weights.structure) if isinstance(weights, KPDetector if base is _KP_NET else HEEstimator) else base
 
 
 def _slabs3d(cout, cin, device):
@@ -442,100 +424,69 @@ def conv3d_sb3(x, slabs, bias=None, *, relu: bool = False, residual=None, up_hw:
     return out
 
 
-def _fold_bias(sd, conv, norm):
-    """(scale, shift) of ``norm(conv(x) + bias)`` in float64: the convolution's bias goes through the BatchNorm."""
-    s, b = bn_fold(sd, norm)
-    return s, b + sd[conv + ".bias"].double() * s
-
-
-def _exact2d(w, scale, shift):
-    """K-major fp32 weight ``[cin][k k][cout]`` of the exact kernel with ``scale`` folded in float64, and the bias."""
-    cout, cin, k, _ = w.shape
-    wt = (w.double() * scale[:, None, None, None]).float().permute(1, 2, 3, 0).reshape(cin, k * k, cout).contiguous()
-    return wt, shift.float().contiguous()
-
-
 def _conv_any(x, prepared, k, stride=1, relu=False, residual=None):
     """A 2-D convolution on whichever kernel its weights were prepared for: the exact one (a K-major tensor: fewer than 16 input channels) or sb3 (slabs)."""
     w, bias = prepared
-    if isinstance(w, tuple):
-        return conv_sb(x, w, bias, k=k, stride=stride, relu=relu, residual=residual)
-    bs, cin, h, wd = x.shape
-    cout, pad = w.shape[2], k // 2
-    out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
-    lib().call("e4s_conv2d", _p(out), _p(x), None, 0, _p(w), _p(bias), None, None, None, _p(residual), 1 if relu else 0, bs, cin, cout, h, wd, k, stride, pad,
-               _stream())
-    return out
+    conv = conv_sb if isinstance(w, tuple) else conv_exact
+    return conv(x, w, bias, k=k, stride=stride, relu=relu, residual=residual)
 
 
 def _prep2d(sd, conv, norm=None):
     w = sd[conv + ".weight"]
-    scale, shift = _fold_bias(sd, conv, norm) if norm is not None else (torch.ones(w.shape[0], dtype=torch.float64, device=w.device), sd[conv + ".bias"].double())
-    if w.shape[1] < 16:
-        return _exact2d(w, scale, shift)
-    return prep_fwd(w, scale, shift)
+    scale, shift = fold_conv_bn(sd, conv, norm) if norm is not None else (torch.ones(w.shape[0], dtype=torch.float64, device=w.device), sd[conv + ".bias"].double())
+    return (prep_exact if w.shape[1] < 16 else prep_fwd)(w, scale, shift)
 
 
-class PreparedKPDetector(_Prepared):
+class PreparedKPDetector(PreparedNet):
     """The kernels' copies of a ``KPDetector``'s weights, rebuilt when a tensor changes version or storage: per DownBlock2d the convolution with its bias and
     BatchNorm folded in float64 (K-major fp32 under 16 input channels, three-way split slabs otherwise), the 1 x 1 convolution's slabs, per UpBlock3d and for
     the heads the 27-tap slabs, and the anti-alias kernel."""
 
     __slots__ = ()
+    _entry = "kp_detector_forward"
 
-    def get(self, weights, checked=None):
-        sd, structure, ts = checked if checked is not None else _validated("kp_detector_forward", weights, _net_of(weights, _KP_NET))
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in kp_detector_structure_shapes(structure) if not k.endswith("num_batches_tracked")}
+    def _net(self, weights):
+        return _net_of(weights, _KP_NET)
+
+    def _build(self, sd, structure, dev):
         _, down, _, up, _, jmaps, k, _ = structure
-        with torch.no_grad():
-            P = dict(down=[_prep2d(sd, f"predictor.down_blocks.down{i}.conv", f"predictor.down_blocks.down{i}.norm") for i in range(len(down))],
-                     conv=_prep2d(sd, "predictor.conv"),
-                     up=[prep_conv3d(sd[f"predictor.up_blocks.up{i}.conv.weight"], *_fold_bias(sd, f"predictor.up_blocks.up{i}.conv", f"predictor.up_blocks.up{i}.norm"))
-                         for i in range(len(up))],
-                     kp=prep_conv3d(sd["kp.weight"], None, sd["kp.bias"].double()),
-                     jac=prep_conv3d(sd["jacobian.weight"], None, sd["jacobian.bias"].double()) if jmaps else None,
-                     taps=sd["down.weight"][0, 0].contiguous() if k else None)
-        return self._publish(key, P)
+        return dict(down=[_prep2d(sd, f"predictor.down_blocks.down{i}.conv", f"predictor.down_blocks.down{i}.norm") for i in range(len(down))],
+                    conv=_prep2d(sd, "predictor.conv"),
+                    up=[prep_conv3d(sd[f"predictor.up_blocks.up{i}.conv.weight"], *fold_conv_bn(sd, f"predictor.up_blocks.up{i}.conv", f"predictor.up_blocks.up{i}.norm"))
+                        for i in range(len(up))],
+                    kp=prep_conv3d(sd["kp.weight"], None, sd["kp.bias"].double()),
+                    jac=prep_conv3d(sd["jacobian.weight"], None, sd["jacobian.bias"].double()) if jmaps else None,
+                    taps=sd["down.weight"][0, 0].contiguous() if k else None)
 
 
-class PreparedHEEstimator(_Prepared):
+class PreparedHEEstimator(PreparedNet):
     """The kernels' copies of an ``HEEstimator``'s weights: ``conv1`` K-major fp32 with ``norm1`` folded, every other convolution as three-way split slabs with
     its bias and BatchNorm folded in float64, and the five heads as one ``[3 num_bins + 3 + 3 num_kp, 2048]`` matrix in key order with its bias."""
 
     __slots__ = ()
+    _entry = "he_estimator_forward"
 
-    def get(self, weights, checked=None):
-        sd, structure, ts = checked if checked is not None else _validated("he_estimator_forward", weights, _net_of(weights, _HE_NET))
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in he_estimator_structure_shapes(structure) if not k.endswith("num_batches_tracked")}
-        dev = ts[0].device
+    def _net(self, weights):
+        return _net_of(weights, _HE_NET)
 
+    def _build(self, sd, structure, dev):
         def bottleneck(p, strided):
             return dict(c1=_prep2d(sd, p + ".conv1", p + ".norm1"), c2=_prep2d(sd, p + ".conv2", p + ".norm2"), c3=_prep2d(sd, p + ".conv3", p + ".norm3"),
                         skip=_prep2d(sd, p + ".skip", p + ".norm4") if strided else None)
 
-        with torch.no_grad():
-            stages = [dict(widen=_prep2d(sd, "conv2", "norm2"), blocks=[bottleneck(f"block1.b1_{i}", False) for i in range(3)])]
-            for (cv, norm, _), strided, (group, letter, n) in _HE_STAGES:
-                stages.append(dict(widen=_prep2d(sd, cv, norm), blocks=[bottleneck(strided, True)] + [bottleneck(f"{group}.{letter}{i}", False) for i in range(n)]))
-            n = sum(sd[h + ".bias"].shape[0] for h in _HE_HEADS)
-            P = dict(stem=_exact2d(sd["conv1.weight"], *_fold_bias(sd, "conv1", "norm1")), stages=stages,
-                     fc_w=torch.cat([sd[h + ".weight"] for h in _HE_HEADS]).contiguous(), fc_b=torch.cat([sd[h + ".bias"] for h in _HE_HEADS]).contiguous(),
-                     ones=torch.ones(n, dtype=torch.float32, device=dev), zeros=torch.zeros(n, dtype=torch.float32, device=dev))
-        return self._publish(key, P)
+        stages = [dict(widen=_prep2d(sd, "conv2", "norm2"), blocks=[bottleneck(f"block1.b1_{i}", False) for i in range(3)])]
+        for (cv, norm, _), strided, (group, letter, n) in _HE_STAGES:
+            stages.append(dict(widen=_prep2d(sd, cv, norm), blocks=[bottleneck(strided, True)] + [bottleneck(f"{group}.{letter}{i}", False) for i in range(n)]))
+        n = sum(sd[h + ".bias"].shape[0] for h in _HE_HEADS)
+        return dict(stem=prep_exact(sd["conv1.weight"], *fold_conv_bn(sd, "conv1", "norm1")), stages=stages,
+                    fc_w=torch.cat([sd[h + ".weight"] for h in _HE_HEADS]).contiguous(), fc_b=torch.cat([sd[h + ".bias"] for h in _HE_HEADS]).contiguous(),
+                    ones=torch.ones(n, dtype=torch.float32, device=dev), zeros=torch.zeros(n, dtype=torch.float32, device=dev))
 
 
 # ------------------------------------------------------------------------------------------------ the forward passes
 def _checked_image(name, x, weights, base):
     """Everything that can be refused, before any launch; returns the checked weights."""
-    _check_loaded(name, weights)
+    check_loaded(name, weights, "the weights")
     checked = _validated(name, weights, _net_of(weights, base))
     _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image")
     if x.shape[1] != 3:
@@ -601,8 +552,7 @@ def kp_detector_forward(x: torch.Tensor, weights, temperature=None, want_heatmap
     D, H, W = kp_volume_size(structure, int(x.shape[2]), int(x.shape[3]))
     if min(D, H, W) < 2:
         raise ValueError(f"{name}: x is {tuple(x.shape)}: the final volume would be {D} x {H} x {W}, every extent must be at least 2")
-    _cuda_checked(name, x=x)
-    _devices_checked(name, "x", x, checked[2])
+    _placed_checked(name, "x", x, checked[2])
     K, jmaps = structure[4], structure[5]
     bs = x.shape[0]
     if bs == 0:
@@ -639,8 +589,7 @@ def he_estimator_forward(x: torch.Tensor, weights):
     name = "he_estimator_forward"
     checked = _checked_image(name, x, weights, _HE_NET)
     _, _, nbins, K = checked[1]
-    _cuda_checked(name, x=x)
-    _devices_checked(name, "x", x, checked[2])
+    _placed_checked(name, "x", x, checked[2])
     bs, _, H, W = x.shape
     n = 3 * nbins + 3 + 3 * K
     y = torch.empty((bs, n), dtype=torch.float32, device=x.device)

@@ -26,9 +26,9 @@ import torch.nn.functional as F
 
 from . import lossnet
 from ._lib import lib
-from .lossnet import bn_fold, conv_sb, weights_key
-from .ops import _Prepared, _c, _p, _stream
-from .netweights import _Net, _cuda_checked, _devices_checked, _tensor_checked, _validated
+from .lossnet import bn_fold, conv_exact, conv_sb, prep_exact, prep_fwd
+from .ops import _p, _stream
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _placed_checked, _validated, bn_shapes, check_loaded
 
 ARITH = "sb3"                                # "sb3": e4s_conv2d_sb3 (fp32-class); "sb": e4s_conv2d_sb (two-way split bf16)
 RETINAFACE_MAX_SIDE = 1500                              # detect resizes a larger image with cv2 first (retinaface_detection.py:67-70): out of scope
@@ -188,12 +188,6 @@ class RetinaFace(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ weights
-def _bn_shapes(out, p, c):
-    for k in ("weight", "bias", "running_mean", "running_var"):
-        out[f"{p}.{k}"] = (c,)
-    out[p + ".num_batches_tracked"] = ()
-
-
 def _bottlenecks():
     """[(key prefix, cin, width, stride, has a downsample convolution)] of the ResNet-50 body in key order."""
     out, cin = [], 64
@@ -221,17 +215,17 @@ def retinaface_state_dict_shapes(out_channel: int = 256):
     """``{key: shape}`` of ``RetinaFace(cfg_re50 with that out_channel, 'test').state_dict()``, in its order."""
     c, out = int(out_channel), {}
     out["body.conv1.weight"] = (64, 3, 7, 7)
-    _bn_shapes(out, "body.bn1", 64)
+    bn_shapes(out, "body.bn1", 64)
     for p, cin, width, _, ds in _bottlenecks():
         for i, (ci, co, k) in enumerate(((cin, width, 1), (width, width, 3), (width, width * 4, 1))):
             out[f"{p}.conv{i + 1}.weight"] = (co, ci, k, k)
-            _bn_shapes(out, f"{p}.bn{i + 1}", co)
+            bn_shapes(out, f"{p}.bn{i + 1}", co)
         if ds:
             out[p + ".downsample.0.weight"] = (width * 4, cin, 1, 1)
-            _bn_shapes(out, p + ".downsample.1", width * 4)
+            bn_shapes(out, p + ".downsample.1", width * 4)
     for p, ci, co, k, _ in _seqs(c):
         out[p + ".0.weight"] = (co, ci, k, k)
-        _bn_shapes(out, p + ".1", co)
+        bn_shapes(out, p + ".1", co)
     for name, n in _HEADS:
         for i in range(3):
             out[f"{name}.{i}.conv1x1.weight"] = (n, c, 1, 1)
@@ -246,8 +240,8 @@ def _variant_of_keys(name, sd):
     return int(t.shape[0])
 
 
-_RETINA_NET = _Net("RetinaFace", retinaface_state_dict_shapes, ("module.",), False, ("body.conv1.weight",), _variant_of_keys,
-                   "the native path is the eval-mode forward (BatchNorm's running statistics)", ("num_batches_tracked",))
+_RETINA_NET = _Net("RetinaFace", retinaface_state_dict_shapes, ("module.",), False, ("body.conv1.weight",), _variant_of_keys, EVAL_ONLY,
+                   ("num_batches_tracked",))
 
 
 def retinaface_weight_tensors(weights, name: str = "retinaface_forward"):
@@ -255,60 +249,37 @@ def retinaface_weight_tensors(weights, name: str = "retinaface_forward"):
     return _validated(name, weights, _RETINA_NET)[2]
 
 
-def _check_loaded(name, weights):
-    if isinstance(weights, nn.Module) and getattr(weights, "_loaded", True) is False:
-        raise RuntimeError(f"{name}: {type(weights).__name__}: the RetinaFace weights were never loaded (nothing is downloaded here); call load_state_dict first")
-
-
-def _prep(w, scale=None, shift=None, terms=3):
-    """(split-bf16 slabs of ``w * scale[co]``: three-way or two-way, the shift as fp32 bias or None) for ``conv_sb``."""
-    cout, cin, k, _ = w.shape
-    if scale is not None:
-        w = (w.double() * scale[:, None, None, None]).float()
-    w = w.contiguous()
-    slabs = lossnet._slabs(terms, cout, cin, k, w.device)
-    entry = "e4s_conv_prep_weights_sb3" if terms == 3 else "e4s_conv_prep_weights_sb"
-    lib().call(entry, *[_p(s) for s in slabs], None, _p(w), None, None, None, None, 0.0, None, cout, cin, k, k, _stream())
-    return slabs, (shift.float().contiguous() if shift is not None else None)
-
-
-class PreparedRetinaFace(_Prepared):
+class PreparedRetinaFace(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage or ``ARITH`` changes.  ``stem``: body.conv1 with bn1
     folded, K-major fp32 ``[3][49][64]`` and bias; per Bottleneck the slabs and biases of its three (four) convolutions with their BatchNorms folded in
     float64; the FPN's and the SSHs' the same way; ``heads``: per level the Bbox, Class and Landmark 1 x 1 convolutions as one with 32 outputs; ``slope``: the
     constant slope vectors of the leaky configuration (``out_channel <= 64``), else None."""
 
     __slots__ = ()
+    _entry, _net = "retinaface_forward", _RETINA_NET
 
-    def get(self, weights, checked=None):
-        sd, c, ts = checked if checked is not None else _validated("retinaface_forward", weights, _RETINA_NET)
-        key = weights_key(ts) + (ts[0].device, ARITH)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
+    def _settings(self):
+        return (ARITH,)
+
+    def _build(self, sd, c, dev):
         if ARITH not in ("sb3", "sb"):
             raise ValueError(f"ops_retinaface.ARITH is {ARITH!r}: 'sb3' or 'sb'")
-        terms, dev = (3 if ARITH == "sb3" else 2), ts[0].device
-        sd = {k: _c(sd[k].detach(), k) for k in retinaface_state_dict_shapes(c) if not k.endswith("num_batches_tracked")}
+        terms = 3 if ARITH == "sb3" else 2
 
         def normed(conv, bn):
-            return _prep(sd[conv + ".weight"], *bn_fold(sd, bn), terms=terms)
+            return prep_fwd(sd[conv + ".weight"], *bn_fold(sd, bn), terms=terms)
 
-        with torch.no_grad():
-            s, b = bn_fold(sd, "body.bn1")
-            stem = (sd["body.conv1.weight"].double() * s[:, None, None, None]).float().permute(1, 2, 3, 0).reshape(3, 49, 64).contiguous()
-            blocks = [dict(stride=stride, c1=normed(p + ".conv1", p + ".bn1"), c2=normed(p + ".conv2", p + ".bn2"), c3=normed(p + ".conv3", p + ".bn3"),
-                           ds=normed(p + ".downsample.0", p + ".downsample.1") if ds else None) for p, _, _, stride, ds in _bottlenecks()]
-            seq = {p: normed(p + ".0", p + ".1") for p, *_ in _seqs(c)}
-            heads = []
-            for i in range(3):
-                w = torch.cat([sd[f"{n}.{i}.conv1x1.weight"] for n in ("BboxHead", "ClassHead", "LandmarkHead")])
-                bias = torch.cat([sd[f"{n}.{i}.conv1x1.bias"] for n in ("BboxHead", "ClassHead", "LandmarkHead")])
-                heads.append(_prep(w, None, bias.double(), terms=terms))
-            lk = _leaky(c)
-            slope = {n: torch.full((n,), lk, dtype=torch.float32, device=dev) for n in (c, c // 4)} if lk else None
-            P = dict(c=c, stem=(stem, b.float().contiguous()), blocks=blocks, seq=seq, heads=heads, slope=slope)
-        return self._publish(key, P)
+        blocks = [dict(stride=stride, c1=normed(p + ".conv1", p + ".bn1"), c2=normed(p + ".conv2", p + ".bn2"), c3=normed(p + ".conv3", p + ".bn3"),
+                       ds=normed(p + ".downsample.0", p + ".downsample.1") if ds else None) for p, _, _, stride, ds in _bottlenecks()]
+        seq = {p: normed(p + ".0", p + ".1") for p, *_ in _seqs(c)}
+        heads = []
+        for i in range(3):
+            w = torch.cat([sd[f"{n}.{i}.conv1x1.weight"] for n in ("BboxHead", "ClassHead", "LandmarkHead")])
+            bias = torch.cat([sd[f"{n}.{i}.conv1x1.bias"] for n in ("BboxHead", "ClassHead", "LandmarkHead")])
+            heads.append(prep_fwd(w, None, bias.double(), terms=terms))
+        lk = _leaky(c)
+        slope = {n: torch.full((n,), lk, dtype=torch.float32, device=dev) for n in (c, c // 4)} if lk else None
+        return dict(c=c, stem=prep_exact(sd["body.conv1.weight"], *bn_fold(sd, "body.bn1")), blocks=blocks, seq=seq, heads=heads, slope=slope)
 
 
 # ------------------------------------------------------------------------------------------------ the forward pass
@@ -327,11 +298,9 @@ def _up_add(a, b):
 
 def _heads(P, x):
     """The three levels' 32-channel head maps of a float ``x [bs, 3, H, W]`` (mean subtracted, BGR planes)."""
-    bs, _, H, W = x.shape
-    dev = x.device
-    ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    cur = torch.empty((bs, 64, ho, wo), dtype=torch.float32, device=dev)
-    lib().call("e4s_conv2d", _p(cur), _p(x), None, 0, _p(P["stem"][0]), _p(P["stem"][1]), None, None, None, None, 1, bs, 3, 64, H, W, 7, 2, 3, _stream())
+    bs, dev = x.shape[0], x.device
+    cur = conv_exact(x, *P["stem"], k=7, stride=2, relu=True)
+    ho, wo = cur.shape[2:]
     pooled = torch.empty((bs, 64, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1), dtype=torch.float32, device=dev)
     lib().call("e4s_maxpool3x3s2", _p(pooled), _p(cur), bs * 64, ho, wo, _stream())
     cur, taps = pooled, []
@@ -409,14 +378,9 @@ def retinaface_detection_tail(score, boxes, lmk, confidence_threshold=0.9, nms_t
 
 def _checked_all(name, weights, x=None, img_u8=None):
     """Everything that can be refused, before any launch: the checked weights."""
-    _check_loaded(name, weights)
+    check_loaded(name, weights, "the RetinaFace weights")
     checked = _validated(name, weights, _RETINA_NET)
-    if x is not None:
-        _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, 3, H, W] image")
-        t, nm, (H, W), c = x, "x", x.shape[2:], x.shape[1]
-    else:
-        _tensor_checked(name, "img_u8", img_u8, torch.uint8, 4, "a uint8 [bs, H, W, 3] image")
-        t, nm, (H, W), c = img_u8, "img_u8", img_u8.shape[1:3], img_u8.shape[3]
+    t, nm, H, W, c = _image_checked(name, x, img_u8, "a float32 [bs, 3, H, W] image", "a uint8 [bs, H, W, 3] image")
     if c != 3:
         raise ValueError(f"{name}: {nm} is {tuple(t.shape)}: expected three colour channels")
     if min(H, W) < 1:
@@ -424,8 +388,7 @@ def _checked_all(name, weights, x=None, img_u8=None):
     if max(H, W) > RETINAFACE_MAX_SIDE:
         raise ValueError(f"{name}: {nm} is {H} x {W}: the longer side is limited to {RETINAFACE_MAX_SIDE} (beyond it the reference resizes the image first, which is "
                          "not done here)")
-    _cuda_checked(name, **{nm: t})
-    _devices_checked(name, nm, t, checked[2])
+    _placed_checked(name, nm, t, checked[2])
     return checked
 
 

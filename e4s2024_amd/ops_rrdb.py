@@ -16,9 +16,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._lib import lib
-from .lossnet import conv_sb, prep_fwd, weights_key
-from .netweights import _Net, _keys_shapes, _validated
-from .ops import _Prepared, _c, _p, _stream
+from .lossnet import conv_sb, prep_fwd
+from .netweights import PreparedNet, _Net, _keys_shapes
+from .ops import _p, _stream
 
 GPEN_SR_FEATS = (32, 64)                     # num_feat: 32 as RealESRNet builds it, 64 as the published x4 checkpoints (RealESRGAN_x4plus.pth among them) have it
 GPEN_SR_SCALES = (1, 2, 4)
@@ -125,7 +125,7 @@ def _gsr_variant(name, sd):
 _GSR_NET = _Net("RRDBNet", _gsr_shapes, _PREFIXES, True, ("conv_first.weight",), _gsr_variant, None, ())
 
 
-class _PreparedRRDB(_Prepared):
+class _PreparedRRDB(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage.  ``first``, ``conv_body``, ``up1``, ``up2``, ``hr`` and
     per block three dense blocks of five convolutions, all as three-way split slabs with their biases; ``conv5`` of a dense block carries the block's ``* 0.2``
     in weight and bias (folded in float64), so that ``x5 * 0.2 + x`` is the convolution's residual epilogue; ``last`` conv_last's float32 weight and bias for
@@ -133,17 +133,9 @@ class _PreparedRRDB(_Prepared):
     is (num_block, num_feat, scale) or, for the network at width 64 and scale 4 alone, the block count."""
 
     __slots__ = ()
-    _entry = _net = None
 
-    def get(self, weights, checked=None):
-        sd, variant, ts = checked if checked is not None else _validated(self._entry, weights, self._net)
+    def _build(self, sd, variant, dev):
         num_block, num_feat, scale = variant if isinstance(variant, tuple) else (variant, 64, 4)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(sd[k].detach(), k) for k in gpen_sr_state_dict_shapes(num_block, num_feat, scale)}
-        dev = ts[0].device
 
         def conv(name, fold=None):
             w, b = sd[name + ".weight"], sd[name + ".bias"]
@@ -151,14 +143,12 @@ class _PreparedRRDB(_Prepared):
                 return prep_fwd(w, None, b)
             return prep_fwd(w, torch.full((w.shape[0],), fold, dtype=torch.float64, device=dev), b.double() * fold)
 
-        with torch.no_grad():
-            body = [[[conv(f"body.{i}.rdb{r}.conv{k}", 0.2 if k == 5 else None) for k in range(1, 6)] for r in (1, 2, 3)] for i in range(num_block)]
-            P = dict(num_block=num_block, num_feat=num_feat, scale=scale, first=conv("conv_first"), body=body, conv_body=conv("conv_body"),
-                     up1=conv("conv_up1"), up2=conv("conv_up2"), hr=conv("conv_hr"),
-                     last=(sd["conv_last.weight"].contiguous(), sd["conv_last.bias"].contiguous()),
-                     slope_feat=torch.full((num_feat,), RRDB_SLOPE, dtype=torch.float32, device=dev),
-                     slope_grow=torch.full((RRDB_GROW,), RRDB_SLOPE, dtype=torch.float32, device=dev))
-        return self._publish(key, P)
+        body = [[[conv(f"body.{i}.rdb{r}.conv{k}", 0.2 if k == 5 else None) for k in range(1, 6)] for r in (1, 2, 3)] for i in range(num_block)]
+        return dict(num_block=num_block, num_feat=num_feat, scale=scale, first=conv("conv_first"), body=body, conv_body=conv("conv_body"),
+                    up1=conv("conv_up1"), up2=conv("conv_up2"), hr=conv("conv_hr"),
+                    last=(sd["conv_last.weight"].contiguous(), sd["conv_last.bias"].contiguous()),
+                    slope_feat=torch.full((num_feat,), RRDB_SLOPE, dtype=torch.float32, device=dev),
+                    slope_grow=torch.full((RRDB_GROW,), RRDB_SLOPE, dtype=torch.float32, device=dev))
 
 
 def _sample(P, x, out_f, out_u8, tail, reads, writes, feat0, ups):
