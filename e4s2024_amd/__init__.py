@@ -120,10 +120,16 @@ REENACT_KP_OVERRIDES = {
     "swap_face_fine.face_vid2vid.modules.keypoint_detector": "swap_face_fine/face_vid2vid/modules/keypoint_detector.py",
 }
 
+# row f18: face-vid2vid reenactment, stage 2: DenseMotionNetwork (the reference's own modules/generator.py imports it from there and constructs it unchanged).
+# ``modules.util`` is still the reference's: the generator's other blocks come from it
+REENACT_MOTION_OVERRIDES = {
+    "swap_face_fine.face_vid2vid.modules.dense_motion": "swap_face_fine/face_vid2vid/modules/dense_motion.py",
+}
+
 
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
-            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES, **REENACT_KP_OVERRIDES}
+            **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES, **REENACT_KP_OVERRIDES, **REENACT_MOTION_OVERRIDES}
 
 
 class _DropinFinder(importlib.abc.MetaPathFinder):
@@ -144,7 +150,7 @@ def install(force: bool = False) -> str:
     ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
     face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``), GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) and
     GPEN's RealESRNet pass with ``FaceEnhancement`` itself (``GPEN_SR_OVERRIDES``) and face-vid2vid's keypoint detector and head-pose estimator
-    (``REENACT_KP_OVERRIDES``) to the drop-in files.
+    (``REENACT_KP_OVERRIDES``) and dense-motion network (``REENACT_MOTION_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the

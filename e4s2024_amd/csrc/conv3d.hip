@@ -8,6 +8,7 @@
 // slabs, so a step is exactly a 3 x 3 step of the 2-D kernel; steps whose slice lies in the depth padding are skipped as a whole (workgroup-uniform).  The next
 // step's global loads are issued before the current step's MFMAs.  The order of accumulation depends on the shapes alone: the same inputs give the same bits, a batch
 // of two equals two batches of one, and up_hw = 2 equals up_hw = 1 on the upsampled volume (the same values reach LDS).
+// f18: x, out and residual carry element batch strides (e4s_conv3d_sb3_strided); the unstrided entry point passes the dense ones.
 #include <stdlib.h>
 
 #include "common.h"
@@ -44,6 +45,7 @@ struct Conv3dParams {
     int bs, cin, cout, D, H, W;      // output extents
     int hin, win;                    // input plane: H / up, W / up
     int tiles_x, tiles_y;
+    size_t x_bs, out_bs, res_bs;     // element strides between samples (f18: a channel slice of a wider buffer is read or written in place)
 };
 
 template <int CB, int PB, int WC, int WP, int LOG_TW>
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_sb3_kernel(const Conv3dParams p
         ginb[j] = (e < C::PATCH) && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
         goffs[j] = ginb[j] ? (p.up == 2 ? (gy >> 1) * p.win + (gx >> 1) : gy * p.win + gx) : 0;
     }
-    const float* xb = p.x + (size_t)b * p.cin * cstride;
+    const float* xb = p.x + (size_t)b * p.x_bs;
 
     int xoff[PB];
 #pragma unroll
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_sb3_kernel(const Conv3dParams p
                 if (pix_ok && co < p.cout) {
                     float v = acc[i][q][r];
                     if (p.bias) v += p.bias[co];
-                    if (p.residual) v += p.residual[((size_t)b * p.cout + co) * odhw + opix];
+                    if (p.residual) v += p.residual[(size_t)b * p.res_bs + (size_t)co * odhw + opix];
                     if (p.act == 1) v = fmaxf(v, 0.f);
                     acc[i][q][r] = v;
                 }
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_sb3_kernel(const Conv3dParams p
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + (wc * CB + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                if (co < p.cout) p.out[((size_t)b * p.cout + co) * odhw + opix] = acc[i][q][r];
+                if (co < p.cout) p.out[(size_t)b * p.out_bs + (size_t)co * odhw + opix] = acc[i][q][r];
             }
         }
     }
@@ -276,8 +278,9 @@ static int launch3d(Conv3dParams& p, hipStream_t st) {
     return check_launch("conv3d_sb3");
 }
 
-extern "C" int e4s_conv3d_sb3(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias, const float* residual,
-                              int act, int up_hw, int bs, int cin, int cout, int D, int H, int W, void* stream) {
+extern "C" int e4s_conv3d_sb3_strided(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias,
+                                      const float* residual, int act, int up_hw, int bs, int cin, int cout, int D, int H, int W, int64_t x_bstride,
+                                      int64_t out_bstride, int64_t res_bstride, void* stream) {
     E4S_REQUIRE(w0 && w1 && w2 && (bs == 0 || (out && x)), "conv3d_sb3: null tensor");
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && cout >= 1 && D >= 1 && H >= 1 && W >= 1, "conv3d_sb3: bad size");
     E4S_REQUIRE(act == 0 || act == 1, "conv3d_sb3: bad activation (0 none, 1 ReLU)");
@@ -285,8 +288,12 @@ extern "C" int e4s_conv3d_sb3(float* out, const float* x, const uint16_t* w0, co
     E4S_REQUIRE(H % up_hw == 0 && W % up_hw == 0, "conv3d_sb3: H and W are the output extents: multiples of up_hw");
     E4S_REQUIRE((int64_t)(H / up_hw) * (W / up_hw) <= 0x7fffffff && cdiv(cout, 32) <= 65535, "conv3d_sb3: volume too large");
     E4S_REQUIRE((((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2) & 15) == 0, "conv3d_sb3: weight slabs must be 16-byte aligned");
+    E4S_REQUIRE(x_bstride >= (int64_t)cin * D * (H / up_hw) * (W / up_hw) && out_bstride >= (int64_t)cout * D * H * W &&
+                    (!residual || res_bstride >= (int64_t)cout * D * H * W),
+                "conv3d_sb3: a batch stride is smaller than its sample");
     if (bs == 0) return 0;
     Conv3dParams p;
+    p.x_bs = (size_t)x_bstride; p.out_bs = (size_t)out_bstride; p.res_bs = (size_t)res_bstride;
     p.out = out; p.x = x; p.bias = bias; p.residual = residual; p.act = act; p.up = up_hw;
     p.wsl[0] = reinterpret_cast<const uint4*>(w0); p.wsl[1] = reinterpret_cast<const uint4*>(w1); p.wsl[2] = reinterpret_cast<const uint4*>(w2);
     p.bs = bs; p.cin = cin; p.cout = cout; p.D = D; p.H = H; p.W = W; p.hin = H / up_hw; p.win = W / up_hw;
@@ -297,4 +304,11 @@ extern "C" int e4s_conv3d_sb3(float* out, const float* x, const uint16_t* w0, co
     }
     if (W > 16) return launch3d<2, 1, 1, 4, 5>(p, st);          // 64 co x 128 px (32 x 4)
     return launch3d<1, 1, 2, 2, 4>(p, st);                      // 64 co x  64 px (16 x 4)
+}
+
+extern "C" int e4s_conv3d_sb3(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias, const float* residual,
+                              int act, int up_hw, int bs, int cin, int cout, int D, int H, int W, void* stream) {
+    E4S_REQUIRE(up_hw == 1 || up_hw == 2, "conv3d_sb3: up_hw %d not supported (1 or 2)", up_hw);
+    const int64_t o = (int64_t)cout * D * H * W;
+    return e4s_conv3d_sb3_strided(out, x, w0, w1, w2, bias, residual, act, up_hw, bs, cin, cout, D, H, W, (int64_t)cin * D * (H / up_hw) * (W / up_hw), o, o, stream);
 }

@@ -231,3 +231,219 @@ extern "C" int e4s_v2v_kp_transform(float* value_out, float* jac_out, float* deg
                        jac, kp_bs, K, nbins);
     return check_launch("v2v_kp_transform");
 }
+
+// ==================================================================================== f18: the glue of DenseMotionNetwork (modules/dense_motion.py:34-128)
+// nn.AvgPool3d((1, 2, 2)) of an encoder block, written through a batch stride into the last channels of the decoder buffer that concatenates it
+__global__ __launch_bounds__(256) void avgpool2x2_strided_kernel(float* __restrict__ out, const float* __restrict__ x, int planes, int h, int w, int ho, int wo,
+                                                                 size_t out_bs) {
+#pragma clang fp contract(off)
+    const int64_t per = (int64_t)planes * ho * wo;
+    const int b = blockIdx.y;
+    const float* xb = x + (size_t)b * planes * h * w;
+    float* ob = out + (size_t)b * out_bs;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
+        const int ox = (int)(i % wo);
+        const int64_t q = i / wo;
+        const int oy = (int)(q % ho);
+        const float* xp = xb + (size_t)(q / ho) * h * w + (size_t)(2 * oy) * w + 2 * ox;
+        ob[i] = (((xp[0] + xp[1]) + xp[w]) + xp[w + 1]) * 0.25f;
+    }
+}
+
+extern "C" int e4s_avgpool2x2_strided(float* out, const float* x, int bs, int planes, int h, int w, int64_t out_bstride, void* stream) {
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && planes >= 0 && h >= 2 && w >= 2, "avgpool2x2_strided: the planes must be at least 2 x 2, got %d x %d", h, w);
+    E4S_REQUIRE(out_bstride >= (int64_t)planes * (h / 2) * (w / 2), "avgpool2x2_strided: the batch stride is smaller than a sample");
+    if (bs == 0 || planes == 0) return 0;
+    E4S_REQUIRE(out && x, "avgpool2x2_strided: null tensor");
+    const int ho = h / 2, wo = w / 2;
+    hipLaunchKernelGGL(avgpool2x2_strided_kernel, dim3(grid_1d((int64_t)planes * ho * wo), bs), dim3(256), 0, (hipStream_t)stream, out, x, planes, h, w, ho, wo,
+                       (size_t)out_bstride);
+    return check_launch("avgpool2x2_strided");
+}
+
+constexpr int V2V_MAX_MOTIONS = 32;          // K + 1, the background included
+
+// make_coordinate_grid at a position, (x, y, z) order: 2 * (i / (n - 1)) - 1 in float32
+__device__ __forceinline__ void v2v_grid(float (&g)[3], int pos, int H, int W, float fx, float fy, float fz) {
+#pragma clang fp contract(off)
+    const int hw = H * W;
+    const int z = pos / hw, r = pos - z * hw;
+    const int y = r / W, x = r - y * W;
+    g[0] = 2.f * ((float)x / fx) - 1.f;
+    g[1] = 2.f * ((float)y / fy) - 1.f;
+    g[2] = 2.f * ((float)z / fz) - 1.f;
+}
+
+// J = jac_s inv(jac_d) of one keypoint: the inverse from the adjugate and the product in float64, rounded once
+__device__ void v2v_motion_jac(float* __restrict__ out9, const float* __restrict__ js, const float* __restrict__ jd) {
+    const double a = jd[0], b = jd[1], c = jd[2], d = jd[3], e = jd[4], f = jd[5], g = jd[6], h = jd[7], i = jd[8];
+    const double A = e * i - f * h, B = c * h - b * i, C = b * f - c * e;
+    const double Dd = f * g - d * i, E = a * i - c * g, F = c * d - a * f;
+    const double G = d * h - e * g, Hh = b * g - a * h, I = a * e - b * d;
+    const double det = a * A + b * Dd + c * G;
+    const double inv[9] = {A / det, B / det, C / det, Dd / det, E / det, F / det, G / det, Hh / det, I / det};
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 3; ++q)
+            out9[r * 3 + q] = (float)(((double)js[r * 3] * inv[q] + (double)js[r * 3 + 1] * inv[3 + q]) + (double)js[r * 3 + 2] * inv[6 + q]);
+}
+
+// the sparse motion of a keypoint at grid point g: J (g - kp_d) + kp_s (J null: the identity), the one function both kernels call: the same bits
+__device__ __forceinline__ void v2v_sparse_motion(float (&m)[3], const float (&g)[3], const float* kd, const float* ks, const float* J) {
+#pragma clang fp contract(off)
+    const float c0 = g[0] - kd[0], c1 = g[1] - kd[1], c2 = g[2] - kd[2];
+    if (J) {
+        m[0] = ((J[0] * c0 + J[1] * c1) + J[2] * c2) + ks[0];
+        m[1] = ((J[3] * c0 + J[4] * c1) + J[5] * c2) + ks[1];
+        m[2] = ((J[6] * c0 + J[7] * c1) + J[8] * c2) + ks[2];
+    } else {
+        m[0] = c0 + ks[0];
+        m[1] = c1 + ks[1];
+        m[2] = c2 + ks[2];
+    }
+}
+
+// floor of an unnormalised grid_sample coordinate as an int, held to [-2, size]: at -2 and at size both taps are outside, as they are beyond
+__device__ __forceinline__ int v2v_floor_clamped(float v, int size) {
+    const float f = fminf(fmaxf(floorf(v), -2.f), (float)size);
+    return (int)f;
+}
+
+__global__ __launch_bounds__(256) void v2v_motion_input_kernel(float* __restrict__ out, const float* __restrict__ feature, const float* __restrict__ kp_d,
+                                                               const float* __restrict__ kp_s, const float* __restrict__ jac_d,
+                                                               const float* __restrict__ jac_s, int K, int c, int D, int H, int W, size_t out_bs) {
+#pragma clang fp contract(off)
+    __shared__ float sJ[9];
+    __shared__ float skp[6];
+    const int k = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+    const int n = D * H * W;
+    if (k > 0) {
+        const size_t bk = (size_t)b * K + (k - 1);
+        if (tid == 0 && jac_d) v2v_motion_jac(sJ, jac_s + bk * 9, jac_d + bk * 9);
+        if (tid >= 64 && tid < 67) skp[tid - 64] = kp_d[bk * 3 + (tid - 64)];
+        if (tid >= 128 && tid < 131) skp[3 + tid - 128] = kp_s[bk * 3 + (tid - 128)];
+    }
+    __syncthreads();
+    const int pos = blockIdx.x * 256 + tid;
+    if (pos >= n) return;
+    float g[3], m[3];
+    v2v_grid(g, pos, H, W, (float)(W - 1), (float)(H - 1), (float)(D - 1));
+    float heat = 0.f;
+    if (k == 0) {
+        m[0] = g[0]; m[1] = g[1]; m[2] = g[2];
+    } else {
+        v2v_sparse_motion(m, g, skp, skp + 3, jac_d ? sJ : nullptr);
+        // kp2gaussian(kp_driving) - kp2gaussian(kp_source), kp_variance 0.01
+        const float d0 = g[0] - skp[0], d1 = g[1] - skp[1], d2 = g[2] - skp[2];
+        const float s0 = g[0] - skp[3], s1 = g[1] - skp[4], s2 = g[2] - skp[5];
+        const float gd = expf(-0.5f * ((d0 * d0 + d1 * d1) + d2 * d2) / 0.01f);
+        const float gs = expf(-0.5f * ((s0 * s0 + s1 * s1) + s2 * s2) / 0.01f);
+        heat = gd - gs;
+    }
+    float* ob = out + (size_t)b * out_bs + (size_t)k * (c + 1) * n + pos;
+    ob[0] = heat;
+    // F.grid_sample's defaults on the 5-D feature: trilinear, zero padding, align_corners = False (grid_sampler_unnormalize: ((coord + 1) size - 1) / 2)
+    const float ix = ((m[0] + 1.f) * (float)W - 1.f) / 2.f, iy = ((m[1] + 1.f) * (float)H - 1.f) / 2.f, iz = ((m[2] + 1.f) * (float)D - 1.f) / 2.f;
+    const int x0 = v2v_floor_clamped(ix, W), y0 = v2v_floor_clamped(iy, H), z0 = v2v_floor_clamped(iz, D);
+    const float fx0 = (float)x0, fy0 = (float)y0, fz0 = (float)z0;
+    const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f, fz1 = fz0 + 1.f;
+    // ATen's eight weights and their order: tnw tne tsw tse bnw bne bsw bse (n / s: y0 / y0 + 1, w / e: x0 / x0 + 1, t / b: z0 / z0 + 1)
+    const float wgt[8] = {(fx1 - ix) * (fy1 - iy) * (fz1 - iz), (ix - fx0) * (fy1 - iy) * (fz1 - iz), (fx1 - ix) * (iy - fy0) * (fz1 - iz),
+                          (ix - fx0) * (iy - fy0) * (fz1 - iz), (fx1 - ix) * (fy1 - iy) * (iz - fz0), (ix - fx0) * (fy1 - iy) * (iz - fz0),
+                          (fx1 - ix) * (iy - fy0) * (iz - fz0), (ix - fx0) * (iy - fy0) * (iz - fz0)};
+    bool ok[8];
+    int off[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int xx = x0 + (t & 1), yy = y0 + ((t >> 1) & 1), zz = z0 + (t >> 2);
+        ok[t] = xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < D;
+        off[t] = ok[t] ? (zz * H + yy) * W + xx : 0;
+    }
+    const float* fb = feature + (size_t)b * c * n;
+    for (int j = 0; j < c; ++j) {
+        const float* fp = fb + (size_t)j * n;
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float v = fp[off[t]];
+            if (ok[t]) acc = acc + v * wgt[t];
+        }
+        ob[(size_t)(1 + j) * n] = acc;
+    }
+}
+
+static int v2v_motion_checked(const char* what, const void* kp_d, const void* kp_s, const void* jac_d, const void* jac_s, int bs, int K, int D, int H, int W) {
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && K >= 1 && K + 1 <= V2V_MAX_MOTIONS, "%s: num_kp + 1 = %d motions: 2 .. %d are supported", what, K + 1, V2V_MAX_MOTIONS);
+    E4S_REQUIRE(D >= 2 && H >= 2 && W >= 2, "%s: every extent of the volume must be at least 2 (the grid divides by n - 1), got %d x %d x %d", what, D, H, W);
+    E4S_REQUIRE((int64_t)D * H * W <= 0x7fffffff - 256, "%s: volume too large", what);
+    E4S_REQUIRE((jac_d == nullptr) == (jac_s == nullptr), "%s: jac_d and jac_s go together", what);
+    E4S_REQUIRE(bs == 0 || (kp_d && kp_s), "%s: null tensor", what);
+    return 0;
+}
+
+extern "C" int e4s_v2v_motion_input(float* out, const float* feature, const float* kp_d, const float* kp_s, const float* jac_d, const float* jac_s, int bs, int K,
+                                    int c, int D, int H, int W, int64_t out_bstride, void* stream) {
+    if (int st = v2v_motion_checked("v2v_motion_input", kp_d, kp_s, jac_d, jac_s, bs, K, D, H, W)) return st;
+    E4S_REQUIRE(c >= 1 && (int64_t)c * D * H * W <= 0x7fffffff, "v2v_motion_input: bad channel count");
+    E4S_REQUIRE(out_bstride >= (int64_t)(K + 1) * (c + 1) * D * H * W, "v2v_motion_input: the batch stride is smaller than a sample");
+    if (bs == 0) return 0;
+    E4S_REQUIRE(out && feature, "v2v_motion_input: null tensor");
+    const int n = D * H * W;
+    hipLaunchKernelGGL(v2v_motion_input_kernel, dim3(cdiv(n, 256), K + 1, bs), dim3(256), 0, (hipStream_t)stream, out, feature, kp_d, kp_s, jac_d, jac_s, K, c, D,
+                       H, W, (size_t)out_bstride);
+    return check_launch("v2v_motion_input");
+}
+
+__global__ __launch_bounds__(256) void v2v_motion_combine_kernel(float* __restrict__ mask, float* __restrict__ deformation, const float* __restrict__ logits,
+                                                                 const float* __restrict__ kp_d, const float* __restrict__ kp_s,
+                                                                 const float* __restrict__ jac_d, const float* __restrict__ jac_s, int K, int D, int H, int W) {
+#pragma clang fp contract(off)
+    __shared__ float sJ[(V2V_MAX_MOTIONS - 1) * 9];
+    __shared__ float skd[(V2V_MAX_MOTIONS - 1) * 3];
+    __shared__ float sks[(V2V_MAX_MOTIONS - 1) * 3];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = D * H * W;
+    if (tid < K && jac_d) v2v_motion_jac(sJ + tid * 9, jac_s + ((size_t)b * K + tid) * 9, jac_d + ((size_t)b * K + tid) * 9);
+    if (tid >= 64 && tid < 64 + K * 3) {
+        skd[tid - 64] = kp_d[(size_t)b * K * 3 + (tid - 64)];
+        sks[tid - 64] = kp_s[(size_t)b * K * 3 + (tid - 64)];
+    }
+    __syncthreads();
+    const int pos = blockIdx.x * 256 + tid;
+    if (pos >= n) return;
+    const float* lg = logits + (size_t)b * (K + 1) * n + pos;
+    float* mk = mask + (size_t)b * (K + 1) * n + pos;
+    float mx = lg[0];
+    for (int k = 1; k <= K; ++k) mx = fmaxf(mx, lg[(size_t)k * n]);
+    float sum = 0.f;
+    for (int k = 0; k <= K; ++k) sum = sum + expf(lg[(size_t)k * n] - mx);
+    float g[3];
+    v2v_grid(g, pos, H, W, (float)(W - 1), (float)(H - 1), (float)(D - 1));
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int k = 0; k <= K; ++k) {
+        const float w = expf(lg[(size_t)k * n] - mx) / sum;
+        mk[(size_t)k * n] = w;
+        float m[3];
+        if (k == 0) {
+            m[0] = g[0]; m[1] = g[1]; m[2] = g[2];
+        } else {
+            v2v_sparse_motion(m, g, skd + (k - 1) * 3, sks + (k - 1) * 3, jac_d ? sJ + (k - 1) * 9 : nullptr);
+        }
+        a0 = a0 + m[0] * w;
+        a1 = a1 + m[1] * w;
+        a2 = a2 + m[2] * w;
+    }
+    float* dp = deformation + ((size_t)b * n + pos) * 3;
+    dp[0] = a0; dp[1] = a1; dp[2] = a2;
+}
+
+extern "C" int e4s_v2v_motion_combine(float* mask, float* deformation, const float* logits, const float* kp_d, const float* kp_s, const float* jac_d,
+                                      const float* jac_s, int bs, int K, int D, int H, int W, void* stream) {
+    if (int st = v2v_motion_checked("v2v_motion_combine", kp_d, kp_s, jac_d, jac_s, bs, K, D, H, W)) return st;
+    E4S_REQUIRE((int64_t)(K + 1) * D * H * W <= 0x7fffffff, "v2v_motion_combine: volume too large");
+    if (bs == 0) return 0;
+    E4S_REQUIRE(mask && deformation && logits, "v2v_motion_combine: null tensor");
+    const int n = D * H * W;
+    hipLaunchKernelGGL(v2v_motion_combine_kernel, dim3(cdiv(n, 256), bs), dim3(256), 0, (hipStream_t)stream, mask, deformation, logits, kp_d, kp_s, jac_d, jac_s, K, D,
+                       H, W);
+    return check_launch("v2v_motion_combine");
+}

@@ -16,6 +16,9 @@ The reference's oddities are kept: ``yaw = fc_roll(out)`` and ``roll = fc_yaw(ou
 yaw_mat roll_mat``.  One difference: the reference's ``keypoint_transformation`` reshapes the caller's ``he['t']`` in place to ``[bs, 1, 3]`` (``unsqueeze_``);
 here ``he`` is left as it was.
 
+Row f18, stage 2, is the second half of this module: ``DenseMotionNetwork`` of modules/dense_motion.py (``dense_motion_forward``; its own overview stands in front
+of it).
+
 Forward only; no host synchronisation; the same inputs give the same bits; after one eager call (which prepares the weights) a call captures in a graph."""
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch.nn.functional as F
 from . import lossnet
 from ._lib import lib
 from .lossnet import conv_exact, conv_sb, fold_conv_bn, prep_exact, prep_fwd
-from .ops import _c, _p, _stream
+from .ops import _c, _p, _req, _stream
 from .netweights import EVAL_ONLY, PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, bn_shapes, check_loaded, module_net
 
 NUM_BINS = 66                                # headpose_pred_to_degree's idx_tensor is range(66) whatever the module's num_bins
@@ -406,22 +409,42 @@ def prep_conv3d(w, scale=None, shift=None):
     return s3, (shift.float().contiguous() if shift is not None else None)
 
 
-def conv3d_sb3(x, slabs, bias=None, *, relu: bool = False, residual=None, up_hw: int = 1):
+def _batch_slice(t):
+    """Whether ``t`` is a tensor the strided kernels take in place: every sample dense (a channel slice ``buf[:, a:b]`` of a dense buffer is)."""
+    return t.dim() >= 2 and (t.shape[0] == 0 or t[0].is_contiguous())
+
+
+def conv3d_sb3(x, slabs, bias=None, *, relu: bool = False, residual=None, up_hw: int = 1, out=None):
     """``act(conv3d(up(x), W, stride 1, zero pad 1) + bias + residual)`` of csrc/conv3d.hip on prepared ``slabs`` (``prep_conv3d``): ``x [bs, cin, D, h, w]``
-    float32, ``up`` the nearest (1, ``up_hw``, ``up_hw``) upsampling folded into the gather; returns ``[bs, cout, D, up_hw h, up_hw w]``."""
-    x = _c(x, "x")
+    float32, ``up`` the nearest (1, ``up_hw``, ``up_hw``) upsampling folded into the gather; returns ``[bs, cout, D, up_hw h, up_hw w]``.  A channel slice of a
+    dense buffer is read in place, and ``out``, a tensor or such a slice of the output's shape, is written in place (``e4s_conv3d_sb3_strided``): a
+    concatenation along the channels is never copied."""
+    x = _req(x, "x") if isinstance(x, torch.Tensor) and _batch_slice(x) else _c(x, "x")
     if x.dim() != 5 or up_hw not in (1, 2) or x.shape[1] > 16 * slabs[0].shape[0] or x.shape[1] <= 16 * (slabs[0].shape[0] - 1):
         raise ValueError(f"conv3d_sb3: x is {tuple(x.shape)} with up_hw {up_hw}: expected [bs, cin, D, h, w] matching the slabs and up_hw 1 or 2")
     bs, cin, D, h, w = x.shape
     cout = slabs[0].shape[3]
-    out = torch.empty((bs, cout, D, up_hw * h, up_hw * w), dtype=torch.float32, device=x.device)
+    shape = (bs, cout, D, up_hw * h, up_hw * w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(_req(out, "out").shape) != shape or not _batch_slice(out):
+        raise ValueError(f"conv3d_sb3: out is {tuple(out.shape)}, strides {out.stride()}: expected {shape} with every sample dense")
     if residual is not None:
         residual = _c(residual, "residual")
         if residual.shape != out.shape:
             raise ValueError(f"conv3d_sb3: residual shape {tuple(residual.shape)} != output {tuple(out.shape)}")
-    lib().call("e4s_conv3d_sb3", _p(out), _p(x), *[_p(s) for s in slabs], _p(bias), _p(residual), 1 if relu else 0, up_hw, bs, cin, cout, D, up_hw * h,
-               up_hw * w, _stream())
+    if x.is_contiguous() and out.is_contiguous():
+        lib().call("e4s_conv3d_sb3", _p(out), _p(x), *[_p(s) for s in slabs], _p(bias), _p(residual), 1 if relu else 0, up_hw, bs, cin, cout, D, up_hw * h,
+                   up_hw * w, _stream())
+    else:
+        lib().call("e4s_conv3d_sb3_strided", _p(out), _p(x), *[_p(s) for s in slabs], _p(bias), _p(residual), 1 if relu else 0, up_hw, bs, cin, cout, D,
+                   up_hw * h, up_hw * w, _bstride(x), _bstride(out), cout * D * up_hw * h * up_hw * w, _stream())
     return out
+
+
+def _bstride(t):
+    """The element stride between the samples of ``t`` (a batch of one has none to speak of: its own size)."""
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t[0].numel())
 
 
 def _conv_any(x, prepared, k, stride=1, relu=False, residual=None):
@@ -524,14 +547,20 @@ def antialias_down(x, taps, stride: int):
     return out
 
 
-def avgpool2x2(x):
-    """``nn.AvgPool2d(2)`` on ``[bs, C, H, W]`` (an odd last row or column is dropped)."""
+def avgpool2x2(x, out=None):
+    """``nn.AvgPool2d(2)`` on ``[bs, C, H, W]`` (an odd last row or column is dropped).  ``out``: a ``[bs, C, H // 2, W // 2]`` tensor or channel slice of a
+    dense buffer to write into (``e4s_avgpool2x2_strided``)."""
     x = _c(x, "x")
     bs, c, h, w = x.shape
     if min(h, w) < 2:
         raise ValueError(f"avgpool2x2: x is {tuple(x.shape)}: the planes must be at least 2 x 2")
-    out = torch.empty((bs, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
-    lib().call("e4s_avgpool2x2", _p(out), _p(x), bs * c, h, w, _stream())
+    if out is None:
+        out = torch.empty((bs, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+        lib().call("e4s_avgpool2x2", _p(out), _p(x), bs * c, h, w, _stream())
+        return out
+    if tuple(_req(out, "out").shape) != (bs, c, h // 2, w // 2) or not _batch_slice(out):
+        raise ValueError(f"avgpool2x2: out is {tuple(out.shape)}, strides {out.stride()}: expected {(bs, c, h // 2, w // 2)} with every sample dense")
+    lib().call("e4s_avgpool2x2_strided", _p(out), _p(x), bs, c, h, w, _bstride(out), _stream())
     return out
 
 
@@ -726,7 +755,417 @@ def reenact_keypoints(source, driving, kp_detector, he_estimator, estimate_jacob
     return kp_canonical, kp_source, kp_driving
 
 
+# ================================================================================================ row f18: stage 2, the dense-motion network
+# ``DenseMotionNetwork`` of swap_face_fine/face_vid2vid/modules/dense_motion.py:9-128 with ``Hourglass`` / ``Encoder`` / ``Decoder`` / ``DownBlock3d`` /
+# ``UpBlock3d``, ``kp2gaussian`` and ``make_coordinate_grid`` of modules/util.py, in eval mode:
+#
+#     compress       1 x 1 x 1 + BatchNorm + ReLU as a 1 x 1 on [bs, C, D H, W] (e4s_conv2d_sb3; the exact e4s_conv2d under 16 channels)
+#     input          e4s_v2v_motion_input: heatmaps and deformed features of the K + 1 motions in one pass, written where the last skip is read
+#     hourglass      e4s_conv3d_sb3(_strided) with BatchNorm folded in float64 and ReLU fused; every torch.cat([out, skip], dim=1) of the decoder is one buffer:
+#                    UpBlock3d (up_hw = 2) writes its first channels, e4s_avgpool2x2_strided pools the encoder's output into its last
+#     mask           e4s_conv3d_k7_sb3 (7 x 7 x 7), then e4s_v2v_motion_combine: softmax over the K + 1 channels and the deformation
+#     occlusion      e4s_conv3d_k7_sb3 with kd 1 on prediction.view(bs, C D, H, W), sigmoid in the epilogue
+#
+# The reference builds the sampling grid with the align_corners=True formula and samples with F.grid_sample's default (False): kept as it is.
+def dense_motion_structure(block_expansion=32, num_blocks=5, max_features=1024, num_kp=15, feature_channel=32, reshape_depth=16, compress=4,
+                           estimate_occlusion_map=True):
+    """The constructor arithmetic of ``DenseMotionNetwork`` / ``Hourglass`` as ``(num_kp, feature_channel, compress, encoder widths, decoder widths, depth of
+    the occlusion head or 0)``; refuses what the native path does not implement."""
+    if not all(_is_int(v) for v in (block_expansion, num_blocks, max_features, num_kp, feature_channel, reshape_depth, compress)):
+        raise ValueError("DenseMotionNetwork: block_expansion, num_blocks, max_features, num_kp, feature_channel, reshape_depth and compress are ints")
+    if min(block_expansion, num_blocks, max_features, num_kp, feature_channel, reshape_depth, compress) < 1:
+        raise ValueError("DenseMotionNetwork: widths, depths and counts are positive")
+    if num_kp + 1 > 32:
+        raise ValueError(f"DenseMotionNetwork: num_kp {num_kp} is not implemented: the mask head has num_kp + 1 outputs and the native kernel takes at most 32")
+    if block_expansion > max_features:
+        raise ValueError(f"DenseMotionNetwork: block_expansion {block_expansion} above max_features {max_features}: the reference's own decoder does not fit")
+    width = lambda i: min(max_features, block_expansion * 2 ** i)      # noqa: E731
+    down = tuple(width(i + 1) for i in range(num_blocks))
+    up = tuple(width(num_blocks - i - 1) for i in range(num_blocks))
+    return int(num_kp), int(feature_channel), int(compress), down, up, int(reshape_depth) if estimate_occlusion_map else 0
+
+
+def _dm_widths(structure):
+    """(hourglass input channels, its output channels, the encoder's output channels per level, level 0 the input)."""
+    K, _, c, down, up, _ = structure
+    infe = (K + 1) * (c + 1)
+    return infe, up[-1] + infe, (infe,) + tuple(down)
+
+
+class _DownBlock3d(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = nn.Conv3d(cin, cout, 3, padding=1)
+        self.norm = nn.BatchNorm3d(cout, affine=True)
+
+    def forward(self, x):
+        return F.avg_pool3d(F.relu(self.norm(self.conv(x))), (1, 2, 2))
+
+
+class _Encoder3d(nn.Module):
+    def __init__(self, levels):
+        super().__init__()
+        self.down_blocks = nn.ModuleList([_DownBlock3d(levels[i], levels[i + 1]) for i in range(len(levels) - 1)])
+
+    def forward(self, x):
+        outs = [x]
+        for block in self.down_blocks:
+            outs.append(block(outs[-1]))
+        return outs
+
+
+class _Decoder3d(nn.Module):
+    def __init__(self, levels, up, out_filters):
+        super().__init__()
+        nb = len(up)
+        self.up_blocks = nn.ModuleList([_UpBlock3d(levels[nb] if j == 0 else up[j - 1] + levels[nb - j], up[j]) for j in range(nb)])
+        self.conv = nn.Conv3d(out_filters, out_filters, 3, padding=1)
+        self.norm = nn.BatchNorm3d(out_filters, affine=True)
+
+    def forward(self, outs):
+        outs = list(outs)
+        out = outs.pop()
+        for block in self.up_blocks:
+            out = torch.cat([block(out), outs.pop()], dim=1)
+        return F.relu(self.norm(self.conv(out)))
+
+
+class _Hourglass3d(nn.Module):
+    def __init__(self, structure):
+        super().__init__()
+        _, self.out_filters, levels = _dm_widths(structure)
+        self.encoder = _Encoder3d(levels)
+        self.decoder = _Decoder3d(levels, structure[4], self.out_filters)
+
+    def forward(self, x):
+        return self.decoder(self.encoder(x))
+
+
+def _grid_xyz(d, h, w, like):
+    ax = lambda n: 2 * (torch.arange(n, dtype=like.dtype, device=like.device) / (n - 1)) - 1      # noqa: E731
+    return torch.stack((ax(w).view(1, 1, w).expand(d, h, w), ax(h).view(1, h, 1).expand(d, h, w), ax(d).view(d, 1, 1).expand(d, h, w)), 3)
+
+
+def _has_jacobian(kp):
+    return "jacobian" in kp and kp["jacobian"] is not None
+
+
+class DenseMotionNetwork(_Loadable):
+    """``DenseMotionNetwork(block_expansion, num_blocks, max_features, num_kp, feature_channel, reshape_depth, compress, estimate_occlusion_map)`` of
+    swap_face_fine/face_vid2vid/modules/dense_motion.py with its ``state_dict`` keys, shapes and order; the defaults are the upstream ``vox-256.yaml`` with the
+    occlusion head (88 tensors, 43 545 549 parameters; the generator checkpoint's ``dense_motion_network.`` keys load with ``strict=True``).
+    ``forward(feature, kp_driving, kp_source)`` is the plain PyTorch composition in eval mode, returning ``{'mask', 'deformation'[, 'occlusion_map']}`` — what
+    the tests compare ``dense_motion_forward`` with; ``dense_motion_forward(feature, kp_driving, kp_source, module)`` runs the same weights on the HIP kernels."""
+    _PROBE = ("mask.weight", "compress.weight")
+
+    def __init__(self, block_expansion=32, num_blocks=5, max_features=1024, num_kp=15, feature_channel=32, reshape_depth=16, compress=4,
+                 estimate_occlusion_map=True):
+        super().__init__()
+        self.structure = dense_motion_structure(block_expansion, num_blocks, max_features, num_kp, feature_channel, reshape_depth, compress,
+                                                estimate_occlusion_map)
+        self.hourglass = _Hourglass3d(self.structure)
+        self.mask = nn.Conv3d(self.hourglass.out_filters, num_kp + 1, kernel_size=7, padding=3)
+        self.compress = nn.Conv3d(feature_channel, compress, kernel_size=1)
+        self.norm = nn.BatchNorm3d(compress, affine=True)
+        self.occlusion = nn.Conv2d(self.hourglass.out_filters * reshape_depth, 1, kernel_size=7, padding=3) if estimate_occlusion_map else None
+        self.num_kp = num_kp
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def forward(self, feature, kp_driving, kp_source):
+        if self.training:
+            raise NotImplementedError("DenseMotionNetwork: training mode is not implemented; call .eval()")
+        with torch.no_grad():
+            bs, _, d, h, w = feature.shape
+            K = self.num_kp
+            f = F.relu(self.norm(self.compress(feature)))
+            grid = _grid_xyz(d, h, w, f)
+            kd, ks = kp_driving["value"].view(bs, K, 1, 1, 1, 3), kp_source["value"].view(bs, K, 1, 1, 1, 3)
+            motion = grid.view(1, 1, d, h, w, 3) - kd
+            if _has_jacobian(kp_driving):
+                jac = torch.matmul(kp_source["jacobian"], torch.inverse(kp_driving["jacobian"]))
+                motion = torch.matmul(jac.view(bs, K, 1, 1, 1, 3, 3), motion.unsqueeze(-1)).squeeze(-1)
+            sparse = torch.cat([grid.view(1, 1, d, h, w, 3).expand(bs, -1, -1, -1, -1, -1), motion + ks], dim=1)
+            c = f.shape[1]
+            deformed = F.grid_sample(f.unsqueeze(1).expand(-1, K + 1, -1, -1, -1, -1).reshape(bs * (K + 1), c, d, h, w), sparse.reshape(bs * (K + 1), d, h, w, 3),
+                                     align_corners=False).view(bs, K + 1, c, d, h, w)
+            gauss = lambda kp: torch.exp(-0.5 * ((grid.view(1, 1, d, h, w, 3) - kp) ** 2).sum(-1) / 0.01)      # noqa: E731
+            heat = torch.cat([torch.zeros_like(f[:, :1]), gauss(kd) - gauss(ks)], dim=1).unsqueeze(2)
+            prediction = self.hourglass(torch.cat([heat, deformed], dim=2).view(bs, -1, d, h, w))
+            mask = F.softmax(self.mask(prediction), dim=1)
+            out = {"mask": mask, "deformation": (sparse.permute(0, 1, 5, 2, 3, 4) * mask.unsqueeze(2)).sum(dim=1).permute(0, 2, 3, 4, 1)}
+            if self.occlusion is not None:
+                out["occlusion_map"] = torch.sigmoid(self.occlusion(prediction.reshape(bs, -1, h, w)))
+            return out
+
+
+def dense_motion_structure_shapes(structure):
+    """``{key: shape}`` of the ``DenseMotionNetwork`` with ``structure`` (``dense_motion_structure``), in ``state_dict`` order."""
+    K, C, c, down, up, occ = structure
+    infe, outf, levels = _dm_widths(structure)
+    nb = len(down)
+    out = {}
+
+    def block(p, co, ci):
+        out[p + ".conv.weight"], out[p + ".conv.bias"] = (co, ci, 3, 3, 3), (co,)
+        bn_shapes(out, p + ".norm", co)
+
+    for i in range(nb):
+        block(f"hourglass.encoder.down_blocks.{i}", levels[i + 1], levels[i])
+    for j in range(nb):
+        block(f"hourglass.decoder.up_blocks.{j}", up[j], levels[nb] if j == 0 else up[j - 1] + levels[nb - j])
+    out["hourglass.decoder.conv.weight"], out["hourglass.decoder.conv.bias"] = (outf, outf, 3, 3, 3), (outf,)
+    bn_shapes(out, "hourglass.decoder.norm", outf)
+    out["mask.weight"], out["mask.bias"] = (K + 1, outf, 7, 7, 7), (K + 1,)
+    out["compress.weight"], out["compress.bias"] = (c, C, 1, 1, 1), (c,)
+    bn_shapes(out, "norm", c)
+    if occ:
+        out["occlusion.weight"], out["occlusion.bias"] = (1, outf * occ, 7, 7), (1,)
+    return out
+
+
+def dense_motion_state_dict_shapes(**config):
+    """``{key: shape}`` of ``DenseMotionNetwork(**config).state_dict()``, in its order (the upstream configuration with the occlusion head by default)."""
+    return dense_motion_structure_shapes(dense_motion_structure(**config))
+
+
+def _dm_structure_of_keys(name, sd):
+    """The structure read off the keys and shapes of a mapping (a ``DenseMotionNetwork`` module hands over its own)."""
+    cls = "DenseMotionNetwork"
+    K = _shape_of(name, sd, "mask.weight", 5, cls)[0] - 1
+    c, C = _shape_of(name, sd, "compress.weight", 5, cls)[:2]
+    down, up, i = [], [], 0
+    while f"hourglass.encoder.down_blocks.{i}.conv.weight" in sd:
+        down.append(_shape_of(name, sd, f"hourglass.encoder.down_blocks.{i}.conv.weight", 5, cls)[0])
+        i += 1
+    i = 0
+    while f"hourglass.decoder.up_blocks.{i}.conv.weight" in sd:
+        up.append(_shape_of(name, sd, f"hourglass.decoder.up_blocks.{i}.conv.weight", 5, cls)[0])
+        i += 1
+    outf = _shape_of(name, sd, "hourglass.decoder.conv.weight", 5, cls)[0]
+    occ = _shape_of(name, sd, "occlusion.weight", 4, cls)[1] // outf if "occlusion.weight" in sd else 0
+    if not down or len(down) != len(up) or not 1 <= K <= 31 or outf != up[-1] + (K + 1) * (c + 1):
+        raise ValueError(f"{name}: the weights are not a DenseMotionNetwork the native path implements ({len(down)} down and {len(up)} up blocks, num_kp {K}, "
+                         f"{outf} hourglass outputs)")
+    return K, C, c, tuple(down), tuple(up), occ
+
+
+_DM_NET = _Net("DenseMotionNetwork", dense_motion_structure_shapes, ("dense_motion_network.", "module.dense_motion_network.", "module."), False,
+               ("mask.weight",), _dm_structure_of_keys, EVAL_ONLY, ("num_batches_tracked",))
+
+
+def _dm_net_of(weights):
+    """A mirror module is held to the structure it was built with, anything else to the structure its keys and shapes spell."""
+    return module_net(_DM_NET, weights.structure) if isinstance(weights, DenseMotionNetwork) else _DM_NET
+
+
+def _pool_into(full, dst):
+    """DownBlock3d's ``AvgPool3d((1, 2, 2))`` of the dense ``full [bs, C, D, h, w]`` into ``dst [bs, C, D, h // 2, w // 2]``, a tensor or a channel slice."""
+    bs, C, D, h, w = full.shape
+    lib().call("e4s_avgpool2x2_strided", _p(dst), _p(full), bs, C * D, h, w, _bstride(dst), _stream())
+
+
+def prep_conv3d_k7(w):
+    """The three-way split slabs ``[ceil(cin / 16), 49 kd, 2, cout, 8]`` of a 7-tap weight for ``conv3d_k7``: a Conv3d's ``[cout, cin, 7, 7, 7]`` (kd 7) or
+    ``[cout, cin, 1, 7, 7]``, or a Conv2d's ``[cout, cin, 7, 7]`` (kd 1); ``cout`` at most 32."""
+    shape = tuple(w.shape)
+    if len(shape) == 4:
+        shape = shape[:2] + (1,) + shape[2:]
+    if len(shape) != 5 or shape[2] not in (1, 7) or shape[3:] != (7, 7) or not 1 <= shape[0] <= 32:
+        raise ValueError(f"prep_conv3d_k7: expected a [cout <= 32, cin, 7 or 1, 7, 7] or [cout <= 32, cin, 7, 7] weight, got {tuple(w.shape)}")
+    cout, cin, kd = shape[:3]
+    w = _c(w, "weight")
+    slabs = tuple(torch.empty(((cin + 15) // 16, 49 * kd, 2, cout, 8), dtype=torch.int16, device=w.device) for _ in range(3))
+    lib().call("e4s_conv3d_k7_prep_weights_sb3", _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), _p(w), cout, cin, kd, _stream())
+    return slabs
+
+
+def conv3d_k7(x, slabs, bias=None, *, sigmoid: bool = False):
+    """``act(conv(x, W, stride 1, zero pad (kd // 2, 3, 3)) + bias)`` of csrc/conv3d_k7.hip on prepared ``slabs`` (``prep_conv3d_k7``): ``x [bs, cin, D, H, W]``
+    float32 to ``[bs, cout, D, H, W]``; with kd 1 slabs also ``x [bs, cin, H, W]`` to ``[bs, cout, H, W]`` (a 7 x 7 Conv2d).  ``act``: none, or the sigmoid."""
+    x = _c(x, "x")
+    kd = slabs[0].shape[1] // 49
+    if x.dim() not in ((4, 5) if kd == 1 else (5,)) or x.shape[1] > 16 * slabs[0].shape[0] or x.shape[1] <= 16 * (slabs[0].shape[0] - 1):
+        raise ValueError(f"conv3d_k7: x is {tuple(x.shape)}: expected [bs, cin, D, H, W]{' or [bs, cin, H, W]' if kd == 1 else ''} matching the slabs")
+    bs, cin = x.shape[:2]
+    D, H, W = (1,) * (5 - x.dim()) + tuple(x.shape[2:])
+    cout = slabs[0].shape[3]
+    out = torch.empty((bs, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    lib().call("e4s_conv3d_k7_sb3", _p(out), _p(x), *[_p(s) for s in slabs], _p(bias), 3 if sigmoid else 0, kd, bs, cin, cout, D, H, W, _stream())
+    return out
+
+
+def _keypoints_checked(name, kp_driving, kp_source, bs=None, K=None):
+    """(kp_d, kp_s, jac_d, jac_s) of the two keypoint dicts, which are left as they are: float32 ``value [bs, K, 3]`` and, in both or in neither, ``jacobian
+    [bs, K, 3, 3]`` (a ``None`` entry counts as absent, as the reference reads it)."""
+    for nm, kp in (("kp_driving", kp_driving), ("kp_source", kp_source)):
+        if not hasattr(kp, "keys") or "value" not in kp:
+            raise TypeError(f"{name}: {nm} is a keypoint dict with a 'value' entry")
+        _tensor_checked(name, f"{nm}['value']", kp["value"], torch.float32, 3, "float32 [bs, num_kp, 3]")
+    vd, vs = kp_driving["value"], kp_source["value"]
+    bs = vd.shape[0] if bs is None else bs
+    K = vd.shape[1] if K is None else K
+    for nm, v in (("kp_driving", vd), ("kp_source", vs)):
+        if tuple(v.shape) != (bs, K, 3):
+            raise ValueError(f"{name}: {nm}['value'] is {tuple(v.shape)}, expected {(bs, K, 3)}: the keypoint shapes do not fit")
+    if not 1 <= K <= 31:
+        raise ValueError(f"{name}: num_kp {K}: the native kernels take num_kp + 1 <= 32 motions")
+    if _has_jacobian(kp_driving) != _has_jacobian(kp_source):
+        raise ValueError(f"{name}: a jacobian in only one of kp_driving and kp_source: give both or neither")
+    jd = js = None
+    if _has_jacobian(kp_driving):
+        jd, js = kp_driving["jacobian"], kp_source["jacobian"]
+        for nm, j in (("kp_driving", jd), ("kp_source", js)):
+            _tensor_checked(name, f"{nm}['jacobian']", j, torch.float32, 4, "float32 [bs, num_kp, 3, 3]")
+            if tuple(j.shape) != (bs, K, 3, 3):
+                raise ValueError(f"{name}: {nm}['jacobian'] is {tuple(j.shape)}, expected {(bs, K, 3, 3)}: the keypoint shapes do not fit")
+    return vd, vs, jd, js
+
+
+def _keypoints_placed(name, x, kps):
+    ts = {nm: t for nm, t in zip(("kp_driving['value']", "kp_source['value']", "kp_driving['jacobian']", "kp_source['jacobian']"), kps) if t is not None}
+    _cuda_checked(name, **ts)
+    if any(t.device != x.device for t in ts.values()):
+        raise RuntimeError(f"{name}: device mismatch among the tensors")
+    return [None if t is None else t.detach().contiguous() for t in kps]
+
+
+def _volume_checked(name, nm, t):
+    _tensor_checked(name, nm, t, torch.float32, 5, "a float32 [bs, C, D, H, W] volume")
+    if min(t.shape[2:]) < 2:
+        raise ValueError(f"{name}: {nm} is {tuple(t.shape)}: every extent of the volume must be at least 2 (the coordinate grid divides by n - 1)")
+
+
+def motion_input(feature, kp_driving, kp_source, out=None):
+    """``e4s_v2v_motion_input``: the hourglass input ``[bs, (K + 1)(c + 1), D, H, W]`` of the compressed ``feature [bs, c, D, H, W]`` and the two keypoint
+    dicts: per motion k (0 the background, the identity grid) the heatmap channel ``k (c + 1)`` and the ``c`` features sampled at the sparse motion behind it.
+    ``out``: a tensor or channel slice of a dense buffer to write into."""
+    name = "motion_input"
+    _volume_checked(name, "feature", feature)
+    kps = _keypoints_checked(name, kp_driving, kp_source, feature.shape[0])
+    _cuda_checked(name, feature=feature)
+    kd, ks, jd, js = _keypoints_placed(name, feature, kps)
+    feature = feature.detach().contiguous()
+    bs, c, D, H, W = feature.shape
+    K = kd.shape[1]
+    shape = (bs, (K + 1) * (c + 1), D, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=feature.device)
+    elif tuple(_req(out, "out").shape) != shape or not _batch_slice(out):
+        raise ValueError(f"{name}: out is {tuple(out.shape)}, strides {out.stride()}: expected {shape} with every sample dense")
+    lib().call("e4s_v2v_motion_input", _p(out), _p(feature), _p(kd), _p(ks), _p(jd), _p(js), bs, K, c, D, H, W, _bstride(out), _stream())
+    return out
+
+
+def motion_combine(logits, kp_driving, kp_source):
+    """``e4s_v2v_motion_combine``: ``(mask [bs, K + 1, D, H, W], deformation [bs, D, H, W, 3])`` of the mask head's ``logits [bs, K + 1, D, H, W]``: the softmax
+    over the K + 1 motions and the sparse motions (the bits ``motion_input`` sampled at) weighted with it."""
+    name = "motion_combine"
+    _volume_checked(name, "logits", logits)
+    kps = _keypoints_checked(name, kp_driving, kp_source, logits.shape[0], logits.shape[1] - 1)
+    _cuda_checked(name, logits=logits)
+    kd, ks, jd, js = _keypoints_placed(name, logits, kps)
+    logits = logits.detach().contiguous()
+    bs, K1, D, H, W = logits.shape
+    mask = torch.empty_like(logits)
+    deformation = torch.empty((bs, D, H, W, 3), dtype=torch.float32, device=logits.device)
+    lib().call("e4s_v2v_motion_combine", _p(mask), _p(deformation), _p(logits), _p(kd), _p(ks), _p(jd), _p(js), bs, K1 - 1, D, H, W, _stream())
+    return mask, deformation
+
+
+class PreparedDenseMotion(PreparedNet):
+    """The kernels' copies of a ``DenseMotionNetwork``'s weights, rebuilt when a tensor changes version or storage: ``compress`` with its bias and ``norm``
+    folded in float64 as a 1 x 1 convolution, per DownBlock3d / UpBlock3d and for the decoder's last convolution the 27-tap slabs with the BatchNorm folded, and
+    the 7-tap slabs of the ``mask`` and ``occlusion`` heads with their biases."""
+
+    __slots__ = ()
+    _entry = "dense_motion_forward"
+
+    def _net(self, weights):
+        return _dm_net_of(weights)
+
+    def _build(self, sd, structure, dev):
+        _, C, c, down, up, occ = structure
+        block = lambda p: prep_conv3d(sd[p + ".conv.weight"], *fold_conv_bn(sd, p + ".conv", p + ".norm"))      # noqa: E731
+        return dict(compress=(prep_exact if C < 16 else prep_fwd)(sd["compress.weight"].view(c, C, 1, 1), *fold_conv_bn(sd, "compress", "norm")),
+                    enc=[block(f"hourglass.encoder.down_blocks.{i}") for i in range(len(down))],
+                    dec=[block(f"hourglass.decoder.up_blocks.{j}") for j in range(len(up))],
+                    dec_conv=prep_conv3d(sd["hourglass.decoder.conv.weight"], *fold_conv_bn(sd, "hourglass.decoder.conv", "hourglass.decoder.norm")),
+                    mask=(prep_conv3d_k7(sd["mask.weight"]), sd["mask.bias"].contiguous()),
+                    occlusion=(prep_conv3d_k7(sd["occlusion.weight"]), sd["occlusion.bias"].contiguous()) if occ else None)
+
+
+def dense_motion_forward(feature, kp_driving, kp_source, weights):
+    """``DenseMotionNetwork.forward(feature, kp_driving, kp_source)`` (dense_motion.py:92-128) in eval mode on the device: ``{'mask' [bs, K + 1, D, H, W],
+    'deformation' [bs, D, H, W, 3][, 'occlusion_map' [bs, 1, H, W]]}`` from a float32 ``feature [bs, C, D, H, W]`` and the keypoint dicts (``'value' [bs, K,
+    3]`` and, in both or in neither, ``'jacobian' [bs, K, 3, 3]``), which are not modified.  ``weights``: a module with the network's keys
+    (``DenseMotionNetwork``, the drop-in), a mapping with them, a generator checkpoint whose keys lie under ``dense_motion_network.``, or the dict ``torch.load``
+    returns with a ``generator`` entry; a mapping's structure is read off its keys and shapes.  A module's prepared weights are cached per parameter version.
+    Refused with ``ValueError`` before any launch: ``H`` or ``W`` no multiple of ``2 ** num_blocks`` (the reference's own ``torch.cat`` fails there), an extent
+    below 2, a depth other than the occlusion head's ``reshape_depth``, ``num_kp + 1 > 32``, keypoint shapes that do not fit, a Jacobian in only one dict,
+    anything that is not float32; then a CPU tensor (``RuntimeError``)."""
+    name = "dense_motion_forward"
+    check_loaded(name, weights, "the weights")
+    if not isinstance(weights, nn.Module) and hasattr(weights, "keys") and isinstance(weights.get("generator"), dict):
+        weights = weights["generator"]                      # the checkpoint file as torch.load gives it
+    checked = _validated(name, weights, _dm_net_of(weights))
+    structure = checked[1]
+    K, C, c, down, up, occ = structure
+    nb = len(down)
+    _volume_checked(name, "feature", feature)
+    bs, _, D, H, W = feature.shape
+    if feature.shape[1] != C:
+        raise ValueError(f"{name}: feature is {tuple(feature.shape)}: expected {C} channels (feature_channel)")
+    if H % 2 ** nb or W % 2 ** nb:
+        raise ValueError(f"{name}: feature is {tuple(feature.shape)}: H and W must be multiples of 2 ** num_blocks = {2 ** nb} (the decoder concatenates each "
+                         "upsampled level with the encoder's)")
+    if occ and D != occ:
+        raise ValueError(f"{name}: feature is {tuple(feature.shape)}: the occlusion head was built for reshape_depth {occ}")
+    kps = _keypoints_checked(name, kp_driving, kp_source, bs, K)
+    _placed_checked(name, "feature", feature, checked[2])
+    kd, ks, jd, js = _keypoints_placed(name, feature, kps)
+    infe, outf, levels = _dm_widths(structure)
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=feature.device)      # noqa: E731
+    if bs == 0:
+        out = {"mask": new(0, K + 1, D, H, W), "deformation": new(0, D, H, W, 3)}
+        if occ:
+            out["occlusion_map"] = new(0, 1, H, W)
+        return out
+    with torch.no_grad():
+        P = lossnet.prepare(PreparedDenseMotion, weights, checked)
+        x = feature.detach().contiguous()
+        comp = _conv_any(x.view(bs, C, D * H, W), P["compress"], 1, relu=True).view(bs, c, D, H, W)
+        # bufs[j]: torch.cat([up_blocks[j](out), skip], dim=1) at level nb - 1 - j, formed in place
+        bufs = [new(bs, up[j] + levels[nb - 1 - j], D, H >> (nb - 1 - j), W >> (nb - 1 - j)) for j in range(nb)]
+        src = bufs[-1][:, up[-1]:]                            # the hourglass input: the encoder's first input and the last skip
+        lib().call("e4s_v2v_motion_input", _p(src), _p(comp), _p(kd), _p(ks), _p(jd), _p(js), bs, K, c, D, H, W, _bstride(src), _stream())
+        for i in range(nb):
+            full = conv3d_sb3(src, *P["enc"][i], relu=True)
+            if i + 1 < nb:
+                j = nb - 2 - i
+                dst = bufs[j][:, up[j]:]
+            else:
+                dst = new(bs, down[i], D, H >> (i + 1), W >> (i + 1))
+            _pool_into(full, dst)
+            src = dst
+        cur = src
+        for j in range(nb):
+            conv3d_sb3(cur, *P["dec"][j], relu=True, up_hw=2, out=bufs[j][:, :up[j]])
+            cur = bufs[j]
+        prediction = conv3d_sb3(cur, *P["dec_conv"], relu=True)
+        logits = conv3d_k7(prediction, *P["mask"])
+        mask = torch.empty_like(logits)
+        deformation = new(bs, D, H, W, 3)
+        lib().call("e4s_v2v_motion_combine", _p(mask), _p(deformation), _p(logits), _p(kd), _p(ks), _p(jd), _p(js), bs, K, D, H, W, _stream())
+        out = {"mask": mask, "deformation": deformation}
+        if occ:
+            out["occlusion_map"] = conv3d_k7(prediction.view(bs, outf * D, H, W), *P["occlusion"], sigmoid=True)
+    return out
+
+
 __all__ = ["KPDetector", "HEEstimator", "PreparedKPDetector", "PreparedHEEstimator", "NUM_BINS", "antialias_kernel", "kp_detector_structure", "kp_volume_size",
            "kp_detector_structure_shapes", "he_estimator_structure_shapes", "kp_detector_state_dict_shapes", "he_estimator_state_dict_shapes", "prep_conv3d",
            "conv3d_sb3", "heatmap_keypoints", "antialias_down", "avgpool2x2", "kp_detector_forward", "he_estimator_forward", "keypoint_transformation",
-           "headpose_degrees", "rotation_matrix", "reenact_keypoints"]
+           "headpose_degrees", "rotation_matrix", "reenact_keypoints", "DenseMotionNetwork", "PreparedDenseMotion", "dense_motion_structure",
+           "dense_motion_structure_shapes", "dense_motion_state_dict_shapes", "prep_conv3d_k7", "conv3d_k7", "motion_input", "motion_combine",
+           "dense_motion_forward"]

@@ -539,6 +539,14 @@ def reenact_keypoints(kp_detector, he_estimator, source: torch.Tensor, driving: 
     return ops.reenact_keypoints(source, driving, kp_detector, he_estimator, estimate_jacobian)
 
 
+def reenact_dense_motion(dense_motion, feature: torch.Tensor, kp_driving, kp_source):
+    """What ``OcclusionAwareSPADEGenerator.forward`` (swap_face_fine/face_vid2vid/modules/generator.py) asks of its ``dense_motion_network`` per driven frame, on
+    the device: the float32 feature volume ``[bs, C, D, H, W]`` and the two keypoint dicts to ``{'mask', 'deformation'[, 'occlusion_map']}``
+    (``ops.dense_motion_forward``).  ``dense_motion`` as ``ops.dense_motion_forward`` takes weights: a module, a mapping, or the generator's checkpoint.  The
+    generator itself stays with the caller."""
+    return ops.dense_motion_forward(feature, kp_driving, kp_source, dense_motion)
+
+
 @torch.no_grad()
 def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_u8: Optional[torch.Tensor] = None, return_faces: bool = False):
     """``FaceEnhancement.process(img, aligned=False)`` (swap_face_fine/gpen/face_enhancement.py:68-110) behind its ``use_sr`` branch, for a batch of frames on

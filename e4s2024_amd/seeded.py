@@ -37,6 +37,7 @@ __all__ = [
     "seeded_retinaface_state_dict",
     "seeded_kp_detector_state_dict",
     "seeded_he_estimator_state_dict",
+    "seeded_dense_motion_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -471,10 +472,28 @@ def seeded_he_estimator_state_dict(template: Mapping[str, torch.Tensor], seed: i
     return seeded_state_dict(template, seed, "v2v_kp")
 
 
+# face-vid2vid's DenseMotionNetwork (modules/dense_motion.py): the rules above for the hourglass, ``compress`` and the BatchNorms.  The ``mask`` head's gain is
+# chosen so that the softmax over the num_kp + 1 motions is neither one-hot nor uniform on the tests' cases (the mean effective count 1 / sum_k mask_k^2 between
+# 1.5 and (num_kp + 1) / 2), the ``occlusion`` head's so that its sigmoid spans at least 0.2 .. 0.8 (tests/golden/make_golden_vid2vid_motion.py asserts both).
+V2V_MASK_HEAD_GAIN = 18.0
+V2V_OCCLUSION_GAIN = 12.0
+
+_RULES_V2V_DM = [
+    (r"^mask\.weight$", _fan_in_std(V2V_MASK_HEAD_GAIN)),
+    (r"^occlusion\.weight$", _fan_in_std(V2V_OCCLUSION_GAIN)),
+] + _RULES_V2V_KP
+
+
+def seeded_dense_motion_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for a network with the keys of face-vid2vid's ``DenseMotionNetwork``: ``template`` is its ``state_dict()`` (meta tensors will do;
+    ``ops.DenseMotionNetwork(...)`` or the reference's class give the same keys)."""
+    return seeded_state_dict(template, seed, "v2v_dm")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
              "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
-             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP}.get(family, _RULES_BISENET)
+             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

@@ -998,6 +998,41 @@ E4S_API int e4s_v2v_kp_transform(float* value_out, float* jac_out, float* deg_ou
                                  const float* deg_in, const float* t, const float* exp, const float* kp, const float* jac, int bs, int kp_bs, int K, int nbins,
                                  void* stream);
 
+/* f18: face-vid2vid reenactment, stage 2 — the dense-motion network (swap_face_fine/face_vid2vid/modules/dense_motion.py:9-128, modules/util.py:13-71, 175-332;
+ * csrc/conv3d_k7.hip, csrc/conv3d.hip, csrc/vid2vid.hip).  `compress` runs on e4s_conv2d_sb3 as a 1 x 1, the hourglass on the strided 3 x 3 x 3 kernel.
+ *   e4s_conv3d_k7_prep_weights_sb3 : a weight [cout][cin][kd][7][7] (kd 7 or 1; the Conv2d [cout][cin][7][7] is kd 1) as three bf16 slabs
+ *                                    [ceil(cin / 16)][49 kd][2][cout][8], the chunk layout of e4s_conv_prep_weights_sb3 with the taps in (kd, kh, kw) order.
+ *   e4s_conv3d_k7_sb3              : out [bs][cout][D][H][W] = act(conv(x, w, stride 1, zero pad (kd / 2, 3, 3)) + bias) on x [bs][cin][D][H][W] float32, kd 7 or 1,
+ *                                    1 <= cout <= 32, any cin >= 1; act 0 none, 3 sigmoid; bias optional.  Implicit GEMM on the three-way bf16 split
+ *                                    (six v_mfma_f32_16x16x32_bf16 per 32-deep step: two (kh, kw) taps of a 16-channel chunk), fp32 accumulation.  Depth steps
+ *                                    that lie in the padding are skipped as a whole.  kd 1 with D 1 is a 7 x 7 Conv2d on [bs][cin][H][W].  Scalar loads of x: any
+ *                                    4-byte alignment gives the same bits.
+ *   e4s_conv3d_sb3_strided         : the 3 x 3 x 3 kernel above with element batch strides: sample b of x starts at x + b x_bstride, of out at out + b out_bstride,
+ *                                    of residual at residual + b res_bstride, so a channel slice of a wider buffer is read or written in place (the decoder's
+ *                                    concatenations are never copied).  With the dense strides it is the unstrided entry point, bit for bit.
+ *   e4s_avgpool2x2_strided         : the 2 x 2 average pool above on x [bs][planes][h][w] (dense) into out + b out_bstride + [planes][h / 2][w / 2]: the same arithmetic.
+ *   e4s_v2v_motion_input           : the hourglass input in one pass: out + b out_bstride + [(K + 1)(c + 1)][D][H][W], channel k (c + 1) the heatmap
+ *                                    exp(-0.5 |g - kp_d|^2 / 0.01) - exp(-0.5 |g - kp_s|^2 / 0.01) (exactly 0 for k = 0), channel k (c + 1) + 1 + j feature j of
+ *                                    feature [bs][c][D][H][W] sampled as F.grid_sample's defaults do (trilinear, zero padding, align_corners = False; the eight taps in
+ *                                    ATen's CPU order) at the sparse motion of (b, k, position): k = 0 the identity grid g = 2 i / (n - 1) - 1 in (x, y, z) order,
+ *                                    otherwise J (g - kp_d[k - 1]) + kp_s[k - 1] with J = jac_s inv(jac_d) when both Jacobians [bs][K][3][3] are given (the inverse
+ *                                    from the adjugate in float64, rounded once), J = I without.  kp_d, kp_s [bs][K][3].  Every extent >= 2.
+ *   e4s_v2v_motion_combine         : mask [bs][K + 1][D][H][W] = softmax over the K + 1 channels of logits (maximum first, then exp, the sum in channel order) and
+ *                                    deformation [bs][D][H][W][3] = sum_k mask_k sparse_motion_k in channel order, the sparse motions from the device function of
+ *                                    e4s_v2v_motion_input: the same bits.  K + 1 <= 32.
+ * No atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_conv3d_k7_prep_weights_sb3(uint16_t* w0, uint16_t* w1, uint16_t* w2, const float* weight, int cout, int cin, int kd, void* stream);
+E4S_API int e4s_conv3d_k7_sb3(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias, int act, int kd, int bs,
+                              int cin, int cout, int D, int H, int W, void* stream);
+E4S_API int e4s_conv3d_sb3_strided(float* out, const float* x, const uint16_t* w0, const uint16_t* w1, const uint16_t* w2, const float* bias,
+                                   const float* residual, int act, int up_hw, int bs, int cin, int cout, int D, int H, int W, int64_t x_bstride,
+                                   int64_t out_bstride, int64_t res_bstride, void* stream);
+E4S_API int e4s_avgpool2x2_strided(float* out, const float* x, int bs, int planes, int h, int w, int64_t out_bstride, void* stream);
+E4S_API int e4s_v2v_motion_input(float* out, const float* feature, const float* kp_d, const float* kp_s, const float* jac_d, const float* jac_s, int bs, int K,
+                                 int c, int D, int H, int W, int64_t out_bstride, void* stream);
+E4S_API int e4s_v2v_motion_combine(float* mask, float* deformation, const float* logits, const float* kp_d, const float* kp_s, const float* jac_d,
+                                   const float* jac_s, int bs, int K, int D, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
