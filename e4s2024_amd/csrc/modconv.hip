@@ -169,10 +169,10 @@ __global__ __launch_bounds__(256) void demod_kernel(float* __restrict__ d, const
 
 extern "C" int e4s_style_demod(float* s, float* d, const float* styles, int64_t stride_b, int64_t stride_r, const float* mod_weight,
                                const float* mod_bias, const float* wsq, int bs, int nreg, int cin, int cout, int sdim, void* stream) {
-    E4S_REQUIRE(s && styles && mod_weight, "style_demod: null tensor");
+    E4S_REQUIRE(((s && styles) || bs == 0) && mod_weight, "style_demod: null tensor");      // (an empty batch has no storage: its pointers may be null)
     E4S_REQUIRE(nreg >= 1 && nreg <= E4S_MAX_REGIONS, "style_demod: %d regions (max %d)", nreg, E4S_MAX_REGIONS);
     E4S_REQUIRE(bs >= 0 && cin >= 1 && sdim >= 1, "style_demod: bad size");
-    E4S_REQUIRE((d == nullptr) == (wsq == nullptr), "style_demod: d and wsq must both be given or both be NULL");
+    E4S_REQUIRE(bs == 0 || (d == nullptr) == (wsq == nullptr), "style_demod: d and wsq must both be given or both be NULL");
     if (bs == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int nbr = bs * nreg;
@@ -861,10 +861,10 @@ __global__ __launch_bounds__(64 * TORGB_NW) void region_torgb_splitc_kernel(floa
 extern "C" int e4s_region_torgb(float* out, const float* x, const float* wt, const float* s, const uint8_t* labels, int lh, int lw,
                                 const float* bias, const float* skip, const float* up_kernel, int bs, int cin, int h, int w, int nreg,
                                 void* stream) {
-    E4S_REQUIRE(out && x && wt && s && bias, "region_torgb: null tensor");
+    E4S_REQUIRE(((out && x && s) || bs == 0) && wt && bias, "region_torgb: null tensor");      // (an empty batch has no storage)
     E4S_REQUIRE(bs >= 0 && cin >= 1 && h >= 1 && w >= 1, "region_torgb: bad size");
     E4S_REQUIRE(nreg >= 1 && nreg <= E4S_MAX_REGIONS, "region_torgb: %d regions (max %d)", nreg, E4S_MAX_REGIONS);
-    E4S_REQUIRE(labels || nreg == 1, "region_torgb: nreg > 1 needs a label map");
+    E4S_REQUIRE(labels || nreg == 1 || bs == 0, "region_torgb: nreg > 1 needs a label map");
     E4S_REQUIRE(!skip || (up_kernel && (h % 2) == 0), "region_torgb: skip needs the 4x4 upsample kernel and even size");
     E4S_REQUIRE(bs <= 65535, "region_torgb: batch too large");
     if (bs == 0) return 0;

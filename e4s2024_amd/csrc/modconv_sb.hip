@@ -550,13 +550,14 @@ static int region_modconv3x3_sb_impl(float* out, const float* x, const uint16_t*
                                      const uint8_t* uniform_blocks, const int* uniform_ctrl, const void* wmx, int arith, int* flags, void* stream) {
     const int layout = up & (E4S_X_NHWC | E4S_OUT_NHWC | E4S_OUT_SP);
     up &= 1;
-    E4S_REQUIRE(!(layout & E4S_OUT_SP) || (s_next && rgb_out && out && cout % 8 == 0 && !(layout & E4S_OUT_NHWC) && ((uintptr_t)out & 15) == 0),
+    const bool empty = bs == 0;      // (an empty batch has no storage: its pointers may be null)
+    E4S_REQUIRE(!(layout & E4S_OUT_SP) || (((s_next && rgb_out && out) || empty) && cout % 8 == 0 && !(layout & E4S_OUT_NHWC) && ((uintptr_t)out & 15) == 0),
                 "region_modconv3x3_sb: split-plane output needs s_next, the fused ToRGB, cout %% 8 == 0 and a 16-byte aligned tensor");
-    E4S_REQUIRE((out || rgb_out) && x && ((whi && wlo) || wmx) && s, "region_modconv3x3_sb: null tensor");
+    E4S_REQUIRE((((out || rgb_out) && x && s) || empty) && ((whi && wlo) || wmx), "region_modconv3x3_sb: null tensor");
     E4S_REQUIRE(!rgb_out || (rgb_wt && rgb_s && rgb_bias && (!rgb_skip || rgb_up_kernel) && w >= 32 && !up), "region_modconv3x3_sb: incomplete fused-ToRGB arguments");
     E4S_REQUIRE(bs >= 0 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "region_modconv3x3_sb: bad size");
     E4S_REQUIRE(nreg >= 1 && nreg <= E4S_MAX_REGIONS, "region_modconv3x3_sb: %d regions (max %d)", nreg, E4S_MAX_REGIONS);
-    E4S_REQUIRE(labels || nreg == 1, "region_modconv3x3_sb: nreg > 1 needs a label map");
+    E4S_REQUIRE(labels || nreg == 1 || empty, "region_modconv3x3_sb: nreg > 1 needs a label map");
     E4S_REQUIRE(!labels || (lh >= 1 && lw >= 1), "region_modconv3x3_sb: bad label map size");
     E4S_REQUIRE(!noise || (noise_weight && (noise_bs == 1 || noise_bs == bs)), "region_modconv3x3_sb: noise needs its weight and batch 1 or bs");
     E4S_REQUIRE(bs <= 65535, "region_modconv3x3_sb: batch too large");
@@ -570,7 +571,7 @@ static int region_modconv3x3_sb_impl(float* out, const float* x, const uint16_t*
     p.out_nhwc = (layout & E4S_OUT_NHWC) ? 1 : 0;
     p.up = up;
     E4S_REQUIRE(!p.x_nhwc || (cin % 16 == 0 && ((uintptr_t)x & 15) == 0), "region_modconv3x3_sb: channels-last input needs cin %% 16 == 0 and a 16-byte aligned tensor");
-    E4S_REQUIRE(!p.out_nhwc || (out && cout % 8 == 0 && ((uintptr_t)out & 15) == 0 && w >= 32),
+    E4S_REQUIRE(!p.out_nhwc || ((out || empty) && cout % 8 == 0 && ((uintptr_t)out & 15) == 0 && w >= 32),
                 "region_modconv3x3_sb: channel-blocked output needs cout %% 8 == 0, a 16-byte aligned tensor and w >= 32 (no split-K)");
     const int ho = up ? 2 * h : h, wo = up ? 2 * w : w;
     p.lscale_y = labels ? (float)lh / (float)ho : 1.f;
@@ -653,7 +654,7 @@ extern "C" int e4s_region_modconv3x3_mx(float* out, const float* x, const void* 
 //     e4s_modconv_prep_weights_sb(..., up = 0) on the layer's 3x3 weight (NOT blur-composed).
 extern "C" int e4s_modconv_tconv_sb(float* z, const float* x, const uint16_t* whi, const uint16_t* wlo, const float* s, int bs, int cin, int cout,
                                     int h, int w, void* stream) {
-    E4S_REQUIRE(z && x && whi && wlo && s, "modconv_tconv_sb: null tensor");
+    E4S_REQUIRE(((z && x && s) || bs == 0) && whi && wlo, "modconv_tconv_sb: null tensor");      // (an empty batch has no storage: its pointers may be null)
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "modconv_tconv_sb: bad size");
     E4S_REQUIRE((((uintptr_t)whi | (uintptr_t)wlo) & 15) == 0, "modconv_tconv_sb: weight slabs must be 16-byte aligned");
     if (bs == 0) return 0;
@@ -753,7 +754,7 @@ __global__ __launch_bounds__(256) void blur_epilogue_kernel(float* __restrict__ 
 
 extern "C" int e4s_blur_epilogue(float* out, const float* z, const float* blur, const float* d, const float* noise, int noise_bs,
                                  const float* noise_weight, const float* act_bias, int act, int bs, int cout, int ho, int wo, void* stream) {
-    E4S_REQUIRE(out && z && blur, "blur_epilogue: null tensor");
+    E4S_REQUIRE(((out && z) || bs == 0) && blur, "blur_epilogue: null tensor");      // (an empty batch has no storage)
     E4S_REQUIRE(bs >= 0 && cout >= 1 && ho >= 1 && wo >= 1 && (int64_t)bs * cout <= 65535, "blur_epilogue: bad size");
     E4S_REQUIRE(!noise || (noise_weight && (noise_bs == 1 || noise_bs == bs)), "blur_epilogue: noise needs its weight and batch 1 or bs");
     if (bs == 0) return 0;

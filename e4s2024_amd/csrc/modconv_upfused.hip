@@ -626,7 +626,7 @@ extern "C" E4S_API int e4s_prof_clear_up() {
 extern "C" int e4s_modconv_up_fused_sb(float* out, const float* x, const uint16_t* whi, const uint16_t* wlo, const float* s, const float* d,
                                        const float* blur, const float* noise, int noise_bs, const float* noise_weight, const float* act_bias,
                                        int act, int bs, int cin, int cout, int h, int w, const float* s_next, void* stream) {
-    E4S_REQUIRE(out && x && whi && wlo && s && blur, "modconv_up_fused_sb: null tensor");
+    E4S_REQUIRE(((out && x && s) || bs == 0) && whi && wlo && blur, "modconv_up_fused_sb: null tensor");      // (an empty batch has no storage: its pointers may be null)
     E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "modconv_up_fused_sb: bad size");
     E4S_REQUIRE((int64_t)cout * 4 * h * w < ((int64_t)1 << 31) && (int64_t)cin * h * w < ((int64_t)1 << 31), "modconv_up_fused_sb: one sample must stay below 2^31 elements");
     E4S_REQUIRE((((uintptr_t)whi | (uintptr_t)wlo) & 15) == 0, "modconv_up_fused_sb: weight slabs must be 16-byte aligned");
@@ -635,7 +635,7 @@ extern "C" int e4s_modconv_up_fused_sb(float* out, const float* x, const uint16_
     act &= 1;
     E4S_REQUIRE(!(x_sp && x_nhwc) && !(out_sp && out_nhwc), "modconv_up_fused_sb: one layout per side");
     E4S_REQUIRE(!x_sp || (cin % 16 == 0 && ((uintptr_t)x & 15) == 0), "modconv_up_fused_sb: split-plane input needs cin %% 16 == 0 and a 16-byte aligned tensor");
-    E4S_REQUIRE(!out_sp || (s_next && cout % 8 == 0 && ((uintptr_t)out & 15) == 0), "modconv_up_fused_sb: split-plane output needs s_next, cout %% 8 == 0 and a 16-byte aligned tensor");
+    E4S_REQUIRE(!out_sp || ((s_next || bs == 0) && cout % 8 == 0 && ((uintptr_t)out & 15) == 0), "modconv_up_fused_sb: split-plane output needs s_next, cout %% 8 == 0 and a 16-byte aligned tensor");
     E4S_REQUIRE(!x_nhwc || (cin % 16 == 0 && ((uintptr_t)x & 15) == 0), "modconv_up_fused_sb: channels-last input needs cin %% 16 == 0 and a 16-byte aligned tensor");
     E4S_REQUIRE(!out_nhwc || cout % 8 == 0, "modconv_up_fused_sb: channels-last output needs cout %% 8 == 0");
     if (bs == 0) return 0;

@@ -260,7 +260,8 @@ def test_channels_last_chain_gives_the_same_image(gpu_net3, links):
 @pytest.mark.parametrize("shape", [(2, 20, 40, 9, 13), (1, 16, 24, 8, 8), (3, 48, 33, 30, 17), (1, 64, 32, 64, 64)])
 def test_up_fused_matches_two_stage_and_oracle(sg2, shape):
     """Single-region up layer: the one-launch kernel (pre-blur tile kept in LDS) against the tconv + blur-epilogue pair and the
-    oracle's ModulatedConv2d upsample branch (model.py:287-301), incl. ragged sizes, cout not a multiple of 32, per-sample noise."""
+    oracle's ModulatedConv2d upsample branch (model.py:287-301), incl. ragged sizes, cout not a multiple of 32, per-sample noise.
+    (Per-kernel bars against the emulation of each kernel's own arithmetic: tests/test_gpu_modconv_variants.py.)"""
     if _ops.MODCONV_MODE != "sb":
         pytest.skip("split-bf16 kernels only")
     bs, cin, cout, h, w = shape
@@ -305,7 +306,8 @@ RAGGED = [  # (bs, cin, cout, h, w, nreg, label_h, label_w)
 @pytest.mark.parametrize("upsample", [False, True])
 def test_masked_layers_ragged_shapes_against_oracle(sg2, shape, upsample):
     """StyledConv (masked, same / up) and ToRGB on ragged sizes: odd spatial sizes, channel tails, few regions, pixels that belong to
-    no region (label 255 -> zero, like the reference's masked sum), label maps at a different resolution than the features."""
+    no region (label 255 -> zero, like the reference's masked sum), label maps at a different resolution than the features.
+    (Which tile and kernel variant a shape reaches, and per-kernel bars against the emulation of its arithmetic: tests/test_gpu_modconv_variants.py.)"""
     bs, cin, cout, h, w, nreg, lh, lw = shape
     rs = np.random.RandomState(100 * cin + h + (7 if upsample else 0))
     lab = rs.randint(0, nreg, (bs, lh, lw)).astype(np.uint8)
