@@ -2,6 +2,7 @@
 // modules/util.py:55-71, 196-213, 372-418, drive_demo.py:67-180).  Everything here is small against the convolutions: one lane per output, or one workgroup per
 // (sample, keypoint); float32 with every sum in a fixed order.
 #include "common.h"
+#include "v2v_sample.h"
 
 using namespace e4s;
 
@@ -302,12 +303,6 @@ __device__ __forceinline__ void v2v_sparse_motion(float (&m)[3], const float (&g
     }
 }
 
-// floor of an unnormalised grid_sample coordinate as an int, held to [-2, size]: at -2 and at size both taps are outside, as they are beyond
-__device__ __forceinline__ int v2v_floor_clamped(float v, int size) {
-    const float f = fminf(fmaxf(floorf(v), -2.f), (float)size);
-    return (int)f;
-}
-
 __global__ __launch_bounds__(256) void v2v_motion_input_kernel(float* __restrict__ out, const float* __restrict__ feature, const float* __restrict__ kp_d,
                                                                const float* __restrict__ kp_s, const float* __restrict__ jac_d,
                                                                const float* __restrict__ jac_s, int K, int c, int D, int H, int W, size_t out_bs) {
@@ -341,23 +336,9 @@ __global__ __launch_bounds__(256) void v2v_motion_input_kernel(float* __restrict
     }
     float* ob = out + (size_t)b * out_bs + (size_t)k * (c + 1) * n + pos;
     ob[0] = heat;
-    // F.grid_sample's defaults on the 5-D feature: trilinear, zero padding, align_corners = False (grid_sampler_unnormalize: ((coord + 1) size - 1) / 2)
-    const float ix = ((m[0] + 1.f) * (float)W - 1.f) / 2.f, iy = ((m[1] + 1.f) * (float)H - 1.f) / 2.f, iz = ((m[2] + 1.f) * (float)D - 1.f) / 2.f;
-    const int x0 = v2v_floor_clamped(ix, W), y0 = v2v_floor_clamped(iy, H), z0 = v2v_floor_clamped(iz, D);
-    const float fx0 = (float)x0, fy0 = (float)y0, fz0 = (float)z0;
-    const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f, fz1 = fz0 + 1.f;
-    // ATen's eight weights and their order: tnw tne tsw tse bnw bne bsw bse (n / s: y0 / y0 + 1, w / e: x0 / x0 + 1, t / b: z0 / z0 + 1)
-    const float wgt[8] = {(fx1 - ix) * (fy1 - iy) * (fz1 - iz), (ix - fx0) * (fy1 - iy) * (fz1 - iz), (fx1 - ix) * (iy - fy0) * (fz1 - iz),
-                          (ix - fx0) * (iy - fy0) * (fz1 - iz), (fx1 - ix) * (fy1 - iy) * (iz - fz0), (ix - fx0) * (fy1 - iy) * (iz - fz0),
-                          (fx1 - ix) * (iy - fy0) * (iz - fz0), (ix - fx0) * (iy - fy0) * (iz - fz0)};
-    bool ok[8];
+    float wgt[8];
     int off[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int xx = x0 + (t & 1), yy = y0 + ((t >> 1) & 1), zz = z0 + (t >> 2);
-        ok[t] = xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < D;
-        off[t] = ok[t] ? (zz * H + yy) * W + xx : 0;
-    }
+    const unsigned okm = v2v_trilinear_taps(wgt, off, m[0], m[1], m[2], D, H, W);
     const float* fb = feature + (size_t)b * c * n;
     for (int j = 0; j < c; ++j) {
         const float* fp = fb + (size_t)j * n;
@@ -365,7 +346,7 @@ __global__ __launch_bounds__(256) void v2v_motion_input_kernel(float* __restrict
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const float v = fp[off[t]];
-            if (ok[t]) acc = acc + v * wgt[t];
+            if ((okm >> t) & 1u) acc = acc + v * wgt[t];
         }
         ob[(size_t)(1 + j) * n] = acc;
     }
@@ -446,4 +427,111 @@ extern "C" int e4s_v2v_motion_combine(float* mask, float* deformation, const flo
     hipLaunchKernelGGL(v2v_motion_combine_kernel, dim3(cdiv(n, 256), bs), dim3(256), 0, (hipStream_t)stream, mask, deformation, logits, kp_d, kp_s, jac_d, jac_s, K, D,
                        H, W);
     return check_launch("v2v_motion_combine");
+}
+
+// ==================================================================================== f19: the glue of the generator's feature warp (modules/generator.py:201-244)
+constexpr int V2V_DEFORM_CG = 4;             // channels per workgroup row of e4s_v2v_deform: a position's taps are computed once per that many channels
+
+// deform_input: F.grid_sample(feature [bs][C][D][H][W], deformation [bs][D][H][W][3]) at its defaults, written as [bs][C D][H][W] (the same element order: the
+// reference's view costs nothing).  One position per lane: the 64 lanes of a wave gather from neighbouring addresses (a deformation is smooth) and store 256
+// contiguous bytes.  A form with four positions per lane and 16-byte stores was measured 1.7x slower at [32][16][64][64] (tools/probes/deform_forms_probe.hip, profiles/f19_deform_forms_probe.txt): a lane that owns four neighbouring
+// positions spreads every gather instruction of its wave over four times the cache lines.
+__global__ __launch_bounds__(256) void v2v_deform_kernel(float* __restrict__ out, const float* __restrict__ feature, const float* __restrict__ deformation, int C,
+                                                         int D, int H, int W, size_t feat_bs, size_t out_bs) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.z;
+    const int n = D * H * W;
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    if (pos >= n) return;
+    const int c0 = blockIdx.y * V2V_DEFORM_CG;
+    const int c1 = min(c0 + V2V_DEFORM_CG, C);
+    float wgt[8];
+    int off[8];
+    const float* dp = deformation + ((size_t)b * n + pos) * 3;
+    const unsigned okm = v2v_trilinear_taps(wgt, off, dp[0], dp[1], dp[2], D, H, W);
+    const float* fb = feature + (size_t)b * feat_bs;
+    float* ob = out + (size_t)b * out_bs + pos;
+    for (int j = c0; j < c1; ++j) {
+        const float* fp = fb + (size_t)j * n;
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float v = fp[off[t]];
+            if ((okm >> t) & 1u) acc = acc + v * wgt[t];
+        }
+        ob[(size_t)j * n] = acc;
+    }
+}
+
+static inline bool v2v_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+extern "C" int e4s_v2v_deform(float* out, const float* feature, const float* deformation, int bs, int C, int D, int H, int W, int64_t feat_bstride,
+                              int64_t out_bstride, void* stream) {
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && C >= 1 && D >= 1 && H >= 1 && W >= 1, "v2v_deform: bad size");
+    E4S_REQUIRE((int64_t)C * D * H * W <= 0x7fffffff - 1024 && cdiv(C, V2V_DEFORM_CG) <= 65535, "v2v_deform: volume too large");
+    E4S_REQUIRE(feat_bstride == 0 || feat_bstride >= (int64_t)C * D * H * W, "v2v_deform: the feature's batch stride is 0 (one feature for every sample) or at least a sample");
+    E4S_REQUIRE(out_bstride >= (int64_t)C * D * H * W, "v2v_deform: the output's batch stride is smaller than a sample");
+    if (bs == 0) return 0;
+    E4S_REQUIRE(out && feature && deformation, "v2v_deform: null tensor");
+    hipLaunchKernelGGL(v2v_deform_kernel, dim3(cdiv(D * H * W, 256), cdiv(C, V2V_DEFORM_CG), bs), dim3(256), 0, (hipStream_t)stream, out, feature, deformation, C, D, H,
+                       W, (size_t)feat_bstride, (size_t)out_bstride);
+    return check_launch("v2v_deform");
+}
+
+// ResBlock3d's norm1 + ReLU in front of conv1: relu(x scale[c] + shift[c]) over [bs][C][n], the product and the sum as one fused multiply-add
+template <int V>
+__global__ __launch_bounds__(256) void v2v_bn_relu_kernel(float* out, const float* x, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, int64_t total, int C, int n) {
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        const int c = (int)((i / n) % C);              // V = 4 only with n % 4 == 0: the four elements share a channel
+        const float s = scale[c], t = shift[c];
+        if constexpr (V == 4) {
+            const float4 v = *reinterpret_cast<const float4*>(x + i);
+            *reinterpret_cast<float4*>(out + i) = make_float4(fmaxf(fmaf(v.x, s, t), 0.f), fmaxf(fmaf(v.y, s, t), 0.f), fmaxf(fmaf(v.z, s, t), 0.f),
+                                                              fmaxf(fmaf(v.w, s, t), 0.f));
+        } else {
+            out[i] = fmaxf(fmaf(x[i], s, t), 0.f);
+        }
+    }
+}
+
+extern "C" int e4s_v2v_bn_relu(float* out, const float* x, const float* scale, const float* shift, int bs, int C, int n, void* stream) {
+    E4S_REQUIRE(bs >= 0 && C >= 1 && n >= 1, "v2v_bn_relu: bad size");
+    const int64_t total = (int64_t)bs * C * n;
+    if (total == 0) return 0;
+    E4S_REQUIRE(out && x && scale && shift, "v2v_bn_relu: null tensor");
+    if (n % 4 == 0 && v2v_aligned16(out) && v2v_aligned16(x))
+        hipLaunchKernelGGL(v2v_bn_relu_kernel<4>, dim3(grid_1d(total / 4)), dim3(256), 0, (hipStream_t)stream, out, x, scale, shift, total, C, n);
+    else
+        hipLaunchKernelGGL(v2v_bn_relu_kernel<1>, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, out, x, scale, shift, total, C, n);
+    return check_launch("v2v_bn_relu");
+}
+
+// out = x [bs][C][hw] * occ [bs][1][hw]; out may be x (every element is read once, by the lane that writes it)
+template <int V>
+__global__ __launch_bounds__(256) void v2v_occlude_kernel(float* out, const float* x, const float* __restrict__ occ, int64_t total, int C, int hw) {
+    const int64_t chw = (int64_t)C * hw;
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        const int64_t b = i / chw;
+        const int p = (int)(i % hw);                   // V = 4 only with hw % 4 == 0: the four elements lie in one plane
+        const float* op = occ + b * hw + p;
+        if constexpr (V == 4) {
+            const float4 v = *reinterpret_cast<const float4*>(x + i), o = *reinterpret_cast<const float4*>(op);
+            *reinterpret_cast<float4*>(out + i) = make_float4(v.x * o.x, v.y * o.y, v.z * o.z, v.w * o.w);
+        } else {
+            out[i] = x[i] * op[0];
+        }
+    }
+}
+
+extern "C" int e4s_v2v_occlude(float* out, const float* x, const float* occ, int bs, int C, int hw, void* stream) {
+    E4S_REQUIRE(bs >= 0 && C >= 1 && hw >= 1, "v2v_occlude: bad size");
+    const int64_t total = (int64_t)bs * C * hw;
+    if (total == 0) return 0;
+    E4S_REQUIRE(out && x && occ, "v2v_occlude: null tensor");
+    if (hw % 4 == 0 && v2v_aligned16(out) && v2v_aligned16(x) && v2v_aligned16(occ))
+        hipLaunchKernelGGL(v2v_occlude_kernel<4>, dim3(grid_1d(total / 4)), dim3(256), 0, (hipStream_t)stream, out, x, occ, total, C, hw);
+    else
+        hipLaunchKernelGGL(v2v_occlude_kernel<1>, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, out, x, occ, total, C, hw);
+    return check_launch("v2v_occlude");
 }

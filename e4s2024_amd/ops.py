@@ -18,7 +18,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_retinaface`` row f14: GPEN face enhancement, stage 3 — the RetinaFace detector (resolved on first use too)
 * ``ops_gpen_paste`` row f15: GPEN face enhancement, stage 4 — align, feather and paste around the three networks (resolved on first use too)
 * ``ops_gpen_sr`` row f16: GPEN face enhancement, stage 5 — the RealESRNet pass and cv2's linear resize (resolved on first use too)
-* ``ops_reenact`` rows f17 - f18: face-vid2vid reenactment, stage 1 — KPDetector, HEEstimator and keypoint_transformation — and stage 2, DenseMotionNetwork (resolved on first use too)
+* ``ops_reenact`` rows f17 - f19: face-vid2vid reenactment, stage 1 — KPDetector, HEEstimator and keypoint_transformation — stage 2, DenseMotionNetwork, and stage 3, the generator in front of its decoder (resolved on first use too)
 """
 from __future__ import annotations
 

@@ -17,7 +17,8 @@ yaw_mat roll_mat``.  One difference: the reference's ``keypoint_transformation``
 here ``he`` is left as it was.
 
 Row f18, stage 2, is the second half of this module: ``DenseMotionNetwork`` of modules/dense_motion.py (``dense_motion_forward``; its own overview stands in front
-of it).
+of it).  Row f19, stage 3, is the third: ``OcclusionAwareSPADEGenerator`` of modules/generator.py in front of its decoder (``appearance_feature``, once per
+clip, and ``generator_warp``, per frame; their overview stands in front of them).
 
 Forward only; no host synchronisation; the same inputs give the same bits; after one eager call (which prepares the weights) a call captures in a graph."""
 from __future__ import annotations
@@ -1163,9 +1164,567 @@ def dense_motion_forward(feature, kp_driving, kp_source, weights):
     return out
 
 
+# ================================================================================================ row f19: stage 3, the generator's feature warp
+# ``OcclusionAwareSPADEGenerator.forward`` of swap_face_fine/face_vid2vid/modules/generator.py:210-244 up to the input of ``self.decoder``, in eval mode:
+#
+#     per clip       first (3 channels: the exact e4s_conv2d) and down_blocks (e4s_conv2d_sb3, e4s_avgpool2x2), BatchNorm folded in float64, ReLU fused; second,
+#                    the 1 x 1 with its bias, whose output [bs, C D, h, w] IS the volume [bs, C, D, h, w]; per ResBlock3d three launches: e4s_v2v_bn_relu (norm1
+#                    and the ReLU stand in front of conv1's zero padding: no fold), e4s_conv3d_sb3 with norm2 folded and ReLU, e4s_conv3d_sb3 with the block's
+#                    input as residual (the Cout <= 32 tile at the upstream width)
+#     per frame      dense_motion_forward (row f18); e4s_v2v_deform, whose output [n, C D, h, w] is the reference's view; third on e4s_conv2d_sb3 with the
+#                    BatchNorm folded and nn.LeakyReLU()'s default slope 0.01 through the PReLU epilogue; fourth, a 1 x 1; e4s_v2v_occlude in place
+#
+# ``make_animation`` calls the generator once per driving frame and so recomputes the per-clip part every frame; here ``appearance_feature`` is computed once and
+# ``generator_warp`` takes it, a batch-1 volume shared by every frame of a call (the gather reads it through a batch stride of 0).  Two branches of the reference
+# cannot be reached with this DenseMotionNetwork, which returns a deformation and an occlusion map at the feature's own size: the trilinear resize of the
+# deformation and the bilinear resize of the occlusion map.  Neither is built; a size mismatch is refused.  The ``SPADEDecoder`` is stage 4: the mirror module
+# holds its keys and a stock-PyTorch forward, the native path ends at its input.
+LEAKY_SLOPE = 0.01                           # nn.LeakyReLU()'s default, SameBlock2d(lrelu=True)
+DENSE_MOTION_PARAMS = dict(block_expansion=32, max_features=1024, num_blocks=5, reshape_depth=16, compress=4)      # vox-256.yaml: dense_motion_params
+_UPSTREAM = object()                         # the default of ``dense_motion_params``: the upstream dict; None is the reference's "no dense-motion network"
+
+
+def generator_structure(image_channel=3, feature_channel=32, num_kp=15, block_expansion=64, max_features=512, num_down_blocks=2, reshape_channel=32,
+                        reshape_depth=16, num_resblocks=6, estimate_occlusion_map=True, dense_motion_params=_UPSTREAM, estimate_jacobian=False):
+    """The constructor arithmetic of ``OcclusionAwareSPADEGenerator`` as ``(image_channel, kernel size of first (3), block_expansion, down widths, max_features,
+    reshape_channel, reshape_depth, num_resblocks, width of third and fourth, the dense-motion structure or None)``; refuses what the reference's own forward
+    cannot run."""
+    if not all(_is_int(v) for v in (image_channel, feature_channel, num_kp, block_expansion, max_features, num_down_blocks, reshape_channel, reshape_depth,
+                                    num_resblocks)):
+        raise ValueError("OcclusionAwareSPADEGenerator: image_channel, feature_channel, num_kp, block_expansion, max_features, num_down_blocks, reshape_channel, "
+                         "reshape_depth and num_resblocks are ints")
+    if min(image_channel, feature_channel, num_kp, block_expansion, max_features, num_down_blocks, reshape_channel, reshape_depth) < 1 or num_resblocks < 0:
+        raise ValueError("OcclusionAwareSPADEGenerator: widths, depths and counts are positive (num_down_blocks at least 1: the reference's `second` takes the "
+                         "last down block's width)")
+    if image_channel != 3:
+        raise ValueError(f"OcclusionAwareSPADEGenerator: image_channel {image_channel} is not implemented: the native network takes three colour channels")
+    if max_features != reshape_channel * reshape_depth:
+        raise ValueError(f"OcclusionAwareSPADEGenerator: max_features {max_features} != reshape_channel * reshape_depth = {reshape_channel} * {reshape_depth}: "
+                         "the output of `second` is viewed as that volume")
+    if block_expansion > max_features:
+        raise ValueError(f"OcclusionAwareSPADEGenerator: block_expansion {block_expansion} above max_features {max_features}: the reference's first down block "
+                         "takes min(max_features, block_expansion) channels from `first`'s block_expansion, its own forward does not fit")
+    dm = None
+    if dense_motion_params is not None:
+        params = dict(DENSE_MOTION_PARAMS if dense_motion_params is _UPSTREAM else dense_motion_params)
+        dm = dense_motion_structure(num_kp=num_kp, feature_channel=feature_channel, estimate_occlusion_map=estimate_occlusion_map, **params)
+        if feature_channel != reshape_channel:
+            raise ValueError(f"OcclusionAwareSPADEGenerator: feature_channel {feature_channel} != reshape_channel {reshape_channel}: the dense-motion network's "
+                             "`compress` takes the feature volume")
+        if dm[5] and dm[5] != reshape_depth:
+            raise ValueError(f"OcclusionAwareSPADEGenerator: the dense-motion network's reshape_depth {dm[5]} != reshape_depth {reshape_depth}: its occlusion head "
+                             "views the volume's depth into channels")
+    down = tuple(min(max_features, block_expansion * 2 ** (i + 1)) for i in range(num_down_blocks))
+    return (int(image_channel), 3, int(block_expansion), down, int(max_features), int(reshape_channel), int(reshape_depth), int(num_resblocks),
+            int(block_expansion * 2 ** num_down_blocks), dm)
+
+
+class _SameBlock2d(nn.Module):
+    def __init__(self, cin, cout, k, lrelu=False):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, k, padding=k // 2)
+        self.norm = nn.BatchNorm2d(cout, affine=True)
+        self.ac = nn.LeakyReLU() if lrelu else nn.ReLU()
+
+    def forward(self, x):
+        return self.ac(self.norm(self.conv(x)))
+
+
+class _ResBlock3d(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv1 = nn.Conv3d(c, c, 3, padding=1)
+        self.conv2 = nn.Conv3d(c, c, 3, padding=1)
+        self.norm1 = nn.BatchNorm3d(c, affine=True)
+        self.norm2 = nn.BatchNorm3d(c, affine=True)
+
+    def forward(self, x):
+        out = self.conv1(F.relu(self.norm1(x)))
+        return self.conv2(F.relu(self.norm2(out))) + x
+
+
+class _SPADE(nn.Module):
+    def __init__(self, norm_nc, label_nc):
+        super().__init__()
+        self.param_free_norm = nn.InstanceNorm2d(norm_nc, affine=False)
+        self.mlp_shared = nn.Sequential(nn.Conv2d(label_nc, 128, 3, padding=1), nn.ReLU())
+        self.mlp_gamma = nn.Conv2d(128, norm_nc, 3, padding=1)
+        self.mlp_beta = nn.Conv2d(128, norm_nc, 3, padding=1)
+
+    def forward(self, x, segmap):
+        actv = self.mlp_shared(F.interpolate(segmap, size=x.shape[2:], mode="nearest"))
+        return self.param_free_norm(x) * (1 + self.mlp_gamma(actv)) + self.mlp_beta(actv)
+
+
+class _SPADEResnetBlock(nn.Module):
+    """``SPADEResnetBlock(fin, fout, 'spadespectralinstance', label_nc)`` of modules/util.py:444-481."""
+
+    def __init__(self, fin, fout, label_nc):
+        super().__init__()
+        self.learned_shortcut = fin != fout
+        fmiddle = min(fin, fout)
+        sn = torch.nn.utils.spectral_norm
+        self.conv_0 = sn(nn.Conv2d(fin, fmiddle, 3, padding=1))
+        self.conv_1 = sn(nn.Conv2d(fmiddle, fout, 3, padding=1))
+        if self.learned_shortcut:
+            self.conv_s = sn(nn.Conv2d(fin, fout, 1, bias=False))
+        self.norm_0 = _SPADE(fin, label_nc)
+        self.norm_1 = _SPADE(fmiddle, label_nc)
+        if self.learned_shortcut:
+            self.norm_s = _SPADE(fin, label_nc)
+
+    def forward(self, x, seg):
+        x_s = self.conv_s(self.norm_s(x, seg)) if self.learned_shortcut else x
+        dx = self.conv_0(F.leaky_relu(self.norm_0(x, seg), 2e-1))
+        dx = self.conv_1(F.leaky_relu(self.norm_1(dx, seg), 2e-1))
+        return x_s + dx
+
+
+class SPADEDecoder(nn.Module):
+    """``SPADEDecoder()`` of modules/generator.py:120-158 with its keys (``torch.nn.utils.spectral_norm``'s ``weight_orig`` / ``weight_u`` / ``weight_v``
+    included): 256 input channels, fixed.  ``forward`` is the plain PyTorch composition in eval mode; the native decoder is stage 4."""
+
+    def __init__(self):
+        super().__init__()
+        ic, oc, label_nc = 256, 64, 256
+        self.fc = nn.Conv2d(ic, 2 * ic, 3, padding=1)
+        for i in range(6):
+            setattr(self, f"G_middle_{i}", _SPADEResnetBlock(2 * ic, 2 * ic, label_nc))
+        self.up_0 = _SPADEResnetBlock(2 * ic, ic, label_nc)
+        self.up_1 = _SPADEResnetBlock(ic, oc, label_nc)
+        self.conv_img = nn.Conv2d(oc, 3, 3, padding=1)
+        self.up = nn.Upsample(scale_factor=2)
+
+    def forward(self, feature):
+        if self.training:
+            raise NotImplementedError("SPADEDecoder: training mode is not implemented (spectral norm's power iteration); call .eval()")
+        x = self.fc(feature)
+        for i in range(6):
+            x = getattr(self, f"G_middle_{i}")(x, feature)
+        x = self.up_0(self.up(x), feature)
+        x = self.up_1(self.up(x), feature)
+        return torch.sigmoid(self.conv_img(F.leaky_relu(x, 2e-1)))
+
+
+class OcclusionAwareSPADEGenerator(_Loadable):
+    """``OcclusionAwareSPADEGenerator(image_channel, feature_channel, num_kp, block_expansion, max_features, num_down_blocks, reshape_channel, reshape_depth,
+    num_resblocks, estimate_occlusion_map, dense_motion_params, estimate_jacobian)`` of swap_face_fine/face_vid2vid/modules/generator.py:161-251 with its
+    ``state_dict`` keys, shapes and order; the defaults are the upstream ``vox-256.yaml`` with the occlusion head (``checkpoint['generator']`` loads with
+    ``strict=True``).  ``forward(source_image, kp_driving, kp_source)`` is the plain PyTorch composition of the whole generator in eval mode, decoder included,
+    returning ``{'mask'[, 'occlusion_map'], 'prediction'}``; ``front`` is its part up to the decoder's input, what the tests compare ``generator_front_forward``
+    with.  ``dense_motion_params=None`` builds, as the reference does, a generator without a dense-motion network, which no forward here runs."""
+    _PROBE = ("second.weight", "third.conv.weight")
+
+    def __init__(self, image_channel=3, feature_channel=32, num_kp=15, block_expansion=64, max_features=512, num_down_blocks=2, reshape_channel=32,
+                 reshape_depth=16, num_resblocks=6, estimate_occlusion_map=True, dense_motion_params=_UPSTREAM, estimate_jacobian=False):
+        super().__init__()
+        self.structure = generator_structure(image_channel, feature_channel, num_kp, block_expansion, max_features, num_down_blocks, reshape_channel,
+                                             reshape_depth, num_resblocks, estimate_occlusion_map, dense_motion_params, estimate_jacobian)
+        _, k, bexp, down, _, _, _, _, outf, dm = self.structure
+        if dm is not None:
+            params = dict(DENSE_MOTION_PARAMS if dense_motion_params is _UPSTREAM else dense_motion_params)
+            self.dense_motion_network = DenseMotionNetwork(num_kp=num_kp, feature_channel=feature_channel, estimate_occlusion_map=estimate_occlusion_map, **params)
+        else:
+            self.dense_motion_network = None
+        self.first = _SameBlock2d(image_channel, bexp, k)
+        self.down_blocks = nn.ModuleList([_DownBlock2d(bexp if i == 0 else down[i - 1], c) for i, c in enumerate(down)])
+        self.second = nn.Conv2d(down[-1], max_features, 1)
+        self.reshape_channel, self.reshape_depth = reshape_channel, reshape_depth
+        self.resblocks_3d = nn.Sequential()
+        for i in range(num_resblocks):
+            self.resblocks_3d.add_module(f"3dr{i}", _ResBlock3d(reshape_channel))
+        self.third = _SameBlock2d(max_features, outf, 3, lrelu=True)
+        self.fourth = nn.Conv2d(outf, outf, 1)
+        self.estimate_occlusion_map, self.image_channel = estimate_occlusion_map, image_channel
+        self.decoder = SPADEDecoder()
+        self.requires_grad_(False)
+        self._loaded = False
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        dm = self.dense_motion_network                        # filled through this module's keys, not through its own load_state_dict
+        if dm is not None and all("dense_motion_network." + k in state_dict for k in dm._PROBE):
+            dm._loaded = True
+        return out
+
+    def source_feature(self, source_image):
+        out = self.first(source_image)
+        for block in self.down_blocks:
+            out = block(out)
+        out = self.second(out)
+        bs, _, h, w = out.shape
+        return self.resblocks_3d(out.view(bs, self.reshape_channel, self.reshape_depth, h, w))
+
+    def warp(self, feature_3d, kp_driving, kp_source):
+        if self.dense_motion_network is None:
+            raise ValueError("OcclusionAwareSPADEGenerator: built with dense_motion_params=None: the reference's forward has no input for its decoder then")
+        n = kp_driving["value"].shape[0]
+        if feature_3d.shape[0] == 1 and n != 1:                  # one source for n driving frames: what n calls of the reference compute
+            feature_3d = feature_3d.expand(n, -1, -1, -1, -1)
+        dense_motion = self.dense_motion_network(feature_3d, kp_driving, kp_source)
+        out = {"mask": dense_motion["mask"], "deformation": dense_motion["deformation"]}
+        warped = F.grid_sample(feature_3d, dense_motion["deformation"], align_corners=False)
+        bs, c, d, h, w = warped.shape
+        feature = self.fourth(self.third(warped.view(bs, c * d, h, w)))
+        if "occlusion_map" in dense_motion:
+            out["occlusion_map"] = dense_motion["occlusion_map"]
+            feature = feature * dense_motion["occlusion_map"]
+        out["feature"] = feature
+        return out
+
+    def front(self, source_image, kp_driving, kp_source):
+        """``{'mask', 'deformation'[, 'occlusion_map'], 'feature'}``: ``forward`` up to the input of ``self.decoder``."""
+        if self.training:
+            raise NotImplementedError("OcclusionAwareSPADEGenerator: training mode is not implemented; call .eval()")
+        with torch.no_grad():
+            return self.warp(self.source_feature(source_image), kp_driving, kp_source)
+
+    def forward(self, source_image, kp_driving, kp_source):
+        out = self.front(source_image, kp_driving, kp_source)
+        with torch.no_grad():
+            out["prediction"] = self.decoder(out.pop("feature"))
+        del out["deformation"]                                # the reference's output_dict holds the mask, the occlusion map and the prediction
+        return out
+
+
+def _spade_shapes(out, p, norm_nc, label_nc):
+    out[p + ".mlp_shared.0.weight"], out[p + ".mlp_shared.0.bias"] = (128, label_nc, 3, 3), (128,)
+    for nm in ("mlp_gamma", "mlp_beta"):
+        out[f"{p}.{nm}.weight"], out[f"{p}.{nm}.bias"] = (norm_nc, 128, 3, 3), (norm_nc,)
+
+
+def spade_decoder_state_dict_shapes():
+    """``{key: shape}`` of ``SPADEDecoder().state_dict()``, in its order."""
+    out = {"fc.weight": (512, 256, 3, 3), "fc.bias": (512,)}
+
+    def sn(p, co, ci, k, bias=True):
+        if bias:
+            out[p + ".bias"] = (co,)
+        out[p + ".weight_orig"], out[p + ".weight_u"], out[p + ".weight_v"] = (co, ci, k, k), (co,), (ci * k * k,)
+
+    for p, fin, fout in [(f"G_middle_{i}", 512, 512) for i in range(6)] + [("up_0", 512, 256), ("up_1", 256, 64)]:
+        mid = min(fin, fout)
+        sn(p + ".conv_0", mid, fin, 3), sn(p + ".conv_1", fout, mid, 3)
+        if fin != fout:
+            sn(p + ".conv_s", fout, fin, 1, bias=False)
+        _spade_shapes(out, p + ".norm_0", fin, 256), _spade_shapes(out, p + ".norm_1", mid, 256)
+        if fin != fout:
+            _spade_shapes(out, p + ".norm_s", fin, 256)
+    out["conv_img.weight"], out["conv_img.bias"] = (3, 64, 3, 3), (3,)
+    return out
+
+
+def generator_structure_shapes(structure, decoder: bool = True):
+    """``{key: shape}`` of the ``OcclusionAwareSPADEGenerator`` with ``structure`` (``generator_structure``), in ``state_dict`` order; without ``decoder`` the
+    keys of the front alone: everything the native path reads."""
+    cin, k, bexp, down, maxf, rc, _, nres, outf, dm = structure
+    out = {}
+    if dm is not None:
+        out.update({"dense_motion_network." + key: v for key, v in dense_motion_structure_shapes(dm).items()})
+
+    def conv(p, co, ci, kk):
+        out[p + ".weight"], out[p + ".bias"] = (co, ci, kk, kk), (co,)
+
+    conv("first.conv", bexp, cin, k), bn_shapes(out, "first.norm", bexp)
+    for i, c in enumerate(down):
+        conv(f"down_blocks.{i}.conv", c, bexp if i == 0 else down[i - 1], 3), bn_shapes(out, f"down_blocks.{i}.norm", c)
+    conv("second", maxf, down[-1], 1)
+    for i in range(nres):
+        p = f"resblocks_3d.3dr{i}"
+        for nm in ("conv1", "conv2"):
+            out[f"{p}.{nm}.weight"], out[f"{p}.{nm}.bias"] = (rc, rc, 3, 3, 3), (rc,)
+        bn_shapes(out, p + ".norm1", rc), bn_shapes(out, p + ".norm2", rc)
+    conv("third.conv", outf, maxf, 3), bn_shapes(out, "third.norm", outf)
+    conv("fourth", outf, outf, 1)
+    if decoder:
+        out.update({"decoder." + key: v for key, v in spade_decoder_state_dict_shapes().items()})
+    return out
+
+
+def generator_front_structure_shapes(structure):
+    """``generator_structure_shapes`` without the ``decoder.`` keys: what ``PreparedGeneratorFront`` validates a mapping against."""
+    return generator_structure_shapes(structure, decoder=False)
+
+
+def generator_state_dict_shapes(**config):
+    """``{key: shape}`` of ``OcclusionAwareSPADEGenerator(**config).state_dict()``, in its order (the upstream configuration by default)."""
+    return generator_structure_shapes(generator_structure(**config))
+
+
+def generator_structure_of_keys(sd, name="generator_structure_of_keys"):
+    """The structure (``generator_structure``) read off the keys and shapes of a mapping with the generator's bare keys; the ``decoder.`` keys are not needed."""
+    cls = "OcclusionAwareSPADEGenerator"
+    first = _shape_of(name, sd, "first.conv.weight", 4, cls)
+    if first[2:] != (3, 3):
+        raise ValueError(f"{name}: 'first.conv.weight' is {first}: the SPADE generator's `first` is a 3 x 3 convolution (7 x 7 is OcclusionAwareGenerator's, which "
+                         "is not implemented)")
+    bexp, cin, k = first[:3]
+    down, i = [], 0
+    while f"down_blocks.{i}.conv.weight" in sd:
+        down.append(_shape_of(name, sd, f"down_blocks.{i}.conv.weight", 4, cls)[0])
+        i += 1
+    maxf = _shape_of(name, sd, "second.weight", 4, cls)[0]
+    nres = 0
+    while f"resblocks_3d.3dr{nres}.conv1.weight" in sd:
+        nres += 1
+    outf = _shape_of(name, sd, "third.conv.weight", 4, cls)[0]
+    dm = None
+    if any(key.startswith("dense_motion_network.") for key in sd.keys()):
+        dm = _dm_structure_of_keys(name, {key[len("dense_motion_network."):]: v for key, v in sd.items() if key.startswith("dense_motion_network.")})
+    # a generator without a ResBlock3d does not say how `second`'s channels split into (channel, depth): the dense-motion network does
+    rc = _shape_of(name, sd, "resblocks_3d.3dr0.conv1.weight", 5, cls)[0] if nres else (dm[1] if dm is not None else 0)
+    if not down or rc < 1 or maxf % rc:
+        raise ValueError(f"{name}: the weights are not an OcclusionAwareSPADEGenerator the native path implements ({len(down)} down blocks, {maxf} channels of "
+                         f"`second` for a reshape_channel of {rc})")
+    return cin, k, bexp, tuple(down), maxf, rc, maxf // rc, nres, outf, dm
+
+
+_GEN_NET = _Net("OcclusionAwareSPADEGenerator", generator_front_structure_shapes, ("generator.", "module.generator.", "module."), True, ("second.weight",),
+                lambda name, sd: generator_structure_of_keys(sd, name), EVAL_ONLY, ("num_batches_tracked",))
+
+
+def _gen_net_of(weights):
+    return module_net(_GEN_NET, weights.structure) if isinstance(weights, OcclusionAwareSPADEGenerator) else _GEN_NET
+
+
+class PreparedGeneratorFront(PreparedNet):
+    """The kernels' copies of the weights of an ``OcclusionAwareSPADEGenerator`` in front of its decoder, rebuilt when a tensor changes version or storage:
+    ``first``, the down blocks and ``third`` with their bias and BatchNorm folded in float64 (K-major fp32 under 16 input channels, three-way split slabs
+    otherwise), ``second`` and ``fourth`` with their bias, per ResBlock3d ``norm1`` as float32 (scale, shift), ``conv1`` with ``norm2`` folded and ``conv2`` with
+    its bias as 27-tap slabs, and ``third``'s slope vector.  Takes a module, the mapping ``torch.load`` returns (``checkpoint['generator']`` or the whole
+    checkpoint) or a mapping without any ``decoder.`` key: the front reads none of them.  The dense-motion network's weights are ``PreparedDenseMotion``'s."""
+
+    __slots__ = ()
+    _entry = "generator_front_forward"
+
+    def _net(self, weights):
+        return _gen_net_of(weights)
+
+    def _build(self, sd, structure, dev):
+        _, _, _, down, _, _, _, nres, outf, _ = structure
+        res = []
+        for i in range(nres):
+            p = f"resblocks_3d.3dr{i}"
+            scale, shift = lossnet.bn_fold(sd, p + ".norm1")
+            res.append(dict(scale=scale.float().contiguous(), shift=shift.float().contiguous(),
+                            c1=prep_conv3d(sd[p + ".conv1.weight"], *fold_conv_bn(sd, p + ".conv1", p + ".norm2")),
+                            c2=prep_conv3d(sd[p + ".conv2.weight"], None, sd[p + ".conv2.bias"].double())))
+        return dict(first=_prep2d(sd, "first.conv", "first.norm"), down=[_prep2d(sd, f"down_blocks.{i}.conv", f"down_blocks.{i}.norm") for i in range(len(down))],
+                    second=_prep2d(sd, "second"), res=res, third=_prep2d(sd, "third.conv", "third.norm"), fourth=_prep2d(sd, "fourth"),
+                    slope=torch.full((outf,), LEAKY_SLOPE, dtype=torch.float32, device=dev))
+
+
+def bn_relu(x, scale, shift, out=None):
+    """``e4s_v2v_bn_relu``: ``relu(x * scale[c] + shift[c])`` over a float32 ``x [bs, C, ...]`` with float32 ``scale``, ``shift [C]`` (an eval-mode BatchNorm as
+    ``lossnet.bn_fold`` gives it, rounded to float32); ``out``: a dense tensor of x's shape, x itself allowed."""
+    name = "bn_relu"
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError(f"{name}: x: expected a float32 [bs, C, ...] tensor, got {getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+    C = x.shape[1]
+    for nm, t in (("scale", scale), ("shift", shift)):
+        _tensor_checked(name, nm, t, torch.float32, 1, f"float32 [{C}]")
+        if t.shape[0] != C:
+            raise ValueError(f"{name}: {nm} is {tuple(t.shape)} for x {tuple(x.shape)}: expected [{C}]")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous()):
+        raise ValueError(f"{name}: out: expected a dense float32 tensor of x's shape {tuple(x.shape)}")
+    _cuda_checked(name, x=x, scale=scale, shift=shift, **({"out": out} if out is not None else {}))
+    x, scale, shift = x.detach().contiguous(), scale.detach().contiguous(), shift.detach().contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    n = x[0, 0].numel() if x.numel() else 1
+    lib().call("e4s_v2v_bn_relu", _p(out), _p(x), _p(scale), _p(shift), x.shape[0], C, max(n, 1), _stream())
+    return out
+
+
+def occlude(x, occlusion_map, out=None):
+    """``e4s_v2v_occlude``: ``x [bs, C, h, w] * occlusion_map [bs, 1, h, w]``, float32; ``out``: a dense tensor of x's shape, x itself allowed (in place).  The
+    reference resizes an occlusion map of another size bilinearly; the dense-motion network never returns one, and a size mismatch is refused."""
+    name = "occlude"
+    _tensor_checked(name, "x", x, torch.float32, 4, "a float32 [bs, C, h, w] tensor")
+    _tensor_checked(name, "occlusion_map", occlusion_map, torch.float32, 4, "a float32 [bs, 1, h, w] map")
+    bs, C, h, w = x.shape
+    if tuple(occlusion_map.shape) != (bs, 1, h, w):
+        raise ValueError(f"{name}: occlusion_map is {tuple(occlusion_map.shape)} for x {tuple(x.shape)}: expected {(bs, 1, h, w)} (the bilinear resize of a map of "
+                         "another size is not implemented: the dense-motion network returns the feature's size)")
+    if C < 1 or h * w < 1:
+        raise ValueError(f"{name}: x is {tuple(x.shape)}: no empty channel or plane")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous()):
+        raise ValueError(f"{name}: out: expected a dense float32 tensor of x's shape {tuple(x.shape)}")
+    _cuda_checked(name, x=x, occlusion_map=occlusion_map, **({"out": out} if out is not None else {}))
+    if out is not None and out.data_ptr() == x.data_ptr() and not x.is_contiguous():
+        raise ValueError(f"{name}: in place needs a dense x")
+    x, occ = x.detach().contiguous(), occlusion_map.detach().contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    lib().call("e4s_v2v_occlude", _p(out), _p(x), _p(occ), bs, C, h * w, _stream())
+    return out
+
+
+def _deform_checked(name, feature_3d, deformation):
+    _tensor_checked(name, "feature_3d", feature_3d, torch.float32, 5, "a float32 [bs, C, D, h, w] volume")
+    _tensor_checked(name, "deformation", deformation, torch.float32, 5, "a float32 [n, D, h, w, 3] sampling grid")
+    fb, C, D, H, W = feature_3d.shape
+    n = deformation.shape[0]
+    if tuple(deformation.shape[1:]) != (D, H, W, 3):
+        raise ValueError(f"{name}: deformation is {tuple(deformation.shape)} for feature_3d {tuple(feature_3d.shape)}: expected [n, {D}, {H}, {W}, 3] (the trilinear "
+                         "resize of a deformation of another size is not implemented: the dense-motion network returns the feature's size)")
+    if fb != n and fb != 1:
+        raise ValueError(f"{name}: feature_3d is {tuple(feature_3d.shape)} for a deformation of batch {n}: expected a batch of {n}, or 1 (shared by every sample)")
+    if min(C, D, H, W) < 1:
+        raise ValueError(f"{name}: feature_3d is {tuple(feature_3d.shape)}: no empty extent")
+    return n, C, D, H, W
+
+
+def deform_feature(feature_3d, deformation, out=None):
+    """``e4s_v2v_deform``: the reference's ``deform_input`` and the ``view`` behind it: ``F.grid_sample(feature_3d [bs, C, D, h, w], deformation [n, D, h, w,
+    3])`` at its defaults (trilinear, zero padding, ``align_corners=False``) as ``[n, C D, h, w]``.  A ``feature_3d`` of batch 1 against a deformation of batch n
+    is read through a batch stride of 0: one source feature for every driving frame, without a copy (so is a batch-1 volume ``expand``ed to n).  ``out``: a
+    ``[n, C D, h, w]`` tensor or channel slice of a dense buffer to write into."""
+    name = "deform_feature"
+    n, C, D, H, W = _deform_checked(name, feature_3d, deformation)
+    shape = (n, C * D, H, W)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not _batch_slice(out)):
+        raise ValueError(f"{name}: out: expected float32 {shape} with every sample dense, got {getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
+    _cuda_checked(name, feature_3d=feature_3d, deformation=deformation, **({"out": out} if out is not None else {}))
+    if deformation.device != feature_3d.device or (out is not None and out.device != feature_3d.device):
+        raise RuntimeError(f"{name}: device mismatch among the tensors")
+    feature_3d = feature_3d.detach()
+    shared = feature_3d.shape[0] == 1 or (n > 1 and feature_3d.stride(0) == 0)
+    if shared:
+        feature_3d = feature_3d[:1]
+    x = feature_3d if _batch_slice(feature_3d) else feature_3d.contiguous()
+    deformation = deformation.detach().contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if n:
+        lib().call("e4s_v2v_deform", _p(out), _p(x), _p(deformation), n, C, D, H, W, 0 if shared else _bstride(x), _bstride(out), _stream())
+    return out
+
+
+def _generator_checked(name, weights):
+    """(weights without the checkpoint's wrapping, what ``_validated`` returns, the structure); a generator without a dense-motion network is refused."""
+    check_loaded(name, weights, "the weights")
+    if not isinstance(weights, nn.Module) and hasattr(weights, "keys") and isinstance(weights.get("generator"), dict):
+        weights = weights["generator"]                      # the checkpoint file as torch.load gives it
+    if isinstance(weights, OcclusionAwareSPADEGenerator) and weights.structure[9] is None:
+        raise ValueError(f"{name}: the generator was built with dense_motion_params=None: without a dense-motion network there is no deformation to warp by")
+    checked = _validated(name, weights, _gen_net_of(weights))
+    if checked[1][9] is None:
+        raise ValueError(f"{name}: the weights hold no dense_motion_network. keys (dense_motion_params=None): without a dense-motion network there is no "
+                         "deformation to warp by")
+    return weights, checked, checked[1]
+
+
+def _feature_size_checked(name, nm, shape, structure, h, w):
+    """The feature plane ``h x w`` must be one the dense-motion network takes: multiples of 2 ** num_blocks, at least 2."""
+    nb = len(structure[9][3])
+    if min(h, w) < 2 or structure[6] < 2:
+        raise ValueError(f"{name}: {nm} is {tuple(shape)}: the feature volume would be {structure[6]} x {h} x {w}, every extent must be at least 2 (the "
+                         "dense-motion network's coordinate grid divides by n - 1)")
+    if h % 2 ** nb or w % 2 ** nb:
+        raise ValueError(f"{name}: {nm} is {tuple(shape)}: the feature plane {h} x {w} must be multiples of 2 ** num_blocks = {2 ** nb} of the dense-motion network")
+
+
+def appearance_feature(source, weights):
+    """The source-only part of ``OcclusionAwareSPADEGenerator.forward`` (generator.py:212-219) in eval mode on the device: ``first``, the down blocks, ``second``,
+    the view and ``resblocks_3d``: ``feature_3d [bs, reshape_channel, reshape_depth, H / 2 ** num_down_blocks, W / 2 ** num_down_blocks]`` from a float32
+    ``source [bs, 3, H, W]``.  It does not depend on the driving frame: compute it once per clip and hand it to ``generator_warp``.  ``weights``: an
+    ``OcclusionAwareSPADEGenerator``, the mapping ``torch.load`` returns (``checkpoint['generator']`` or the checkpoint itself) or a mapping without the
+    ``decoder.`` keys.  Refused with ``ValueError`` before any launch: anything not float32, other than three channels, a size that ``2 ** num_down_blocks`` does
+    not divide or that leaves the dense-motion network an extent it refuses, a generator without a dense-motion network; then a CPU tensor (``RuntimeError``)."""
+    name = "appearance_feature"
+    weights, checked, structure = _generator_checked(name, weights)
+    _tensor_checked(name, "source", source, torch.float32, 4, "a float32 [bs, 3, H, W] image")
+    _, k, _, down, maxf, rc, depth, _, _, _ = structure
+    bs, ch, H, W = source.shape
+    if ch != 3:
+        raise ValueError(f"{name}: source is {tuple(source.shape)}: expected three colour channels")
+    f = 2 ** len(down)
+    if H % f or W % f or min(H, W) < f or max(H, W) > 16384:
+        raise ValueError(f"{name}: source is {tuple(source.shape)}: H and W must be multiples of 2 ** num_down_blocks = {f} (the reference's pools would drop a row "
+                         "or column), up to 16384")
+    h, w = H // f, W // f
+    _feature_size_checked(name, "source", source.shape, structure, h, w)
+    _placed_checked(name, "source", source, checked[2])
+    if bs == 0:
+        return source.new_empty((0, rc, depth, h, w))
+    with torch.no_grad():
+        P = lossnet.prepare(PreparedGeneratorFront, weights, checked)
+        cur = _conv_any(source.detach().contiguous(), P["first"], k, relu=True)
+        for L in P["down"]:
+            cur = avgpool2x2(_conv_any(cur, L, 3, relu=True))
+        cur = _conv_any(cur, P["second"], 1).view(bs, rc, depth, h, w)
+        for R in P["res"]:
+            t = torch.empty_like(cur)
+            lib().call("e4s_v2v_bn_relu", _p(t), _p(cur), _p(R["scale"]), _p(R["shift"]), bs, rc, depth * h * w, _stream())
+            t = conv3d_sb3(t, *R["c1"], relu=True)
+            cur = conv3d_sb3(t, *R["c2"], residual=cur)
+    return cur
+
+
+def generator_warp(feature_3d, kp_driving, kp_source, weights):
+    """The per-frame part of ``OcclusionAwareSPADEGenerator.forward`` (generator.py:221-244) in eval mode on the device: the dense-motion network, ``deform_input``,
+    ``third``, ``fourth`` and the product with the occlusion map: ``{'mask' [n, K + 1, D, h, w], 'deformation' [n, D, h, w, 3][, 'occlusion_map' [n, 1, h, w]],
+    'feature' [n, block_expansion 2 ** num_down_blocks, h, w]}``, ``feature`` the decoder's input.  The batch n is that of the keypoint dicts; a ``feature_3d``
+    (``appearance_feature``) of batch 1 is shared by all n frames.  ``weights`` and the refusals as ``appearance_feature``'s, and ``dense_motion_forward``'s for
+    the keypoints."""
+    name = "generator_warp"
+    weights, checked, structure = _generator_checked(name, weights)
+    _, _, _, _, maxf, rc, depth, _, outf, dm = structure
+    _tensor_checked(name, "feature_3d", feature_3d, torch.float32, 5, "a float32 [bs, C, D, h, w] volume")
+    fb, _, _, h, w = feature_3d.shape
+    if tuple(feature_3d.shape[1:3]) != (rc, depth):
+        raise ValueError(f"{name}: feature_3d is {tuple(feature_3d.shape)}: expected [bs, {rc}, {depth}, h, w] (reshape_channel, reshape_depth)")
+    _feature_size_checked(name, "feature_3d", feature_3d.shape, structure, h, w)
+    kps = _keypoints_checked(name, kp_driving, kp_source, None, dm[0])
+    n = kps[0].shape[0]
+    if fb != n and fb != 1:
+        raise ValueError(f"{name}: feature_3d is {tuple(feature_3d.shape)} for keypoints of batch {n}: expected a batch of {n}, or 1 (shared by every frame)")
+    _placed_checked(name, "feature_3d", feature_3d, checked[2])
+    _keypoints_placed(name, feature_3d, kps)
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=feature_3d.device)      # noqa: E731
+    if n == 0:
+        out = {"mask": new(0, dm[0] + 1, depth, h, w), "deformation": new(0, depth, h, w, 3)}
+        if dm[5]:
+            out["occlusion_map"] = new(0, 1, h, w)
+        out["feature"] = new(0, outf, h, w)
+        return out
+    with torch.no_grad():
+        P = lossnet.prepare(PreparedGeneratorFront, weights, checked)
+        feature_3d = feature_3d.detach()
+        # dense_motion_forward takes a dense batch: the shared volume is copied n times here (8 MB per frame at the upstream size), the gather reads it in place
+        # a mapping goes on as the validated bare keys (a `generator.` prefix or the file's nesting is gone): its dense_motion_network. keys are what
+        # dense_motion_forward understands
+        dmw = weights.dense_motion_network if isinstance(weights, nn.Module) else checked[0]
+        out = dense_motion_forward(feature_3d.expand(n, -1, -1, -1, -1) if fb != n else feature_3d, kp_driving, kp_source, dmw)
+        warped = deform_feature(feature_3d, out["deformation"])
+        w3, b3 = P["third"]
+        conv = conv_sb if isinstance(w3, tuple) else conv_exact
+        feature = _conv_any(conv(warped, w3, b3, k=3, slope=P["slope"]), P["fourth"], 1)
+        if "occlusion_map" in out:
+            lib().call("e4s_v2v_occlude", _p(feature), _p(feature), _p(out["occlusion_map"]), n, outf, h * w, _stream())
+        out["feature"] = feature
+    return out
+
+
+def generator_front_forward(source, kp_driving, kp_source, weights):
+    """``OcclusionAwareSPADEGenerator.forward(source, kp_driving, kp_source)`` up to the input of its decoder: ``generator_warp(appearance_feature(source,
+    weights), kp_driving, kp_source, weights)``.  ``source`` holds one image, or one per keypoint set."""
+    name = "generator_front_forward"
+    _generator_checked(name, weights)
+    _tensor_checked(name, "source", source, torch.float32, 4, "a float32 [bs, 3, H, W] image")
+    kps = _keypoints_checked(name, kp_driving, kp_source)
+    if source.shape[0] not in (1, kps[0].shape[0]):
+        raise ValueError(f"{name}: source is {tuple(source.shape)} for keypoints of batch {kps[0].shape[0]}: expected that batch, or 1")
+    return generator_warp(appearance_feature(source, weights), kp_driving, kp_source, weights)
+
+
 __all__ = ["KPDetector", "HEEstimator", "PreparedKPDetector", "PreparedHEEstimator", "NUM_BINS", "antialias_kernel", "kp_detector_structure", "kp_volume_size",
            "kp_detector_structure_shapes", "he_estimator_structure_shapes", "kp_detector_state_dict_shapes", "he_estimator_state_dict_shapes", "prep_conv3d",
            "conv3d_sb3", "heatmap_keypoints", "antialias_down", "avgpool2x2", "kp_detector_forward", "he_estimator_forward", "keypoint_transformation",
            "headpose_degrees", "rotation_matrix", "reenact_keypoints", "DenseMotionNetwork", "PreparedDenseMotion", "dense_motion_structure",
            "dense_motion_structure_shapes", "dense_motion_state_dict_shapes", "prep_conv3d_k7", "conv3d_k7", "motion_input", "motion_combine",
-           "dense_motion_forward"]
+           "dense_motion_forward", "OcclusionAwareSPADEGenerator", "SPADEDecoder", "PreparedGeneratorFront", "LEAKY_SLOPE", "DENSE_MOTION_PARAMS",
+           "generator_structure", "generator_structure_shapes", "generator_front_structure_shapes", "generator_state_dict_shapes",
+           "spade_decoder_state_dict_shapes", "generator_structure_of_keys", "bn_relu", "occlude", "deform_feature", "appearance_feature", "generator_warp",
+           "generator_front_forward"]

@@ -547,6 +547,20 @@ def reenact_dense_motion(dense_motion, feature: torch.Tensor, kp_driving, kp_sou
     return ops.dense_motion_forward(feature, kp_driving, kp_source, dense_motion)
 
 
+def reenact_source_feature(generator, source: torch.Tensor):
+    """The part of ``OcclusionAwareSPADEGenerator.forward`` that sees the source alone (generator.py:212-219), once per clip: float32 ``source [1, 3, H, W]`` in
+    [0, 1] to the appearance volume ``feature_3d [1, reshape_channel, reshape_depth, h, w]`` (``ops.appearance_feature``).  ``make_animation`` recomputes it for
+    every driving frame; here it is held and handed to ``reenact_warp``.  ``generator`` as ``ops.appearance_feature`` takes weights."""
+    return ops.appearance_feature(source, generator)
+
+
+def reenact_warp(generator, feature_3d: torch.Tensor, kp_driving, kp_source):
+    """The per-frame part of the generator in front of its decoder (generator.py:221-244), for the n driving frames of the keypoint dicts at once: the dense-motion
+    network, the warp of the held ``feature_3d`` (batch 1: shared by every frame), ``third``, ``fourth`` and the occlusion product, to ``{'mask',
+    'deformation'[, 'occlusion_map'], 'feature'}`` (``ops.generator_warp``); ``feature`` is the ``SPADEDecoder``'s input.  The decoder stays with the caller."""
+    return ops.generator_warp(feature_3d, kp_driving, kp_source, generator)
+
+
 @torch.no_grad()
 def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_u8: Optional[torch.Tensor] = None, return_faces: bool = False):
     """``FaceEnhancement.process(img, aligned=False)`` (swap_face_fine/gpen/face_enhancement.py:68-110) behind its ``use_sr`` branch, for a batch of frames on

@@ -38,6 +38,7 @@ __all__ = [
     "seeded_kp_detector_state_dict",
     "seeded_he_estimator_state_dict",
     "seeded_dense_motion_state_dict",
+    "seeded_generator_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -490,10 +491,40 @@ def seeded_dense_motion_state_dict(template: Mapping[str, torch.Tensor], seed: i
     return seeded_state_dict(template, seed, "v2v_dm")
 
 
+# face-vid2vid's OcclusionAwareSPADEGenerator (modules/generator.py).  The front (first, down_blocks, second, resblocks_3d, third, fourth) follows the rules above:
+# BatchNorm scales of either sign with one exact zero per layer, statistics off the identity, biases away from zero.  The decoder's SPADE blocks follow the
+# recolouring feature network's rules (a fan-in scaled bulk plus a leading component of size FPN_SIGMA along weight_v), except that ``weight_u`` is not drawn but
+# set to normalize(W v): then sigma = u . W v = |W v| is a norm, about FPN_SIGMA, and never near zero.
+_RULES_V2V_GEN = [
+    (r"^decoder\..*\.weight_orig$", _spectral_weight),
+    (r"^decoder\..*\.weight_[uv]$", _unit_vector),
+    (r"^decoder\..*\.mlp_shared\.0\.weight$", _fan_in_std(1.4)),
+    (r"^decoder\..*\.bias$", (0.0, 0.2)),
+    (r"^decoder\..*\.weight$", _fan_in_std(1.0)),
+    (r"^fourth\.weight$", _fan_in_std(1.0)),
+] + _RULES_V2V_KP
+
+
+def seeded_generator_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for a network with the keys of face-vid2vid's ``OcclusionAwareSPADEGenerator``, or any part of them (``template``: its
+    ``state_dict()``, meta tensors will do; the ``decoder.`` keys may be left out).  The ``dense_motion_network.`` keys get what
+    ``seeded_dense_motion_state_dict`` gives the bare keys with the same seed."""
+    dm = "dense_motion_network."
+    inner = seeded_dense_motion_state_dict({k[len(dm):]: v for k, v in template.items() if k.startswith(dm)}, seed)
+    rest = seeded_state_dict({k: v for k, v in template.items() if not k.startswith(dm)}, seed, "v2v_gen")
+    out = {k: (inner[k[len(dm):]] if k.startswith(dm) else rest[k]) for k in template}
+    for k in out:
+        if k.endswith(".weight_u"):
+            w, v = out[k[:-2] + "_orig"].double(), out[k[:-2] + "_v"].double()
+            u = w.reshape(w.shape[0], -1) @ v
+            out[k] = (u / u.norm()).float()
+    return out
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
              "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
-             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM}.get(family, _RULES_BISENET)
+             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM, "v2v_gen": _RULES_V2V_GEN}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

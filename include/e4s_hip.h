@@ -1033,6 +1033,28 @@ E4S_API int e4s_v2v_motion_input(float* out, const float* feature, const float* 
 E4S_API int e4s_v2v_motion_combine(float* mask, float* deformation, const float* logits, const float* kp_d, const float* kp_s, const float* jac_d,
                                    const float* jac_s, int bs, int K, int D, int H, int W, void* stream);
 
+/* f19: face-vid2vid reenactment, stage 3 — the generator's feature warp (swap_face_fine/face_vid2vid/modules/generator.py:161-244, modules/util.py:131-153,
+ * 196-259; csrc/vid2vid.hip).  The appearance encoder runs on the 2-D convolutions and the 2 x 2 pool above, `resblocks_3d` on the 3 x 3 x 3 kernel (norm2 folded
+ * into conv1, the block's input as conv2's residual), `third` and `fourth` on the split-bf16 2-D convolution.
+ *   v2v_deform  : deform_input: out + b out_bstride + [C D][H][W] = F.grid_sample(feature, deformation) at its defaults (trilinear, zero padding, align_corners =
+ *                 False), feature sample b at feature + b feat_bstride + [C][D][H][W], deformation [bs][D][H][W][3] in (x, y, z) order.  Unnormalisation, floor,
+ *                 the eight weights and the order in which the taps join the sum are the device function of the motion-input kernel above: the same bits on the
+ *                 same coordinates, and exactly 0 where all eight taps are outside.  A position's taps are computed once per 4 channels.  feat_bstride 0: one
+ *                 feature serves every sample (the source's, for all driving frames of a launch); otherwise at least a sample.  One position per lane, so a
+ *                 wave gathers from neighbouring addresses and stores 256 contiguous bytes; any 4-byte alignment gives the same bits.  (Four positions per
+ *                 lane with 16-byte stores were measured 1.7x slower on a smooth deformation: every gather of a wave then spreads over four times the cache
+ *                 lines; tools/probes/deform_forms_probe.hip holds both forms.)
+ *   v2v_bn_relu : out [bs][C][n] = max(fma(x, scale[c], shift[c]), 0): an eval-mode BatchNorm and ReLU that stand in front of a zero-padded convolution
+ *                 (ResBlock3d's norm1), which no fold into the weights can express.  out may be x.  A NaN input gives 0 (fmaxf returns its other
+ *                 operand), where F.relu would hand the NaN on.
+ *   v2v_occlude : out [bs][C][hw] = x * occ [bs][1][hw]; out may be x.
+ * The last two take 16-byte accesses where the plane size is a multiple of 4 and the pointers are aligned.  fp32, no atomics, no host synchronisation, no
+ * scratch memory, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_v2v_deform(float* out, const float* feature, const float* deformation, int bs, int C, int D, int H, int W, int64_t feat_bstride,
+                           int64_t out_bstride, void* stream);
+E4S_API int e4s_v2v_bn_relu(float* out, const float* x, const float* scale, const float* shift, int bs, int C, int n, void* stream);
+E4S_API int e4s_v2v_occlude(float* out, const float* x, const float* occ, int bs, int C, int hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
