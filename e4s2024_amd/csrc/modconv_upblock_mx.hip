@@ -12,21 +12,34 @@
 // x * s[r] -> a1 = f16, fp6(a1), fp6(x s - a1) with one block scale per patch pixel and 32-channel chunk, made once per staged value; the K loop reads LDS and issues
 // MFMAs (1.667 units per MAC: 3.3 per algorithmic MAC at 2.0x).  The weights arrive by LDS-DMA (a ring of three tap-pair units of 15 KB) instead of through registers.
 //
-//   workgroup: a PAIR of horizontally adjacent blocks x 64 output channels, 512 threads = 2 groups of 4 waves x 32 positions (10 x 10 positions feed a block's 19 x 19
-//              pre-blur window; a position owns z[2a + i][2b + j]); the two groups share ONE weight ring of six 15 KB units.  (The first version — one block per
-//              256-thread workgroup, two per CU, a ring of three — was 5 % faster than the round-2 kernel, not 40 %: a block streams 600 KB of weights for 100
-//              positions, 1.2 GB of LDS-DMA per launch, at the ~5 TB/s that 60 KB in flight per CU sustain (in flight / latency): the kernel was bound by weight
-//              ingest, like its predecessor.  A pair halves the bytes per MFMA to the other kernels' 160 B and the deeper ring keeps 75 KB in flight.)
+//   workgroup: a PAIR of horizontally adjacent blocks x 64 output channels, 512 threads = 2 groups of 4 waves; a wave's 32 MFMA columns are two 3 x 5 sub-tiles of
+//              the block's 10 x 10 positions, laid out so that a 16-byte activation read meets no LDS bank twice (at `xoff`; 10 x 10 positions feed a block's
+//              19 x 19 pre-blur window; a position owns z[2a + i][2b + j]); the two groups share ONE weight ring of six 15 KB units.  (The first version — one
+//              block per 256-thread workgroup, two per CU, a ring of three — was 5 % faster than the round-2 kernel, not 40 %: a block streams 600 KB of weights
+//              for 100 positions, 1.2 GB of LDS-DMA per launch, at the ~5 TB/s that 60 KB in flight per CU sustain (in flight / latency): the kernel was bound by
+//              weight ingest, like its predecessor.  A pair halves the bytes per MFMA to the other kernels' 160 B and the deeper ring keeps 75 KB in flight.)
+//   staging:   a chunk's raw activations land by LDS-DMA, 16 four-byte requests per wave (all eight waves), and are converted by two waves per group — group 0's
+//              waves 0, 1, group 1's waves 6, 7: one per SIMD — behind the chunk's last barrier
 //   K loop:    chunk = 32 input channels; five units = tap pairs that share an accumulator parity — (0,0)|(0,2) and (2,0)|(2,2) -> (0,0); (1,0)|(1,2) -> (1,0);
-//              (0,1)|(2,1) -> (0,1); (1,1) -> (1,1) — 8 f16 + 4 fp6 MFMAs per wave and unit, one barrier per unit (the ring slot's hand-over)
+//              (0,1)|(2,1) -> (0,1); (1,1) -> (1,1) — 8 f16 + 4 fp6 MFMAs per wave and unit in four groups, each group's operands read from LDS under the group
+//              before it; one barrier per unit, between the fp6 halves (the ring slot's hand-over: by then every wave holds all of the unit's operands)
 //   epilogue:  the round-2 kernel's (8 channels at a time through a pre-blur tile in LDS, 4 x 4 FIR with a rolling four-row window, demodulation / noise / bias /
 //              leaky ReLU, fp32 NCHW stores)
+// Where its time goes and what each change of the staging / loop pass returned: profiles/upblk_parts.txt, profiles/upblk_ab.txt (256 -> 128 @128^2, batch 4: 262 ->
+// 227 us alone on the chip).  Built, measured and taken out there, all with the same bits: the conversion on the five-instruction pair (v_pk_mul_f32 + packed
+// conversion + two mix-fmas; 0 us: hipcc's code for the value-by-value form is as short), the tables' loads behind the first requests in the prologue (0 us),
+// both taps' f16 operands read ahead instead of one (+3 us).  What is left: the epilogue (about 28 % of the kernel) and the conversion with its requests (21 %).
 // f16 range: a wave that sees |x s| >= 65520 raises flags[0] bit 0 and bumps flags[1] (ops.MxGuard re-runs the pass on the split-bf16 kernels).
 #include "modconv_mx_tile.h"
 
 // Tuning builds only (-DUX_ABL=bits; results are then meaningless): 1 = no K loop, 2 = no epilogue, 4 = no activation loads / conversions after the first chunk
 #ifndef UX_ABL
 #define UX_ABL 0
+#endif
+// Tuning builds only (-DUX_BACK=bits; same bits either way, profiles/upblk_ab.txt): 1 = activation requests and conversion on waves 0, 1, 4, 5 as in the first form,
+// 2 = positions in lane order
+#ifndef UX_BACK
+#define UX_BACK 0
 #endif
 
 namespace {
@@ -87,6 +100,7 @@ __device__ __forceinline__ void ux_wait_vm(int n) {      // s_waitcnt vmcnt(n) f
     switch (n) {
 #define UX_CASE(v) case v: E4S_WAIT_VM(v); break;
         UX_CASE(0) UX_CASE(1) UX_CASE(2) UX_CASE(3) UX_CASE(4) UX_CASE(5) UX_CASE(6) UX_CASE(8) UX_CASE(10)
+        UX_CASE(16) UX_CASE(17) UX_CASE(18) UX_CASE(19) UX_CASE(20) UX_CASE(21) UX_CASE(22) UX_CASE(24) UX_CASE(26)
         UX_CASE(32) UX_CASE(33) UX_CASE(34) UX_CASE(35) UX_CASE(36) UX_CASE(38) UX_CASE(40)
 #undef UX_CASE
         default: E4S_WAIT_VM(0); break;
@@ -186,12 +200,24 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
         }
     };
 
-    // ---- staging thread = patch pixel (threads 0..120 of a group: its waves 0 and 1)
-    const bool has_x = gw < 2 && live;
+    // ---- staging.  Requests: every wave of a live group carries a quarter of a chunk's 64 — patch pixels 64 (gw & 1) .. + 63 x channels 16 (gw >> 1) .. + 15 — so
+    // no SIMD issues more of them than another (waves w and w + 4 share SIMD w % 4: on waves 0, 1, 4, 5 alone, the first form, SIMDs 0 and 1 issued all 128 of a
+    // workgroup and chunk, and every barrier waits for the slowest SIMD).  Conversion: thread = patch pixel (121 of 128), two waves per group — group 0's on waves
+    // 0, 1 and group 1's on waves 6, 7, i.e. on all four SIMDs.
+    const int pt = (gw & 1) * 64 + lane;                        // this thread's patch pixel, for its requests and for its conversion
+#if UX_BACK & 1
+    const bool has_x = gw < 2 && live, has_cv = has_x;
+    constexpr int LD_NC = UX_CK;
+    const int ld_c0 = 0;
+#else
+    const bool has_x = live, has_cv = live && (gw >> 1) == grp;
+    constexpr int LD_NC = UX_CK / 2;
+    const int ld_c0 = (gw >> 1) * LD_NC;
+#endif
     const int PCS = wave < 7 ? 2 : 1;
-    const int NLD = has_x ? UX_CK : 0;
+    const int NLD = has_x ? LD_NC : 0;                          // this wave's activation requests per chunk
     auto patch_pixel = [&](bool& in) __attribute__((always_inline)) {
-        int t = lt;
+        int t = pt;
         pin_here(t);
         const int se_y = t / UX_PW, se_x = t - se_y * UX_PW;
         const int sgy = tyt * (UX_OUT / 2) - 2 + se_y, sgx = txt * (UX_OUT / 2) - 2 + se_x;
@@ -200,24 +226,24 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
     };
     // the next chunk's activations go straight to LDS (global_load_lds_dword: one channel x this wave's 64 patch pixels per request, per-lane addresses) instead of
     // through 32 registers per thread — the accumulators (128) and a unit's operands leave no room for them; the conversion reads them back at the chunk's end
-    const unsigned raw_dst = (unsigned)(UX_GRP0 + grp * UX_GRPB + UX_RAW + gw * 64 * 4);
+    const unsigned raw_dst = (unsigned)(UX_GRP0 + grp * UX_GRPB + UX_RAW + (gw & 1) * 64 * 4);
     auto load_x = [&](int chunk) __attribute__((always_inline)) {
         if (has_x) {
             bool in;
             const unsigned goff = patch_pixel(in);
 #pragma unroll
-            for (int c = 0; c < UX_CK; ++c) dma4_asm(xb + (size_t)(chunk * UX_CK + c) * hw, goff, raw_dst + (unsigned)(c * UX_EST * 4));
+            for (int c = 0; c < LD_NC; ++c) dma4_asm(xb + (size_t)(chunk * UX_CK + ld_c0 + c) * hw, goff, raw_dst + (unsigned)((ld_c0 + c) * UX_EST * 4));
         }
     };
     unsigned ovf = 0u;
     auto store_x = [&](int chunk) __attribute__((always_inline)) {
-        if (!has_x) return;
+        if (!has_cv) return;
         bool in;
         (void)patch_pixel(in);
         const float4* st = reinterpret_cast<const float4*>(gl + UX_SROW) + chunk * (UX_CK / 4);
         float xr[UX_CK];
         {
-            int t = lt;
+            int t = pt;
             pin_here(t);
             const float* raw = reinterpret_cast<const float*>(gl + UX_RAW) + t;
 #pragma unroll
@@ -256,7 +282,7 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
         const unsigned e1 = ex > 3u ? ex - 2u : 1u, e2 = ex > 14u ? ex - 13u : 1u;
         const u32x6 c1 = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(__builtin_bit_cast(f16x32, q1), __builtin_bit_cast(float, e1 << 23));
         const u32x6 c2 = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(__builtin_bit_cast(f16x32, q2), __builtin_bit_cast(float, e2 << 23));
-        int t = lt;
+        int t = pt;
         pin_here(t);
         if (t < UX_PATCH) {
             uint4* a1p = reinterpret_cast<uint4*>(gl + UX_A1);
@@ -301,12 +327,27 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
     store_x(0);
     E4S_LDS_BARRIER();
 
+#if UX_BACK & 2
     // this lane's position (gw * 32 + l5 of the group's 100) and its patch element
     const int pos = gw * 32 + l5;
     const bool pos_ok = pos < UX_NPOS;
     const int posc = pos_ok ? pos : UX_NPOS - 1;
     const int pty = posc / UX_T, ptx = posc - pty * UX_T;
     const int xoff = pty * UX_PW + ptx;
+#else
+    // This lane's position and its patch element.  A 16-byte LDS read serves the lanes {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of each half-wave together,
+    // conflict-free if their 16-byte entries differ modulo 16.  Each such set of 16 lanes takes a sub-tile of 3 rows x 5 columns of the 10 x 10 positions (wave gw:
+    // rows 3 gw .. 3 gw + 2, the two sets: columns 0-4 and 5-9; wave 3 has row 9 only): patch entries 11 r + c relative to the sub-tile's corner = {0-4, 11-15,
+    // 22-26}, all different modulo 16 under every tap's shift; the sixteenth lane idles on entry 5.  (Positions in lane order, 32 per wave: entries 0 and 16 of
+    // one set met on a bank — every activation read of the K loop took two passes.)  The idle lanes' columns of the MFMAs are never stored; their rows beyond the
+    // patch read 32 entries lower (the same banks, inside the plane).
+    const int lq = l5 >> 2;
+    const int li = l5 - 4 * ((lq + 1) >> 1);                    // 0 .. 15 inside the lane set
+    const int lr = li == 15 ? 0 : li / 5, lc = li == 15 ? 5 : li - 5 * lr;
+    const int pty = 3 * gw + lr, ptx = 5 * ((0x96 >> lq) & 1) + lc;
+    const bool pos_ok = li < 15 && pty < UX_T;
+    const int xoff = pty * UX_PW + ptx - (pty >= UX_T ? 32 : 0);
+#endif
 
     f32x16 accs[4][2];
 #pragma unroll
@@ -316,94 +357,126 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
 #pragma unroll
             for (int r = 0; r < 16; ++r) accs[a][i][r] = 0.f;
 
-    // One phase per unit: operands, MFMAs, the wait for the next unit's weights, one barrier (the ring slot's hand-over); the next chunk's conversion behind the chunk's
-    // last barrier.  (A two-phase schedule — group 1 half a unit behind group 0, R / M phases, each group converting behind its own last M phase — was built and measured
-    // in this round: correct, 307 against 281 us on the 128 -> 256 layer.  Neither schedule is what bounds this tile: see the note on weight ingest in the header.)
+    // One barrier per unit, in the MIDDLE of it, and every operand read issued one MFMA group ahead of its use:
+    //     fp6 reads (g) | f16 MFMAs (g) | wait: unit g + 1 has landed | barrier | request unit g + 6 into unit g's slot | f16 reads (g + 1) | fp6 MFMAs (g)
+    // The fp6 operands arrive under the eight f16 MFMAs, the next unit's f16 operands under the four fp6 MFMAs.  (The first form read a unit's operands and ran its
+    // MFMAs between two barriers; hipcc placed each read right in front of the MFMA that takes it — the smallest register count — so with two waves per SIMD in lock
+    // step most MFMAs waited a whole LDS latency: 260 TFLOP/s executed against the four-parity kernel's 520.)  At the barrier every wave has all of unit g's
+    // operands in registers (lgkmcnt(0)): its slot is free, and behind the chunk's last unit so are the chunk's prepared planes — the next chunk's conversion sits
+    // behind that barrier, one more barrier behind it, and only then the next unit's f16 reads.
+    // (A two-phase schedule — group 1 half a unit behind group 0, R / M phases, each group converting behind its own last M phase — was built and measured in round
+    // 5: correct, 307 against 281 us on the 128 -> 256 layer.)
     const unsigned char* wl = lds + UX_RING + (khalf * UX_TN + l5) * 16;
+    // (The reads are NOT under `live`: a register read on one side of a branch only keeps its old value alive up to the branch's end — 24 registers across the
+    // conversion, which then spills.  The idle group of a pair with one mixed block reads its never-written planes, in bounds, and drops the values.)
+    uint4 xa[2][2], wv[2][2][2];                // f16 operands of the unit about to run: a1 of its two taps, w1 [cb][tap][16-channel half]
+    // patch elements of a unit's two taps: position (pty, ptx) reads x[a - (ky >> 1)] = patch row pty + 1 - (ky >> 1)
+    // (recomputed from an opaque copy in every unit: as loop invariants the five units' fifteen LDS addresses would sit in registers the loop needs)
+    auto tap_entry = [&](int u, int d) __attribute__((always_inline)) {
+        int xo = xoff;
+        pin_here(xo);
+        return xo + (1 - (ux_tap_ky(u, d) >> 1)) * UX_PW + (1 - (ux_tap_kx(u, d) >> 1));
+    };
+    auto read_f16 = [&](int u, int d, int slot) __attribute__((always_inline)) {         // tap d of unit u
+        const unsigned char* ws = wl + slot * UX_UNITB;
+        const int e = tap_entry(u, d);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            xa[d][j] = *reinterpret_cast<const uint4*>(gl + UX_A1 + ((2 * j + khalf) * UX_EST + e) * 16);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) wv[cb][d][j] = *reinterpret_cast<const uint4*>(ws + ((d * 2 + j) * 2 * UX_TN + cb * 32) * 16);
+        }
+    };
+    auto mfma_f16 = [&](int ai, int d) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+                accs[ai][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wv[cb][d][j]), __builtin_bit_cast(f16x8, xa[d][j]), accs[ai][cb], 0, 0, 0);
+    };
     int slot = 0, g = 0;
+    if (!(UX_ABL & 1)) read_f16(0, 0, 0);
 #pragma unroll 1
     for (int chunk = 0; chunk < ((UX_ABL & 1) ? 0 : nchunk); ++chunk) {
         const bool more = chunk + 1 < nchunk;
         if (more && !(UX_ABL & 4)) load_x(chunk + 1);
 #pragma unroll
         for (int u = 0; u < UX_NUNIT; ++u, ++g) {
-            // the slot unit g - 1 left (every wave passed that unit's barrier) takes unit g - 1 + NSLOT
-            if (g >= 1 && g - 1 + UX_NSLOT < nunits) dma_unit(g - 1 + UX_NSLOT, slot == 0 ? UX_NSLOT - 1 : slot - 1);
-            // patch elements of the unit's two taps: position (pty, ptx) reads x[a - (ky >> 1)] = patch row pty + 1 - (ky >> 1)
-            // (recomputed from an opaque copy in every unit: as loop invariants the five units' fifteen LDS addresses would sit in registers the loop needs)
-            int xo = xoff;
-            pin_here(xo);
-            const int e0 = xo + (1 - (ux_tap_ky(u, 0) >> 1)) * UX_PW + (1 - (ux_tap_kx(u, 0) >> 1));
-            const int e1 = u == UX_NUNIT - 1 ? e0 : xo + (1 - (ux_tap_ky(u, 1) >> 1)) * UX_PW + (1 - (ux_tap_kx(u, 1) >> 1));
             const int ai = ux_parity(u);
-            const unsigned char* ws = wl + slot * UX_UNITB;
-            if (live) {
-                {   // f16 part: a1 x w1
-                    uint4 xa[2][2], wv[2][2][2];
+            const int nslot = slot == UX_NSLOT - 1 ? 0 : slot + 1;
+            const bool two = u < UX_NUNIT - 1;                       // (unit 4 has one tap)
+            // fp6 operands: [0] = fp6(a1) with fp6(w - w1), [1] = fp6(a - a1) with fp6(w1); the tap of this lane's K half; block scales of both
+            uint4 calo[2], wclo[2][2];
+            uint2 cahi[2], wchi[2][2];
+            int scw[2], sca = 0;
+            auto read_fp6 = [&](int term) __attribute__((always_inline)) {
+                const int ek = (khalf && two) ? tap_entry(u, 1) : tap_entry(u, 0);
+                calo[term] = *reinterpret_cast<const uint4*>(gl + UX_CLO + (term * UX_EST + ek) * 16);
+                cahi[term] = *reinterpret_cast<const uint2*>(gl + UX_CHI + (term * UX_EST + ek) * 8);
+                const unsigned char* wc = lds + UX_RING + slot * UX_UNITB + UX_U_W16 + (khalf * UX_TN + l5) * 16;
+                const unsigned char* wh = lds + UX_RING + slot * UX_UNITB + UX_U_W16 + UX_U_CLO + (khalf * UX_TN + l5) * 8;
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        xa[0][j] = *reinterpret_cast<const uint4*>(gl + UX_A1 + ((2 * j + khalf) * UX_EST + e0) * 16);
-                        xa[1][j] = *reinterpret_cast<const uint4*>(gl + UX_A1 + ((2 * j + khalf) * UX_EST + e1) * 16);
-                    }
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                        for (int d = 0; d < 2; ++d)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) wv[cb][d][j] = *reinterpret_cast<const uint4*>(ws + ((d * 2 + j) * 2 * UX_TN + cb * 32) * 16);
-#pragma unroll
-                    for (int d = 0; d < 2; ++d) {
-                        if (d == 1 && u == UX_NUNIT - 1) break;          // (unit 4 has one tap)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int cb = 0; cb < 2; ++cb)
-                                accs[ai][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wv[cb][d][j]), __builtin_bit_cast(f16x8, xa[d][j]), accs[ai][cb], 0, 0, 0);
-                    }
+                for (int cb = 0; cb < 2; ++cb) {
+                    wclo[cb][1 - term] = *reinterpret_cast<const uint4*>(wc + ((1 - term) * 2 * UX_TN + cb * 32) * 16);
+                    wchi[cb][1 - term] = *reinterpret_cast<const uint2*>(wh + ((1 - term) * 2 * UX_TN + cb * 32) * 8);
                 }
-                {   // fp6 part: fp6(w - w1) x fp6(a1) and fp6(w1) x fp6(a - a1)
-                    const int ek = khalf ? e1 : e0;
-                    uint4 calo[2], wclo[2][2];
-                    uint2 cahi[2], wchi[2][2];
-                    int scw[2];
-#pragma unroll
-                    for (int term = 0; term < 2; ++term) {
-                        calo[term] = *reinterpret_cast<const uint4*>(gl + UX_CLO + (term * UX_EST + ek) * 16);
-                        cahi[term] = *reinterpret_cast<const uint2*>(gl + UX_CHI + (term * UX_EST + ek) * 8);
-                    }
-                    const int sca = *reinterpret_cast<const int*>(gl + UX_SC + ek * 4);
-                    const unsigned char* wc = lds + UX_RING + slot * UX_UNITB + UX_U_W16 + (khalf * UX_TN + l5) * 16;
-                    const unsigned char* wh = lds + UX_RING + slot * UX_UNITB + UX_U_W16 + UX_U_CLO + (khalf * UX_TN + l5) * 8;
+                if (term == 0) {
+                    sca = *reinterpret_cast<const int*>(gl + UX_SC + ek * 4);
                     const unsigned char* wsc = lds + UX_RING + slot * UX_UNITB + UX_U_W16 + UX_U_CLO + UX_U_CHI + (khalf * UX_TN + l5) * 4;
 #pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-#pragma unroll
-                        for (int term = 0; term < 2; ++term) {
-                            wclo[cb][term] = *reinterpret_cast<const uint4*>(wc + (term * 2 * UX_TN + cb * 32) * 16);
-                            wchi[cb][term] = *reinterpret_cast<const uint2*>(wh + (term * 2 * UX_TN + cb * 32) * 8);
-                        }
-                        scw[cb] = *reinterpret_cast<const int*>(wsc + cb * 32 * 4);
-                    }
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-                        accs[ai][cb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(wclo[cb][1], wchi[cb][1]), mx_op6(calo[0], cahi[0]), accs[ai][cb], 2, 2, 1, scw[cb], 0, sca);
-                        accs[ai][cb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(wclo[cb][0], wchi[cb][0]), mx_op6(calo[1], cahi[1]), accs[ai][cb], 2, 2, 0, scw[cb], 1, sca);
-                    }
+                    for (int cb = 0; cb < 2; ++cb) scw[cb] = *reinterpret_cast<const int*>(wsc + cb * 32 * 4);
                 }
+            };
+            if (two) read_f16(u, 1, slot);
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) mfma_f16(ai, 0);                                // f16 part: a1 x w1, first tap
+            __builtin_amdgcn_sched_barrier(0);
+            read_fp6(0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (live && two) mfma_f16(ai, 1);                         // ... second tap
+            __builtin_amdgcn_sched_barrier(0);
+            read_fp6(1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) {     // fp6 part, first terms: fp6(w - w1) x fp6(a1)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+                    accs[ai][cb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(wclo[cb][1], wchi[cb][1]), mx_op6(calo[0], cahi[0]), accs[ai][cb], 2, 2, 1, scw[cb], 0, sca);
             }
-            // Unit g + 1 must have landed before the next unit reads it.  Requests younger than it: the units requested after it (up to g - 1 + NSLOT, the last one
-            // requested so far) and — while g + 1 belongs to this chunk, i.e. it was requested before the chunk's prefetch — the prefetch.
+            __builtin_amdgcn_sched_barrier(0);
+            // Unit g + 1 must have landed before anyone reads it.  Requests younger than it: the units requested after it (up to g + 5, requested behind unit
+            // g - 1's barrier) and — while g + 1 belongs to this chunk — the chunk's prefetch.  The next chunk's first unit was requested BEFORE the prefetch (behind
+            // the last barrier of the chunk before): the four units that may stay in flight at the chunk's last wait are all younger than the prefetch, which the
+            // conversion behind the barrier reads: it has landed too.
             {
-                const int last_req = (g - 1 + UX_NSLOT < nunits - 1) ? (g >= 1 ? g - 1 + UX_NSLOT : UX_NSLOT - 1) : nunits - 1;
+                const int last_req = g - 1 + UX_NSLOT < nunits - 1 ? g - 1 + UX_NSLOT : nunits - 1;
                 const int younger = last_req > g + 1 ? last_req - (g + 1) : 0;
-                ux_wait_vm(younger * PCS + ((u < UX_NUNIT - 1 && more && !(UX_ABL & 4)) ? NLD : 0));
+                const bool addx = u < UX_NUNIT - 1 && more && !(UX_ABL & 4) && NLD != 0;
+                if (younger == UX_NSLOT - 2 && LD_NC == 16) {       // every unit but a layer's last five: three uniform branches instead of ux_wait_vm's tree over 25 values,
+                                                     // which every wave walked once per unit (9 of 235 us on the 256 -> 128 layer: profiles/upblk_ab.txt)
+                    static_assert(UX_NSLOT == 6, "the literals below are 4 units of 2 / 1 pieces + 16 activation requests");
+                    if (addx) { if (PCS == 2) E4S_WAIT_VM(24); else E4S_WAIT_VM(20); }
+                    else { if (PCS == 2) E4S_WAIT_VM(8); else E4S_WAIT_VM(4); }
+                } else
+                    ux_wait_vm(younger * PCS + (addx ? NLD : 0));
             }
             E4S_LDS_BARRIER();
-            slot = slot == UX_NSLOT - 1 ? 0 : slot + 1;
+            // every wave holds unit g's operands: its slot takes unit g + NSLOT
+            if (g + UX_NSLOT < nunits) dma_unit(g + UX_NSLOT, slot);
+            if (two) {
+                read_f16(u + 1, 0, nslot);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (live) {     // ... second terms: fp6(w1) x fp6(a - a1)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+                    accs[ai][cb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(mx_op6(wclo[cb][0], wchi[cb][0]), mx_op6(calo[1], cahi[1]), accs[ai][cb], 2, 2, 0, scw[cb], 1, sca);
+            }
+            slot = nslot;
         }
-        if (more) {                 // (every wave is past its last read of this chunk's patch; the prefetch is older than the unit just waited for: it has landed)
+        if (more) {                 // (every wave is past its last read of this chunk's planes, and the prefetch has landed: above)
             if (!(UX_ABL & 4)) store_x(chunk + 1);
             E4S_LDS_BARRIER();
+            read_f16(0, 0, slot);
         }
     }
     E4S_WAIT_VM(0);
