@@ -12,6 +12,7 @@
 //              the interior element, and stored to every padded cell that mirrors it (up to nine for a corner's neighbour when h or w is 2 or 3).
 //              Four elements of a row per lane with 16-byte loads when w % 4 == 0 and the pointers allow, one otherwise: the same expressions per element.
 #include "common.h"
+#include "spade_value.h"
 
 namespace e4s {
 
@@ -58,18 +59,7 @@ __global__ __launch_bounds__(256) void spade_shared_kernel(float* __restrict__ a
     }
 }
 
-// One element of the modulation, every rounding written out (no contraction left to the compiler): the difference, its product with rstd, 1 + gamma, the product,
-// the sum with beta, and the activation's product.  slope 1 is the identity (v * 1 is v, bit for bit).
-__device__ __forceinline__ float spade_value(float x, float m, float r, float gamma, float beta, bool modulated, float slope) {
-#pragma clang fp contract(off)
-    float v = (x - m) * r;
-    if (modulated) {
-        const float g = 1.f + gamma;
-        v = v * g;
-        v = v + beta;
-    }
-    return v > 0.f ? v : v * slope;
-}
+// One element of the modulation is spade_value (spade_value.h), every rounding written out.
 
 // A group is V consecutive elements of one row (V = 4: w % 4 == 0).  n: groups in all.  gb [bs][2C][h][w] or null.
 template <int V, bool PAD>

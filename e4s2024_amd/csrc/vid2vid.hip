@@ -2,6 +2,7 @@
 // modules/util.py:55-71, 196-213, 372-418, drive_demo.py:67-180).  Everything here is small against the convolutions: one lane per output, or one workgroup per
 // (sample, keypoint); float32 with every sum in a fixed order.
 #include "common.h"
+#include "spade_value.h"
 #include "v2v_sample.h"
 
 using namespace e4s;
@@ -534,4 +535,201 @@ extern "C" int e4s_v2v_occlude(float* out, const float* x, const float* occ, int
     else
         hipLaunchKernelGGL(v2v_occlude_kernel<1>, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, out, x, occ, total, C, hw);
     return check_launch("v2v_occlude");
+}
+
+// ==================================================================================== f20: the glue of the SPADEDecoder (modules/generator.py:120-158, modules/util.py:421-481)
+// spade_norm: the modulation of one or two SPADE norms that normalise the same x (norm_0, and norm_s of a learned shortcut), x read once, the decoder's nearest x2
+// folded into the read: x [bs][C][h / UP][w / UP] at (y / UP, x / UP).  The statistics are those of the low-resolution plane: a nearest x2 plane repeats every value
+// four times, its mean and biased variance are the same.  Every element is spade_value (spade_value.h), e4s_spade_modulate's function: the same bits.
+// A group is V consecutive OUTPUT elements of one row (V = 4: w % 4 == 0, hence w / UP even: the two x values of a group are one 8-byte read).  n: groups in all.
+template <int V, int UP>
+__global__ __launch_bounds__(256) void v2v_spade_norm_kernel(float* __restrict__ out_a, float* __restrict__ out_s, const float* __restrict__ x,
+                                                             const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gb_a,
+                                                             const float* __restrict__ gb_s, int64_t n, int C, int h, int w) {
+    const int hw = h * w, gpp = hw / V, ws = w / UP;
+    const int64_t xhw = (int64_t)(h / UP) * ws;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+        const int64_t plane = g / gpp;
+        const int i0 = (int)(g - plane * gpp) * V;
+        const int y = i0 / w, x0 = i0 - y * w;
+        const float m = mean[plane], r = rstd[plane];
+        const float* xp = x + plane * xhw + (int64_t)(y / UP) * ws + x0 / UP;
+        const int64_t b = plane / C, c = plane - b * C;
+        const int64_t go = (b * 2 * C + c) * hw + i0, oo = plane * hw + i0;
+        float xv[V];
+        if constexpr (V == 4) {
+            if constexpr (UP == 1) {
+                const float4 q = *reinterpret_cast<const float4*>(xp);
+                xv[0] = q.x; xv[1] = q.y; xv[2] = q.z; xv[3] = q.w;
+            } else {
+                const float2 q = *reinterpret_cast<const float2*>(xp);
+                xv[0] = q.x; xv[1] = q.x; xv[2] = q.y; xv[3] = q.y;
+            }
+        } else {
+            xv[0] = xp[0];
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {                                           // k = 0: norm_0 with the leaky activation; k = 1: norm_s without
+            const float* gb = k ? gb_s : gb_a;
+            float* out = k ? out_s : out_a;
+            if (!gb) continue;
+            const float slope = k ? 1.f : 0.2f;
+            const float *gp = gb + go, *bp = gp + (int64_t)C * hw;
+            if constexpr (V == 4) {
+                const float4 ga = *reinterpret_cast<const float4*>(gp), be = *reinterpret_cast<const float4*>(bp);
+                *reinterpret_cast<float4*>(out + oo) =
+                    make_float4(spade_value(xv[0], m, r, ga.x, be.x, true, slope), spade_value(xv[1], m, r, ga.y, be.y, true, slope),
+                                spade_value(xv[2], m, r, ga.z, be.z, true, slope), spade_value(xv[3], m, r, ga.w, be.w, true, slope));
+            } else {
+                out[oo] = spade_value(xv[0], m, r, gp[0], bp[0], true, slope);
+            }
+        }
+    }
+}
+
+extern "C" int e4s_v2v_spade_norm(float* out_a, float* out_s, const float* x, const float* mean, const float* rstd, const float* gb_a, const float* gb_s, int bs,
+                                  int C, int h, int w, int up, void* stream) {
+    E4S_REQUIRE(bs >= 0 && C >= 1 && h >= 1 && w >= 1 && h <= 16384 && w <= 16384, "v2v_spade_norm: bad size");
+    E4S_REQUIRE((up == 1 || up == 2) && h % up == 0 && w % up == 0, "v2v_spade_norm: up is 1 or 2 and divides h = %d and w = %d", h, w);
+    E4S_REQUIRE((out_s == nullptr) == (gb_s == nullptr), "v2v_spade_norm: out_s and gb_s go together");
+    if (bs == 0) return 0;
+    E4S_REQUIRE(out_a && x && mean && rstd && gb_a, "v2v_spade_norm: null tensor");
+    const int64_t n = (int64_t)bs * C * h * w;
+    const bool vec = w % 4 == 0 && v2v_aligned16(out_a) && v2v_aligned16(out_s) && v2v_aligned16(x) && v2v_aligned16(gb_a) && v2v_aligned16(gb_s);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && up == 1)
+        hipLaunchKernelGGL((v2v_spade_norm_kernel<4, 1>), dim3(grid_1d(n / 4)), dim3(256), 0, st, out_a, out_s, x, mean, rstd, gb_a, gb_s, n / 4, C, h, w);
+    else if (vec)
+        hipLaunchKernelGGL((v2v_spade_norm_kernel<4, 2>), dim3(grid_1d(n / 4)), dim3(256), 0, st, out_a, out_s, x, mean, rstd, gb_a, gb_s, n / 4, C, h, w);
+    else if (up == 1)
+        hipLaunchKernelGGL((v2v_spade_norm_kernel<1, 1>), dim3(grid_1d(n)), dim3(256), 0, st, out_a, out_s, x, mean, rstd, gb_a, gb_s, n, C, h, w);
+    else
+        hipLaunchKernelGGL((v2v_spade_norm_kernel<1, 2>), dim3(grid_1d(n)), dim3(256), 0, st, out_a, out_s, x, mean, rstd, gb_a, gb_s, n, C, h, w);
+    return check_launch("v2v_spade_norm");
+}
+
+// image_head: out [bs][3][H][W] = sigmoid(conv3x3(leaky_0.2(x), weight [3][cin][3][3], zero pad 1) + bias): the decoder's last three lines.  Three output channels
+// would waste an output-channel tile of the MFMA kernel; this is the form of the RRDB tail (csrc/rrdb.hip): a workgroup owns a 64 x 16 tile, a lane four pixels of
+// a row and all three outputs; eight input channels at a time are staged in LDS with their halo, the activation applied once per staged value (0 stays 0: the
+// padding), their 27 weights per channel beside them.  Exact float32: every sum starts at the bias and takes 9 cin fused multiply-adds in (input channel, row,
+// column) order; the sigmoid is 1 / (1 + expf(-v)).
+constexpr int HEAD_TW = 64, HEAD_TH = 16;        // the tile of a workgroup: 16 lanes x 4 pixels across, 16 rows
+constexpr int HEAD_CH = 8;                       // input channels per LDS chunk
+constexpr int HEAD_LW = 72;                      // LDS row: the left halo at column 3, the tile at 4 .. 67 (16-byte aligned), the right halo at 68
+constexpr int HEAD_LH = HEAD_TH + 2;
+constexpr int HEAD_WROW = 28;                    // 27 weights of an input channel, [row][column][output], padded to seven 16-byte reads
+
+__device__ __forceinline__ float v2v_leaky02(float v) { return v > 0.f ? v : v * 0.2f; }
+
+// grid (ceil(W / 64), ceil(H / 16), bs).  VEC: W % 4 == 0, x and out 16-byte aligned.
+template <bool VEC>
+__global__ __launch_bounds__(256) void v2v_image_head_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ wgt,
+                                                             const float* __restrict__ bias, int C, int H, int W) {
+    __shared__ __attribute__((aligned(16))) float tile[HEAD_CH * HEAD_LH * HEAD_LW];
+    __shared__ __attribute__((aligned(16))) float wl[HEAD_CH * HEAD_WROW];
+    const int tid = threadIdx.x;
+    const int lx = tid & 15, ly = tid >> 4;
+    const int tx0 = blockIdx.x * HEAD_TW, ty0 = blockIdx.y * HEAD_TH;
+    const int64_t b = blockIdx.z;
+    const int64_t hw = (int64_t)H * W;
+    const float* xb = x + b * C * hw;
+
+    float acc[3][4];
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[o][j] = bias[o];
+
+    for (int c0 = 0; c0 < C; c0 += HEAD_CH) {
+        const int nc = min(HEAD_CH, C - c0);                                    // the last chunk may be short: its missing channels are neither staged nor read
+        __syncthreads();                                                        // the previous chunk has been read (first pass: nothing yet)
+        if (tid < HEAD_CH * HEAD_WROW) {
+            const int ci = tid / HEAD_WROW, r = tid - ci * HEAD_WROW;
+            const int tap = r / 3, o = r - tap * 3;
+            wl[tid] = (ci < nc && r < 27) ? wgt[((int64_t)o * C + c0 + ci) * 9 + tap] : 0.f;
+        }
+        if constexpr (VEC) {
+            for (int i = tid; i < nc * HEAD_LH * (HEAD_TW / 4); i += 256) {
+                const int rr = i / (HEAD_TW / 4), q = i - rr * (HEAD_TW / 4);   // rr = c * LH + r
+                const int c = rr / HEAD_LH, r = rr - c * HEAD_LH;
+                const int gy = ty0 - 1 + r, gx = tx0 + 4 * q;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (gy >= 0 && gy < H && gx < W) {
+                    v = *reinterpret_cast<const float4*>(xb + (c0 + c) * hw + (int64_t)gy * W + gx);
+                    v = make_float4(v2v_leaky02(v.x), v2v_leaky02(v.y), v2v_leaky02(v.z), v2v_leaky02(v.w));
+                }
+                *reinterpret_cast<float4*>(tile + rr * HEAD_LW + 4 + 4 * q) = v;
+            }
+            for (int i = tid; i < nc * HEAD_LH * 2; i += 256) {
+                const int rr = i >> 1, side = i & 1;
+                const int c = rr / HEAD_LH, r = rr - c * HEAD_LH;
+                const int gy = ty0 - 1 + r, gx = side ? tx0 + HEAD_TW : tx0 - 1;
+                float v = 0.f;
+                if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = v2v_leaky02(xb[(c0 + c) * hw + (int64_t)gy * W + gx]);
+                tile[rr * HEAD_LW + (side ? 4 + HEAD_TW : 3)] = v;
+            }
+        } else {
+            for (int i = tid; i < nc * HEAD_LH * (HEAD_TW + 2); i += 256) {
+                const int rr = i / (HEAD_TW + 2), cx = i - rr * (HEAD_TW + 2);
+                const int c = rr / HEAD_LH, r = rr - c * HEAD_LH;
+                const int gy = ty0 - 1 + r, gx = tx0 - 1 + cx;
+                float v = 0.f;
+                if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = v2v_leaky02(xb[(c0 + c) * hw + (int64_t)gy * W + gx]);
+                tile[rr * HEAD_LW + 3 + cx] = v;
+            }
+        }
+        __syncthreads();
+        for (int c = 0; c < nc; ++c) {
+            float wv[HEAD_WROW];
+            const float4* wp = reinterpret_cast<const float4*>(wl + c * HEAD_WROW);             // the same address in every lane
+#pragma unroll
+            for (int k = 0; k < HEAD_WROW / 4; ++k) {
+                const float4 q = wp[k];
+                wv[4 * k] = q.x; wv[4 * k + 1] = q.y; wv[4 * k + 2] = q.z; wv[4 * k + 3] = q.w;
+            }
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                const float* rp = tile + (c * HEAD_LH + ly + ky) * HEAD_LW + 4 * lx + 3;
+                const float4 mid = *reinterpret_cast<const float4*>(rp + 1);
+                const float v[6] = {rp[0], mid.x, mid.y, mid.z, mid.w, rp[5]};
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                    for (int o = 0; o < 3; ++o)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[o][j] = fmaf(wv[(ky * 3 + kx) * 3 + o], v[j + kx], acc[o][j]);
+            }
+        }
+    }
+
+    const int y = ty0 + ly, x0 = tx0 + 4 * lx;
+    if (y >= H || x0 >= W) return;
+    const int64_t pix = (int64_t)y * W + x0;
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[o][j] = 1.0f / (1.0f + expf(-acc[o][j]));
+    if constexpr (VEC) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) *reinterpret_cast<float4*>(out + (b * 3 + o) * hw + pix) = make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (x0 + j >= W) break;
+#pragma unroll
+            for (int o = 0; o < 3; ++o) out[(b * 3 + o) * hw + pix + j] = acc[o][j];
+        }
+    }
+}
+
+extern "C" int e4s_v2v_image_head(float* out, const float* x, const float* weight, const float* bias, int bs, int cin, int H, int W, void* stream) {
+    E4S_REQUIRE(bs >= 0 && bs <= 65535 && cin >= 1 && H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "v2v_image_head: bad size");
+    if (bs == 0) return 0;
+    E4S_REQUIRE(out && x && weight && bias, "v2v_image_head: null tensor");
+    const dim3 grid(cdiv(W, HEAD_TW), cdiv(H, HEAD_TH), bs);
+    if (W % 4 == 0 && v2v_aligned16(x) && v2v_aligned16(out))
+        hipLaunchKernelGGL(v2v_image_head_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, x, weight, bias, cin, H, W);
+    else
+        hipLaunchKernelGGL(v2v_image_head_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, x, weight, bias, cin, H, W);
+    return check_launch("v2v_image_head");
 }

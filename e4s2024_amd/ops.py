@@ -19,6 +19,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_gpen_paste`` row f15: GPEN face enhancement, stage 4 — align, feather and paste around the three networks (resolved on first use too)
 * ``ops_gpen_sr`` row f16: GPEN face enhancement, stage 5 — the RealESRNet pass and cv2's linear resize (resolved on first use too)
 * ``ops_reenact`` rows f17 - f19: face-vid2vid reenactment, stage 1 — KPDetector, HEEstimator and keypoint_transformation — stage 2, DenseMotionNetwork, and stage 3, the generator in front of its decoder (resolved on first use too)
+* ``ops_reenact_frames`` row f20: face-vid2vid reenactment, stage 4 — the SPADEDecoder, the whole generator, its module wrapper and make_animation (resolved on first use too)
 """
 from __future__ import annotations
 
@@ -1406,7 +1407,8 @@ def __getattr__(name):        # PEP 562
     import importlib
     import sys
     if not name.startswith("__"):
-        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr", "ops_reenact"):
+        for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr", "ops_reenact",
+                    "ops_reenact_frames"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

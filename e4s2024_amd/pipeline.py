@@ -561,6 +561,20 @@ def reenact_warp(generator, feature_3d: torch.Tensor, kp_driving, kp_source):
     return ops.generator_warp(feature_3d, kp_driving, kp_source, generator)
 
 
+def reenact_frames(generator, feature_3d: torch.Tensor, kp_driving, kp_source):
+    """The per-frame part of the generator with its ``SPADEDecoder`` (generator.py:221-250), for the n driving frames of the keypoint dicts at once:
+    ``reenact_warp`` and the decoder, to the reference's ``output_dict`` ``{'mask'[, 'occlusion_map'], 'prediction' [n, 3, H, W]}``
+    (``ops.generator_frames``).  ``feature_3d`` is ``reenact_source_feature``'s, held once per clip."""
+    return ops.generator_frames(feature_3d, kp_driving, kp_source, generator)
+
+
+def reenact_clip(generator, kp_detector, he_estimator, source: torch.Tensor, driving: torch.Tensor, **kw):
+    """``make_animation`` (swap_face_fine/face_vid2vid/drive_demo.py:182-211) for a clip on the device: float32 ``source [1, 3, H, W]`` and ``driving
+    [n, 3, H, W]`` in [0, 1] to the reenacted frames ``[n, 3, H', W']`` (``ops.make_animation``; ``kw``: its ``estimate_jacobian``, ``free_view``, ``yaw``,
+    ``pitch``, ``roll`` and ``batch``).  Nothing stays with the caller."""
+    return ops.make_animation(source, driving, generator, kp_detector, he_estimator, **kw)
+
+
 @torch.no_grad()
 def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_u8: Optional[torch.Tensor] = None, return_faces: bool = False):
     """``FaceEnhancement.process(img, aligned=False)`` (swap_face_fine/gpen/face_enhancement.py:68-110) behind its ``use_sr`` branch, for a batch of frames on

@@ -1055,6 +1055,25 @@ E4S_API int e4s_v2v_deform(float* out, const float* feature, const float* deform
 E4S_API int e4s_v2v_bn_relu(float* out, const float* x, const float* scale, const float* shift, int bs, int C, int n, void* stream);
 E4S_API int e4s_v2v_occlude(float* out, const float* x, const float* occ, int bs, int C, int hw, void* stream);
 
+/* f20: face-vid2vid reenactment, stage 4 — the glue of the SPADEDecoder (swap_face_fine/face_vid2vid/modules/generator.py:120-158, modules/util.py:421-481;
+ * csrc/vid2vid.hip).  The decoder's convolutions (fc, mlp_shared + ReLU, mlp_gamma | mlp_beta as one convolution, conv_0, conv_1 with the shortcut as residual,
+ * conv_s) run on e4s_conv2d_sb3, the instance norms' statistics on e4s_plane_stats, the nearest picks of the label map on e4s_esr_up2.
+ *   v2v_spade_norm : the modulation of one or two SPADE norms that normalise the same x, with the decoder's nearest x2 folded into the read:
+ *                    out_a [bs][C][h][w] = leaky_0.2((x - mean) rstd (1 + gamma_a) + beta_a) and, when gb_s and out_s are given (together, or both NULL),
+ *                    out_s = (x - mean) rstd (1 + gamma_s) + beta_s without an activation (the norm_s of a learned shortcut); x is read once for both.
+ *                    x [bs][C][h / up][w / up] is read at (y / up, x / up), up 1 or 2 dividing h and w; mean / rstd [bs * C] are e4s_plane_stats' of that
+ *                    low-resolution plane: a nearest x2 plane has exactly the statistics of the plane it repeats, so the upsampled x is never formed.
+ *                    gb_* [bs][2 C][h][w] = gamma | beta, the two halves of one convolution's output.  Every operation is rounded on its own by the device
+ *                    function e4s_spade_modulate runs (csrc/spade_value.h): the same bits as that call on x upsampled by e4s_esr_up2.  16-byte accesses when w % 4 == 0
+ *                    and every pointer is 16-byte aligned, one element per lane otherwise: the same bits.
+ *   v2v_image_head : out [bs][3][H][W] = sigmoid(conv3x3(leaky_0.2(x [bs][cin][H][W]), weight [3][cin][3][3], zero pad 1) + bias [3]): conv_img behind its
+ *                    activation.  Exact float32 in the form of e4s_esr_tail: every sum starts at the bias and takes 9 cin fused multiply-adds in (input
+ *                    channel, row, column) order; the sigmoid is 1 / (1 + expf(-v)).  16-byte accesses when W % 4 == 0 and x and out are 16-byte aligned.
+ * fp32, no atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_v2v_spade_norm(float* out_a, float* out_s, const float* x, const float* mean, const float* rstd, const float* gb_a, const float* gb_s, int bs,
+                               int C, int h, int w, int up, void* stream);
+E4S_API int e4s_v2v_image_head(float* out, const float* x, const float* weight, const float* bias, int bs, int cin, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
