@@ -23,21 +23,31 @@
 //   K loop:    chunk = 32 input channels; five units = tap pairs that share an accumulator parity — (0,0)|(0,2) and (2,0)|(2,2) -> (0,0); (1,0)|(1,2) -> (1,0);
 //              (0,1)|(2,1) -> (0,1); (1,1) -> (1,1) — 8 f16 + 4 fp6 MFMAs per wave and unit in four groups, each group's operands read from LDS under the group
 //              before it; one barrier per unit, between the fp6 halves (the ring slot's hand-over: by then every wave holds all of the unit's operands)
-//   epilogue:  the round-2 kernel's (8 channels at a time through a pre-blur tile in LDS, 4 x 4 FIR with a rolling four-row window, demodulation / noise / bias /
-//              leaky ReLU, fp32 NCHW stores)
+//   epilogue:  16 channels at a time through a pre-blur tile in LDS (over the weight ring), 4 x 4 FIR with a rolling four-row window, demodulation / noise / bias /
+//              leaky ReLU, fp32 NCHW stores; a thread owns four adjacent outputs of a channel and four rows: two 16-byte LDS reads per pre-blur row, one 16-byte
+//              store per output row, one fmaf chain per output in the order of the first epilogue (same bits), two rows' chains per packed fmaf
 // Where its time goes and what each change of the staging / loop pass returned: profiles/upblk_parts.txt, profiles/upblk_ab.txt (256 -> 128 @128^2, batch 4: 262 ->
 // 227 us alone on the chip).  Built, measured and taken out there, all with the same bits: the conversion on the five-instruction pair (v_pk_mul_f32 + packed
 // conversion + two mix-fmas; 0 us: hipcc's code for the value-by-value form is as short), the tables' loads behind the first requests in the prologue (0 us),
-// both taps' f16 operands read ahead instead of one (+3 us).  What is left: the epilogue (about 28 % of the kernel) and the conversion with its requests (21 %).
+// both taps' f16 operands read ahead instead of one (+3 us).
+// The epilogue pass (profiles/upblk_epilogue_ab.txt): four outputs per thread with 16-byte reads and stores, a bank-conflict-free tile pitch and the blur taps through
+// LDS return 6 - 7 us alone on the chip, two output rows' chains in one v_pk_fma_f32 another 2.6, same bits.  Built, measured and taken out there, all with the same bits: eight rows per thread on half the
+// threads (+ 20 us), every pre-blur row of a pass read ahead of the FIR (0), two tiles per group with one barrier per pass (about - 1 us, inside the spread), and
+// the conversion on all four waves of a group, a thread per pixel and 16-channel half (+ 4 us: four waves issue seven LDS stores and two fp6 conversions each where two did).
+// What is left: the epilogue is still about 55 us of 214 (its global stores 16 of them; what a single wave issues and waits for between the two barriers of a pass
+// bounds the rest, not the SIMDs' or the LDS's throughput), the conversion with its requests about 50 us.
 // f16 range: a wave that sees |x s| >= 65520 raises flags[0] bit 0 and bumps flags[1] (ops.MxGuard re-runs the pass on the split-bf16 kernels).
+#include <type_traits>
+
 #include "modconv_mx_tile.h"
 
-// Tuning builds only (-DUX_ABL=bits; results are then meaningless): 1 = no K loop, 2 = no epilogue, 4 = no activation loads / conversions after the first chunk
+// Tuning builds only (-DUX_ABL=bits; results are then meaningless): 1 = no K loop, 2 = no epilogue, 4 = no activation loads / conversions after the first chunk,
+// 8 = the epilogue without its global stores
 #ifndef UX_ABL
 #define UX_ABL 0
 #endif
 // Tuning builds only (-DUX_BACK=bits; same bits either way, profiles/upblk_ab.txt): 1 = activation requests and conversion on waves 0, 1, 4, 5 as in the first form,
-// 2 = positions in lane order
+// 2 = positions in lane order, 4 = the first epilogue (one output column, eight rows and two channels per thread, four-byte LDS reads and stores; profiles/upblk_epilogue_ab.txt)
 #ifndef UX_BACK
 #define UX_BACK 0
 #endif
@@ -51,7 +61,7 @@ constexpr int UX_PW = UX_T + 1;                   // 11: activation patch side
 constexpr int UX_PATCH = UX_PW * UX_PW;           // 121
 constexpr int UX_NPOS = UX_T * UX_T;              // 100
 constexpr int UX_EST = 128;                       // entry stride of the patch planes
-constexpr int UX_ZR = 2 * UX_T, UX_ZS = UX_ZR + 2;
+constexpr int UX_ZR = 2 * UX_T;
 constexpr int UX_NUNIT = 5;
 constexpr int UX_U_W16 = 2 * 2 * 2 * UX_TN * 16;  // 8 192
 constexpr int UX_U_CLO = 2 * 2 * UX_TN * 16;      // 4 096
@@ -73,9 +83,22 @@ constexpr int UX_MAX_CIN = 512;
 constexpr int UX_EP = UX_SROW + UX_MAX_CIN * 4;               //   d [64] | bias [64] | noise [256]
 constexpr int UX_RAW = UX_EP + (2 * UX_TN + UX_OUT * UX_OUT) * 4;       //   the NEXT chunk's raw activations [channel 32][pixel 128] fp32, landed by LDS-DMA
 constexpr int UX_GRPB = UX_RAW + UX_CK * UX_EST * 4;          // 34 816 per group
-constexpr int UX_LDS = UX_GRP0 + 2 * UX_GRPB;                 // 161 792
-constexpr int UX_ZTB = 16 * UX_ZR * UX_ZS * 4;                // 28 160: a group's pre-blur tile of 16 channels (epilogue, over the weight ring)
-static_assert(UX_LDS <= 160 * 1024 && 2 * UX_ZTB <= UX_GRP0 && UX_GRPB % 16 == 0, "LDS plan; the pre-blur tiles overlay the weight ring");
+constexpr int UX_KF = UX_GRP0 + 2 * UX_GRPB;                  // 161 792: the 16 blur taps, flipped (one copy per workgroup, written in the prologue)
+constexpr int UX_LDS = UX_KF + 16 * 4;                        // 161 856
+// A group's pre-blur tile of 16 channels (epilogue, over the weight ring): [channel][row 20][column 20].  A thread reads columns 4 xg .. 4 xg + 7 of a row with two
+// 16-byte reads, so the row pitch is a multiple of four floats; such a read serves 16 lanes = (channel c: row groups 0, 3; channel c + 1: row groups 1, 2) x the
+// four column groups together (or the same with the channels swapped), 16 consecutive floats each, at c ZCP + {0, 12 ZP} and (c + 1) ZCP + {4 ZP, 8 ZP} floats =
+// banks {0, 48, 16, 32} + 0 .. 15 of 64 with ZP = 20, ZCP = 448: no bank twice.  (The first epilogue: [16][20][22], four-byte reads.)
+#if UX_BACK & 4
+constexpr int UX_ZP = UX_ZR + 2, UX_ZCP = UX_ZR * UX_ZP;
+#else
+constexpr int UX_ZP = 20, UX_ZCP = 448;
+static_assert(UX_ZP % 4 == 0 && UX_ZP >= UX_ZR && UX_ZCP % 4 == 0 && UX_ZCP >= UX_ZR * UX_ZP && UX_ZCP % 64 == 0 && (12 * UX_ZP) % 64 == 48 && (4 * UX_ZP) % 64 == 16,
+              "pre-blur tile: 16-byte aligned rows, a 16-byte read meets no bank twice");
+#endif
+constexpr int UX_ZTB = 16 * UX_ZCP * 4;                       // 28 672 (the first epilogue: 28 160)
+static_assert(UX_LDS <= 160 * 1024 && 2 * UX_ZTB <= UX_GRP0 && UX_ZTB % 16 == 0 && UX_GRPB % 16 == 0 && UX_EP % 16 == 0,
+              "LDS plan; the pre-blur tiles overlay the weight ring");
 
 struct UpBlockMxParams {
     float* out;
@@ -299,6 +322,9 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
     };
 
     // ---- the block's modulation row and epilogue operands (plain loads: counted by the compiler, landed at the wait below)
+#if !(UX_BACK & 4)
+    if (tid < 16) reinterpret_cast<float*>(lds + UX_KF)[tid] = p.blur[15 - tid];        // (with the tables: at the epilogue's top nothing would hide these loads)
+#endif
     if (live) {
         const float* srow = p.s + ((size_t)b * p.nreg + reg) * p.cin;
         float* sl = reinterpret_cast<float*>(gl + UX_SROW);
@@ -485,13 +511,119 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
     if (UX_ABL & 2) { if (accs[0][0][0] == 12345.f) p.out[tid] = accs[1][1][1] + accs[2][0][2] + accs[3][1][3]; return; }
     // ---- epilogue: pre-blur tiles of 16 channels at a time (four passes), z[2 pty + i][2 ptx + j]; output pixel (y, x) = sum_{t,u} k[t][u] z[y + 1 + t][x + 1 + u] with a
     // rolling four-row window.  (The round-2 kernel's epilogue — 8 channels per pass, one FIR chain per thread in a loop the compiler must not unroll — cost 84 of this
-    // kernel's 283 us on the 128 -> 256 layer: tuning builds.  Here a thread runs two independent chains, fully unrolled, and the workgroup synchronises half as often.)
+    // kernel's 283 us on the 128 -> 256 layer: tuning builds.)
+    // A thread owns four horizontally adjacent outputs of one channel and four rows: per pre-blur row two 16-byte LDS reads (columns 4 xg .. 4 xg + 7, of which
+    // 1 .. 7 are used) feed four outputs, and an output row leaves as one 16-byte store.  Every output is still ONE fmaf chain from 0.f over its 16 taps, row-major,
+    // as the rolling window runs them (two rows' chains advance in one packed fmaf) — nothing is shared between outputs, so the bits are those of the first epilogue (UX_BACK & 4: one column, eight rows
+    // and two channels per thread, 88 four-byte reads and 16 four-byte stores per thread and pass).
     __syncthreads();
-    float* zt = reinterpret_cast<float*>(lds + grp * UX_ZTB);       // this group's [16][ZR][ZS] over the weight ring
+    float* zt = reinterpret_cast<float*>(lds + grp * UX_ZTB);       // this group's [16][ZCP] over the weight ring
     const float* ep_d = reinterpret_cast<const float*>(gl + UX_EP);
     const float* ep_b = ep_d + UX_TN;
     const float* ep_n = ep_b + UX_TN;
     float kf[16];
+    const float neg = p.act ? 0.2f : 1.f, gain = p.act ? 1.41421356237309515f : 1.f;
+    auto put_tile = [&](int i, int gh) __attribute__((always_inline)) {       // channels i * 32 + 16 gh .. + 15 of the accumulators -> the pre-blur tile
+        if (pos_ok && live) {
+#pragma unroll
+            for (int g2 = 0; g2 < 2; ++g2)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int col = 8 * g2 + 4 * khalf + rr;
+#pragma unroll
+                    for (int ci = 0; ci < 2; ++ci)
+                        *reinterpret_cast<float2*>(&zt[col * UX_ZCP + (2 * pty + ci) * UX_ZP + 2 * ptx]) =
+                            make_float2(accs[2 * ci][i][4 * (2 * gh + g2) + rr], accs[2 * ci + 1][i][4 * (2 * gh + g2) + rr]);
+                }
+        }
+    };
+#if !(UX_BACK & 4)
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+        kf[t] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(lds + UX_KF)[t]));     // (written in the prologue)
+    constexpr int ER = 4;                                         // output rows per thread (8 rows on 128 threads of a group: + 20 us, profiles/upblk_epilogue_ab.txt)
+    const int xg = lt & 3, yg = (lt >> 2) & 3, ech = lt >> 4;     // column group, row group, channel of the pass
+    const int oy0 = tyt * UX_OUT + ER * yg, ox = txt * UX_OUT + 4 * xg;
+    int nrow = ho - oy0;
+    nrow = (!live || nrow < 0) ? 0 : (nrow > ER ? ER : nrow);
+    const bool col_ok = ox < wo;                                  // (wo is a multiple of 32: all four columns or none)
+    // ox and wo are multiples of 4: a thread's four outputs of a row are 16-byte aligned exactly when `out` is (launch-uniform)
+    const bool al16 = (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
+    float4 nzr[ER];
+#pragma unroll
+    for (int r = 0; r < ER; ++r) nzr[r] = *reinterpret_cast<const float4*>(ep_n + (ER * yg + r) * UX_OUT + 4 * xg);
+    // (The 16-byte reads go through an opaque copy: column 4 xg of a row is never used, and hipcc narrows a vector load with an unused element to four-byte reads.
+    // The store width is chosen OUTSIDE the passes, one instance of them each: with the choice at the store, hipcc merges the two sides into 12 + 4 bytes.)
+    auto read16 = [](const float* q) __attribute__((always_inline)) {
+        typedef float f32x4v __attribute__((ext_vector_type(4)));
+        f32x4v v = *reinterpret_cast<const f32x4v*>(q);
+        asm("" : "+v"(v));
+        return v;
+    };
+    auto passes = [&](auto wide) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int gh = 0; gh < 2; ++gh) {
+            put_tile(i, gh);
+            __syncthreads();
+            const int cl = i * 32 + 16 * gh + ech;
+            const int co = co0 + cl;
+            if (nrow > 0 && col_ok && co < p.cout) {
+                const float dd = ep_d[cl], bi = ep_b[cl];
+                const float* zc = zt + ech * UX_ZCP + (ER * yg + 1) * UX_ZP + 4 * xg;
+                float* orow = p.out + ((size_t)b * p.cout + co) * ho * wo + (size_t)oy0 * wo + ox;
+                // The chains C0 .. C3 of an output column = the thread's four output rows; at pre-blur row R chain C_r runs its stage s = R - r, the taps kf[4 s + u]
+                // (the rolling window's a3 .. a0).  C0 | C1 and C2 | C3 sit in register pairs: where both chains of a pair run (three of a pair's five rows) ONE
+                // v_pk_fma_f32 — z broadcast, two taps — advances both, each still by its own fmaf: 176 instead of 272 FIR instructions per thread and pass.
+                f32x2 pa[4], pb[4];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) { pa[o] = (f32x2){0.f, 0.f}; pb[o] = (f32x2){0.f, 0.f}; }
+#pragma unroll
+                for (int zr = 0; zr < ER + 3; ++zr) {
+                    const auto za = read16(zc + zr * UX_ZP), zb = read16(zc + zr * UX_ZP + 4);
+                    const float z[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const float zz = z[o + 1 + u];
+                            // pair a: C0 stage zr, C1 stage zr - 1
+                            if (zr == 0) pa[o][0] = __builtin_fmaf(zz, kf[u], pa[o][0]);
+                            else if (zr <= 3) pa[o] = __builtin_elementwise_fma((f32x2){zz, zz}, (f32x2){kf[4 * zr + u], kf[4 * (zr - 1) + u]}, pa[o]);
+                            else if (zr == 4) pa[o][1] = __builtin_fmaf(zz, kf[12 + u], pa[o][1]);
+                            // pair b: C2 stage zr - 2, C3 stage zr - 3
+                            if (zr == 2) pb[o][0] = __builtin_fmaf(zz, kf[u], pb[o][0]);
+                            else if (zr >= 3 && zr <= 5) pb[o] = __builtin_elementwise_fma((f32x2){zz, zz}, (f32x2){kf[4 * (zr - 2) + u], kf[4 * (zr - 3) + u]}, pb[o]);
+                            else if (zr == 6) pb[o][1] = __builtin_fmaf(zz, kf[12 + u], pb[o][1]);
+                        }
+                    }
+                    if (zr >= 3 && zr - 3 < nrow) {
+                        const float nz[4] = {nzr[zr - 3].x, nzr[zr - 3].y, nzr[zr - 3].z, nzr[zr - 3].w};
+                        float v[4];
+#pragma unroll
+                        for (int o = 0; o < 4; ++o) {
+                            const float acc = zr == 3 ? pa[o][0] : zr == 4 ? pa[o][1] : zr == 5 ? pb[o][0] : pb[o][1];
+                            v[o] = __builtin_fmaf(acc, dd, bi) + nz[o];
+                            v[o] = fmaxf(v[o], v[o] * neg) * gain;
+                        }
+                        float* op = orow + (size_t)(zr - 3) * wo;
+                        if (UX_ABL & 8) { if (v[0] == 12345.f) op[0] = v[1] + v[2] + v[3]; }
+                        else if (decltype(wide)::value)
+                            *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
+                        else {
+#pragma unroll
+                            for (int o = 0; o < 4; ++o) op[o] = v[o];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    };
+    if (al16) passes(std::true_type{}); else passes(std::false_type{});
+#else
 #pragma unroll
     for (int t = 0; t < 16; ++t) kf[t] = p.blur[15 - t];
     const int bx = lt & 15, bco = (lt >> 4) & 7, byg = (lt >> 7) & 1;
@@ -503,23 +635,11 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
     float nzr[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) nzr[r] = nzp[r * UX_OUT];
-    const float neg = p.act ? 0.2f : 1.f, gain = p.act ? 1.41421356237309515f : 1.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int gh = 0; gh < 2; ++gh) {               // channels i * 32 + 16 gh .. + 15
-            if (pos_ok && live) {
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        const int col = 8 * g2 + 4 * khalf + rr;
-#pragma unroll
-                        for (int ci = 0; ci < 2; ++ci)
-                            *reinterpret_cast<float2*>(&zt[(col * UX_ZR + 2 * pty + ci) * UX_ZS + 2 * ptx]) =
-                                make_float2(accs[2 * ci][i][4 * (2 * gh + g2) + rr], accs[2 * ci + 1][i][4 * (2 * gh + g2) + rr]);
-                    }
-            }
+            put_tile(i, gh);
             __syncthreads();
             if (nrow > 0 && col_ok) {
 #pragma unroll
@@ -529,12 +649,12 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
                     const int co = co0 + cl;
                     if (co >= p.cout) continue;
                     const float dd = ep_d[cl], bi = ep_b[cl];
-                    const float* zc = zt + (lc * UX_ZR + 8 * byg + 1) * UX_ZS + bx + 1;
+                    const float* zc = zt + lc * UX_ZCP + (8 * byg + 1) * UX_ZP + bx + 1;
                     float* orow = p.out + ((size_t)b * p.cout + co) * ho * wo + (size_t)oy0 * wo + ox;
                     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3;
 #pragma unroll
                     for (int zr = 0; zr < 8 + 3; ++zr) {
-                        const float* zp = zc + zr * UX_ZS;
+                        const float* zp = zc + zr * UX_ZP;
                         const float z0 = zp[0], z1 = zp[1], z2 = zp[2], z3 = zp[3];
                         a3 = 0.f;
                         a0 = __builtin_fmaf(z0, kf[12], a0); a1 = __builtin_fmaf(z0, kf[8], a1); a2 = __builtin_fmaf(z0, kf[4], a2); a3 = __builtin_fmaf(z0, kf[0], a3);
@@ -553,6 +673,7 @@ __global__ __launch_bounds__(512, 2) void masked_up_block_mx_kernel(const UpBloc
             __syncthreads();
         }
     }
+#endif
 }
 
 }  // namespace
