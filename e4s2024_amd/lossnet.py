@@ -1,8 +1,8 @@
 """What the frozen loss networks of the PTI objective (``ops_lpips``, ``ops_id``, ``ops_fp``) have in common on the host side, and what the stage networks
-(``ops_recolor``, ``ops_rrdb``, ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) take from it: the cache of prepared weights, BatchNorm
-folding, weight preparation for and the calls of the convolutions of csrc/conv.hip (split-bf16: ``prep_fwd`` / ``prep_dgrad`` / ``conv_sb``; exact float32:
+(``ops_recolor``, ``ops_rrdb``, ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) take from it: BatchNorm folding, weight preparation for and the calls of the convolutions of csrc/conv.hip (split-bf16: ``prep_fwd`` / ``prep_dgrad`` / ``conv_sb``; exact float32:
 ``prep_exact`` / ``conv_exact``), the banded resampler of csrc/idloss.hip and its adjoint, the cosine heads, two small kernels, and the checks and call
-arguments of the multi-target heads.  The library is resolved inside the calls only, so the module imports on a machine without it.
+arguments of the multi-target heads.  Taking a network's weights from a caller (validation, the cache of prepared copies) is ``netweights``'.  The library is
+resolved inside the calls only, so the module imports on a machine without it.
 
 Multi-target terms: PTI compares one reconstruction with the driven frame and with the recoloured driven frame (training/video_swap_ft_coach.py:274-287).
 Both terms see the same input, so each loss network runs its forward pass and input gradient once; only the heads read the k <= 4 targets' features.
@@ -10,7 +10,6 @@ Target features are tensors with ``rows`` samples: the batch of the step (``fram
 which a device int32 ``frame`` selects (a captured step picks its frame by writing that scalar before the replay, with no copy of the features)."""
 from __future__ import annotations
 
-import weakref
 from typing import Optional, Sequence
 
 import numpy as np
@@ -25,31 +24,6 @@ MULTI_STATS = 1 + 2 * MAX_TARGETS            # e4s_id_head_*_multi: |x|^2 (|x|),
 
 
 # ------------------------------------------------------------------------------------------------ weights
-def weights_key(tensors) -> tuple:
-    """What the prepared copies are keyed on: storage and version of every tensor."""
-    return tuple((t.data_ptr(), t._version) for t in tensors)
-
-
-_CACHES = {}                                 # cache class -> WeakKeyDictionary[module, cache]
-
-
-def prepare(cache_cls, weights, *checked):
-    """Prepared copies (``cache_cls().get``) for ``weights``, cached on a module; a plain mapping is prepared on every call.  ``checked``: what the
-    caller's own validation of ``weights`` already produced, handed to ``get`` so that it is not made twice."""
-    if not isinstance(weights, torch.nn.Module):
-        return cache_cls().get(weights, *checked)
-    per_module = _CACHES.setdefault(cache_cls, weakref.WeakKeyDictionary())
-    cache = per_module.get(weights)
-    if cache is None:
-        cache = per_module[weights] = cache_cls()
-    return cache.get(weights, *checked)
-
-
-def caches_of(module):
-    """The caches ``prepare`` holds for ``module`` and the modules under it (``ops.invalidate_weight_caches`` empties them)."""
-    return [per_module[m] for per_module in _CACHES.values() for m in module.modules() if m in per_module]
-
-
 def bn_fold(sd, prefix):
     """Eval-mode BatchNorm as float64 (scale, shift): y = x * scale + shift."""
     g, b = sd[prefix + ".weight"].double(), sd[prefix + ".bias"].double()

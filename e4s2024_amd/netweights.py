@@ -1,17 +1,18 @@
-"""What the stage modules (``ops_recolor``, ``ops_rrdb``, ``ops_gpen*``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) and ``pipeline`` share when they take a
-network's weights and tensors from a caller: the description of a network (``_Net``; ``module_net`` pins it to the structure a mirror module was built with), the
-one validation of a module or mapping against it (``_validated``: keys, shapes and dtypes checked once per public call and handed on to ``lossnet.prepare``), the
-cache of the kernels' copies of the weights (``PreparedNet``: a network states its ``_Net`` and builds its payload, the key and the look-up are here), and the
-tensor checks every public call makes before any launch."""
+"""What every network of the package (the stage modules ``ops_recolor``, ``ops_rrdb``, ``ops_gpen*``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact*``, the
+frozen loss networks ``ops_lpips``, ``ops_id``, ``ops_fp``) and ``pipeline`` share when they take a network's weights and tensors from a caller: the description
+of a network (``_Net``; ``module_net`` pins it to the structure a mirror module was built with), the one validation of a module or mapping against it
+(``_validated``: keys, shapes and dtypes checked once per public call and handed on to ``prepare``), the cache of the kernels' copies of the weights
+(``PreparedNet``: a network states its ``_Net`` and builds its payload, the key and the look-up are here; ``prepare`` keeps one per module, ``weights_key`` is
+what it is keyed on), and the tensor checks every public call makes before any launch."""
 from __future__ import annotations
 
 import functools
+import weakref
 from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
-from .lossnet import weights_key
 from .ops import _Prepared, _c
 
 EVAL_ONLY = "the native path is the eval-mode forward (BatchNorm's running statistics)"       # a ``_Net.training`` most networks with a BatchNorm share
@@ -48,8 +49,8 @@ def _placed_checked(name, nm, t, ts):
 
 # What ``_validated`` needs to know of a network: ``cls`` its name in messages; ``shapes(variant)`` the public ``{key: shape}`` function; ``prefixes`` the key
 # prefixes a checkpoint may carry (``nested``: or a mapping of that name inside it); ``variant(name, sd)`` reads the width / small or full / block count off
-# the bare keys and raises for a missing probe key; ``training``: why a module in training mode is refused (None: it makes no difference); ``skip``: the key
-# suffixes that are not float weights.
+# the bare keys and raises for a missing probe key (None: one fixed structure, ``shapes()`` takes no argument and the variant is ``()``); ``training``: why a
+# module in training mode is refused (None: it makes no difference); ``skip``: the key suffixes that are not float weights.
 _Net = namedtuple("_Net", "cls shapes prefixes nested probes variant training skip")
 
 
@@ -59,9 +60,23 @@ def _keys_shapes(cls, *args):
         return tuple((k, tuple(v.shape)) for k, v in cls(*args).state_dict().items())
 
 
-@functools.lru_cache(maxsize=8)
+# One entry per (network, structure) a process meets: a dozen stage networks, the three loss networks (LPIPS in two forms) and every structure ``module_net``
+# pins pass through here in one process (PTI and the pipeline), several times per step.  64 holds them all, so that no call rebuilds a table another evicted.
+@functools.lru_cache(maxsize=64)
 def _float_keys(net, variant):
-    return tuple((k, shape) for k, shape in net.shapes(variant).items() if not k.endswith(net.skip))
+    shapes = net.shapes() if net.variant is None else net.shapes(variant)
+    return tuple((k, shape) for k, shape in shapes.items() if not k.endswith(net.skip))
+
+
+def _shapes_call(net, variant):
+    """The call that lists the keys ``net`` expects, as a reader can type it: ``ops_id.state_dict_shapes()``."""
+    return f"{net.shapes.__module__.rpartition('.')[2]}.{net.shapes.__name__}({'' if net.variant is None else repr(variant)})"
+
+
+def check_eval(name, weights, net):
+    """Raises for a module in training mode, if that changes what ``net`` computes; ``name`` None: no entry in front."""
+    if isinstance(weights, nn.Module) and weights.training and net.training:
+        raise RuntimeError(f"{name + ': ' if name else ''}{type(weights).__name__} is in training mode; {net.training}: call .eval()")
 
 
 def _validated(name, weights, net):
@@ -69,8 +84,7 @@ def _validated(name, weights, net):
     once per public call (one ``state_dict()``) and handed on.  Refused, in this order: a module in training mode, anything without keys, a missing probe key,
     a missing key, a wrong shape or dtype."""
     if isinstance(weights, nn.Module):
-        if weights.training and net.training:
-            raise RuntimeError(f"{name}: {type(weights).__name__} is in training mode; {net.training}: call .eval()")
+        check_eval(name, weights, net)
         sd = weights.state_dict()
     elif hasattr(weights, "keys"):
         sd = weights
@@ -84,13 +98,13 @@ def _validated(name, weights, net):
             if any(prefix + p in sd for p in net.probes):
                 sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
                 break
-    variant = net.variant(name, sd)
+    variant = net.variant(name, sd) if net.variant else ()
     out = []
     for k, shape in _float_keys(net, variant):
         t = sd.get(k)
         if t is None:
-            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {net.cls} (ops.{net.shapes.__name__}({variant!r}))")
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise KeyError(f"{name}: the weights lack '{k}': expected the keys of {net.cls} ({_shapes_call(net, variant)})")
+        if not isinstance(t, torch.Tensor) or t.shape != shape or t.dtype != torch.float32:      # (a torch.Size is a tuple)
             raise ValueError(f"{name}: '{k}' is {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}, expected float32 {shape}")
         out.append(t)
     return sd, variant, out
@@ -127,8 +141,33 @@ def bn_shapes(out, prefix, c):
     out[prefix + ".num_batches_tracked"] = ()
 
 
+def weights_key(tensors) -> tuple:
+    """What the prepared copies are keyed on: storage and version of every tensor."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+_CACHES = {}                                 # cache class -> WeakKeyDictionary[module, cache]
+
+
+def prepare(cache_cls, weights, *checked):
+    """Prepared copies (``cache_cls().get``) for ``weights``, cached on a module; a plain mapping is prepared on every call.  ``checked``: what the
+    caller's own validation of ``weights`` already produced, handed to ``get`` so that it is not made twice."""
+    if not isinstance(weights, nn.Module):
+        return cache_cls().get(weights, *checked)
+    per_module = _CACHES.setdefault(cache_cls, weakref.WeakKeyDictionary())
+    cache = per_module.get(weights)
+    if cache is None:
+        cache = per_module[weights] = cache_cls()
+    return cache.get(weights, *checked)
+
+
+def caches_of(module):
+    """The caches ``prepare`` holds for ``module`` and the modules under it (``ops.invalidate_weight_caches`` empties them)."""
+    return [per_module[m] for per_module in _CACHES.values() for m in module.modules() if m in per_module]
+
+
 class PreparedNet(_Prepared):
-    """The kernels' copies of a stage network's weights, cached per storage and version of every tensor, the device and ``_settings()``.  A network states
+    """The kernels' copies of a network's weights, cached per storage and version of every tensor, the device and ``_settings()``.  A network states
     ``_entry``, the public name its messages carry; ``_net``, its ``_Net``, or a method ``_net(weights)`` where a mirror module pins the structure; if its payload
     depends on module knobs, ``_settings()``, read at call time; and ``_build(sd, variant, dev)``: the payload from the contiguous float tensors ``sd`` by bare
     key, called under ``no_grad``."""

@@ -377,7 +377,7 @@ def invalidate_weight_caches(module: torch.nn.Module) -> int:
     """Drop every re-laid-out weight copy held by the drop-in modules under ``module`` (they are rebuilt by the next forward).  Needed only
     after writing parameters behind autograd's back between two ``no_grad`` forwards — ``p.data.copy_(...)``, an EMA update, a replay of a
     captured optimiser step (``pti.GraphedPTIStep`` does it itself) — which leaves no trace the caches could key on; ``load_state_dict``,
-    ordinary in-place ops and any training forward are tracked.  The copies ``lossnet.prepare`` keeps for the modules under ``module`` (the frozen loss
+    ordinary in-place ops and any training forward are tracked.  The copies ``netweights.prepare`` keeps for the modules under ``module`` (the frozen loss
     networks, the recolouring networks) are dropped too."""
     seen = set()
 
@@ -393,8 +393,8 @@ def invalidate_weight_caches(module: torch.nn.Module) -> int:
             return sum(drop(c) for c in v.values())
         return 0
 
-    from . import lossnet                  # (imports this module: resolved here, not at import time)
-    return sum(drop(v) for m in module.modules() for v in vars(m).values()) + sum(drop(c) for c in lossnet.caches_of(module))
+    from . import netweights               # (imports this module: resolved here, not at import time)
+    return sum(drop(v) for m in module.modules() for v in vars(m).values()) + sum(drop(c) for c in netweights.caches_of(module))
 
 
 class _Prepared:

@@ -18,23 +18,23 @@ on the HIP kernels: forward and gradient with respect to the reconstruction, for
 ``unet``-shaped module (``FaceParsingNet``, or the drop-in ``criteria.face_parsing.face_parsing_loss.FaceParsingLoss`` / its ``G``) or a mapping with
 at least the encoder's keys (``state_dict_keys()`` lists all 136; the decoder's ``up_concat*`` / ``final`` are not used by the loss).  They are
 frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the reference puts the network in eval mode); a module left in
-training mode is refused.  The weight cache, BN folding, split-bf16 weight preparation and convolution wrapper, the resampler, the heads and
-the multi-target helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_id``.
+training mode is refused.  Validation of the weights (keys, shapes, dtypes: once per public call) and the cache of their prepared copies are
+``netweights``', as for every network of the package; BN folding, split-bf16 weight preparation and convolution wrapper, the resampler, the heads
+and the multi-target helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_id``.
 """
 from __future__ import annotations
-
-import functools
 
 import torch
 import torch.nn as nn
 
 from typing import Optional
 
-from . import lossnet
+from . import lossnet, netweights
 from ._lib import lib
-from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_exact, conv_sb, cos_heads, cos_heads_multi, pool_matrix, prep_dgrad,
-                      prep_fwd, relu_mask, target_rows, weights_key)
-from .ops import _Prepared, _c, _p, _stream
+from .lossnet import (call_args, check_frame, check_image, check_targets, conv_exact, conv_sb, cos_heads, cos_heads_multi, fold_conv_bn, pool_matrix,
+                      prep_dgrad, prep_exact, prep_fwd, relu_mask, target_rows)
+from .netweights import PreparedNet, _Net, _keys_shapes, _validated, weights_key
+from .ops import _c, _p, _stream
 
 SIDE = 512                                   # FaceParsingLoss.face_pool: AdaptiveAvgPool2d((512, 512)) unless x.shape[2] == 512
 FILTERS = (16, 32, 64, 128, 256)             # unet(feature_scale=4): [64, 128, 256, 512, 1024] / 4
@@ -92,20 +92,14 @@ class FaceParsingNet(nn.Module):
         return unet_features(x, self)
 
 
-@functools.lru_cache(maxsize=1)
-def _keys_shapes():
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in FaceParsingNet().state_dict().items())
-
-
 def state_dict_keys():
     """The 136 keys of ``unet().state_dict()``, in its order."""
-    return [k for k, _ in _keys_shapes()]
+    return [k for k, _ in _keys_shapes(FaceParsingNet)]
 
 
 def state_dict_shapes():
     """``{key: shape}`` of ``unet().state_dict()``."""
-    return dict(_keys_shapes())
+    return dict(_keys_shapes(FaceParsingNet))
 
 
 def encoder_keys():
@@ -113,88 +107,67 @@ def encoder_keys():
     return [k for k in state_dict_keys() if k.split(".")[0] in BLOCKS]
 
 
+def encoder_shapes():
+    """``{key: shape}`` of the encoder's 70 keys: what the weights of the loss are checked against."""
+    return {k: shape for k, shape in _keys_shapes(FaceParsingNet) if k.split(".")[0] in BLOCKS}
+
+
 # ------------------------------------------------------------------------------------------------ weights
-def _net(weights):
-    return getattr(weights, "G", weights)          # the drop-in FaceParsingLoss holds the network as ``G``
+_FP_NET = _Net("unet(feature_scale=4)'s encoder", encoder_shapes, ("G.",), False, ("conv1.conv1.0.weight",), None,
+               "the face-parsing loss runs the network in eval mode", ("num_batches_tracked",))
+
+
+def _network(weights):
+    """The network of ``weights``: the drop-in FaceParsingLoss holds it as ``G``.  Its ``_loaded`` and ``training`` flags are the ones that count."""
+    return getattr(weights, "G", weights) if isinstance(weights, nn.Module) else weights
 
 
 def check_loaded(weights):
     """``weights`` itself; raises if it is a module whose weights were never loaded (a loss from initial parameters would be a silently wrong
     objective) or one left in training mode (BatchNorm on batch statistics: different arithmetic from the eval-mode reference)."""
-    if isinstance(weights, nn.Module):
-        net = _net(weights)
-        if getattr(net, "_loaded", True) is False:
-            raise RuntimeError(f"{type(weights).__name__}: the face-parsing weights were never loaded (nothing is downloaded here); call load_state_dict first")
-        if net.training:
-            raise RuntimeError(f"{type(net).__name__} is in training mode; the face-parsing loss runs the network in eval mode: call .eval()")
+    netweights.check_loaded(None, _network(weights), "the face-parsing weights")
+    netweights.check_eval(None, _network(weights), _FP_NET)
     return weights
 
 
-def _mapping(weights):
-    check_loaded(weights)
-    if isinstance(weights, nn.Module):
-        weights = _net(weights).state_dict()
-    if "conv1.conv1.0.weight" not in weights and "G.conv1.conv1.0.weight" in weights:
-        weights = {k[len("G."):]: v for k, v in weights.items() if k.startswith("G.")}
-    return weights
+def _checked(name, weights):
+    """(the network of ``weights``, what ``_validated`` returns of its encoder): what a public call makes once, before it looks at its images, and
+    hands to ``netweights.prepare``.  Refused in this order: weights never loaded, training mode, a missing key, a wrong shape or dtype."""
+    net = _network(weights)
+    netweights.check_loaded(name, net, "the face-parsing weights")
+    return net, _validated(name, net, _FP_NET)
 
 
-def weight_tensors(weights):
-    """The float tensors of the encoder (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
-    sd = _mapping(weights)
-    try:
-        return [sd[k] for k in encoder_keys() if not k.endswith("num_batches_tracked")]
-    except KeyError as e:
-        raise KeyError(f"face-parsing weights lack {e}: expected the keys of unet(feature_scale=4) (ops_fp.state_dict_keys())") from None
+def weight_tensors(weights, name: str = "fp_loss"):
+    """The float tensors of the encoder (``num_batches_tracked`` aside), in key order, their shapes checked: what ``weights_key`` watches."""
+    return _checked(name, weights)[1][2]
 
 
-def _fold(sd, p):
-    """Conv ``p.0`` + eval BatchNorm ``p.1`` as float64 (scale, shift): BN(conv(x) + b) = conv(x) * scale + shift."""
-    s, t = bn_fold(sd, p + ".1")
-    return s, t + sd[p + ".0.bias"].double() * s
-
-
-def _prep_fp32(w, scale, shift):
-    """The fp32 direct kernel's layout (e4s_conv2d, 3 input channels) of ``w * scale[co]``, the shift as bias."""
-    cout, cin, k, _ = w.shape
-    wf = (w.double() * scale[:, None, None, None]).float().contiguous()
-    wt = torch.empty((cin * k * k * cout,), dtype=torch.float32, device=w.device)
-    bias = torch.empty((cout,), dtype=torch.float32, device=w.device)
-    lib().call("e4s_conv_prep_weights", _p(wt), _p(bias), _p(wf), None, None, None, None, 0.0, _p(shift.float().contiguous()), cout, cin, k, k, _stream())
-    return wt, bias
-
-
-class PreparedFaceParsingNet(_Prepared):
+class PreparedFaceParsingNet(PreparedNet):
     """The kernels' copies of the encoder weights, rebuilt when a tensor changes version or storage: per block the forward weights of both convolutions
     (conv bias and BN folded in; fp32 layout for the 3-channel input, three-way split slabs otherwise) and two-way split slabs of their data gradients
     (BN scales folded in)."""
 
     __slots__ = ()
 
-    def get(self, weights):
-        ts = weight_tensors(weights)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        enc = set(encoder_keys())
-        sd = {k: _c(v.detach(), k) for k, v in _mapping(weights).items() if k in enc and not k.endswith("num_batches_tracked")}
+    _entry, _net = "fp_loss", _FP_NET
+
+    def _build(self, sd, variant, dev):
         blocks = []
-        with torch.no_grad():
-            for i, name in enumerate(BLOCKS):
-                cin, cout = (3 if i == 0 else FILTERS[i - 1]), FILTERS[i]
-                w1, w2 = sd[name + ".conv1.0.weight"], sd[name + ".conv2.0.weight"]
-                s1, t1 = _fold(sd, name + ".conv1")
-                s2, t2 = _fold(sd, name + ".conv2")
-                fwd1 = _prep_fp32(w1, s1, t1) if cin < 16 else prep_fwd(w1, s1, t1)
-                blocks.append(dict(cin=cin, cout=cout, fwd1=fwd1, fwd2=prep_fwd(w2, s2, t2), bwd1=prep_dgrad(w1, out_scale=s1),
-                                   bwd2=prep_dgrad(w2, out_scale=s2)))
-        return self._publish(key, tuple(blocks))
+        for i, name in enumerate(BLOCKS):
+            cin, cout = (3 if i == 0 else FILTERS[i - 1]), FILTERS[i]
+            w1, w2 = sd[name + ".conv1.0.weight"], sd[name + ".conv2.0.weight"]
+            s1, t1 = fold_conv_bn(sd, name + ".conv1.0", name + ".conv1.1")
+            s2, t2 = fold_conv_bn(sd, name + ".conv2.0", name + ".conv2.1")
+            fwd1 = (prep_exact if cin < 16 else prep_fwd)(w1, s1, t1)
+            blocks.append(dict(cin=cin, cout=cout, fwd1=fwd1, fwd2=prep_fwd(w2, s2, t2), bwd1=prep_dgrad(w1, out_scale=s1),
+                               bwd2=prep_dgrad(w2, out_scale=s2)))
+        return tuple(blocks)
 
 
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    return lossnet.prepare(PreparedFaceParsingNet, weights)
+    return netweights.prepare(PreparedFaceParsingNet, *_checked("fp_loss", weights))
 
 
 # ------------------------------------------------------------------------------------------------ input pooling
@@ -329,9 +302,9 @@ class _FpLossMulti(torch.autograd.Function):
 def target_features(images: torch.Tensor, weights):
     """The raw block outputs of ``images`` ``[n, 3, H, W]`` that ``fp_loss_multi`` reads for a target: five ``[n, D]`` tensors.  Computed a frame at a
     time; no gradient."""
-    check_loaded(weights)
+    W = _checked("ops_fp.target_features", weights)
     images = _check(images.detach(), "images")
-    P, R = prepare(weights), resampler(images.shape[2], images.shape[3], images.device)
+    P, R = netweights.prepare(PreparedFaceParsingNet, *W), resampler(images.shape[2], images.shape[3], images.device)
     with torch.no_grad():
         return target_rows(lambda x: [c2.reshape(x.shape[0], -1) for _, c2 in _encoder(_network_input((x.contiguous(),), R), P)], images)
 
@@ -339,12 +312,12 @@ def target_features(images: torch.Tensor, weights):
 def fp_loss_multi(y_hat: torch.Tensor, targets, tw, weights, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sum_j tw[j] * fp_loss(y_hat, y_j)`` (0-d, differentiable in ``y_hat`` only) with one encoder pass and input gradient of ``y_hat``:
     ``targets[j] = target_features(y_j, weights)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
-    check_loaded(weights)
+    W = _checked("fp_loss_multi", weights)
     y_hat = _check(y_hat, "y_hat")
     frame = check_frame(frame, y_hat.device)
     bs = y_hat.shape[0]
     side_h, side_w = (y_hat.shape[2], y_hat.shape[3]) if y_hat.shape[2] == SIDE else (SIDE, SIDE)
-    P = prepare(weights)
+    P = netweights.prepare(PreparedFaceParsingNet, *W)
     dims = [B["cout"] * (side_h >> i) * (side_w >> i) for i, B in enumerate(P)]
     ys = check_targets([torch.empty((bs, d), device="meta") for d in dims], targets, tw, frame, "fp_loss_multi")
     return _FpLossMulti.apply(y_hat, P, resampler(y_hat.shape[2], y_hat.shape[3], y_hat.device), ys, [float(w) for w in tw], frame)
@@ -359,11 +332,11 @@ def _check(x: torch.Tensor, name: str) -> torch.Tensor:
 
 
 def _apply(y_hat, y, weights):
-    check_loaded(weights)
+    W = _checked("fp_loss", weights)
     y_hat, y = _check(y_hat, "y_hat"), _check(y.detach(), "y")
     if y_hat.shape != y.shape:
         raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ")
-    return _FpLoss.apply(y_hat, y, prepare(weights), resampler(y.shape[2], y.shape[3], y.device))
+    return _FpLoss.apply(y_hat, y, netweights.prepare(PreparedFaceParsingNet, *W), resampler(y.shape[2], y.shape[3], y.device))
 
 
 def fp_loss_terms(y_hat: torch.Tensor, y: torch.Tensor, weights):
@@ -379,26 +352,29 @@ def fp_loss(y_hat: torch.Tensor, y: torch.Tensor, weights) -> torch.Tensor:
     return _apply(y_hat, y, weights)[0]
 
 
-def unet_features(x: torch.Tensor, weights):
-    """unet.extract_feats(x): the l2-normalised block outputs of the image as it is (H, W multiples of 16; no gradient)."""
-    check_loaded(weights)
+def _unet_features(x, W):
     x = _c(x, "x")
     if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 16 or x.shape[3] % 16:
         raise ValueError(f"x: expected [bs, 3, H, W] with H, W multiples of 16, got {tuple(x.shape)}")
     with torch.no_grad():
-        acts = _encoder(x, prepare(weights))
+        acts = _encoder(x, netweights.prepare(PreparedFaceParsingNet, *W))
     bs = x.shape[0]
     return [c2.reshape(bs, -1) / c2.reshape(bs, -1).norm(dim=1, keepdim=True) for _, c2 in acts]
 
 
+def unet_features(x: torch.Tensor, weights):
+    """unet.extract_feats(x): the l2-normalised block outputs of the image as it is (H, W multiples of 16; no gradient)."""
+    return _unet_features(x, _checked("unet_features", weights))
+
+
 def fp_features(x: torch.Tensor, weights):
     """FaceParsingLoss.extract_feats(x): the l2-normalised features after the pooling to 512 x 512 (unless H is 512; no gradient)."""
-    check_loaded(weights)
+    W = _checked("fp_features", weights)
     x = _check(x, "x")
     with torch.no_grad():
         x512 = _network_input((x,), resampler(x.shape[2], x.shape[3], x.device))
-    return unet_features(x512, weights)
+    return _unet_features(x512, W)
 
 
 __all__ = ["FaceParsingNet", "PreparedFaceParsingNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes",
-           "encoder_keys", "resampler", "fp_features", "unet_features", "fp_loss", "fp_loss_terms", "target_features", "fp_loss_multi"]
+           "encoder_keys", "encoder_shapes", "resampler", "fp_features", "unet_features", "fp_loss", "fp_loss_terms", "target_features", "fp_loss_multi"]

@@ -40,10 +40,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet, netweights
+from . import netweights
 from ._lib import MAX_STYLE_JOBS, StyleJob, lib
 from .ops import _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
-from .netweights import PreparedNet, _Net, _cuda_checked, _image_checked, _keys_shapes, _placed_checked, _tensor_checked, _validated, module_net
+from .netweights import PreparedNet, _Net, _cuda_checked, _image_checked, _keys_shapes, _placed_checked, _tensor_checked, _validated, module_net, prepare
 
 ARITH = "sb"                                 # "sb" | "f32" (module attribute, no environment variable: tests and tools set it)
 UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form (measured: see the module text)
@@ -567,7 +567,7 @@ def gpen_forward(x: torch.Tensor, weights, return_latents: bool = False):
         n_latent = 2 * int(math.log2(size)) - 2
         return x.new_empty((0, 3, size, size)), (x.new_empty((0, n_latent, sdim)) if return_latents else None)
     with torch.no_grad():
-        return _gpen_run(lossnet.prepare(PreparedGPEN, weights, checked), x.detach().contiguous(), None, return_latents)
+        return _gpen_run(prepare(PreparedGPEN, weights, checked), x.detach().contiguous(), None, return_latents)
 
 
 def gpen_image(img_u8: torch.Tensor, weights) -> torch.Tensor:
@@ -581,7 +581,7 @@ def gpen_image(img_u8: torch.Tensor, weights) -> torch.Tensor:
     if bs == 0:
         return out
     with torch.no_grad():
-        r, _ = _gpen_run(lossnet.prepare(PreparedGPEN, weights, checked), None, img_u8.contiguous(), False)
+        r, _ = _gpen_run(prepare(PreparedGPEN, weights, checked), None, img_u8.contiguous(), False)
         lib().call("e4s_gpen_to_u8", _p(out), _p(r), bs, size, size, _stream())
     return out
 

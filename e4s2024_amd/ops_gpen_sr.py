@@ -15,9 +15,9 @@ from __future__ import annotations
 
 import torch
 
-from . import lossnet, ops_rrdb
+from . import ops_rrdb
 from ._lib import lib
-from .netweights import _cuda_checked, _devices_checked, _tensor_checked, _validated
+from .netweights import _cuda_checked, _devices_checked, _tensor_checked, _validated, prepare
 from .ops import _p, _stream
 from .ops_rrdb import GPEN_SR_FEATS, GPEN_SR_SCALES, _GSR_NET, _UNSHUFFLE, GpenSRNet, gpen_sr_state_dict_shapes
 
@@ -72,7 +72,7 @@ def gpen_sr_forward(x: torch.Tensor, weights) -> torch.Tensor:
         x = x.detach()
         if r > 1:
             x = x.reshape(bs, 3, h // r, r, w // r, r).permute(0, 1, 3, 5, 2, 4).reshape(bs, 3 * r * r, h // r, w // r)
-        return _gsr_run(x.contiguous(), lossnet.prepare(PreparedGpenSRNet, weights, checked), True, None)[0]
+        return _gsr_run(x.contiguous(), prepare(PreparedGpenSRNet, weights, checked), True, None)[0]
 
 
 def gpen_sr_output_size(H: int, W: int, scale: int):
@@ -114,7 +114,7 @@ def gpen_sr_image(img_u8: torch.Tensor, weights, bgr: bool = True) -> torch.Tens
     with torch.no_grad():
         x = torch.empty((bs, 3 * r * r, (H + ph) // r, (W + pw) // r), dtype=torch.float32, device=img_u8.device)
         lib().call("e4s_gsr_input", _p(x), _p(img_u8.contiguous()), bs, H, W, r, int(bool(bgr)), _stream())
-        return _gsr_run(x, lossnet.prepare(PreparedGpenSRNet, weights, checked), False, (Ho, Wo), bool(bgr))[1]
+        return _gsr_run(x, prepare(PreparedGpenSRNet, weights, checked), False, (Ho, Wo), bool(bgr))[1]
 
 
 def cv_resize_linear(img_u8: torch.Tensor, dsize) -> torch.Tensor:

@@ -14,12 +14,12 @@ kernels: forward and gradient with respect to the reconstruction, for the identi
 
 Weights are a ``Backbone``-shaped module (``IdNet``, or the drop-in ``criteria.id_loss.IDLoss`` / its ``facenet``) or a mapping with the
 reference's 397 keys (``state_dict_keys()``).  They are frozen: no weight gradient is computed.  BatchNorm uses its running statistics (the
-reference puts the network in eval mode); a module left in training mode is refused.  The weight cache, BN folding, split-bf16 weight preparation
-and convolution wrapper, the resampler, the heads and the multi-target helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_fp``.
+reference puts the network in eval mode); a module left in training mode is refused.  Validation of the weights (keys, shapes, dtypes: once per public call) and the cache of their prepared copies are ``netweights``',
+as for every network of the package; BN folding, split-bf16 weight preparation and convolution wrapper, the resampler, the heads and the multi-target
+helpers are ``lossnet``'s, shared with ``ops_lpips`` and ``ops_fp``.
 """
 from __future__ import annotations
 
-import functools
 import math
 
 import numpy as np
@@ -28,13 +28,14 @@ import torch.nn as nn
 
 from typing import Optional
 
-from . import lossnet
+from . import lossnet, netweights
 from ._lib import lib
 from .lossnet import (bn_fold, call_args, check_frame, check_image, check_targets, conv_sb, cos_heads, cos_heads_multi as heads_multi, pool_matrix,
-                      prep_dgrad, prep_fwd, target_rows, weights_key)
+                      prep_dgrad, prep_fwd, target_rows)
+from .netweights import PreparedNet, _Net, _keys_shapes, _validated, weights_key
 
 _pool_matrix, _bands = pool_matrix, lossnet.bands       # their names before they moved to lossnet, kept for callers outside the package
-from .ops import _Prepared, _c, _p, _stream
+from .ops import _c, _p, _stream
 
 SIDE = 112                                   # the network's input side (IDLoss.face_pool_2)
 CROP = ((35, 223), (32, 220))                # IDLoss.extract_feats: rows, columns of the 256 x 256 image
@@ -90,52 +91,46 @@ class IdNet(nn.Module):
         return features_112(x, self, multi_scale)
 
 
-@functools.lru_cache(maxsize=1)
-def _keys_shapes():
-    with torch.device("meta"):
-        return tuple((k, tuple(v.shape)) for k, v in IdNet().state_dict().items())
-
-
 def state_dict_keys():
     """The 397 keys of ``Backbone(112, 50, 'ir_se').state_dict()``, in its order."""
-    return [k for k, _ in _keys_shapes()]
+    return [k for k, _ in _keys_shapes(IdNet)]
 
 
 def state_dict_shapes():
     """``{key: shape}`` of ``Backbone(112, 50, 'ir_se').state_dict()``."""
-    return dict(_keys_shapes())
+    return dict(_keys_shapes(IdNet))
 
 
 # ------------------------------------------------------------------------------------------------ weights
+_ID_NET = _Net("Backbone(112, 50, 'ir_se')", state_dict_shapes, ("facenet.",), False, ("input_layer.0.weight",), None,
+               "the identity loss runs the network in eval mode", ("num_batches_tracked",))
+
+
+def _network(weights):
+    """The network of ``weights``: the drop-in IDLoss holds it as ``facenet``.  Its ``_loaded`` and ``training`` flags are the ones that count."""
+    return getattr(weights, "facenet", weights) if isinstance(weights, nn.Module) else weights
+
+
 def check_loaded(weights):
     """``weights`` itself; raises if it is a module whose weights were never loaded (a loss from initial parameters would be a silently wrong
     objective) or one left in training mode (BatchNorm on batch statistics and active dropout: different arithmetic from the eval-mode
     reference)."""
-    if isinstance(weights, nn.Module):
-        net = getattr(weights, "facenet", weights)          # the drop-in IDLoss holds the network as ``facenet``
-        if getattr(net, "_loaded", True) is False:
-            raise RuntimeError(f"{type(weights).__name__}: the ArcFace weights were never loaded (nothing is downloaded here); call load_state_dict first")
-        if net.training:
-            raise RuntimeError(f"{type(net).__name__} is in training mode; the identity loss runs the network in eval mode: call .eval()")
+    netweights.check_loaded(None, _network(weights), "the ArcFace weights")
+    netweights.check_eval(None, _network(weights), _ID_NET)
     return weights
 
 
-def _mapping(weights):
-    check_loaded(weights)
-    if isinstance(weights, nn.Module):
-        weights = getattr(weights, "facenet", weights).state_dict()
-    if "input_layer.0.weight" not in weights and "facenet.input_layer.0.weight" in weights:
-        weights = {k[len("facenet."):]: v for k, v in weights.items() if k.startswith("facenet.")}
-    return weights
+def _checked(name, weights):
+    """(the network of ``weights``, what ``_validated`` returns of it): what a public call makes once, before it looks at its images, and hands to
+    ``netweights.prepare``.  Refused in this order: weights never loaded, training mode, a missing key, a wrong shape or dtype."""
+    net = _network(weights)
+    netweights.check_loaded(name, net, "the ArcFace weights")
+    return net, _validated(name, net, _ID_NET)
 
 
-def weight_tensors(weights):
-    """The float tensors of ``weights`` (``num_batches_tracked`` aside), in key order: what ``weights_key`` watches."""
-    sd = _mapping(weights)
-    try:
-        return [sd[k] for k in state_dict_keys() if not k.endswith("num_batches_tracked")]
-    except KeyError as e:
-        raise KeyError(f"ArcFace weights lack {e}: expected the keys of Backbone(112, 50, 'ir_se') (ops_id.state_dict_keys())") from None
+def weight_tensors(weights, name: str = "id_loss"):
+    """The float tensors of ``weights`` (``num_batches_tracked`` aside), in key order, their shapes checked: what ``weights_key`` watches."""
+    return _checked(name, weights)[1][2]
 
 
 def _prep_tconv(w, out_scale):
@@ -149,55 +144,50 @@ def _prep_tconv(w, out_scale):
     return whi, wlo
 
 
-class PreparedIdNet(_Prepared):
+class PreparedIdNet(PreparedNet):
     """The kernels' copies of the ArcFace weights, rebuilt when a tensor changes version or storage: per unit the input BN's scale / shift, three-way
     split slabs of both convolutions (the second with its BN folded in) and of the shortcut convolution, two-way split slabs of their data gradients
     (BN scales folded in), the SE and PReLU weights; the output layer folded into one weight and bias."""
 
     __slots__ = ()
 
-    def get(self, weights):
-        ts = weight_tensors(weights)
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        sd = {k: _c(v.detach(), k) for k, v in _mapping(weights).items() if not k.endswith("num_batches_tracked")}
-        with torch.no_grad():
-            s0, t0 = bn_fold(sd, "input_layer.1")
-            w0 = sd["input_layer.0.weight"]
-            inp = (prep_fwd(w0, s0, t0), prep_dgrad(w0, out_scale=s0), sd["input_layer.2.weight"])
-            us = []
-            for i, (cin, depth, stride) in enumerate(units()):
-                p = f"body.{i}."
-                s1, t1 = bn_fold(sd, p + "res_layer.0")
-                w1, w2 = sd[p + "res_layer.1.weight"], sd[p + "res_layer.3.weight"]
-                s2, t2 = bn_fold(sd, p + "res_layer.4")
-                fwd1, _ = prep_fwd(w1)
-                fwd2 = prep_fwd(w2, s2, t2)
-                bwd2 = _prep_tconv(w2, s2) if stride == 2 else prep_dgrad(w2, out_scale=s2)
-                sc = None
-                if cin != depth:
-                    ssc, tsc = bn_fold(sd, p + "shortcut_layer.1")
-                    wsc = sd[p + "shortcut_layer.0.weight"]
-                    sc = (prep_fwd(wsc, ssc, tsc), prep_dgrad(wsc, out_scale=ssc))
-                us.append(dict(cin=cin, depth=depth, stride=stride, bn_scale=s1.float().contiguous(), bn_shift=t1.float().contiguous(), fwd1=fwd1,
-                               bwd1=prep_dgrad(w1, in_scale=s1), slope=sd[p + "res_layer.2.weight"], fwd2=fwd2, bwd2=bwd2,
-                               fc1=sd[p + "res_layer.5.fc1.weight"].reshape(depth // 16, depth).contiguous(),
-                               fc2=sd[p + "res_layer.5.fc2.weight"].reshape(depth, depth // 16).contiguous(), sc=sc))
-            so, to = bn_fold(sd, "output_layer.0")
-            s4, t4 = bn_fold(sd, "output_layer.4")
-            W = sd["output_layer.3.weight"].double()
-            b = sd["output_layer.3.bias"].double()
-            so, to = so.repeat_interleave(49), to.repeat_interleave(49)          # BN2d's channel c covers features c * 49 .. c * 49 + 48 (Flatten)
-            wout = (W * so[None, :] * s4[:, None]).float().contiguous()
-            bout = (((W * to[None, :]).sum(1) + b) * s4 + t4).float().contiguous()
-        return self._publish(key, (inp, tuple(us), wout, bout))
+    _entry, _net = "id_loss", _ID_NET
+
+    def _build(self, sd, variant, dev):
+        s0, t0 = bn_fold(sd, "input_layer.1")
+        w0 = sd["input_layer.0.weight"]
+        inp = (prep_fwd(w0, s0, t0), prep_dgrad(w0, out_scale=s0), sd["input_layer.2.weight"])
+        us = []
+        for i, (cin, depth, stride) in enumerate(units()):
+            p = f"body.{i}."
+            s1, t1 = bn_fold(sd, p + "res_layer.0")
+            w1, w2 = sd[p + "res_layer.1.weight"], sd[p + "res_layer.3.weight"]
+            s2, t2 = bn_fold(sd, p + "res_layer.4")
+            fwd1, _ = prep_fwd(w1)
+            fwd2 = prep_fwd(w2, s2, t2)
+            bwd2 = _prep_tconv(w2, s2) if stride == 2 else prep_dgrad(w2, out_scale=s2)
+            sc = None
+            if cin != depth:
+                ssc, tsc = bn_fold(sd, p + "shortcut_layer.1")
+                wsc = sd[p + "shortcut_layer.0.weight"]
+                sc = (prep_fwd(wsc, ssc, tsc), prep_dgrad(wsc, out_scale=ssc))
+            us.append(dict(cin=cin, depth=depth, stride=stride, bn_scale=s1.float().contiguous(), bn_shift=t1.float().contiguous(), fwd1=fwd1,
+                           bwd1=prep_dgrad(w1, in_scale=s1), slope=sd[p + "res_layer.2.weight"], fwd2=fwd2, bwd2=bwd2,
+                           fc1=sd[p + "res_layer.5.fc1.weight"].reshape(depth // 16, depth).contiguous(),
+                           fc2=sd[p + "res_layer.5.fc2.weight"].reshape(depth, depth // 16).contiguous(), sc=sc))
+        so, to = bn_fold(sd, "output_layer.0")
+        s4, t4 = bn_fold(sd, "output_layer.4")
+        W = sd["output_layer.3.weight"].double()
+        b = sd["output_layer.3.bias"].double()
+        so, to = so.repeat_interleave(49), to.repeat_interleave(49)          # BN2d's channel c covers features c * 49 .. c * 49 + 48 (Flatten)
+        wout = (W * so[None, :] * s4[:, None]).float().contiguous()
+        bout = (((W * to[None, :]).sum(1) + b) * s4 + t4).float().contiguous()
+        return inp, tuple(us), wout, bout
 
 
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    return lossnet.prepare(PreparedIdNet, weights)
+    return netweights.prepare(PreparedIdNet, *_checked("id_loss", weights))
 
 
 # ------------------------------------------------------------------------------------------------ pre-processing operator
@@ -382,9 +372,9 @@ class _IdLossMulti(torch.autograd.Function):
 def target_features(images: torch.Tensor, weights, multiscale: bool = True):
     """The raw (not normalised) features of ``images`` ``[n, 3, H, W]`` that ``id_loss_multi`` reads for a target: a list of ``[n, D]`` tensors
     (five with ``multiscale``, the embedding alone without).  Computed a frame at a time; no gradient."""
-    check_loaded(weights)
+    W = _checked("ops_id.target_features", weights)
     images = check_image(images.detach(), "images")
-    P, R = prepare(weights), resampler(images.shape[2], images.shape[3], images.device)
+    P, R = netweights.prepare(PreparedIdNet, *W), resampler(images.shape[2], images.shape[3], images.device)
     with torch.no_grad():
         return target_rows(lambda x: _features(R.apply(x.contiguous()), P, bool(multiscale), save=False)[0], images)
 
@@ -392,23 +382,23 @@ def target_features(images: torch.Tensor, weights, multiscale: bool = True):
 def id_loss_multi(y_hat: torch.Tensor, targets, tw, weights, multiscale: bool = True, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sum_j tw[j] * id_loss(y_hat, y_j)`` (0-d, differentiable in ``y_hat`` only) with one network pass and input gradient of ``y_hat``:
     ``targets[j] = target_features(y_j, weights, multiscale)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
-    check_loaded(weights)
+    W = _checked("id_loss_multi", weights)
     y_hat = check_image(y_hat, "y_hat")
     frame = check_frame(frame, y_hat.device)
     bs = y_hat.shape[0]
     ys = check_targets([torch.empty((bs, d), device="meta") for d in _feature_dims(multiscale)], targets, tw, frame, "id_loss_multi")
-    return _IdLossMulti.apply(y_hat, prepare(weights), resampler(y_hat.shape[2], y_hat.shape[3], y_hat.device), bool(multiscale), ys,
+    return _IdLossMulti.apply(y_hat, netweights.prepare(PreparedIdNet, *W), resampler(y_hat.shape[2], y_hat.shape[3], y_hat.device), bool(multiscale), ys,
                               [float(w) for w in tw], frame)
 
 
 def id_loss_terms(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = True):
     """``(loss, sim_improvement, per_scale)``: the loss (0-d, differentiable in ``y_hat``), IDLoss's similarity improvement (0-d, on the device) and
     ``per_scale [scales]`` = mean over the batch of 1 - cos per scale (no gradient).  No host synchronisation."""
-    check_loaded(weights)
+    W = _checked("id_loss", weights)
     y_hat, y = check_image(y_hat, "y_hat"), check_image(y.detach(), "y")
     if y_hat.shape != y.shape:
         raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ")
-    loss, sim, stats = _IdLoss.apply(y_hat, y, prepare(weights), resampler(y.shape[2], y.shape[3], y.device), bool(multiscale))
+    loss, sim, stats = _IdLoss.apply(y_hat, y, netweights.prepare(PreparedIdNet, *W), resampler(y.shape[2], y.shape[3], y.device), bool(multiscale))
     return loss, sim, (1.0 - stats[..., 2]).mean(1)
 
 
@@ -419,24 +409,27 @@ def id_loss(y_hat: torch.Tensor, y: torch.Tensor, weights, multiscale: bool = Tr
     return id_loss_terms(y_hat, y, weights, multiscale)[0]
 
 
-def features_112(x: torch.Tensor, weights, multiscale: bool = True):
-    """Backbone.forward(x, multi_scale): the l2-normalised features of a 112 x 112 input (no gradient)."""
-    check_loaded(weights)
+def _features_112(x, W, multiscale):
     x = check_image(x, "x")
     if x.shape[2:] != (SIDE, SIDE):
         raise ValueError(f"x: the network takes 112 x 112 inputs, got {tuple(x.shape[2:])}")
     with torch.no_grad():
-        taps, _ = _features(x, prepare(weights), multiscale, save=False)
+        taps, _ = _features(x, netweights.prepare(PreparedIdNet, *W), multiscale, save=False)
     return [t / t.norm(dim=1, keepdim=True) for t in taps]
+
+
+def features_112(x: torch.Tensor, weights, multiscale: bool = True):
+    """Backbone.forward(x, multi_scale): the l2-normalised features of a 112 x 112 input (no gradient)."""
+    return _features_112(x, _checked("features_112", weights), multiscale)
 
 
 def id_features(x: torch.Tensor, weights, multiscale: bool = True):
     """IDLoss.extract_feats(x): the l2-normalised features of an image batch after the pool -> crop -> pool pre-processing (no gradient)."""
-    check_loaded(weights)
+    W = _checked("id_features", weights)
     x = check_image(x, "x")
     with torch.no_grad():
         x112 = resampler(x.shape[2], x.shape[3], x.device).apply(x)
-    return features_112(x112, weights, multiscale)
+    return _features_112(x112, W, multiscale)
 
 
 __all__ = ["IdNet", "PreparedIdNet", "check_loaded", "weights_key", "weight_tensors", "prepare", "state_dict_keys", "state_dict_shapes", "axis_matrix", "resampler",

@@ -11,7 +11,8 @@ optimization.py:111-146).
 Weights are a ``state_dict``-shaped mapping or a module with the reference's layout: ``net.mean``, ``net.std``,
 ``net.layers.{0,3,6,8,10}.{weight,bias}``, ``lin.{0..4}.1.weight``.  They are frozen: no weight gradient is computed.
 Every launch goes on the current stream with no host synchronisation, so the term can be captured in a hipGraph (``pti.GraphedPTIStep``).
-The weight cache, the split-bf16 weight preparation and convolution wrapper and the multi-target helpers are ``lossnet``'s.
+Validation of the weights (keys, shapes, dtypes: once per public call) and the cache of their prepared copies are ``netweights``', as for every
+network of the package; the split-bf16 weight preparation and convolution wrapper and the multi-target helpers are ``lossnet``'s.
 """
 from __future__ import annotations
 
@@ -19,10 +20,11 @@ from typing import Optional
 
 import torch
 
-from . import lossnet
+from . import lossnet, netweights
 from ._lib import lib
-from .lossnet import call_args, check_frame, check_image, check_targets, conv_sb, relu_mask, sum_partials, target_rows, weights_key
-from .ops import _Prepared, _c, _p, _stream
+from .lossnet import call_args, check_frame, check_image, check_targets, conv_sb, relu_mask, sum_partials, target_rows
+from .netweights import PreparedNet, _Net, _validated, weights_key
+from .ops import _c, _p, _stream
 
 LAYERS = (0, 3, 6, 8, 10)                 # AlexNet ``features`` indices of the five convolutions
 CHANNELS = (64, 192, 384, 256, 256)
@@ -36,77 +38,85 @@ def state_dict_keys():
     return ["net.mean", "net.std"] + [f"net.layers.{i}.{n}" for i in LAYERS for n in ("weight", "bias")] + [f"lin.{i}.1.weight" for i in range(5)]
 
 
+def state_dict_shapes(full: bool = True):
+    """``{key: shape}`` of the drop-in ``LPIPS`` module's ``state_dict`` or, with ``full`` False, of its ``net`` alone (a ``BaseNet``: the 12 network
+    tensors under their bare names, no ``lin``)."""
+    p = "net." if full else ""
+    out = {p + "mean": (1, 3, 1, 1), p + "std": (1, 3, 1, 1)}
+    for i, (layer, c, k) in enumerate(zip(LAYERS, CHANNELS, KERNELS)):
+        out[f"{p}layers.{layer}.weight"], out[f"{p}layers.{layer}.bias"] = (c, 3 if i == 0 else CHANNELS[i - 1], k, k), (c,)
+    if full:
+        out.update({f"lin.{i}.1.weight": (1, c, 1, 1) for i, c in enumerate(CHANNELS)})
+    return out
+
+
+def _full(name, sd):
+    """True for the keys of an ``LPIPS``, False for those of its ``net`` alone (without either, ``mean`` is reported as missing)."""
+    return "net.mean" in sd
+
+
+_LPIPS_NET = _Net("LPIPS", state_dict_shapes, (), False, ("net.mean", "mean"), _full, None, ())
+
+
 def check_loaded(weights):
     """``weights`` itself; raises if it is a module that has never had its weights loaded (the drop-in ``LPIPS`` / ``BaseNet`` start
     without weights and never download: a loss from their initial parameters would be a silently wrong objective)."""
-    if isinstance(weights, torch.nn.Module) and getattr(weights, "_loaded", True) is False:
-        raise RuntimeError(f"{type(weights).__name__}: weights were never loaded (nothing is downloaded here); call load_state_dict first")
+    netweights.check_loaded(None, weights, "weights")
     return weights
 
 
-def _tensors(weights):
-    """(the 12 network tensors, the 5 lin weights) of ``weights``: an ``LPIPS`` module, its ``net`` (then no lin weights) or a mapping."""
-    check_loaded(weights)
-    if isinstance(weights, torch.nn.Module):
-        weights = weights.state_dict()
-    keys = state_dict_keys()
-    if "net.mean" not in weights and "mean" in weights:                  # a BaseNet's own state_dict
-        weights = {"net." + k: v for k, v in weights.items()}
-        keys = keys[:12]
-    try:
-        ts = [weights[k] for k in keys]
-    except KeyError as e:
-        raise KeyError(f"LPIPS weights lack {e}: expected the keys {state_dict_keys()}") from None
-    return ts[:12], ts[12:]
+def _checked(name, weights):
+    """What ``_validated`` returns of ``weights``: what a public call makes once, before it looks at its images, and hands to ``netweights.prepare``
+    and ``lin_weights``.  Refused in this order: weights never loaded, a missing key, a wrong shape or dtype."""
+    netweights.check_loaded(name, weights, "weights")
+    return _validated(name, weights, _LPIPS_NET)
 
 
-def weight_tensors(weights):
-    """The network and lin tensors of ``weights`` (see ``weights_key``)."""
-    net, lin = _tensors(weights)
-    return net + lin
+def weight_tensors(weights, name: str = "lpips"):
+    """The network and lin tensors of ``weights``, their shapes checked (see ``weights_key``)."""
+    return _checked(name, weights)[2]
 
 
-class PreparedLpips(_Prepared):
+class PreparedLpips(PreparedNet):
     """The kernels' copies of the LPIPS weights, rebuilt when a tensor changes version or storage: conv1's weight with the output channel
-    innermost, three-way split slabs of conv2..5 (forward) and two-way split slabs of their flipped, transposed weights (data gradient)."""
+    innermost, three-way split slabs of conv2..5 (forward) and two-way split slabs of their flipped, transposed weights (data gradient).
+    Keyed on every tensor ``weights`` has, the five ``lin`` weights of a full ``LPIPS`` included although no copy of them is kept: the weights
+    are frozen, so the wider key costs no rebuild."""
 
     __slots__ = ()
+    _entry, _net = "lpips", _LPIPS_NET
 
-    def get(self, weights):
-        ts = _tensors(weights)[0]
-        key = weights_key(ts) + (ts[0].device,)
-        hit = self._lookup(key)
-        if hit is not None:
-            return hit
-        ts = [_c(t.detach(), k) for t, k in zip(ts, state_dict_keys())]
-        mean, std = ts[0].reshape(3).contiguous(), ts[1].reshape(3).contiguous()
-        ws, bs = ts[2:12:2], ts[3:12:2]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            cin = 3 if i == 0 else CHANNELS[i - 1]
-            if tuple(w.shape) != (CHANNELS[i], cin, KERNELS[i], KERNELS[i]) or tuple(b.shape) != (CHANNELS[i],):
-                raise ValueError(f"net.layers.{LAYERS[i]}: weight {tuple(w.shape)} / bias {tuple(b.shape)} is not AlexNet's")
+    def _build(self, sd, full, dev):
+        p = "net." if full else ""
+        mean, std = sd[p + "mean"].reshape(3).contiguous(), sd[p + "std"].reshape(3).contiguous()
+        ws, bs = [sd[f"{p}layers.{i}.weight"] for i in LAYERS], [sd[f"{p}layers.{i}.bias"] for i in LAYERS]
         w1t = ws[0].permute(1, 2, 3, 0).contiguous()                   # [3][11][11][64]
         fwd, bwd = [], []
         for w in ws[1:]:
             fwd.append(lossnet.prep_fwd(w)[0])
             bwd.append(lossnet.prep_dgrad(w))                  # the data gradient is a convolution with the flipped, transposed weights
-        payload = (mean, std, w1t, tuple(bs), tuple(fwd), tuple(bwd))
-        return self._publish(key, payload)
+        return mean, std, w1t, tuple(bs), tuple(fwd), tuple(bwd)
 
 
 def prepare(weights):
     """Prepared copies for ``weights`` (cached on a module; a plain mapping is prepared on every call)."""
-    return lossnet.prepare(PreparedLpips, weights)
+    return netweights.prepare(PreparedLpips, weights, _checked("lpips", weights))
 
 
-def lin_weights(weights):
-    """The five ``lin`` weights of ``weights`` as flat fp32 vectors (views)."""
-    out = []
-    for i, t in enumerate(_tensors(weights)[1]):
-        if tuple(t.shape) != (1, CHANNELS[i], 1, 1):
-            raise ValueError(f"lin.{i}.1.weight: {tuple(t.shape)}, expected (1, {CHANNELS[i]}, 1, 1)")
-        out.append(_c(t.detach(), f"lin.{i}.1.weight").reshape(-1))
-    return out
+def lin_weights(weights, checked=None, name: str = "lpips"):
+    """The five ``lin`` weights of ``weights`` as flat fp32 vectors (views); ``checked``: what the caller's own validation of ``weights`` returned.
+    Weights without them (a ``BaseNet``'s) are refused."""
+    sd, full, _ = checked if checked is not None else _checked(name, weights)
+    if not full:
+        raise KeyError(f"{name}: the weights lack 'lin.0.1.weight': the loss needs the keys of LPIPS (ops_lpips.state_dict_shapes()), a BaseNet's give the "
+                       "features alone")
+    return [_c(sd[f"lin.{i}.1.weight"].detach(), f"lin.{i}.1.weight").reshape(-1) for i in range(5)]
+
+
+def _checked_with_lins(name, weights):
+    """(``_checked``'s triple, the lin weights): the weights of a call that computes the loss, refused before its images are looked at."""
+    checked = _checked(name, weights)
+    return checked, lin_weights(weights, checked, name)
 
 
 def _conv_out(side: int, i: int) -> int:
@@ -241,12 +251,12 @@ class _LpipsScaleMulti(torch.autograd.Function):
 def target_features(images: torch.Tensor, weights, scales: int = 3):
     """The raw AlexNet taps of ``images`` ``[n, 3, H, W]`` at the ``scales`` box-mean factors 1, 2, 4 — what ``lpips_multiscale_multi`` reads for a target:
     a flat list, scale-major (five taps per scale), of tensors ``[n, C, h, w]``.  Computed a frame at a time; no gradient."""
-    check_loaded(weights)
+    checked = _checked("ops_lpips.target_features", weights)
     if not 1 <= scales <= 3:
         raise ValueError(f"scales must be 1, 2 or 3, got {scales}")
     for i in range(scales):
         _check(images, "images", 1 << i)
-    P = prepare(weights)
+    P = netweights.prepare(PreparedLpips, weights, checked)
     with torch.no_grad():
         return target_rows(lambda x: [t for i in range(scales) for t in _features(x.contiguous(), P, 1 << i)], images.detach())
 
@@ -254,7 +264,7 @@ def target_features(images: torch.Tensor, weights, scales: int = 3):
 def lpips_multiscale_multi(x: torch.Tensor, targets, tw, weights, frame: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sum_j tw[j] * lpips_multiscale(x, y_j)`` (0-d, differentiable in ``x`` only) with one AlexNet forward pass and input gradient of ``x``:
     ``targets[j] = target_features(y_j, weights)`` (``bs`` rows, or frames x ``bs`` rows with ``frame``, a device int32 frame index)."""
-    check_loaded(weights)
+    checked, lins = _checked_with_lins("lpips_multiscale_multi", weights)
     x = _check(x, "x", 1)
     scales = len(targets[0]) // 5 if targets else 0
     if not 1 <= scales <= 3 or any(len(t) != 5 * scales for t in targets):
@@ -262,7 +272,7 @@ def lpips_multiscale_multi(x: torch.Tensor, targets, tw, weights, frame: Optiona
     for i in range(scales):
         _check(x, "x", 1 << i)
     frame = check_frame(frame, x.device)
-    P, lins = prepare(weights), lin_weights(weights)
+    P = netweights.prepare(PreparedLpips, weights, checked)
     loss = None
     for i in range(scales):
         f = 1 << i
@@ -283,10 +293,10 @@ def _tap_shapes(h: int, w: int):
 
 def features(x: torch.Tensor, weights, factor: int = 1):
     """The five normalised AlexNet taps of ``x`` (``BaseNet.forward``; no gradient).  ``weights``: a ``BaseNet`` / ``LPIPS`` module or mapping."""
-    check_loaded(weights)
+    checked = _checked("ops_lpips.features", weights)
     x = _check(x, "x", factor)
     with torch.no_grad():
-        taps = _features(x, prepare(weights), factor)
+        taps = _features(x, netweights.prepare(PreparedLpips, weights, checked), factor)
     return [t / (torch.sqrt((t * t).sum(1, keepdim=True) + 1e-16) + 1e-10) for t in taps]
 
 
@@ -300,33 +310,38 @@ def _check(x: torch.Tensor, name: str, factor: int) -> torch.Tensor:
     return x
 
 
-def lpips(x: torch.Tensor, y: torch.Tensor, weights, factor: int = 1) -> torch.Tensor:
-    """``LPIPS(boxmean_f(x), boxmean_f(y))`` (a 0-d tensor): ``x``, ``y`` fp32 ``[bs, 3, H, W]`` on the device, the sides divisible by ``factor``
-    (1, 2 or 4: the exact f x f box mean is ``adaptive_avg_pool2d`` to ``H / f``).  Differentiable in ``x`` and ``y``."""
-    check_loaded(weights)
+def _lpips(x, y, weights, checked, lins, factor):
+    """``lpips`` on weights its caller has validated."""
     if factor not in (1, 2, 4):
         raise ValueError(f"factor must be 1, 2 or 4, got {factor}")
     x, y = _check(x, "x", factor), _check(y, "y", factor)
     if x.shape != y.shape:
         raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} differ")
-    return _LpipsScale.apply(x, y, prepare(weights), lin_weights(weights), factor)
+    return _LpipsScale.apply(x, y, netweights.prepare(PreparedLpips, weights, checked), lins, factor)
+
+
+def lpips(x: torch.Tensor, y: torch.Tensor, weights, factor: int = 1) -> torch.Tensor:
+    """``LPIPS(boxmean_f(x), boxmean_f(y))`` (a 0-d tensor): ``x``, ``y`` fp32 ``[bs, 3, H, W]`` on the device, the sides divisible by ``factor``
+    (1, 2 or 4: the exact f x f box mean is ``adaptive_avg_pool2d`` to ``H / f``).  Differentiable in ``x`` and ``y``."""
+    return _lpips(x, y, weights, *_checked_with_lins("lpips", weights), factor)
 
 
 def lpips_multiscale(x: torch.Tensor, y: torch.Tensor, weights, scales: int = 3, foreground_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sum_{i < scales} LPIPS(boxmean_{2^i}(x), boxmean_{2^i}(y))`` — the perceptual term of calc_loss (video_swap_ft_coach.py:201-211 at
     1024 x 1024: ``adaptive_avg_pool2d(., 1024 // 2**i)``).  ``foreground_mask`` (broadcast over channels): both images are multiplied by it
     first, as the video coach does (:188-190)."""
-    check_loaded(weights)
+    checked, lins = _checked_with_lins("lpips_multiscale", weights)
     if not 1 <= scales <= 3:
         raise ValueError(f"scales must be 1, 2 or 3, got {scales}")
     if foreground_mask is not None:
         x, y = x * foreground_mask, y * foreground_mask
     loss = None
     for i in range(scales):
-        t = lpips(x, y, weights, 1 << i)
+        t = _lpips(x, y, weights, checked, lins, 1 << i)
         loss = t if loss is None else loss + t
     return loss
 
 
-__all__ = ["PreparedLpips", "check_loaded", "weights_key", "weight_tensors", "prepare", "lin_weights", "features", "lpips", "lpips_multiscale", "state_dict_keys", "LAYERS", "CHANNELS",
+__all__ = ["PreparedLpips", "check_loaded", "weights_key", "weight_tensors", "prepare", "lin_weights", "features", "lpips", "lpips_multiscale", "state_dict_keys",
+           "state_dict_shapes", "LAYERS", "CHANNELS",
            "target_features", "lpips_multiscale_multi"]

@@ -26,11 +26,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet
 from ._lib import lib
 from .lossnet import bn_fold, conv_sb, prep_fwd
 from .ops import _p, _stream
-from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _keys_shapes, _placed_checked, _validated, bn_shapes, check_loaded, module_net
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _keys_shapes, _placed_checked, _validated, bn_shapes, check_loaded, module_net, prepare
 
 SLOPE = 0.2                                  # ReluLayer's LeakyReLU (blocks.py:58)
 # FaceParse.MASK_COLORMAP (face_parsing.py:30): background, hat (14) and cloth (18) are 0, every other class 255
@@ -347,7 +346,7 @@ def parsenet_forward(x: torch.Tensor, weights, with_image: bool = False):
     if x.shape[0] == 0:
         return x.new_empty((0, checked[1][3], oh, ow)), (x.new_empty((0, 3, oh, ow)) if with_image else None)
     with torch.no_grad():
-        return _run(lossnet.prepare(PreparedParseNet, weights, checked), x.detach().contiguous(), None, False, with_image)
+        return _run(prepare(PreparedParseNet, weights, checked), x.detach().contiguous(), None, False, with_image)
 
 
 def _mask_of(P, logits):
@@ -367,7 +366,7 @@ def parsenet_mask(img_u8: torch.Tensor, weights, bgr: bool = True) -> torch.Tens
     if img_u8.shape[0] == 0:
         return torch.empty((0, oh, ow), dtype=torch.uint8, device=img_u8.device)
     with torch.no_grad():
-        P = lossnet.prepare(PreparedParseNet, weights, checked)
+        P = prepare(PreparedParseNet, weights, checked)
         return _mask_of(P, _run(P, None, img_u8.contiguous(), bool(bgr), False)[0])
 
 
@@ -379,7 +378,7 @@ def parsenet_mask_from_tensor(imt: torch.Tensor, weights) -> torch.Tensor:
     if imt.shape[0] == 0:
         return torch.empty((1, 0, oh, ow), dtype=torch.int64, device=imt.device)
     with torch.no_grad():
-        P = lossnet.prepare(PreparedParseNet, weights, checked)
+        P = prepare(PreparedParseNet, weights, checked)
         x = (imt.detach().flip(1) * 2 - 1).contiguous()
         return _mask_of(P, _run(P, x, None, False, False)[0]).to(torch.int64).unsqueeze(0)
 

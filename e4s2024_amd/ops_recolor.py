@@ -1,6 +1,6 @@
 """Rows f8 to f11: Blender recolouring (``ct_mode='blender'``), four stages: f8 the semantic colour reference, f9 the Res-U-Net that consumes its packages,
 f10 the SPADE feature network that feeds it, f11 the Real-ESRGAN step behind them.  The three networks share one weights path (``netweights._validated``:
-keys, shapes and dtypes checked once per public call and handed on to ``lossnet.prepare``) and one convolution call (``lossnet.conv_sb``).
+keys, shapes and dtypes checked once per public call and handed on to ``netweights.prepare``) and one convolution call (``lossnet.conv_sb``).
 
 Row f8, stage 1 — the semantic colour reference on the device (``csrc/colorref.hip``).
 
@@ -31,7 +31,7 @@ Row f9, stage 2 — the network that consumes the packages, ``ResUNet`` (swap_fa
     head               sigmoid(W x + b)                           e4s_resunet_head (full-precision exponential)
 
 BatchNorm runs on its running statistics; a module in training mode is refused.  Prepared weights are cached per module and parameter version
-(``lossnet.prepare`` / ``weights_key``); the width (64, or 16 for the reference's ``small_FPN``) is read off the weights.
+(``netweights.prepare`` / ``weights_key``); the width (64, or 16 for the reference's ``small_FPN``) is read off the weights.
 
 Row f10, stage 3 — the feature network that produces ``feats_a`` / ``feats_t``, ``AdaptiveFeatureGenerator`` (swap_face_fine/Blender/model_center/backbone.py)
 at the reference's default arguments, or ``SmallFPN``; eval mode, forward only (``blender_fpn``, ``blender_features``, ``blender_forward``).  Its 19
@@ -60,10 +60,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet, ops_rrdb
+from . import ops_rrdb
 from ._lib import lib
 from .lossnet import bn_fold, conv_sb, fold_conv_bn, prep_fwd
-from .netweights import PreparedNet, _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated
+from .netweights import PreparedNet, _Net, _cuda_checked, _devices_checked, _keys_shapes, _tensor_checked, _validated, prepare
 from .ops import _p, _stream
 from .ops_post import GREY_MORPH_MAX_RADIUS, grey_dilate
 from .ops_rrdb import GpenSRNet
@@ -410,7 +410,7 @@ def _unet(name, packages, weights, checked=None):
     if bs == 0:
         return torch.empty((0, 3, H, W), dtype=torch.float32, device=packages.device)
     with torch.no_grad():
-        return _unet_forward(lossnet.prepare(PreparedResUNet, weights, checked), packages.detach().contiguous())
+        return _unet_forward(prepare(PreparedResUNet, weights, checked), packages.detach().contiguous())
 
 
 def blender_unet(packages: torch.Tensor, weights) -> torch.Tensor:
@@ -682,7 +682,7 @@ def _features_run(img_a, img_t, weights, checked, flip_target):
 
     def prepared():
         if not P:
-            P.append(lossnet.prepare(PreparedFPN, weights, checked))
+            P.append(prepare(PreparedFPN, weights, checked))
         return P[0]
 
     feats_a = _fpn_run(img_a, prepared)
@@ -697,7 +697,7 @@ def blender_fpn(img: torch.Tensor, weights) -> torch.Tensor:
     are cached per parameter version; a mapping is prepared on every call.  Forward only, no gradient.  Every argument is checked before any launch; no
     host synchronisation, the same inputs give the same bits, and after one eager call (which prepares the weights) the call captures in a graph."""
     checked = _fpn_checked_all("blender_fpn", weights, img=img)
-    return _fpn_run(img, lambda: lossnet.prepare(PreparedFPN, weights, checked))
+    return _fpn_run(img, lambda: prepare(PreparedFPN, weights, checked))
 
 
 def flip_choice(flip_target=None) -> bool:
@@ -826,7 +826,7 @@ def realesr_forward(x: torch.Tensor, weights) -> torch.Tensor:
     if bs == 0:
         return torch.empty((0, 3, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
     with torch.no_grad():
-        return _rrdb_run(x.detach().contiguous(), lossnet.prepare(PreparedRRDBNet, weights, checked), True, False)[0]
+        return _rrdb_run(x.detach().contiguous(), prepare(PreparedRRDBNet, weights, checked), True, False)[0]
 
 
 def realesr_input(img_u8: torch.Tensor, out_hw, name: str = "realesr_input") -> torch.Tensor:
@@ -858,7 +858,7 @@ def realesr_image(img_u8: torch.Tensor, weights, in_size: int = 256) -> torch.Te
         x = realesr_input(img_u8, (in_size, in_size), name)
         if x.shape[0] == 0:
             return torch.empty((0, 4 * in_size, 4 * in_size, 3), dtype=torch.uint8, device=x.device)
-        return _rrdb_run(x, lossnet.prepare(PreparedRRDBNet, weights, checked), False, True)[1]
+        return _rrdb_run(x, prepare(PreparedRRDBNet, weights, checked), False, True)[1]
 
 
 __all__ = ["BLENDER_PARTS", "BLENDER_PART_IDS", "COLORREF_CHANNELS", "COLORREF_MAX_PIXELS", "blender_part_masks", "color_reference", "blender_packages",

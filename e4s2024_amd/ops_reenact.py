@@ -32,7 +32,7 @@ from . import lossnet
 from ._lib import lib
 from .lossnet import conv_exact, conv_sb, fold_conv_bn, prep_exact, prep_fwd
 from .ops import _c, _p, _req, _stream
-from .netweights import EVAL_ONLY, PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, bn_shapes, check_loaded, module_net
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, bn_shapes, check_loaded, module_net, prepare
 
 NUM_BINS = 66                                # headpose_pred_to_degree's idx_tensor is range(66) whatever the module's num_bins
 
@@ -591,7 +591,7 @@ def kp_detector_forward(x: torch.Tensor, weights, temperature=None, want_heatmap
             out["jacobian"] = x.new_empty((0, K, 3, 3))
         return out
     with torch.no_grad():
-        P = lossnet.prepare(PreparedKPDetector, weights, checked)
+        P = prepare(PreparedKPDetector, weights, checked)
         cur = x.detach().contiguous()
         if P["taps"] is not None:
             cur = antialias_down(cur, P["taps"], structure[7])
@@ -625,7 +625,7 @@ def he_estimator_forward(x: torch.Tensor, weights):
     y = torch.empty((bs, n), dtype=torch.float32, device=x.device)
     if bs:
         with torch.no_grad():
-            P = lossnet.prepare(PreparedHEEstimator, weights, checked)
+            P = prepare(PreparedHEEstimator, weights, checked)
             cur = _conv_any(x.detach().contiguous(), P["stem"], 7, stride=2, relu=True)
             pooled = torch.empty((bs, cur.shape[1], (cur.shape[2] - 1) // 2 + 1, (cur.shape[3] - 1) // 2 + 1), dtype=torch.float32, device=x.device)
             lib().call("e4s_maxpool3x3s2", _p(pooled), _p(cur), bs * cur.shape[1], cur.shape[2], cur.shape[3], _stream())
@@ -1133,7 +1133,7 @@ def dense_motion_forward(feature, kp_driving, kp_source, weights):
             out["occlusion_map"] = new(0, 1, H, W)
         return out
     with torch.no_grad():
-        P = lossnet.prepare(PreparedDenseMotion, weights, checked)
+        P = prepare(PreparedDenseMotion, weights, checked)
         x = feature.detach().contiguous()
         comp = _conv_any(x.view(bs, C, D * H, W), P["compress"], 1, relu=True).view(bs, c, D, H, W)
         # bufs[j]: torch.cat([up_blocks[j](out), skip], dim=1) at level nb - 1 - j, formed in place
@@ -1649,7 +1649,7 @@ def appearance_feature(source, weights):
     if bs == 0:
         return source.new_empty((0, rc, depth, h, w))
     with torch.no_grad():
-        P = lossnet.prepare(PreparedGeneratorFront, weights, checked)
+        P = prepare(PreparedGeneratorFront, weights, checked)
         cur = _conv_any(source.detach().contiguous(), P["first"], k, relu=True)
         for L in P["down"]:
             cur = avgpool2x2(_conv_any(cur, L, 3, relu=True))
@@ -1690,7 +1690,7 @@ def generator_warp(feature_3d, kp_driving, kp_source, weights):
         out["feature"] = new(0, outf, h, w)
         return out
     with torch.no_grad():
-        P = lossnet.prepare(PreparedGeneratorFront, weights, checked)
+        P = prepare(PreparedGeneratorFront, weights, checked)
         feature_3d = feature_3d.detach()
         # dense_motion_forward takes a dense batch: the shared volume is copied n times here (8 MB per frame at the upstream size), the gather reads it in place
         # a mapping goes on as the validated bare keys (a `generator.` prefix or the file's nesting is gone): its dense_motion_network. keys are what

@@ -26,10 +26,9 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import lossnet
 from ._lib import lib
 from .lossnet import conv_sb, prep_fwd
-from .netweights import PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, check_loaded
+from .netweights import PreparedNet, _Net, _cuda_checked, _placed_checked, _tensor_checked, _validated, check_loaded, prepare, weights_key
 from .ops import _p, _stream
 from .ops_recolor import _plane_stats, _sigma_folded
 from .ops_reenact import (_generator_checked, _keypoints_checked, appearance_feature, generator_warp, he_estimator_forward, keypoint_transformation,
@@ -51,19 +50,8 @@ _LEVELS = (tuple(n for p, fin, fout, _ in _BLOCKS[:6] for n in _block_norms(p, f
 
 
 # ------------------------------------------------------------------------------------------------ weights
-def _decoder_variant(name, sd):
-    if "fc.weight" not in sd:
-        raise KeyError(f"{name}: the weights lack 'fc.weight': expected the keys of SPADEDecoder (ops.spade_decoder_state_dict_shapes()), bare or behind "
-                       "'decoder.', 'generator.decoder.' or 'module.'")
-    return ()
-
-
-def _decoder_shapes(variant=()):
-    return spade_decoder_state_dict_shapes()
-
-
-_DEC_NET = _Net("SPADEDecoder", _decoder_shapes, ("generator.decoder.", "module.generator.decoder.", "module.decoder.", "decoder.", "module."), False,
-                ("fc.weight",), _decoder_variant, None, ())
+_DEC_NET = _Net("SPADEDecoder", spade_decoder_state_dict_shapes, ("generator.decoder.", "module.generator.decoder.", "module.decoder.", "decoder.", "module."),
+                False, ("fc.weight",), None, None, ())
 
 
 def _decoder_checked(name, weights):
@@ -257,7 +245,7 @@ def _decoder_checked_run(name, feature, weights, checked):
     if n == 0:
         return feature.new_empty((0, 3, 4 * h, 4 * w))
     with torch.no_grad():
-        P = lossnet.prepare(PreparedSPADEDecoder, weights, checked)
+        P = prepare(PreparedSPADEDecoder, weights, checked)
         return _decoder_run(P, feature.detach().contiguous())
 
 
@@ -279,7 +267,7 @@ def _frames_checked(name, weights):
     the front's tensors are keyed on: storage and version of each)."""
     dec_weights, dec_checked = _decoder_checked(name, weights)
     front, front_checked, _ = _generator_checked(name, weights)
-    return front, dec_weights, dec_checked, lossnet.weights_key(front_checked[2])
+    return front, dec_weights, dec_checked, weights_key(front_checked[2])
 
 
 def _frames(name, feature_3d, kp_driving, kp_source, front, dec_weights, dec_checked):

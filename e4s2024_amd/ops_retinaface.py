@@ -24,11 +24,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lossnet
 from ._lib import lib
 from .lossnet import bn_fold, conv_exact, conv_sb, prep_exact, prep_fwd
 from .ops import _p, _stream
-from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _placed_checked, _validated, bn_shapes, check_loaded
+from .netweights import EVAL_ONLY, PreparedNet, _Net, _image_checked, _placed_checked, _validated, bn_shapes, check_loaded, prepare
 
 ARITH = "sb3"                                # "sb3": e4s_conv2d_sb3 (fp32-class); "sb": e4s_conv2d_sb (two-way split bf16)
 RETINAFACE_MAX_SIDE = 1500                              # detect resizes a larger image with cv2 first (retinaface_detection.py:67-70): out of scope
@@ -404,7 +403,7 @@ def retinaface_forward(x: torch.Tensor, net):
         N = retinaface_level_sizes(H, W)[1]
         return x.new_empty((0, N, 4)), x.new_empty((0, N, 2)), x.new_empty((0, N, 10))
     with torch.no_grad():
-        P = lossnet.prepare(PreparedRetinaFace, net, checked)
+        P = prepare(PreparedRetinaFace, net, checked)
         return _decode(_heads(P, x.detach().contiguous()), H, W, True, False)[0]
 
 
@@ -421,7 +420,7 @@ def retinaface_detect_padded(img_u8: torch.Tensor, net, bgr: bool = True, confid
     if bs == 0:
         return (torch.zeros((0, keep_top_k, 5), device=dev), torch.zeros((0, keep_top_k, 10), device=dev), torch.zeros((0,), dtype=torch.int32, device=dev))
     with torch.no_grad():
-        P = lossnet.prepare(PreparedRetinaFace, net, checked)
+        P = prepare(PreparedRetinaFace, net, checked)
         x = torch.empty((bs, 3, H, W), dtype=torch.float32, device=dev)
         lib().call("e4s_retina_input", _p(x), _p(img_u8.contiguous()), 1 if bgr else 0, bs, H, W, _stream())
         score, boxes, lmk = _decode(_heads(P, x), H, W, False, True)[1]

@@ -28,7 +28,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import ops, ops_fp, ops_id, ops_lpips, ops_multi
-from .lossnet import weights_key
+from .netweights import weights_key
 
 
 def trainable_parameters(net):

@@ -99,7 +99,7 @@ def test_refuses_unloaded_and_training_mode(sd):
     net.load_state_dict(sd)
     with pytest.raises(RuntimeError, match="training mode"):
         ops_fp.check_loaded(net.train())
-    with pytest.raises(KeyError, match="face-parsing weights lack"):
+    with pytest.raises(KeyError, match=r"fp_loss: the weights lack 'center\.conv2\.1\.running_var'"):
         ops_fp.weight_tensors({k: v for k, v in sd.items() if k != "center.conv2.1.running_var"})
     from e4s2024_amd import pti
     with pytest.raises(RuntimeError, match="never loaded"):

@@ -1,5 +1,10 @@
-"""What the stage networks share on the host, without a GPU: ``netweights.module_net`` / ``check_loaded`` / ``bn_shapes`` and ``lossnet.fold_conv_bn`` /
-``prep_exact`` (plain torch).  The messages are the ones ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface`` and ``ops_reenact`` raise, written out here."""
+"""What the networks share on the host, without a GPU: ``netweights.module_net`` / ``check_loaded`` / ``bn_shapes`` and ``lossnet.fold_conv_bn`` /
+``prep_exact`` (plain torch).  The messages are the ones ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface`` and ``ops_reenact`` raise, written out here.
+Then the three frozen loss networks (``ops_lpips``, ``ops_id``, ``ops_fp``) on that path: what ``weight_tensors`` accepts, and what it refuses."""
+import importlib
+import re
+import types
+
 import pytest
 import torch
 import torch.nn as nn
@@ -108,3 +113,111 @@ def test_prep_exact_is_the_k_major_layout_bit_for_bit(shape, scaled):
     assert wt[cin - 1, k * k - 1, 1] == folded[1, cin - 1, k - 1, k - 1]
     assert bias.dtype == torch.float32 and torch.equal(bias, shift.float())
     assert lossnet.prep_exact(w, scale)[1] is None
+
+
+# ------------------------------------------------------------------------------------------------ the loss networks on the same path
+class _Case:
+    """One loss network: its ops module, seeded weights under bare keys, the prefix a checkpoint of the drop-in wrapper carries, the wrapper around a
+    loaded module, the float keys ``weight_tensors`` returns in order, and one of them that is not the probe key."""
+
+    def __init__(self, which):
+        from conftest import install_dropin
+        from e4s2024_amd import ops_fp, ops_id, ops_lpips, seeded
+        install_dropin()
+        self.which = which
+        if which == "id":
+            from criteria.id_loss import IDLoss
+            self.ops, self.sd, self.prefix, self.victim = ops_id, seeded.seeded_irse50_state_dict(3), "facenet.", "body.5.res_layer.4.running_var"
+            self.keys = [k for k in ops_id.state_dict_keys() if not k.endswith("num_batches_tracked")]
+            self.wrapper = self._loaded_from_file(IDLoss, types.SimpleNamespace(ir_se50_path="-", id_loss_multiscale=True))
+        elif which == "fp":
+            from criteria.face_parsing.face_parsing_loss import FaceParsingLoss
+            self.ops, self.sd, self.prefix, self.victim = ops_fp, seeded.seeded_unet_state_dict(3), "G.", "center.conv2.1.running_var"
+            self.keys = [k for k in ops_fp.encoder_keys() if not k.endswith("num_batches_tracked")]
+            self.wrapper = self._loaded_from_file(FaceParsingLoss, types.SimpleNamespace(face_parsing_model_path="-"))
+        else:                                                                                  # "lpips": the full LPIPS; "lpips_net": its BaseNet alone
+            from criteria.lpips.lpips import LPIPS
+            full = seeded.seeded_lpips_state_dict(3)
+            m = LPIPS()
+            m.load_state_dict(full)
+            self.ops, self.prefix = ops_lpips, None
+            if which == "lpips":
+                self.sd, self.wrapper, self.victim = full, m, "net.layers.3.bias"
+            else:
+                self.sd, self.wrapper, self.victim = {k[len("net."):]: v for k, v in full.items() if k.startswith("net.")}, m.net, "layers.3.bias"
+            self.keys = list(self.sd)
+
+    def _loaded_from_file(self, cls, opts):
+        load, torch.load = torch.load, lambda *a, **k: self.sd                                # the drop-ins read their checkpoint in the constructor
+        try:
+            return cls(opts)
+        finally:
+            torch.load = load
+
+
+COUNTS = {"id": 397 - 54, "fp": 60, "lpips": 17, "lpips_net": 12}
+
+
+@pytest.fixture(scope="module", params=sorted(COUNTS))
+def case(request):
+    return _Case(request.param)
+
+
+def test_loss_network_weights_in_every_accepted_form_are_the_same_tensors_in_key_order(case):
+    want = [case.sd[k] for k in case.keys]
+    assert len(want) == COUNTS[case.which]
+    assert all(not k.endswith("num_batches_tracked") and v.dtype == torch.float32 for k, v in zip(case.keys, want))
+    bare = case.ops.weight_tensors(case.sd)
+    assert len(bare) == len(want) and all(a is b for a, b in zip(bare, want))
+    if case.prefix:
+        prefixed = case.ops.weight_tensors({case.prefix + k: v for k, v in case.sd.items()})
+        assert len(prefixed) == len(want) and all(a is b for a, b in zip(prefixed, want))
+    wrapped = case.ops.weight_tensors(case.wrapper)
+    assert len(wrapped) == len(want) and all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(wrapped, want))
+    if case.prefix:                                                                           # the wrapper and the network inside it: the same storage
+        inner = case.ops.weight_tensors(getattr(case.wrapper, case.prefix[:-1]))
+        assert [t.data_ptr() for t in inner] == [t.data_ptr() for t in wrapped]
+
+
+def test_face_parsing_weights_are_the_encoder_alone():
+    from e4s2024_amd import ops_fp, seeded
+    sd = seeded.seeded_unet_state_dict(3)
+    enc = {k: sd[k] for k in ops_fp.encoder_keys()}
+    assert len(enc) == 70 and list(ops_fp.encoder_shapes()) == list(enc)
+    assert all(a is b for a, b in zip(ops_fp.weight_tensors(enc), ops_fp.weight_tensors(sd)))
+    bad = dict(sd)
+    bad["up_concat4.up.weight"], bad["final.weight"] = torch.zeros(3, 5), torch.zeros(1, dtype=torch.float64)      # the decoder: not used, not checked
+    assert all(a is b for a, b in zip(ops_fp.weight_tensors(bad), ops_fp.weight_tensors(sd)))
+
+
+def test_loss_network_weights_refusals_carry_the_entry_name(case):
+    entry = "the_entry"
+    good = case.sd[case.victim]
+    with pytest.raises(KeyError) as e:
+        case.ops.weight_tensors({k: v for k, v in case.sd.items() if k != case.victim}, entry)
+    msg = e.value.args[0]
+    assert msg.startswith(entry + ": ") and f"'{case.victim}'" in msg
+    mod, fn = re.search(r"\((ops_\w+)\.(\w+)\(", msg).groups()                                # the hint names a function a reader can call
+    assert importlib.import_module("e4s2024_amd." + mod) is case.ops and callable(getattr(case.ops, fn))
+    assert case.victim in getattr(case.ops, fn)(*([case.which == "lpips"] if case.which.startswith("lpips") else []))
+    with pytest.raises(ValueError) as e:
+        case.ops.weight_tensors(dict(case.sd, **{case.victim: good.reshape(1, -1)}), entry)
+    msg = str(e.value)
+    assert msg.startswith(entry + ": ") and f"'{case.victim}'" in msg and str((1, good.numel())) in msg and str(tuple(good.shape)) in msg
+    with pytest.raises(ValueError) as e:
+        case.ops.weight_tensors(dict(case.sd, **{case.victim: good.double()}), entry)
+    assert str(e.value).startswith(entry + ": ") and f"'{case.victim}'" in str(e.value) and "float64" in str(e.value)
+    with pytest.raises(TypeError) as e:
+        case.ops.weight_tensors(7, entry)
+    assert str(e.value).startswith(entry + ": ") and "int" in str(e.value)
+
+
+def test_lpips_loss_refuses_weights_without_the_lin_layers_before_it_looks_at_the_images():
+    from e4s2024_amd import ops_lpips, seeded
+    net = {k[len("net."):]: v for k, v in seeded.seeded_lpips_state_dict(3).items() if k.startswith("net.")}
+    x = torch.zeros(1, 3, 32, 32)                                                             # on the CPU: an image check would refuse it
+    for name, call in (("lpips", lambda: ops_lpips.lpips(x, x, net)), ("lpips_multiscale", lambda: ops_lpips.lpips_multiscale(x, x, net, 1)),
+                       ("lpips_multiscale_multi", lambda: ops_lpips.lpips_multiscale_multi(x, [[x] * 5], [1.0], net))):
+        with pytest.raises(KeyError, match=name + r": the weights lack 'lin\.0\.1\.weight'"):
+            call()
+    assert len(ops_lpips.weight_tensors(net)) == 12                                           # the features alone take them

@@ -200,19 +200,19 @@ def test_dropin_looks_for_the_checkpoint_where_the_reference_does(tmp_path, monk
         image_infer.RealESRBatchInfer()
 
 
-def test_invalidate_weight_caches_reaches_the_caches_of_lossnet():
-    """``lossnet.prepare`` keeps a module's prepared weights beside the module, not on it; ``invalidate_weight_caches`` empties those of every module under
+def test_invalidate_weight_caches_reaches_the_caches_of_netweights():
+    """``netweights.prepare`` keeps a module's prepared weights beside the module, not on it; ``invalidate_weight_caches`` empties those of every module under
     its argument, once each, and leaves other modules' alone."""
     import weakref
-    from e4s2024_amd import lossnet, ops
+    from e4s2024_amd import netweights, ops
     esr, other = ops.RRDBNet(1), ops.RRDBNet(1)
     holder = torch.nn.Sequential(torch.nn.Identity(), torch.nn.Sequential(esr))
-    per_module = lossnet._CACHES.setdefault(ops.PreparedRRDBNet, weakref.WeakKeyDictionary())
+    per_module = netweights._CACHES.setdefault(ops.PreparedRRDBNet, weakref.WeakKeyDictionary())
     caches = {}
     for m in (esr, other):
         caches[m] = per_module[m] = ops.PreparedRRDBNet()
         caches[m]._state = (("stale",), None, None, None, frozenset())
-    assert lossnet.caches_of(holder) == [caches[esr]] and lossnet.caches_of(torch.nn.Identity()) == []
+    assert netweights.caches_of(holder) == [caches[esr]] and netweights.caches_of(torch.nn.Identity()) == []
     assert ops.invalidate_weight_caches(holder) == 1
     assert caches[esr].key is None and caches[other].key == ("stale",)
     assert ops.invalidate_weight_caches(other) == 1 and caches[other].key is None

@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
 import gpen_model as GM
-from e4s2024_amd import lossnet, ops, ops_gpen, seeded
+from e4s2024_amd import netweights, ops, ops_gpen, seeded
 from time_resunet import alternate, graphed
 
 dev = "cuda:0"
@@ -58,7 +58,7 @@ def layer_table(net, x, rounds):
     default_width = ops_gpen.UP_COMPOSED_MAX_WIDTH
     for width, label in ((ops_gpen.UP_COMPOSED_MAX_WIDTH, "default"), (0, "up layers fused"), (4096, "up layers composed")):
         ops_gpen.UP_COMPOSED_MAX_WIDTH = width
-        P = lossnet.prepare(ops_gpen.PreparedGPEN, net, checked)
+        P = netweights.prepare(ops_gpen.PreparedGPEN, net, checked)
         S = ops_gpen._scratch(P, x.device)
         out = torch.empty((1, 3, SIZE, SIZE), device=dev)
         lat = torch.empty((1, 1, SDIM), device=dev)
