@@ -708,3 +708,23 @@ def color_transfer_blender(swapped_u8: torch.Tensor, target_u8: torch.Tensor, pa
     lt = parser.parse_batch(to01(target_u8), seg12=False)
     small = blender_infer_image(blender, swapped_u8, target_u8, la, lt, flip_target)
     return realesr_infer_image(esr, ops.pil_resize(small, (w, h)))
+
+
+@torch.no_grad()
+def codeformer_front(net, faces_u8: torch.Tensor, adain: bool = True):
+    """The tensor end in front of ``CodeFormer`` (swap_face_fine/inference_codeformer.py:160-163: ``img2tensor(img / 255., bgr2rgb=False)``, then
+    ``normalize(x, 0.5, 0.5)``) and ``ops.codeformer_front`` for a batch of uint8 ``[n, 3, 512, 512]`` RGB faces on the device: ``dict(quant_feat, logits,
+    lq_feat, idx, taps)``, the tensors stage 2's generator starts from.  Faces of another size go through ``ops.pil_resize`` to 512 x 512 first.  ``net``: an
+    ``ops.CodeFormer`` in eval mode, or a mapping with its keys."""
+    name = "codeformer_front"
+    from . import ops_codeformer
+    checked = ops_codeformer._weights_checked(name, net)
+    netweights._tensor_checked(name, "faces_u8", faces_u8, torch.uint8, 4, "uint8 [n, 3, H, W] RGB faces")
+    if faces_u8.shape[1] != 3 or faces_u8.shape[2] < 1 or faces_u8.shape[3] < 1:
+        raise ValueError(f"{name}: faces_u8: expected uint8 [n, 3, H, W] RGB faces, got {tuple(faces_u8.shape)}")
+    netweights._devices_checked(name, "faces_u8", faces_u8, checked[2])
+    netweights._cuda_checked(name, faces_u8=faces_u8)
+    if tuple(faces_u8.shape[2:]) != (512, 512):
+        faces_u8 = ops.pil_resize(faces_u8.permute(0, 2, 3, 1).contiguous(), (512, 512)).permute(0, 3, 1, 2)
+    x = ((faces_u8.float() / 255.0) - 0.5) / 0.5
+    return ops_codeformer.codeformer_front(x.contiguous(), net, adain=adain)

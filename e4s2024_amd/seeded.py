@@ -39,6 +39,7 @@ __all__ = [
     "seeded_he_estimator_state_dict",
     "seeded_dense_motion_state_dict",
     "seeded_generator_state_dict",
+    "seeded_codeformer_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -521,10 +522,47 @@ def seeded_generator_state_dict(template: Mapping[str, torch.Tensor], seed: int)
     return out
 
 
+# CodeFormer (swap_face_fine/archs/codeformer_arch.py, vqgan_arch.py): every convolution and linear fan-in scaled in front of a GroupNorm or on a pre-LayerNorm
+# residual stream, so activations stay O(1) through the encoder's 32 GroupNorms and the 9 transformer layers; norm gains around 1, biases away from zero.  ``position_emb`` is
+# large enough to matter beside norm1's unit-variance output.  The reference's own initialisation of ``idx_pred_layer.1.weight`` (0.02) and of the codebook
+# (1 / 1024) would leave every logit and every code vector near zero: the head's gain spreads a token's logits over several units, so that top-1 and top-2 lie
+# more than 64 float32 errors apart on all but a few tokens, and the codebook has unit variance, so that the AdaIN has something to normalise
+# (tests/golden/make_golden_codeformer.py asserts both conditions on the codes).
+CF_HEAD_GAIN = 4.0
+CF_CODEBOOK_STD = 1.0
+CF_POS_STD = 0.5
+
+
+def _cf_weight(gain: float):
+    def rule(seed, key, shape):
+        if len(shape) == 1:                                     # a GroupNorm / LayerNorm gain
+            return seeded_array(seed, key, shape, 1.0, 0.2)
+        return _fan_in_std(gain)(seed, key, shape)
+    return rule
+
+
+_RULES_CODEFORMER = [
+    (r"^position_emb$", (0.0, CF_POS_STD)),
+    (r"^quantize\.embedding\.weight$", (0.0, CF_CODEBOOK_STD)),
+    (r"^idx_pred_layer\.1\.weight$", _fan_in_std(CF_HEAD_GAIN)),
+    (r"in_proj_weight$", _fan_in_std(1.0)),
+    (r"bias$", (0.0, 0.1)),
+    (r"weight$", _cf_weight(1.2)),
+]
+
+
+def seeded_codeformer_state_dict(seed: int, dim_embd: int = 512, n_head: int = 8, n_layers: int = 9, codebook_size: int = 1024, latent_size: int = 256,
+                                 connect_list=("32", "64", "128", "256")) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``CodeFormer`` (``ops.CodeFormer`` and the reference's class have the same keys) at the given configuration."""
+    from .ops_codeformer import codeformer_state_dict_shapes
+    shapes = codeformer_state_dict_shapes(dim_embd, n_head, n_layers, codebook_size, latent_size, tuple(connect_list))
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "codeformer")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
              "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
-             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM, "v2v_gen": _RULES_V2V_GEN}.get(family, _RULES_BISENET)
+             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM, "v2v_gen": _RULES_V2V_GEN, "codeformer": _RULES_CODEFORMER}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

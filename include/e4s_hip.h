@@ -1074,6 +1074,43 @@ E4S_API int e4s_v2v_spade_norm(float* out_a, float* out_s, const float* x, const
                                int C, int h, int w, int up, void* stream);
 E4S_API int e4s_v2v_image_head(float* out, const float* x, const float* weight, const float* bias, int bs, int cin, int H, int W, void* stream);
 
+/* f21: CodeFormer face restoration, stage 1 — what CodeFormer.forward needs up to quant_feat between its convolutions (swap_face_fine/archs/codeformer_arch.py:
+ * 12-43, 99-134, 161-262, archs/vqgan_arch.py:14-20, 72-84, 117-273; csrc/codeformer.hip).  Every 3 x 3 and 1 x 1 convolution and every linear of the transformer
+ * runs on e4s_conv2d_sb3, conv_in (3 channels) and the logits head on the exact e4s_conv2d.  "Channel-major": a
+ * tensor [bs][C][T] with the tokens innermost, which is NCHW with T = H W.
+ *   cf_group_stats: stats [runs][3] = (mean, corr, rstd) of each of the `runs` contiguous runs of `run` floats in x: in NCHW a GroupNorm group of one sample is
+ *                   such a run of C / groups hw floats.  Two launches: part [runs][chunks][2] (scratch the caller provides) takes the mean and the sum of squares
+ *                   about that mean of each of the `chunks` equal pieces of a run (the last one shorter; two passes per piece, so a run whose mean is a hundred
+ *                   times its deviation keeps its variance); one thread per run then merges its pieces in piece order in float64: mean is the float32 rounding
+ *                   of the merged mean, corr what that rounding left, rstd = 1 / sqrt(var + eps) with the biased variance.  1 .. 64 chunks, a function of the
+ *                   shapes alone (the host layer: one per 16384 floats).
+ *   cf_group_norm : out = s sigmoid(s) (swish != 0) or s, s = ((x - mean_g) - corr_g) rstd_g gamma[c] + beta[c] for x [bs][C][hw] and stats = cf_group_stats'
+ *                   output over the bs groups runs.  The sigmoid is 1 / (1 + expf(-s)).  bs C <= 65535.
+ *   cf_attention  : out[b][h d + c][i] = sum_j softmax_j(scale q_i . k_j) v[c][j] on channel-major q, k, v, out with `heads` heads of d channels; sample b of an
+ *                   operand starts b * its batch stride (elements) behind the pointer, so q, k, v may be slices of one convolution's output.  T = 1 .. 1024, d a
+ *                   multiple of 16 up to 512.  Exact float32: the scores are fmaf chains in channel order, the row maximum is subtracted, the row sum and the
+ *                   output sums run over the keys in a fixed order.
+ *   cf_layer_norm : y[b][c][t] = (x - mean_t) rstd_t gamma[c] + beta[c] over the C <= 512 channels of a token (biased variance, eps inside the root) and, when
+ *                   pos [C][T] and y_pos are given (together), y_pos = y + pos.
+ *   cf_gelu       : out = 0.5 x (1 + erf(x / sqrt 2)) over n elements; out may be x.
+ *   cf_pad_rb     : out [planes][h + 1][w + 1] = x with one zero column on the right and one zero row below (Downsample's F.pad (0, 1, 0, 1)).
+ *   cf_argmax     : idx[b][t] (int64) = the lowest n at which logits[b b_stride + t t_stride + n n_stride] is largest, n < K.
+ *   cf_quant      : out[b][c][t] = emb[idx[b][t]][c] (idx int64 [bs][T]; emb [K][C]; an index outside 0 .. K - 1 is clamped) and, with adain != 0, adaptive_instance_normalization
+ *                   of it against style [bs][C][T]: (q - mean_q) / sqrt(var_q + eps) * sqrt(var_s + eps) + mean_s per plane, var unbiased.  T <= 1024, and
+ *                   T >= 2 with adain.
+ * fp32, no atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_cf_group_stats(float* stats, float* part, const float* x, int runs, int run, int chunks, float eps, void* stream);
+E4S_API int e4s_cf_group_norm(float* out, const float* x, const float* stats, const float* gamma, const float* beta, int bs, int C, int groups, int hw, int swish,
+                              void* stream);
+E4S_API int e4s_cf_attention(float* out, const float* q, const float* k, const float* v, int64_t q_bstride, int64_t k_bstride, int64_t v_bstride,
+                             int64_t out_bstride, int bs, int heads, int d, int T, float scale, void* stream);
+E4S_API int e4s_cf_layer_norm(float* y, float* y_pos, const float* x, const float* gamma, const float* beta, const float* pos, int bs, int C, int T, float eps,
+                              void* stream);
+E4S_API int e4s_cf_gelu(float* out, const float* x, int64_t n, void* stream);
+E4S_API int e4s_cf_pad_rb(float* out, const float* x, int planes, int h, int w, void* stream);
+E4S_API int e4s_cf_argmax(int64_t* idx, const float* logits, int bs, int T, int K, int64_t b_stride, int64_t t_stride, int64_t n_stride, void* stream);
+E4S_API int e4s_cf_quant(float* out, const void* idx, const float* emb, const float* style, int bs, int C, int T, int K, int adain, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
