@@ -1,7 +1,7 @@
 """Row f21: CodeFormer face restoration, stage 1 — everything in ``CodeFormer.forward`` (swap_face_fine/archs/codeformer_arch.py:219-262) up to ``quant_feat``,
 eval mode, forward only, float32 NCHW on the device: the VQGAN encoder with its four taps, the 9-layer transformer, the logits head, the top-1 codes, the
-codebook lookup and the AdaIN.  The VQGAN generator with its ``Fuse_sft_block``s is stage 2: ``CodeFormer`` below constructs and loads it, nothing here runs it
-natively.
+codebook lookup and the AdaIN.  The VQGAN generator with its ``Fuse_sft_block``s is stage 2 (row f22, ``ops_codeformer_gen``): ``CodeFormer`` below constructs
+and loads it, nothing in this module runs it natively.
 
     conv_in                 3 channels: the exact e4s_conv2d
     GroupNorm(32, 1e-6)     e4s_cf_group_stats over the bs 32 contiguous runs of a group (one block per 16384 floats, the pieces merged in float64), then
@@ -197,7 +197,8 @@ def _config_checked(name, dim_embd, n_head, n_layers, codebook_size, latent_size
 class CodeFormer(nn.Module):
     """``CodeFormer`` of swap_face_fine/archs/codeformer_arch.py with its constructor arguments and ``state_dict`` layout (``codeformer.pth['params_ema']`` loads
     with ``strict=True``), without basicsr.  ``front`` is the plain PyTorch composition of everything up to ``quant_feat`` — what the tests and the timing
-    compare ``codeformer_front`` with; ``forward`` goes on through the generator as the reference does (stock PyTorch: the generator half is stage 2)."""
+    compare ``codeformer_front`` with; ``forward`` goes on through the generator as the reference does, in stock PyTorch too (what the tests and the timing compare
+``ops_codeformer_gen.codeformer_restore`` with), choosing the fuse blocks by block index so that it runs at any size."""
 
     def __init__(self, dim_embd=512, n_head=8, n_layers=9, codebook_size=1024, latent_size=256, connect_list=("32", "64", "128", "256"),
                  fix_modules=("quantize", "generator"), quantizer="nearest"):
@@ -295,7 +296,8 @@ class PreparedCodeFormer(PreparedNet):
     """The kernels' copies of the front's weights, rebuilt when a tensor changes version or storage: per encoder block its convolutions as three-way split slabs
     with their biases (conv_in as the exact kernel's K-major float32 weight; q | k | v of an AttnBlock concatenated to one convolution) and its GroupNorm
     vectors; the transformer's linears as 1 x 1 slabs (the in-projection cut into q | k and v), ``pos`` = position_emb transposed to ``[E, T]``; the head's
-    LayerNorm and its exact K-major weight; the codebook.  The generator's and the fuse blocks' weights are validated and watched, not prepared."""
+    LayerNorm and its exact K-major weight; the codebook.  The generator's and the fuse blocks' weights are validated and watched, not prepared: those are
+    ``ops_codeformer_gen.PreparedCodeFormerGenerator``'s."""
 
     __slots__ = ()
     _entry = "codeformer_front"
@@ -339,15 +341,15 @@ def _new(like, *shape):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
-def _gn_run(x, gamma, beta, swish):
+def _gn_run(x, gamma, beta, swish, groups=CF_GROUPS):
     bs, C, h, w = x.shape
     hw = h * w
-    run = C // CF_GROUPS * hw
+    run = C // groups * hw
     chunks = min(64, -(-run // CF_GN_CHUNK))                                                  # from the shapes alone
-    part, stats = _new(x, bs * CF_GROUPS, chunks, 2), _new(x, bs * CF_GROUPS, 3)
-    lib().call("e4s_cf_group_stats", _p(stats), _p(part), _p(x), bs * CF_GROUPS, run, chunks, CF_GN_EPS, _stream())
+    part, stats = _new(x, bs * groups, chunks, 2), _new(x, bs * groups, 3)
+    lib().call("e4s_cf_group_stats", _p(stats), _p(part), _p(x), bs * groups, run, chunks, CF_GN_EPS, _stream())
     out = torch.empty_like(x)
-    lib().call("e4s_cf_group_norm", _p(out), _p(x), _p(stats), _p(gamma), _p(beta), bs, C, CF_GROUPS, hw, int(swish), _stream())
+    lib().call("e4s_cf_group_norm", _p(out), _p(x), _p(stats), _p(gamma), _p(beta), bs, C, groups, hw, int(swish), _stream())
     return out
 
 
@@ -593,11 +595,16 @@ def codeformer_front(x: torch.Tensor, weights, adain: bool = True):
     _image_checked(name, x, checked[1], adain)
     _placed(name, "x", x, checked)
     with torch.no_grad():
-        P = prepare(PreparedCodeFormer, weights, checked)
-        lq_feat, taps = _encode(x.detach().contiguous(), P, checked[1][5])
-        logits = _logits(lq_feat, P)
-        idx = _codes(logits)
-        return dict(quant_feat=_quant(idx, lq_feat, P["emb"], adain), logits=logits, lq_feat=lq_feat, idx=idx, taps=taps)
+        return _front_run(x, weights, checked, adain)
+
+
+def _front_run(x, weights, checked, adain):
+    """The front on checked arguments (``codeformer_front``, and ``ops_codeformer_gen.codeformer_restore`` after its own checks)."""
+    P = prepare(PreparedCodeFormer, weights, checked)
+    lq_feat, taps = _encode(x.detach().contiguous(), P, checked[1][5])
+    logits = _logits(lq_feat, P)
+    idx = _codes(logits)
+    return dict(quant_feat=_quant(idx, lq_feat, P["emb"], adain), logits=logits, lq_feat=lq_feat, idx=idx, taps=taps)
 
 
 __all__ = ["CodeFormer", "PreparedCodeFormer", "ENCODER_PLAN", "CF_TAP_BLOCKS", "adain_reference", "codeformer_state_dict_shapes", "group_norm_swish", "attention_cm",

@@ -716,15 +716,33 @@ def codeformer_front(net, faces_u8: torch.Tensor, adain: bool = True):
     ``normalize(x, 0.5, 0.5)``) and ``ops.codeformer_front`` for a batch of uint8 ``[n, 3, 512, 512]`` RGB faces on the device: ``dict(quant_feat, logits,
     lq_feat, idx, taps)``, the tensors stage 2's generator starts from.  Faces of another size go through ``ops.pil_resize`` to 512 x 512 first.  ``net``: an
     ``ops.CodeFormer`` in eval mode, or a mapping with its keys."""
-    name = "codeformer_front"
+    from . import ops_codeformer
+    return ops_codeformer.codeformer_front(_codeformer_input("codeformer_front", net, faces_u8), net, adain=adain)
+
+
+def _codeformer_input(name, net, faces_u8, max_batch=None):
+    """The tensor end in front of ``CodeFormer``, checked before its first launch: float32 ``[n, 3, 512, 512]`` in [-1, 1] of uint8 RGB faces."""
     from . import ops_codeformer
     checked = ops_codeformer._weights_checked(name, net)
     netweights._tensor_checked(name, "faces_u8", faces_u8, torch.uint8, 4, "uint8 [n, 3, H, W] RGB faces")
     if faces_u8.shape[1] != 3 or faces_u8.shape[2] < 1 or faces_u8.shape[3] < 1:
         raise ValueError(f"{name}: faces_u8: expected uint8 [n, 3, H, W] RGB faces, got {tuple(faces_u8.shape)}")
+    if max_batch is not None and faces_u8.shape[0] > max_batch:
+        raise ValueError(f"{name}: faces_u8 is {tuple(faces_u8.shape)}: at most {max_batch} faces a call")
     netweights._devices_checked(name, "faces_u8", faces_u8, checked[2])
     netweights._cuda_checked(name, faces_u8=faces_u8)
     if tuple(faces_u8.shape[2:]) != (512, 512):
         faces_u8 = ops.pil_resize(faces_u8.permute(0, 2, 3, 1).contiguous(), (512, 512)).permute(0, 3, 1, 2)
-    x = ((faces_u8.float() / 255.0) - 0.5) / 0.5
-    return ops_codeformer.codeformer_front(x.contiguous(), net, adain=adain)
+    return (((faces_u8.float() / 255.0) - 0.5) / 0.5).contiguous()
+
+
+@torch.no_grad()
+def codeformer_restore(net, faces_u8: torch.Tensor, w=0.8, adain: bool = True) -> torch.Tensor:
+    """``CodeFormerInfer.infer_image`` on the device for a batch of uint8 ``[n, 3, 512, 512]`` RGB faces: ``codeformer_front``'s tensor end,
+    ``ops.codeformer_restore`` at fusion weight ``w`` (the caller's recolor target uses 0.8), and ``tensor2img(output, min_max=(-1, 1))`` as ``ops.image_u8``:
+    uint8 ``[n, 3, 512, 512]``, RGB like the input (the reference's ``rgb2bgr`` and the caller's ``[:, :, ::-1]`` cancel)."""
+    name = "codeformer_restore"
+    from . import ops_codeformer_gen as G
+    w = G._w_checked(name, w)
+    x = _codeformer_input(name, net, faces_u8, max_batch=65535 // G._WIDEST)
+    return G.image_u8(G.codeformer_restore(x, net, w=w, adain=adain)[0])

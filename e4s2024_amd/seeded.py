@@ -527,7 +527,11 @@ def seeded_generator_state_dict(template: Mapping[str, torch.Tensor], seed: int)
 # large enough to matter beside norm1's unit-variance output.  The reference's own initialisation of ``idx_pred_layer.1.weight`` (0.02) and of the codebook
 # (1 / 1024) would leave every logit and every code vector near zero: the head's gain spreads a token's logits over several units, so that top-1 and top-2 lie
 # more than 64 float32 errors apart on all but a few tokens, and the codebook has unit variance, so that the AdaIN has something to normalise
-# (tests/golden/make_golden_codeformer.py asserts both conditions on the codes).
+# (tests/golden/make_golden_codeformer.py asserts both conditions on the codes).  A fuse block's ``scale`` is linear in the decoder stream (through
+# ``encode_enc.conv_out``), so ``dec * scale`` is quadratic in it: under the generic rules the stream's deviation went 3, 10, 109, 2e4, 8e8 through the four
+# blocks.  The last convolutions of ``scale`` and ``shift`` alone are drawn at a tenth of the generic gain: the stream then grows by at most 1.3 per block while
+# the fused term stays a quarter to four fifths of it (tests/golden/make_golden_codeformer_gen.py asserts both).  No other key's bytes change.
+CF_SFT_GAIN = 0.1
 CF_HEAD_GAIN = 4.0
 CF_CODEBOOK_STD = 1.0
 CF_POS_STD = 0.5
@@ -542,6 +546,8 @@ def _cf_weight(gain: float):
 
 
 _RULES_CODEFORMER = [
+    (r"^fuse_convs_dict\.\d+\.(scale|shift)\.2\.weight$", _fan_in_std(1.2 * CF_SFT_GAIN)),
+    (r"^fuse_convs_dict\.\d+\.(scale|shift)\.2\.bias$", (0.0, 0.1 * CF_SFT_GAIN)),
     (r"^position_emb$", (0.0, CF_POS_STD)),
     (r"^quantize\.embedding\.weight$", (0.0, CF_CODEBOOK_STD)),
     (r"^idx_pred_layer\.1\.weight$", _fan_in_std(CF_HEAD_GAIN)),

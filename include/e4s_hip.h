@@ -1111,6 +1111,19 @@ E4S_API int e4s_cf_pad_rb(float* out, const float* x, int planes, int h, int w, 
 E4S_API int e4s_cf_argmax(int64_t* idx, const float* logits, int bs, int T, int K, int64_t b_stride, int64_t t_stride, int64_t n_stride, void* stream);
 E4S_API int e4s_cf_quant(float* out, const void* idx, const float* emb, const float* style, int bs, int C, int T, int K, int adain, float eps, void* stream);
 
+/* f22: CodeFormer face restoration, stage 2 — what CodeFormer.forward needs from quant_feat to out beyond block f21 (swap_face_fine/archs/codeformer_arch.py:
+ * 136-157, 264-276, archs/vqgan_arch.py:60-70, 276-323; csrc/codeformer_gen.hip), and the caller's uint8 tail (inference_codeformer.py: tensor2img with
+ * min_max = (-1, 1)).  The generator's GroupNorms and AttnBlocks run on block f21's entry points, its Upsample on e4s_esr_up2, every convolution on
+ * e4s_conv2d_sb3 (the last one, 64 -> 3, included); a Fuse_sft_block's concatenation is the two-input form of that convolution and two GroupNorm calls with 16
+ * groups each.
+ *   cf_sft      : out = dec + w (dec scale + shift) for four contiguous [planes][hw] tensors, rounded as t = dec * scale; t = t + shift; t = w * t; out = dec + t.
+ *                 16-byte accesses when hw % 4 == 0 and all four pointers are 16-byte aligned.
+ *   cf_image_u8 : out (uint8) = rint(((min(max(x, -1), 1) - (-1)) / 2) * 255) over n elements, every step a float32 rounding, rint half to even.  16-byte reads
+ *                 and 4-byte stores when n % 4 == 0, x is 16-byte and out 4-byte aligned.
+ * fp32, no atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.  An empty tensor returns at once. */
+E4S_API int e4s_cf_sft(float* out, const float* dec, const float* scale, const float* shift, float w, int planes, int hw, void* stream);
+E4S_API int e4s_cf_image_u8(uint8_t* out, const float* x, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
