@@ -16,7 +16,8 @@
 // After that every lane holds FINISHED outputs (2 rows x 2 columns x 16 channels): demodulation, noise, bias, leaky ReLU, the next layer's
 // modulation and the bf16 hi / lo split happen in registers, the two half-waves exchange halves (v_permlane32_swap) so that each lane owns all 8
 // channels of one pixel, and the tile leaves in 16-byte stores.  The epilogue has no LDS traffic and no barrier at all.
-// MACs: 2 x (16 / 14) = 2.29x the algorithmic ones (fused kernel: 1.31x) — on a layer that was nowhere near MFMA-bound.
+// MACs: 2 x (16 / 14) = 2.29x the algorithmic ones (fused kernel: 1.31x) — on a layer that was nowhere near MFMA-bound; the persistent form below runs rows of
+// 32 positions across the whole wave and keeps 30 of them: 2 x (32 / 30) = 2.13x.
 //
 // Staging: LDS-DMA of split planes (modconv_chain.hip) issued from inline asm by all eight waves; ring = two activation chunks (16 channels each) +
 // two weight UNITS (unit = (chunk, row parity): [hi|lo][9 taps][half][32 co] = 18 KB), 76 KB per workgroup -> two workgroups per CU, so that one's
@@ -65,34 +66,56 @@ constexpr int HC_LDS = HC_BODY + HC_EP_FLOATS * 4;          // 76 800: two workg
 constexpr int HC_G = 3;                          // DMA requests per wave for one activation chunk, and for one weight unit
 static_assert(HC_LDS <= 80 * 1024, "two workgroups per CU");
 
-// v_mov_b32_dpp with a row shift: lane i of each row of 16 receives lane i -/+ 1 (0 at the row's ends)
+// v_mov_b32_dpp with a shift by one lane (0 where no lane is the source).  Row shifts stay inside a row of 16 lanes (the 16-column tile: one tile row per DPP row);
+// wave shifts run across all 64 lanes (the 32-column tile: one tile row per half-wave, so lane 32 receives lane 31's value and lane 31 lane 32's — both are
+// positions 0 / 31 of a row, whose outputs are discarded).
 template <int CTRL>
 __device__ __forceinline__ float dpp_row(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 constexpr int DPP_ROW_SHL1 = 0x101;              // lane i <- lane i + 1
 constexpr int DPP_ROW_SHR1 = 0x111;              // lane i <- lane i - 1
+constexpr int DPP_WAVE_SHL1 = 0x130;
+constexpr int DPP_WAVE_SHR1 = 0x138;
+
+// The two tile geometries.  NARROW (up_hc_kernel): 16 rows x 16 columns, a wave owns 2 rows, a lane's own fragment is patch column ptx + 1 of a 17-wide patch.
+// WIDE (up_hcp_kernel): 8 rows x 32 columns, a wave owns 1 row, patch column ptx of a 32-wide patch (the column left of position 0 would only feed the kx = 2
+// term of position 0, which is discarded: it is not loaded).
+constexpr int HP_TW = 32, HP_TH = 8;             // positions per tile: 8 rows x 32 columns (compute wave v owns row v)
+constexpr int HP_STEP = HP_TW - 2;               // 30 new positions per tile in x
+constexpr int HP_PW = HP_TW, HP_PH = HP_TH + 2;
+constexpr int HP_PATCH = HP_PW * HP_PH;          // 320 patch pixels: rows m0 - 1 .. m0 + 8, columns p0x .. p0x + 31
+template <bool WIDE> struct HcGeo;
+template <> struct HcGeo<false> {
+    static constexpr int PW = HC_PW, PATCH = HC_PATCH, XO = 1, SHR1 = DPP_ROW_SHR1, SHL1 = DPP_ROW_SHL1;
+};
+template <> struct HcGeo<true> {
+    static constexpr int PW = HP_PW, PATCH = HP_PATCH, XO = 0, SHR1 = DPP_WAVE_SHR1, SHL1 = DPP_WAVE_SHL1;
+};
 
 // One unit (16-channel chunk x row parity PAR) of the K loop: nine taps (dyi, kx) x three split-bf16 MFMAs into accs[2 PAR + (kx & 1)].  `xs` = this lane's
-// patch element (its position's row m - 1, column b - 1) in the hi plane of its K half (+ 2 * HC_PATCH = lo plane), `whalf` = its weight fragment of tap 0.
+// patch element (its position's row m - 1; column b - 1 of the 17-wide patch, column b of the 32-wide one: G::XO steps to its own column) in the hi plane of its K
+// half (+ 2 * PATCH = lo plane), `whalf` = its weight fragment of tap 0.
 // LDS traffic is what these kernels are short of (tuning build: DMA, MFMA and epilogue times ADD — the compute waves' fragment reads and the DMA writes share one
 // LDS port), so the activation fragment of input row dyi is read ONCE: taps kx = 0 and kx = 1 both multiply x[m - 1 + dyi][b], and tap kx = 2 multiplies
-// x[..][b - 1] = the LEFT neighbour lane's fragment, a DPP row shift (lane ptx = 0 receives zeros there: its kx = 2 term only enters column parity 0 of a
-// position whose outputs are discarded, and its right neighbour's filter reads its parity-1 value only) — 24 LDS reads per unit instead of 36.
-__device__ __forceinline__ uint4 dpp_row_shr1(uint4 v) {
+// x[..][b - 1] = the LEFT neighbour lane's fragment, a DPP shift (lane ptx = 0 receives zeros or another row's fragment there: its kx = 2 term only enters column
+// parity 0 of a position whose outputs are discarded, and its right neighbour's filter reads its parity-1 value only) — 24 LDS reads per unit instead of 36.
+template <int CTRL>
+__device__ __forceinline__ uint4 dpp_shr1(uint4 v) {
     uint4 r;
-    r.x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.x, DPP_ROW_SHR1, 0xf, 0xf, true);
-    r.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.y, DPP_ROW_SHR1, 0xf, 0xf, true);
-    r.z = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.z, DPP_ROW_SHR1, 0xf, 0xf, true);
-    r.w = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.w, DPP_ROW_SHR1, 0xf, 0xf, true);
+    r.x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.x, CTRL, 0xf, 0xf, true);
+    r.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.y, CTRL, 0xf, 0xf, true);
+    r.z = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.z, CTRL, 0xf, 0xf, true);
+    r.w = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.w, CTRL, 0xf, 0xf, true);
     return r;
 }
-template <int PAR>
+template <int PAR, bool WIDE>
 __device__ __forceinline__ void hc_unit(f32x16 (&accs)[4], const uint4* xs, const uint4* whalf) {
+    using G = HcGeo<WIDE>;
     uint4 bh[2], bl[2], ah[2], al[2];
     auto fetch_b = [&](int dyi, int slot) __attribute__((always_inline)) {
-        bh[slot] = xs[dyi * HC_PW + 1];
-        bl[slot] = xs[2 * HC_PATCH + dyi * HC_PW + 1];
+        bh[slot] = xs[dyi * G::PW + G::XO];
+        bl[slot] = xs[2 * G::PATCH + dyi * G::PW + G::XO];
     };
     auto fetch_a = [&](int tap, int slot) __attribute__((always_inline)) {
         ah[slot] = whalf[tap * 64];
@@ -104,7 +127,7 @@ __device__ __forceinline__ void hc_unit(f32x16 (&accs)[4], const uint4* xs, cons
     for (int dyi = 0; dyi < 3; ++dyi) {
         const int bs = dyi & 1;
         if (dyi + 1 < 3) fetch_b(dyi + 1, bs ^ 1);
-        const uint4 sh = dpp_row_shr1(bh[bs]), sl = dpp_row_shr1(bl[bs]);          // column b - 1
+        const uint4 sh = dpp_shr1<G::SHR1>(bh[bs]), sl = dpp_shr1<G::SHR1>(bl[bs]);          // column b - 1
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
             const int tap = dyi * 3 + kx, cs = tap & 1;
@@ -124,8 +147,12 @@ E4S_PROF_DECL(g_prof_hc)
 // The register epilogue shared by both kernels: horizontal four-tap filter across the lanes of a DPP row, demodulation, noise, bias, leaky ReLU, the next
 // layer's modulation, bf16 hi / lo split, half exchange, 16-byte stores.  `accs[2 a + pb]` = V[2 pm + a][2 pbx + pb] of this lane's position for the 16 channels
 // 8 g + 4 khalf + j of its registers 4 g + j; the d / bias / s_next tables of the workgroup's 32 channels sit at LDS byte `ep_off` (64 floats apart).
+// Store addresses: `row0` (the first position row of this wave) and `p0x` (position column of lane ptx = 0) are wave-uniform, so the base of every store
+// (g, row parity, plane) is scalar arithmetic and a lane adds one 32-bit byte offset.
+template <bool WIDE>
 __device__ __forceinline__ void hc_epilogue(const UpHcParams& p, const f32x16 (&accs)[4], const unsigned char* lds_raw, int ep_off, const float2 (&nz)[2], bool lane_ok,
-                                            int b, int co0, int pm, int pbx, int khalf) {
+                                            int b, int co0, int row0, int p0x, int l5, int khalf) {
+    using G = HcGeo<WIDE>;
     const int ho = 2 * p.h, wo = 2 * p.w;
     // kh'[u] = flipped horizontal factor: out[ox] = sum_u kh'[u] V[ox - 1 + u]
     float khf[4];
@@ -140,8 +167,11 @@ __device__ __forceinline__ void hc_epilogue(const UpHcParams& p, const f32x16 (&
     const float nw = p.noise ? p.noise_weight[0] : 0.f;
     const float neg = p.act ? 0.2f : 1.f, gain = p.act ? 1.41421356237309515f : 1.f;
     const size_t opl = (size_t)ho * wo;
-    // uint4 index of this lane's pixel after the half exchange (lower half-wave: column 2b, upper: 2b + 1) in 8-channel block 0 of this workgroup, row parity 0
-    const size_t o_base = ((size_t)b * (p.cout >> 3) + (size_t)(co0 >> 3)) * opl + (size_t)(2 * pm) * wo + (size_t)(2 * pbx + khalf);
+    // uint4 index of the pixel of lane ptx = 0 of the wave's first row in 8-channel block 0 of this workgroup, row parity 0 (uniform; p0x may be -1: that lane
+    // stores nothing), and this lane's byte offset from it after the half exchange (lower half-wave: column 2b, upper: 2b + 1)
+    const int64_t o_base = (int64_t)(((size_t)b * (p.cout >> 3) + (size_t)(co0 >> 3)) * opl + (size_t)(2 * row0) * wo) + 2 * p0x;
+    const unsigned o_lane = (unsigned)((WIDE ? 0 : (l5 >> 4) * 2 * wo) + 2 * (WIDE ? l5 : l5 & 15) + khalf) * 16u;
+    unsigned char* const out_b = reinterpret_cast<unsigned char*>(p.out);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         // registers 4g .. 4g + 3 = channels 8g + 4 khalf + (0..3)
@@ -159,9 +189,9 @@ __device__ __forceinline__ void hc_epilogue(const UpHcParams& p, const f32x16 (&
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float z0 = accs[2 * pa][4 * g + j], z1 = accs[2 * pa + 1][4 * g + j];
-                const float l1 = dpp_row<DPP_ROW_SHR1>(z1);                // column 2b - 1
-                const float r0 = dpp_row<DPP_ROW_SHL1>(z0);                // column 2b + 2
-                const float r1 = dpp_row<DPP_ROW_SHL1>(z1);                // column 2b + 3
+                const float l1 = dpp_row<G::SHR1>(z1);                     // column 2b - 1
+                const float r0 = dpp_row<G::SHL1>(z0);                     // column 2b + 2
+                const float r1 = dpp_row<G::SHL1>(z1);                     // column 2b + 3
                 float oe = __fmul_rn(khf[0], l1);
                 oe = __builtin_fmaf(khf[1], z0, oe);
                 oe = __builtin_fmaf(khf[2], z1, oe);
@@ -194,9 +224,11 @@ __device__ __forceinline__ void hc_epilogue(const UpHcParams& p, const f32x16 (&
             if ((p.exp & 4) && he[0] != 0x12345678u) continue;        // experiment: everything but the stores
 #endif
             if (lane_ok) {
-                const size_t o4 = o_base + (size_t)g * opl + (size_t)pa * wo;
-                p.out[o4] = make_uint4(he[0], he[1], ho_[0], ho_[1]);
-                p.out[(size_t)p.plane_out + o4] = make_uint4(le[0], le[1], lo_[0], lo_[1]);
+                unsigned char* const ohi = out_b + (o_base + (int64_t)((size_t)g * opl + (size_t)pa * wo)) * 16;
+                unsigned ol = o_lane;
+                asm volatile("" : "+v"(ol));          // (keeps the zero extension in this block: scalar base + 32-bit lane offset is then the store's own addressing)
+                *reinterpret_cast<uint4*>(ohi + ol) = make_uint4(he[0], he[1], ho_[0], ho_[1]);
+                *reinterpret_cast<uint4*>(ohi + p.plane_out * 16 + ol) = make_uint4(le[0], le[1], lo_[0], lo_[1]);
             }
         }
     }
@@ -302,7 +334,7 @@ __global__ __launch_bounds__(HC_NT, 4) void up_hc_kernel(const UpHcParams p) {
             asm volatile("" : "+v"(xb_i), "+v"(wb_i));
             const uint4* xs = lds4 + xb_i;
             const uint4* whalf = lds4 + wb_i;
-            if (par == 0) hc_unit<0>(accs, xs, whalf); else hc_unit<1>(accs, xs, whalf);
+            if (par == 0) hc_unit<0, false>(accs, xs, whalf); else hc_unit<1, false>(accs, xs, whalf);
             E4S_LDS_BARRIER();                                   // everyone is done with this unit's weight slot (and, behind par 1, with the chunk's buffer)
             if (!last) {
                 issue_w(2 * c + par + 2);
@@ -314,7 +346,7 @@ __global__ __launch_bounds__(HC_NT, 4) void up_hc_kernel(const UpHcParams p) {
 
     E4S_PROF_MARK(g_prof_hc, 3);
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid < 1) p.out[(size_t)p.plane_out * 2] = make_uint4(0u, 0u, 0u, 0u);   // zero tail
-    hc_epilogue(p, accs, lds_raw, HC_BODY, nz, lane_ok, b, co0, pm, pbx, khalf);
+    hc_epilogue<false>(p, accs, lds_raw, HC_BODY, nz, lane_ok, b, co0, m0 + 2 * wave, p0x, l5, khalf);
     E4S_PROF_MARK(g_prof_hc, 4);
     E4S_PROF_DRAIN();
     E4S_PROF_MARK(g_prof_hc, 5);
@@ -334,13 +366,20 @@ __global__ __launch_bounds__(HC_NT, 4) void up_hc_kernel(const UpHcParams p) {
 // CU = 5.4 TB/s for the chip).  Each loader wave has its own counter: wave 8 owns the weight ring (four units, three in flight: 54 requests), wave 9 the
 // activation ring (four chunks, three in flight: 60 requests) — 114 KB in flight per CU instead of 56.
 // A tile's co tiles (cout / 32) are consecutive items of the SAME workgroup, so the second one's activation patch comes out of this XCD's L2.
+// Tile geometry (HcGeo<true>): 8 rows x 32 columns, compute wave v owns row v = one half-wave per K half.  The horizontal filter discards positions 0 and 31 of a
+// row, so 30 of 32 executed columns are kept (16 x 16 tiles: 14 of 16) — MFMAs, weight-fragment reads, weight DMA per output and the register epilogue run at
+// 1.067x instead of 1.143x of what is stored; executed MACs 2 x 32 / 30 = 2.13x the algorithmic ones.  The patch is 10 rows x 32 columns = five full 64-lane
+// pieces per (plane, half), 20 requests per chunk as before, and a wave's fragment read is 32 consecutive uint4 per half-wave (conflict-free).
 constexpr int HP_NCW = 8;                                   // compute waves; wave 8 loads weights (+ the epilogue tables), wave 9 activations
 constexpr int HP_NT = 64 * (HP_NCW + 2);                    // 640 threads
 constexpr int HP_NX = 4, HP_NW = 4;                         // activation buffers (chunks), weight slots (units)
-constexpr int HP_W0 = HP_NX * HC_XB4;                       // uint4 offset of the weight ring
-constexpr int HP_BODY = (HP_NX * HC_XB4 + HP_NW * HC_W4) * 16;     // 152 064
-constexpr int HP_LDS = HP_BODY + HC_EP_FLOATS * 4;          // 152 832
-constexpr int HP_GX = 20, HP_GW = 18;                       // requests of one activation chunk / one weight unit
+constexpr int HP_XB4 = 4 * HP_PATCH;                        // uint4 per activation buffer: [hi|lo][half][320]
+constexpr int HP_W0 = HP_NX * HP_XB4;                       // uint4 offset of the weight ring
+constexpr int HP_BODY = (HP_NX * HP_XB4 + HP_NW * HC_W4) * 16;     // 155 648
+constexpr int HP_LDS = HP_BODY + HC_EP_FLOATS * 4;          // 156 416
+constexpr int HP_XPIECES = HP_PATCH / 64;                   // 5
+constexpr int HP_GX = 4 * HP_XPIECES, HP_GW = 18;           // requests of one activation chunk / one weight unit
+static_assert(HP_NCW == HP_TH && HP_PATCH % 64 == 0, "one compute wave per tile row; whole 64-lane pieces");
 static_assert(HP_LDS <= 160 * 1024 && (HP_NX - 1) * HP_GX <= 63 && (HP_NW - 1) * HP_GW + 3 <= 63, "LDS per CU; vmcnt is a 6-bit counter");
 
 __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
@@ -352,16 +391,23 @@ __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
     const int hw = p.h * p.w, wo = 2 * p.w;
     const int nchunk = p.cin >> 4, NU = 2 * nchunk;
     const int stride = gridDim.x, first = walk_offset(blockIdx.x, stride, p.walk & 1);
-    const int my_tiles = (p.ntile - first + stride - 1) / stride;
-    const int my_items = my_tiles * p.ncot;
+    // The walk.  In the `full` rounds every workgroup has a tile: workgroup `first` takes tile first + round * stride with all its co tiles.  The tiles left over
+    // (fewer than a round) are handed out by ITEM, `per` consecutive (tile, co tile) pairs per workgroup, so that the last round costs every workgroup
+    // ceil(items left / workgroups) items instead of a whole tile's ncot: 128 -> 64 @256^2 at batch 4 is 1152 tiles x 2 on 256 workgroups = 9 items each, not 10 and 8.
+    const int full = p.ntile / stride;                                     // (>= 1: the grid has at most ntile workgroups)
+    const int full_items = full * p.ncot;
+    const int rem_items = (p.ntile - full * stride) * p.ncot;
+    const int per = (rem_items + stride - 1) / stride;
+    const int rem_mine = rem_items - first * per;
+    const int my_items = full_items + (rem_mine < 0 ? 0 : rem_mine < per ? rem_mine : per);
     const int per_img = p.tiles_x * p.tiles_y;
     const int total = my_items * NU;                                       // units of this workgroup's walk = barriers every wave passes
-    // item i of this workgroup: tile first + (i / ncot) * stride, co tile i % ncot
     auto item_coords = [&](int i, int& b, int& cot, int& tyt, int& txt) __attribute__((always_inline)) {
         i = i < my_items ? i : my_items - 1;                               // (ghost items past the end repeat the last one)
-        int t = first + (i / p.ncot) * stride;
+        const int r = i < full_items ? i : first * per + (i - full_items); // index in this workgroup's full rounds / in the items left over
+        int t = i < full_items ? first + (r / p.ncot) * stride : full * stride + r / p.ncot;
         t = p.rev ? p.ntile - 1 - t : t;
-        cot = i % p.ncot;
+        cot = r % p.ncot;
         b = t / per_img;
         walk_tile_xy(t - b * per_img, p.tiles_x, p.tiles_y, p.walk >> 8, tyt, txt);
     };
@@ -415,22 +461,20 @@ __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
             const int c = q % nchunk;
             int b, cot, tyt, txt;
             item_coords(q / nchunk, b, cot, tyt, txt);
-            const unsigned xst = (unsigned)((q % HP_NX) * (HC_XB4 * 16));
-            const int m0 = tyt * HC_T, p0x = txt * HC_STEP - 1;
+            const unsigned xst = (unsigned)((q % HP_NX) * (HP_XB4 * 16));
+            const int m0 = tyt * HP_TH, p0x = txt * HP_STEP - 1;
             const unsigned cb0 = (unsigned)((b * cb8 + 2 * c) * hw);
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {                                     // this lane's patch pixel of piece j: the same for the 4 (plane, half)
+            for (int j = 0; j < HP_XPIECES; ++j) {                            // this lane's patch pixel of piece j (two patch rows): the same for the 4 (plane, half)
                 const int e = j * 64 + lane;
-                const int py = e / HC_PW, px = e - py * HC_PW;
-                const int gy = m0 - 1 + py, gx = p0x - 1 + px;
+                const int py = e / HP_PW, px = e - py * HP_PW;
+                const int gy = m0 - 1 + py, gx = p0x + px;
                 const bool inb = gy >= 0 && gy < p.h && gx >= 0 && gx < p.w;
                 const unsigned pix = (unsigned)(gy * p.w + gx);
-                if (e < HC_PATCH) {
 #pragma unroll
-                    for (int combo = 0; combo < 4; ++combo) {
-                        const unsigned cbase = (unsigned)((combo >> 1) * p.plane_in) + cb0 + (unsigned)((combo & 1) * hw);
-                        dma16(p.x, inb ? (cbase + pix) * 16u : zero_off, lds_b + xst + (combo * HC_PATCH + j * 64) * 16);
-                    }
+                for (int combo = 0; combo < 4; ++combo) {
+                    const unsigned cbase = (unsigned)((combo >> 1) * p.plane_in) + cb0 + (unsigned)((combo & 1) * hw);
+                    dma16(p.x, inb ? (cbase + pix) * 16u : zero_off, lds_b + xst + (combo * HP_PATCH + j * 64) * 16);
                 }
             }
         };
@@ -449,16 +493,16 @@ __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
 
     // ======================================================================================= compute waves
     const int l5 = lane & 31, khalf = lane >> 5;
-    const int pty = 2 * wave + (l5 >> 4), ptx = l5 & 15;
-    const int xoff = pty * HC_PW + ptx;
+    const int pty = wave, ptx = l5;
+    const int xoff = pty * HP_PW + ptx;
     if (blockIdx.x == 0 && tid < 1) p.out[(size_t)p.plane_out * 2] = make_uint4(0u, 0u, 0u, 0u);   // the zero element behind the output planes
     int xbuf = 0;                                        // (chunk of the walk) % HP_NX, carried along
 #pragma unroll 1
     for (int ti = 0; ti < my_items; ++ti) {
         int b, cot, tyt, txt;
         item_coords(ti, b, cot, tyt, txt);
-        const int pm = tyt * HC_T + pty, pbx = txt * HC_STEP - 1 + ptx;
-        const bool lane_ok = ptx >= 1 && ptx <= HC_STEP && pbx < p.w && pm < p.h;
+        const int pm = tyt * HP_TH + pty, p0x = txt * HP_STEP - 1, pbx = p0x + ptx;
+        const bool lane_ok = ptx >= 1 && ptx <= HP_STEP && pbx < p.w && pm < p.h;
         float2 nz[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
         if (p.noise && lane_ok) {                        // requested now, used after the K loop
             const float* np = p.noise + (size_t)b * p.noise_bstride + (size_t)(2 * pm) * wo + 2 * pbx;
@@ -476,7 +520,7 @@ __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
             for (int par = 0; par < 2; ++par) {
                 const int k = ti * NU + 2 * c + par;
                 E4S_LDS_BARRIER();
-                unsigned xb_i = (unsigned)(xbuf * HC_XB4 + khalf * HC_PATCH + xoff);
+                unsigned xb_i = (unsigned)(xbuf * HP_XB4 + khalf * HP_PATCH + xoff);
                 unsigned wb_i = (unsigned)(HP_W0 + (k % HP_NW) * HC_W4 + khalf * 32 + l5);
                 asm volatile("" : "+v"(xb_i), "+v"(wb_i));
                 const uint4* xs = lds4 + xb_i;
@@ -484,14 +528,14 @@ __global__ __launch_bounds__(HP_NT) void up_hcp_kernel(const UpHcParams p) {
 #ifdef E4S_PHASE_PROF
                 if (p.exp & 2) continue;
 #endif
-                if (par == 0) hc_unit<0>(accs, xs, whalf); else hc_unit<1>(accs, xs, whalf);
+                if (par == 0) hc_unit<0, true>(accs, xs, whalf); else hc_unit<1, true>(accs, xs, whalf);
             }
             xbuf = xbuf + 1 < HP_NX ? xbuf + 1 : 0;
         }
 #ifdef E4S_PHASE_PROF
         if (p.exp & 1) { asm volatile("" :: "v"(accs[0][0]), "v"(accs[1][0]), "v"(accs[2][0]), "v"(accs[3][0])); continue; }
 #endif
-        hc_epilogue(p, accs, lds_raw, HP_BODY, nz, lane_ok, b, cot * 32, pm, pbx, khalf);
+        hc_epilogue<true>(p, accs, lds_raw, HP_BODY, nz, lane_ok, b, cot * 32, pm, p0x, l5, khalf);
     }
 }
 
@@ -585,7 +629,8 @@ extern "C" int e4s_modconv_up_hc(uint16_t* out_sp, const uint16_t* x_sp, const u
     p.d = d; p.blur = blur; p.noise = noise; p.noise_weight = noise_weight; p.act_bias = act_bias; p.s_next = s_next; p.zeros = zeros;
     p.noise_bstride = (noise && noise_bs > 1) ? 4 * h * w : 0;
     p.act = act & 1; p.bs = bs; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-    p.tiles_x = cdiv(2 * w, 2 * HC_STEP); p.tiles_y = cdiv(h, HC_T);
+    const bool persistent = cin >= 32;             // (below; its tiles are 8 rows x 32 columns, 30 kept)
+    p.tiles_x = cdiv(w, persistent ? HP_STEP : HC_STEP); p.tiles_y = cdiv(h, persistent ? HP_TH : HC_T);
     p.ntile = p.tiles_x * p.tiles_y * bs; p.ncot = cout / 32;
     p.plane_in = (int64_t)bs * (cin / 8) * h * w;
     p.plane_out = (int64_t)bs * (cout / 8) * 4 * h * w;
@@ -602,7 +647,7 @@ extern "C" int e4s_modconv_up_hc(uint16_t* out_sp, const uint16_t* x_sp, const u
 #endif
     // (cin = 16 has too few units per item for the persistent loader's table hand-over: the two-workgroups-per-CU form serves it; at cin >= 32 the two forms
     //  tie — 0.315 against 0.320 ms on the 64 -> 32 layer, 0.265 against 0.255 on 128 -> 64 — and the persistent one is the one the f16 + fp6 arithmetic needs next)
-    if (cin >= 32) {
+    if (persistent) {
         static const int ncu = [] {
             int dev = 0, n = 256;
             if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
