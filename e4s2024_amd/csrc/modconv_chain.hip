@@ -15,9 +15,20 @@
 // walks over tiles so that the next tile's chunks land while the current tile's epilogue runs.  Arithmetic is unchanged: fl(v * s) then
 // the RNE split is exactly what the old consumers computed while staging, MFMA order and epilogue formulas are the same.
 //
+// Instruction pass of chain_conv_kernel (same bits: tests/test_gpu_chain_bits.py holds the hashes of the form before it; counts in
+// profiles/chain_loop_mix.txt, times in profiles/chain_ab.txt).  K loop: a wave's two pixel rows use four patch rows, and row q = 1 of tap
+// (ky, kx) is row q = 0 of tap (ky + 1, kx), so those fragments stay in registers for the next input row: 24 activation reads per chunk and
+// wave instead of 36 (42 / 60 LDS reads with the weights, were 54 / 72; the fragment reads and the DMA writes share the LDS port).  Epilogue:
+// d, bias, s_next and the ToRGB weights (stored by channel quad: four (w0, w1) pairs, then four w2) are read once per group of four channels as
+// 16-byte reads and serve both pixel rows; the values go through as channel pairs on packed fp32 instructions, each element rounded as before;
+// with the split-plane output the two half-waves exchange halves (v_permlane32_swap) so that a lane owns a pixel's 8 channels, and a plane's two
+// rows leave in one 16-byte store from a wave-uniform base plus a 32-bit lane offset.
+//
 // Reference semantics: ModulatedConv2d.forward fused branch (models/stylegan2/model.py:276-320), StyledConv noise / bias / activation
 // (:417-421), ToRGB (:439-479) — the single-region case (mask_op False) of each.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "sb_common.h"
@@ -42,7 +53,35 @@ __device__ __forceinline__ void wait_vm(int n) {
 // LDS-DMA stays in flight across this barrier (a __syncthreads() would drain it: its fence waits vmcnt(0) while a DMA is pending)
 #define CH_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-constexpr int CT_TW = 32, CT_TH = 16;                 // conv output tile (pixels): 8 compute waves x 2 rows of 32
+// The epilogue's arithmetic on register PAIRS (two channels of one pixel): packed fp32 multiply / add / fma round each element exactly as the scalar
+// instruction does.  Written as instructions so that nothing is contracted or re-paired; `lo` / `hi` forms broadcast one element of a pair to both results.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+template <int HI> __device__ __forceinline__ f32x2 pk_add_bc(f32x2 a, f32x2 b) {            // a + b[HI] (both elements)
+    f32x2 r;
+    if constexpr (HI) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
+    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <int HI> __device__ __forceinline__ f32x2 pk_fma_cbc(f32x2 a, f32x2 b, f32x2 c) {   // fma(a, b, c[HI]) (both elements)
+    f32x2 r;
+    if constexpr (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ f32x2 pk_fms(f32x2 a, f32x2 b, f32x2 c) {                          // fma(a, b, -c)
+    f32x2 r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+template <int HI> __device__ __forceinline__ void pk_fma_bc(f32x2& c, f32x2 v, f32x2 w) {   // c = fma(v[HI], w, c) (both elements)
+    if constexpr (HI) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(c) : "v"(v), "v"(w));
+    else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(c) : "v"(v), "v"(w));
+}
+__device__ __forceinline__ float max_f32(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
+constexpr int CT_TW = 32, CT_TH = 16;                // conv output tile (pixels): 8 compute waves x 2 rows of 32
 constexpr int CT_PW = CT_TW + 2, CT_PH = CT_TH + 2;
 constexpr int CT_PATCH = CT_PW * CT_PH;               // 612 patch pixels
 constexpr int CT_NPIECE = (CT_PATCH + 63) / 64;       // 10 DMA pieces of 64 pixels per (plane, half)
@@ -229,7 +268,8 @@ __global__ __launch_bounds__(CT_NT) void chain_conv_kernel(const ChainParams p) 
                     if constexpr (RGB) {
                         const float rs = ok ? p.rgb_s[(size_t)b * p.cout + v] : 0.f;
 #pragma unroll
-                        for (int o = 0; o < 3; ++o) epw[K_EP_WSR + v * 3 + o] = epw[K_EP_RW + v * 3 + o] * rs;
+                        for (int o = 0; o < 3; ++o)      // a quad's 12 values: (w0, w1) of its four channels, then the four w2 — the epilogue's three 16-byte reads
+                            epw[K_EP_WSR + (v & ~3) * 3 + (o < 2 ? 2 * (v & 3) + o : 8 + (v & 3))] = epw[K_EP_RW + v * 3 + o] * rs;
                     }
                 }
             }
@@ -287,13 +327,16 @@ __global__ __launch_bounds__(CT_NT) void chain_conv_kernel(const ChainParams p) 
             const uint4* whalf = lds4 + wb_i;
             // one tap of fragments is fetched ahead of the MFMAs that use it; the scheduling barriers keep hipcc from hoisting all nine
             // taps' LDS reads to the top of the chunk
-            uint4 bh[2][2], bl[2][2], ah[2][CB], al[2][CB];
+            // Activation fragments by patch row (0 .. 3 below the wave's first pixel row) and column: tap (ky, kx) multiplies pixel row q with patch row
+            // ky + q, so row q = 1 of tap (ky, kx) is row q = 0 of tap (ky + 1, kx) and stays in registers for it (3 columns x hi / lo = 24 VGPRs carried):
+            // input row 0 reads both patch rows of a tap, rows 1 and 2 only the new one — 24 activation reads per chunk and wave, each fragment once.
+            uint4 xh[4][3], xl[4][3], ah[2][CB], al[2][CB];
             auto fetch = [&](int tap, int slot) __attribute__((always_inline)) {
-                const int toff = (tap / 3) * CT_PW + (tap % 3);
+                const int ky = tap / 3, kx = tap % 3;
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    bh[slot][q] = xs[q * CT_PW + toff];
-                    bl[slot][q] = xs[2 * CT_PATCH + q * CT_PW + toff];
+                for (int pr = (ky == 0 ? 0 : ky + 1); pr <= ky + 1; ++pr) {
+                    xh[pr][kx] = xs[pr * CT_PW + kx];
+                    xl[pr][kx] = xs[2 * CT_PATCH + pr * CT_PW + kx];
                 }
 #pragma unroll
                 for (int i = 0; i < CB; ++i) {
@@ -305,23 +348,23 @@ __global__ __launch_bounds__(CT_NT) void chain_conv_kernel(const ChainParams p) 
             fetch(0, 0);
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                const int cs = tap & 1;
+                const int cs = tap & 1, ky = tap / 3, kx = tap % 3;
                 if (tap + 1 < 9) fetch(tap + 1, cs ^ 1);
 #pragma unroll
                 for (int i = 0; i < CB; ++i)
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
-                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[cs][i]), __builtin_bit_cast(bf16x8, bh[cs][q]), acc[i][q], 0, 0, 0);
+                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[cs][i]), __builtin_bit_cast(bf16x8, xh[ky + q][kx]), acc[i][q], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < CB; ++i)
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
-                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[cs][i]), __builtin_bit_cast(bf16x8, bl[cs][q]), acc[i][q], 0, 0, 0);
+                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[cs][i]), __builtin_bit_cast(bf16x8, xl[ky + q][kx]), acc[i][q], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < CB; ++i)
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
-                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[cs][i]), __builtin_bit_cast(bf16x8, bh[cs][q]), acc[i][q], 0, 0, 0);
+                        acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[cs][i]), __builtin_bit_cast(bf16x8, xh[ky + q][kx]), acc[i][q], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -333,18 +376,20 @@ __global__ __launch_bounds__(CT_NT) void chain_conv_kernel(const ChainParams p) 
             const int* desc = reinterpret_cast<const int*>(epw + C::EP_DESC);
             b = __builtin_amdgcn_readfirstlane(desc[0]); y0 = __builtin_amdgcn_readfirstlane(desc[1]); x0 = __builtin_amdgcn_readfirstlane(desc[2]);
         }
+        // opaque base, immediates after it (LDS is 160 KB: absolute addresses do not fit a ds_read offset field); epc = this half-wave's channel quad of the
+        // per-channel tables, epq its 12 ToRGB weights of a quad
+        unsigned ep_i = (unsigned)(C::EP_OFF / 4);
+        asm volatile("" : "+v"(ep_i));
+        const float* ep = reinterpret_cast<const float*>(lds_raw) + ep_i;
+        const float* epc = ep + 4 * khalf;
+        const float* epq = ep + 12 * khalf;
+        // ---- per pixel row: noise term, skip taps + ToRGB bias
+        float nzq[2], rgbadd[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            // opaque base, immediates after it — and opaque PER pixel block: the per-channel tables are the same for both blocks, and given
-            // the chance hipcc keeps all of them in registers across the two
-            unsigned ep_i = (unsigned)(C::EP_OFF / 4);
-            asm volatile("" : "+v"(ep_i));
-            const float* ep = reinterpret_cast<const float*>(lds_raw) + ep_i;
             const int row = 2 * wave + q;
             const int oy = y0 + row, ox = x0 + l5;
-            const size_t opix = (size_t)oy * p.w + ox;
-            const float nz = __fmul_rn(nw, ep[C::EP_NOISE + row * CT_TW + l5]);
-            float rgbadd[3] = {0.f, 0.f, 0.f};
+            nzq[q] = __fmul_rn(nw, ep[C::EP_NOISE + row * CT_TW + l5]);
             if constexpr (RGB) {
                 const int iy0 = (oy - 1) >> 1, ix0 = (ox - 1) >> 1;
                 const int ky0 = 2 * iy0 + 2 - oy, kx0 = 2 * ix0 + 2 - ox;
@@ -359,54 +404,114 @@ __global__ __launch_bounds__(CT_NT) void chain_conv_kernel(const ChainParams p) 
                             for (int tx = 0; tx < 2; ++tx)      // out-of-image skip pixels were staged as zeros: fma with 0 leaves u unchanged
                                 u = __builtin_fmaf(ep[C::EP_SKIP + (o * CT_SKH + sy0 + ty) * CT_SKW + sx0 + tx], ep[C::EP_KF + (ky0 + 2 * ty) * 4 + kx0 + 2 * tx], u);
                     }
-                    rgbadd[o] = u;
+                    rgbadd[q][o] = u;
                 }
             }
-            float rgb0 = 0.f, rgb1 = 0.f, rgb2 = 0.f;
+        }
+        // ---- per group of four channels (registers 4 r4 .. + 3 = channels 32 i + 8 r4 + 4 khalf + (0 .. 3)): d, bias, s_next and the 12 ToRGB weights are read
+        // ONCE, as 16-byte reads, and serve both pixel rows; the values go through as channel PAIRS (adjacent accumulator registers, adjacent table entries):
+        //   v = fma(acc, d, nz) + bias v_pk_fma_f32 (nz of the row broadcast), v_pk_add_f32
+        //   leaky ReLU * gain          v_pk_mul_f32 by 0.2, v_max_f32 x 2 (max(v, 0.2 v) is v for v > 0 and 0.2 v otherwise, signed zeros included), v_pk_mul_f32
+        //                              (activation off: 1.0 and 1.0 — exact)
+        //   ToRGB                      (rgb0, rgb1) += v * (w0, w1) as ONE v_pk_fma_f32 per channel, rgb2 its own fmaf: per row, channel ascending, as before
+        //   hand-over                  hi = bf16(fl(v * s_next)) (v_pk_mul_f32), lo = bf16(fma(v, s_next, -hi)) (v_pk_fma_f32)
+        // WHERE THE ROUNDINGS ARE.  The first form of this epilogue spelled fl(fl(fl(acc * d) + nz) + bias) and split2(fl(v * s_next)), but under the
+        // compiler's default floating-point contraction it was never built that way: hipcc fused acc * d + nz into one fma and the residual fl(v * s) - hi
+        // into fma(v, s, -hi) — everywhere except accumulator registers 14 and 15 of the 32 -> 32 kernel, whose products it had paired with other
+        // multiplies and so kept apart.  Those are the bits every image since has had and tests/golden/chain_bits.json records, so they are written out
+        // here as instructions, the two exceptions included (the fused forms are the more exact ones; all of it is inside the parity bars).
+        const float negf = p.act ? 0.2f : 1.f, gainf = p.act ? 1.41421356237309515f : 1.f;
+        const f32x2 neg2 = {negf, negf}, gain2 = {gainf, gainf}, nz2 = {nzq[0], nzq[1]};
+        f32x2 rgb01[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        float rgb2[2] = {0.f, 0.f};
+        // split-plane stores: the wave's first pixel (row 2 wave, column x0) of 8-channel block 0 is wave-uniform; after the half exchange below the lower half-wave
+        // owns row 0 and the upper one row 1, so a lane adds (khalf * w + l5) uint4
+        [[maybe_unused]] const int64_t o_base = (int64_t)b * (p.cout >> 3) * hw + (int64_t)(y0 + 2 * wave) * p.w + x0;
+        [[maybe_unused]] const unsigned o_lane = (unsigned)(khalf * p.w + l5) * 16u;
 #pragma unroll
-            for (int i = 0; i < CB; ++i) {
+        for (int i = 0; i < CB; ++i) {
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const int n0 = i * 32 + 8 * r4 + 4 * khalf;
-                    const float4 d4 = *reinterpret_cast<const float4*>(ep + C::EP_D + n0);
-                    const float4 b4 = *reinterpret_cast<const float4*>(ep + C::EP_BIAS + n0);
-                    const float dd[4] = {d4.x, d4.y, d4.z, d4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-                    float v4[4];
+            for (int r4 = 0; r4 < 4; ++r4) {
+                const int n0 = i * 32 + 8 * r4;                                      // (+ 4 khalf: in epc / epq)
+                const f32x4 d4 = *reinterpret_cast<const f32x4*>(epc + C::EP_D + n0);
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(epc + C::EP_BIAS + n0);
+                const f32x2 dd[2] = {__builtin_shufflevector(d4, d4, 0, 1), __builtin_shufflevector(d4, d4, 2, 3)};
+                const f32x2 bb[2] = {__builtin_shufflevector(b4, b4, 0, 1), __builtin_shufflevector(b4, b4, 2, 3)};
+                f32x2 w01[4];
+                f32x4 w2 = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (RGB) {
+                    const f32x4 wa = *reinterpret_cast<const f32x4*>(epq + C::EP_WSR + 3 * n0);
+                    const f32x4 wb = *reinterpret_cast<const f32x4*>(epq + C::EP_WSR + 3 * n0 + 4);
+                    w2 = *reinterpret_cast<const f32x4*>(epq + C::EP_WSR + 3 * n0 + 8);
+                    w01[0] = __builtin_shufflevector(wa, wa, 0, 1); w01[1] = __builtin_shufflevector(wa, wa, 2, 3);
+                    w01[2] = __builtin_shufflevector(wb, wb, 0, 1); w01[3] = __builtin_shufflevector(wb, wb, 2, 3);
+                }
+                f32x2 ss[2];
+                if constexpr (OUT_SP) {
+                    const f32x4 s4 = *reinterpret_cast<const f32x4*>(epc + C::EP_SN + n0);
+                    ss[0] = __builtin_shufflevector(s4, s4, 0, 1); ss[1] = __builtin_shufflevector(s4, s4, 2, 3);
+                }
+                [[maybe_unused]] unsigned hq[2][2], lq[2][2];                        // [pixel row][channel pair]
+                auto pixel_row = [&](auto Q) __attribute__((always_inline)) {
+                    constexpr int q = decltype(Q)::value;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = __fadd_rn(__fadd_rn(__fmul_rn(acc[i][q][4 * r4 + e], dd[e]), nz), bb[e]);
-                        if (p.act) v = __fmul_rn(v > 0.f ? v : __fmul_rn(v, 0.2f), 1.41421356237309515f);
-                        v4[e] = v;
+                    for (int h = 0; h < 2; ++h) {
+                        const f32x2 a = {acc[i][q][4 * r4 + 2 * h], acc[i][q][4 * r4 + 2 * h + 1]};
+                        // (acc * d + nz: ONE rounding — except registers 14 / 15 of the 32-channel kernel, see above)
+                        const bool two_roundings = CB == 1 && r4 == 3 && h == 1;
+                        f32x2 v = pk_add(two_roundings ? pk_add_bc<q>(pk_mul(a, dd[h]), nz2) : pk_fma_cbc<q>(a, dd[h], nz2), bb[h]);
+                        const f32x2 t = pk_mul(v, neg2);
+                        v = pk_mul((f32x2){max_f32(v[0], t[0]), max_f32(v[1], t[1])}, gain2);
                         if constexpr (RGB) {
-                            const float* wq = ep + C::EP_WSR + (n0 + e) * 3;
-                            rgb0 = __builtin_fmaf(v, wq[0], rgb0);
-                            rgb1 = __builtin_fmaf(v, wq[1], rgb1);
-                            rgb2 = __builtin_fmaf(v, wq[2], rgb2);
+                            pk_fma_bc<0>(rgb01[q], v, w01[2 * h]);
+                            rgb2[q] = __builtin_fmaf(v[0], w2[2 * h], rgb2[q]);
+                            pk_fma_bc<1>(rgb01[q], v, w01[2 * h + 1]);
+                            rgb2[q] = __builtin_fmaf(v[1], w2[2 * h + 1], rgb2[q]);
+                        }
+                        if constexpr (OUT_SP) {
+                            const f32x2 u = pk_mul(v, ss[h]);
+                            const unsigned hi = pack_bf16_rne(u[0], u[1]);
+                            const f32x2 hf = {__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
+                            const f32x2 lo = pk_fms(v, ss[h], hf);                   // (the residual of the EXACT product, see above)
+                            hq[q][h] = hi;
+                            lq[q][h] = pack_bf16_rne(lo[0], lo[1]);
                         }
                     }
-                    if constexpr (OUT_SP) {
-                        const float4 s4 = *reinterpret_cast<const float4*>(ep + C::EP_SN + n0);
-                        unsigned h0, l0, h1, l1;
-                        split2(__fmul_rn(v4[0], s4.x), __fmul_rn(v4[1], s4.y), h0, l0);
-                        split2(__fmul_rn(v4[2], s4.z), __fmul_rn(v4[3], s4.w), h1, l1);
-                        // 8-channel block n0 / 8 of this pixel: this half-wave owns bytes [8 khalf, 8 khalf + 8) of its 16
-                        const size_t o8 = (((size_t)b * (p.cout >> 3) + (n0 >> 3)) * hw + opix) * 2 + khalf;
-                        uint2* osp = reinterpret_cast<uint2*>(p.out_sp);
-                        osp[o8] = make_uint2(h0, h1);
-                        osp[(size_t)p.plane_out * 2 + o8] = make_uint2(l0, l1);
+                };
+                pixel_row(std::integral_constant<int, 0>{});
+                pixel_row(std::integral_constant<int, 1>{});
+                if constexpr (OUT_SP) {
+                    // Half exchange: the lower half-wave keeps its row-0 values (channels + 0 .. 3) and receives the upper half-wave's (channels + 4 .. 7 of the
+                    // same pixel); the upper half-wave receives the lower one's row-1 values and keeps its own: every lane then holds the 8 channels = 16 bytes
+                    // of ONE pixel of 8-channel block 4 i + r4, and a plane's two rows leave in one 16-byte store from a uniform base + a 32-bit lane offset.
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        auto r = __builtin_amdgcn_permlane32_swap(hq[0][h], hq[1][h], false, false);
+                        hq[0][h] = r[0]; hq[1][h] = r[1];
+                        auto r2 = __builtin_amdgcn_permlane32_swap(lq[0][h], lq[1][h], false, false);
+                        lq[0][h] = r2[0]; lq[1][h] = r2[1];
                     }
-                    __builtin_amdgcn_sched_barrier(0);   // one group of four channels at a time
+                    unsigned char* const ohi = reinterpret_cast<unsigned char*>(p.out_sp) + (o_base + (int64_t)(4 * i + r4) * hw) * 16;
+                    unsigned ol = o_lane;
+                    asm volatile("" : "+v"(ol));          // (keeps the zero extension in this block: scalar base + 32-bit lane offset is then the store's own addressing)
+                    *reinterpret_cast<uint4*>(ohi + ol) = make_uint4(hq[0][0], hq[0][1], hq[1][0], hq[1][1]);
+                    *reinterpret_cast<uint4*>(ohi + p.plane_out * 16 + ol) = make_uint4(lq[0][0], lq[0][1], lq[1][0], lq[1][1]);
                 }
+                __builtin_amdgcn_sched_barrier(0);   // one group of four channels at a time
             }
-            if constexpr (RGB) {
+        }
+        if constexpr (RGB) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                float rgb0 = rgb01[q][0], rgb1 = rgb01[q][1], rgb2q = rgb2[q];
                 rgb0 += __shfl_xor(rgb0, 32, 64);
                 rgb1 += __shfl_xor(rgb1, 32, 64);
-                rgb2 += __shfl_xor(rgb2, 32, 64);
+                rgb2q += __shfl_xor(rgb2q, 32, 64);
                 if (khalf == 0) {
-                    float* ro = p.rgb_out + (size_t)b * 3 * hw + opix;
-                    ro[0] = rgb0 + rgbadd[0];
-                    ro[(size_t)hw] = rgb1 + rgbadd[1];
-                    ro[2 * (size_t)hw] = rgb2 + rgbadd[2];
+                    float* ro = p.rgb_out + (size_t)b * 3 * hw + (size_t)(y0 + 2 * wave + q) * p.w + x0 + l5;
+                    ro[0] = rgb0 + rgbadd[q][0];
+                    ro[(size_t)hw] = rgb1 + rgbadd[q][1];
+                    ro[2 * (size_t)hw] = rgb2q + rgbadd[q][2];
                 }
             }
         }
