@@ -746,3 +746,86 @@ def codeformer_restore(net, faces_u8: torch.Tensor, w=0.8, adain: bool = True) -
     w = G._w_checked(name, w)
     x = _codeformer_input(name, net, faces_u8, max_batch=65535 // G._WIDEST)
     return G.image_u8(G.codeformer_restore(x, net, w=w, adain=adain)[0])
+
+
+# ------------------------------------------------------------------------------------ f23: the tiled Real-ESRGAN x2 step and the recolor loop
+def _upscale_checked(name, upscale):
+    import math
+    if isinstance(upscale, bool) or not isinstance(upscale, (int, float)) or not math.isfinite(upscale) or upscale <= 0:
+        raise ValueError(f"{name}: upscale is a finite positive real, got {upscale!r}")
+    return upscale
+
+
+def _enhance_args_checked(name, net, esr, faces_u8, w, upscale):
+    """What ``codeformer_enhance`` refuses, in front of its first launch: both networks, ``w``, ``upscale`` and the faces, in ``codeformer_restore``'s order."""
+    from . import ops_codeformer, ops_codeformer_gen as G, ops_esrgan
+    w = G._w_checked(name, w)
+    _upscale_checked(name, upscale)
+    checked = ops_codeformer._weights_checked(name, net)
+    netweights._tensor_checked(name, "faces_u8", faces_u8, torch.uint8, 4, "uint8 [n, 3, H, W] RGB faces")
+    if faces_u8.shape[1] != 3 or faces_u8.shape[2] < 1 or faces_u8.shape[3] < 1:
+        raise ValueError(f"{name}: faces_u8: expected uint8 [n, 3, H, W] RGB faces, got {tuple(faces_u8.shape)}")
+    probe = torch.empty((faces_u8.shape[0], 3, 512, 512), dtype=torch.uint8, device="meta")   # what the restoration hands the Real-ESRGAN step: shapes only
+    esr_checked = ops_esrgan._enhance_checked(name, probe, esr, upscale, ops_esrgan.ESRGAN_TILE, ops_esrgan.ESRGAN_TILE_PAD, ops_esrgan.ESRGAN_PRE_PAD, True)[0]
+    netweights._devices_checked(name, "faces_u8", faces_u8, checked[2])
+    netweights._devices_checked(name, "faces_u8", faces_u8, esr_checked[2])
+    return w
+
+
+@torch.no_grad()
+def codeformer_enhance(net, esr, faces_u8: torch.Tensor, w=0.8, adain: bool = True, upscale=2) -> torch.Tensor:
+    """The whole of ``CodeFormerInfer.infer_image`` (swap_face_fine/inference_codeformer.py:157-178) for a batch on the device: ``codeformer_restore`` (the
+    resize to 512 x 512, the network, ``tensor2img``) and ``RealESRGANer.enhance(restored_face, outscale=upscale)`` as ``ops.esrgan_enhance(..., chw=True)`` at
+    the reference's ``tile=400, tile_pad=40, pre_pad=0``: 2 x 2 overlapping tiles through RRDBNet x4plus, the 2048 x 2048 image, ``cv2.resize`` at INTER_LANCZOS4
+    on uint8.  uint8 ``[n, 3, H, W]`` RGB faces to uint8 ``[n, 3, 512 upscale, 512 upscale]``, in ``codeformer_restore``'s layout.  ``net`` as
+    ``codeformer_restore`` takes it, ``esr`` as ``ops.esrgan_enhance`` takes weights (the x4 network, in eval mode).  The Real-ESRGAN step runs the reference's
+    ``half=False`` arithmetic (``ops_esrgan`` says why).  The reference's ``except`` fallback — the input face where CodeFormer fails — is not reproduced: errors
+    raise.  Both networks and every argument are checked before the first launch."""
+    name = "codeformer_enhance"
+    w = _enhance_args_checked(name, net, esr, faces_u8, w, upscale)
+    netweights._cuda_checked(name, faces_u8=faces_u8)
+    restored = codeformer_restore(net, faces_u8, w=w, adain=adain)
+    return ops.esrgan_enhance(restored, esr, outscale=upscale, chw=True).permute(0, 3, 1, 2).contiguous()
+
+
+@torch.no_grad()
+def recolor_frames(parser, blender, codeformer, esr, swapped_u8: torch.Tensor, targets_u8: torch.Tensor, flip_target=None, w=0.8) -> torch.Tensor:
+    """The body of the video pipeline's recolor loop (face_swap_video_pipeline.py:270-304) for a batch on the device: the ``D_recolor`` frames, uint8
+    ``[bs, 1024, 1024, 3]``, from the swapped crops uint8 ``[bs, S, S, 3]`` and the target crops uint8 ``[bs, Ht, Wt, 3]``:
+
+        T       = targets.resize(swapped.size)                                   (:274; ops.pil_resize)
+        la, lt  = the 19-class maps of the swapped face and of T                  (:276-277; as color_transfer_blender takes them)
+        small   = BlenderInfer.infer_image(swapped, T, la, lt)                   (:278-281; blender_infer_image, uint8 [bs, 256, 256, 3])
+        recolor = small.resize(swapped.size)                                     (:283)
+        recolor = CodeFormerInfer.infer_image(recolor)                           (:284; codeformer_enhance, whose input end resizes to 512 x 512: 1024 x 1024)
+        recolor = recolor.resize((512, 512)).resize(recolor.size)                (:285, "resize down to avoid too high-res")
+
+    ``parser``: the ``FaceParser``; ``blender`` as ``ops.blender_forward`` takes weights, ``codeformer`` and ``esr`` as ``codeformer_enhance`` takes them;
+    ``flip_target`` as ``ops.blender_features``; ``w`` the fusion weight.  Every argument is checked before the first launch.  The whole-clip chain from
+    ``reenact_clip`` (skimage's float resize, ``GPENInfer.infer_image``'s glue) is not part of this."""
+    name = "recolor_frames"
+    for nm, t in (("swapped_u8", swapped_u8), ("targets_u8", targets_u8)):
+        netweights._tensor_checked(name, nm, t, torch.uint8, 4, "uint8 [bs, H, W, 3] crops")
+        if t.shape[3] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+            raise ValueError(f"{name}: {nm}: expected uint8 [bs, H, W, 3] crops, got {tuple(t.shape)}")
+    if swapped_u8.shape[1] != swapped_u8.shape[2]:
+        raise ValueError(f"{name}: swapped_u8: the swapped crops are square, got {tuple(swapped_u8.shape)}")
+    if targets_u8.shape[0] != swapped_u8.shape[0] or targets_u8.device != swapped_u8.device:
+        raise ValueError(f"{name}: {swapped_u8.shape[0]} swapped crops on {swapped_u8.device}, {targets_u8.shape[0]} target crops on {targets_u8.device}")
+    if not callable(getattr(parser, "parse_batch", None)):
+        raise TypeError(f"{name}: parser has no parse_batch (the FaceParser), got {type(parser).__name__}")
+    ops_recolor._blender_weights(name, blender)
+    bs, S = swapped_u8.shape[0], swapped_u8.shape[1]
+    w = _enhance_args_checked(name, codeformer, esr, swapped_u8.permute(0, 3, 1, 2), w, 2)
+    netweights._cuda_checked(name, swapped_u8=swapped_u8, targets_u8=targets_u8)
+    if bs == 0:
+        return torch.empty((0, 1024, 1024, 3), dtype=torch.uint8, device=swapped_u8.device)
+    T = ops.pil_resize(targets_u8, (S, S))
+    to01 = lambda u8: u8.permute(0, 3, 1, 2).float() / 255                    # noqa: E731  (parse_batch takes [bs, 3, S, S] in [0, 1])
+    la = parser.parse_batch(to01(swapped_u8), seg12=False)
+    lt = parser.parse_batch(to01(T), seg12=False)
+    small = blender_infer_image(blender, swapped_u8, T, la, lt, flip_target)
+    recolor = ops.pil_resize(small, (S, S))
+    recolor = codeformer_enhance(codeformer, esr, recolor.permute(0, 3, 1, 2), w=w).permute(0, 2, 3, 1).contiguous()
+    size = (recolor.shape[2], recolor.shape[1])
+    return ops.pil_resize(ops.pil_resize(recolor, (512, 512)), size)

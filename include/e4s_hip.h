@@ -1124,6 +1124,32 @@ E4S_API int e4s_cf_quant(float* out, const void* idx, const float* emb, const fl
 E4S_API int e4s_cf_sft(float* out, const float* dec, const float* scale, const float* shift, float w, int planes, int hw, void* stream);
 E4S_API int e4s_cf_image_u8(uint8_t* out, const float* x, int64_t n, void* stream);
 
+/* f23: CodeFormer face restoration, stage 3 — the tile ends of RealESRGANer.enhance (swap_face_fine/realesrgan_utils.py:69-172 pre_process, tile_process,
+ * post_process around RRDBNet x4plus at half=False) and its cv2.resize(..., INTER_LANCZOS4) on uint8 (:243-248); csrc/esrgan_tile.hip.  The network between
+ * the ends is block f11 / f16's (e4s_conv2d_sb3, e4s_esr_scale_add, e4s_esr_up2).
+ *   e4s_esrt_input            : out [bs][3][th][tw] = float(v) / 255.0f (a correctly rounded float32 division, numpy's img.astype(float32) / 255) of the window
+ *                               rows y0 .. y0 + th, columns x0 .. x0 + tw of the PRE-PADDED image [Hp][Wp] (Hp = H + pre_pad, Wp = W + pre_pad, which is never
+ *                               formed: row H + i reads row H - 2 - i, F.pad(..., 'reflect'); Hp - H < H, Wp - W < W).  img uint8 [bs][H][W][3] (chw 0) or
+ *                               [bs][3][H][W] (chw 1); the channel order is kept.
+ *   e4s_esrt_tail             : q = conv3x3(x [bs][C][H][W], weight [3][C][3][3], zero pad 1) + bias [3] in exact float32 as e4s_esr_tail forms it (bias, then C * 9
+ *                               fused multiply-adds per output in (input channel, row, column) order; C a multiple of 8 up to 64), evaluated ONLY on the window rows
+ *                               oy0 .. oy1, columns ox0 .. ox1 of the tile's output; then clamp(q, 0, 1), * 255.0f, round half to even, uint8, stored at row Y0, column
+ *                               X0 of canvas [bs][CH] rows of `pitch` bytes holding CW pixels of three bytes.  No byte outside the window is written; out_f must be null
+ *                               (the argument keeps the shape of the other tails).  Plain vector stores.
+ *   e4s_cv_resize_lanczos4_u8 : out [bs][Ho][Wo][3] = cv2.resize(img [bs][H][W][3], (Wo, Ho), interpolation=INTER_LANCZOS4) in OpenCV's portable fixed-point
+ *                               arithmetic, given the tables of the rule, made on the host: per axis ofs int32 [dst] = s - 3 with s = floor(float((d + 0.5) scale
+ *                               - 0.5)), scale = 1.0 / (double(dst) / src), and coef int16 [dst][8] = short(rint(c[k] 2048)) of interpolateLanczos4 at the fraction
+ *                               (not reset at the borders; no fix-up of the sum); the taps read index clamp(ofs + k, 0, src - 1).  h = sum S[x_k] a_k in int32,
+ *                               v = sum h_k b_k in int32, out = saturate_u8((v + (1 << 21)) >> 22).  A workgroup owns 16 x 64 output pixels; where their source window
+ *                               is at most 40 rows by 136 columns it is staged through LDS and every source row filtered once, otherwise the pixels are formed directly.
+ *                               Both forms give the same bits; no table content makes an access leave a tensor.  The coef tables are 16-byte aligned.
+ * No atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_esrt_input(float* out, const uint8_t* img, int bs, int H, int W, int Hp, int Wp, int chw, int y0, int x0, int th, int tw, void* stream);
+E4S_API int e4s_esrt_tail(uint8_t* canvas, float* out_f, const float* x, const float* weight, const float* bias, int bs, int C, int H, int W, int oy0, int oy1,
+                          int ox0, int ox1, int Y0, int X0, int CH, int CW, int64_t pitch, void* stream);
+E4S_API int e4s_cv_resize_lanczos4_u8(uint8_t* out, const uint8_t* img, const int* yofs, const void* ycoef, const int* xofs, const void* xcoef, int bs, int H,
+                                      int W, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
