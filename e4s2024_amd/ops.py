@@ -23,6 +23,7 @@ One module per stage of the path (split in round 5; ``ops`` re-exports all of th
 * ``ops_codeformer`` row f21: CodeFormer face restoration, stage 1 — the VQGAN encoder, the code transformer, the top-1 codes, the codebook lookup and the AdaIN (resolved on first use too)
 * ``ops_codeformer_gen`` row f22: CodeFormer face restoration, stage 2 — the VQGAN generator with its four SFT fuse blocks and the uint8 tail (resolved on first use too)
 * ``ops_esrgan`` row f23: CodeFormer face restoration, stage 3 — the tiled Real-ESRGAN x2 step: tile geometry, RealESRGANer.enhance and cv2's Lanczos4 resize (resolved on first use too)
+* ``ops_sk`` row f24: the ends of the whole-clip reenactment chain — skimage's float64 resize on host-made composite tables and the uint8 frames behind make_animation (resolved on first use too)
 """
 from __future__ import annotations
 
@@ -1411,7 +1412,7 @@ def __getattr__(name):        # PEP 562
     import sys
     if not name.startswith("__"):
         for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr", "ops_reenact",
-                    "ops_reenact_frames", "ops_codeformer", "ops_codeformer_gen", "ops_esrgan"):
+                    "ops_reenact_frames", "ops_codeformer", "ops_codeformer_gen", "ops_esrgan", "ops_sk"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

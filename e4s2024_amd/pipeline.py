@@ -788,22 +788,8 @@ def codeformer_enhance(net, esr, faces_u8: torch.Tensor, w=0.8, adain: bool = Tr
     return ops.esrgan_enhance(restored, esr, outscale=upscale, chw=True).permute(0, 3, 1, 2).contiguous()
 
 
-@torch.no_grad()
-def recolor_frames(parser, blender, codeformer, esr, swapped_u8: torch.Tensor, targets_u8: torch.Tensor, flip_target=None, w=0.8) -> torch.Tensor:
-    """The body of the video pipeline's recolor loop (face_swap_video_pipeline.py:270-304) for a batch on the device: the ``D_recolor`` frames, uint8
-    ``[bs, 1024, 1024, 3]``, from the swapped crops uint8 ``[bs, S, S, 3]`` and the target crops uint8 ``[bs, Ht, Wt, 3]``:
-
-        T       = targets.resize(swapped.size)                                   (:274; ops.pil_resize)
-        la, lt  = the 19-class maps of the swapped face and of T                  (:276-277; as color_transfer_blender takes them)
-        small   = BlenderInfer.infer_image(swapped, T, la, lt)                   (:278-281; blender_infer_image, uint8 [bs, 256, 256, 3])
-        recolor = small.resize(swapped.size)                                     (:283)
-        recolor = CodeFormerInfer.infer_image(recolor)                           (:284; codeformer_enhance, whose input end resizes to 512 x 512: 1024 x 1024)
-        recolor = recolor.resize((512, 512)).resize(recolor.size)                (:285, "resize down to avoid too high-res")
-
-    ``parser``: the ``FaceParser``; ``blender`` as ``ops.blender_forward`` takes weights, ``codeformer`` and ``esr`` as ``codeformer_enhance`` takes them;
-    ``flip_target`` as ``ops.blender_features``; ``w`` the fusion weight.  Every argument is checked before the first launch.  The whole-clip chain from
-    ``reenact_clip`` (skimage's float resize, ``GPENInfer.infer_image``'s glue) is not part of this."""
-    name = "recolor_frames"
+def _recolor_args_checked(name, parser, blender, codeformer, esr, swapped_u8, targets_u8, w):
+    """What ``recolor_frames`` refuses, in front of its first launch: (bs, S, w)."""
     for nm, t in (("swapped_u8", swapped_u8), ("targets_u8", targets_u8)):
         netweights._tensor_checked(name, nm, t, torch.uint8, 4, "uint8 [bs, H, W, 3] crops")
         if t.shape[3] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
@@ -818,6 +804,26 @@ def recolor_frames(parser, blender, codeformer, esr, swapped_u8: torch.Tensor, t
     bs, S = swapped_u8.shape[0], swapped_u8.shape[1]
     w = _enhance_args_checked(name, codeformer, esr, swapped_u8.permute(0, 3, 1, 2), w, 2)
     netweights._cuda_checked(name, swapped_u8=swapped_u8, targets_u8=targets_u8)
+    return bs, S, w
+
+
+@torch.no_grad()
+def recolor_frames(parser, blender, codeformer, esr, swapped_u8: torch.Tensor, targets_u8: torch.Tensor, flip_target=None, w=0.8) -> torch.Tensor:
+    """The body of the video pipeline's recolor loop (face_swap_video_pipeline.py:270-304) for a batch on the device: the ``D_recolor`` frames, uint8
+    ``[bs, 1024, 1024, 3]``, from the swapped crops uint8 ``[bs, S, S, 3]`` and the target crops uint8 ``[bs, Ht, Wt, 3]``:
+
+        T       = targets.resize(swapped.size)                                   (:274; ops.pil_resize)
+        la, lt  = the 19-class maps of the swapped face and of T                  (:276-277; as color_transfer_blender takes them)
+        small   = BlenderInfer.infer_image(swapped, T, la, lt)                   (:278-281; blender_infer_image, uint8 [bs, 256, 256, 3])
+        recolor = small.resize(swapped.size)                                     (:283)
+        recolor = CodeFormerInfer.infer_image(recolor)                           (:284; codeformer_enhance, whose input end resizes to 512 x 512: 1024 x 1024)
+        recolor = recolor.resize((512, 512)).resize(recolor.size)                (:285, "resize down to avoid too high-res")
+
+    ``parser``: the ``FaceParser``; ``blender`` as ``ops.blender_forward`` takes weights, ``codeformer`` and ``esr`` as ``codeformer_enhance`` takes them;
+    ``flip_target`` as ``ops.blender_features``; ``w`` the fusion weight.  Every argument is checked before the first launch.  The whole-clip chain from
+    the source image and the target crops to these frames is ``reenact_recolor_clip``."""
+    name = "recolor_frames"
+    bs, S, w = _recolor_args_checked(name, parser, blender, codeformer, esr, swapped_u8, targets_u8, w)
     if bs == 0:
         return torch.empty((0, 1024, 1024, 3), dtype=torch.uint8, device=swapped_u8.device)
     T = ops.pil_resize(targets_u8, (S, S))
@@ -829,3 +835,140 @@ def recolor_frames(parser, blender, codeformer, esr, swapped_u8: torch.Tensor, t
     recolor = codeformer_enhance(codeformer, esr, recolor.permute(0, 3, 1, 2), w=w).permute(0, 2, 3, 1).contiguous()
     size = (recolor.shape[2], recolor.shape[1])
     return ops.pil_resize(ops.pil_resize(recolor, (512, 512)), size)
+
+
+# ------------------------------------------------------------------------------------ f24: the whole-clip reenactment chain
+_ANIMATION_KW = ("estimate_jacobian", "free_view", "yaw", "pitch", "roll")
+
+
+def _stage_checked(name, fn, *args):
+    """``fn(*args)`` — a stage's own check, or the stage on an EMPTY batch, which refuses what it refuses and launches nothing — with this entry's name in front."""
+    try:
+        return fn(*args)
+    except (TypeError, ValueError, KeyError, RuntimeError) as e:
+        raise type(e)(f"{name}: {e.args[0] if e.args else e}") from None
+
+
+def _reenact_args_checked(name, generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, enhance, channel_order, batch, chunk,
+                          kw):
+    """What ``reenact_drivens`` refuses, in front of its first launch: ((H', W') of the predictions, (Ho, Wo) of the D frames)."""
+    from . import ops_gpen, ops_gpen_sr, ops_parsenet, ops_reenact_frames, ops_retinaface, ops_rrdb, ops_sk
+    for nm, v in (("size", size), ("batch", batch), ("chunk", chunk)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name}: {nm} is a positive int, got {v!r}")
+    if channel_order not in ("reference", "rgb"):
+        raise ValueError(f"{name}: channel_order is 'reference' (the reference's RGB array handed to a BGR interface) or 'rgb', got {channel_order!r}")
+    unknown = sorted(set(kw) - set(_ANIMATION_KW))
+    if unknown:
+        raise TypeError(f"{name}: unexpected keyword {unknown[0]!r}: make_animation takes {', '.join(_ANIMATION_KW)}")
+    for nm in ("yaw", "pitch", "roll"):
+        v = kw.get(nm, 0)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))):
+            raise TypeError(f"{name}: {nm} is a number of degrees or None, got {type(v).__name__}")
+    ops_sk._sk_resize_checked(name, "source_u8", source_u8, (size, size))
+    ops_sk._sk_resize_checked(name, "targets_u8", targets_u8, (size, size))
+    if source_u8.shape[0] != 1:
+        raise ValueError(f"{name}: source_u8 is ONE image, uint8 [1, H, W, 3], got {tuple(source_u8.shape)}")
+    if targets_u8.device != source_u8.device:
+        raise ValueError(f"{name}: source_u8 on {source_u8.device}, targets_u8 on {targets_u8.device}")
+    netweights._cuda_checked(name, source_u8=source_u8, targets_u8=targets_u8)
+    probe = torch.empty((0, 3, size, size), dtype=torch.float32, device=source_u8.device)     # an empty batch: every refusal of a stage, no launch
+    ops_reenact_frames._frames_checked(name, generator)
+    f3 = _stage_checked(name, ops.appearance_feature, probe, generator)
+    _stage_checked(name, ops.kp_detector_forward, probe, kp_detector)
+    _stage_checked(name, ops.he_estimator_forward, probe, he_estimator)
+    pred_hw = (4 * f3.shape[3], 4 * f3.shape[4])                               # as make_animation sizes an empty clip
+    if not enhance:
+        return pred_hw, pred_hw
+    ops_gpen.check_loaded(gpen)
+    g_checked = netweights._validated(name, gpen, ops_gpen._net_of(gpen))
+    S = int(g_checked[1][0])
+    p_checked = netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))
+    if ops_parsenet.parsenet_output_size(p_checked[1], S, S) != (S, S):
+        raise ValueError(f"{name}: the ParseNet turns a {S} x {S} face into a {ops_parsenet.parsenet_output_size(p_checked[1], S, S)} mask: expected {S} x {S} "
+                         "(the reference resizes the mask with cv2, which is not done here)")
+    tensors = [g_checked[2], p_checked[2], ops_retinaface.retinaface_weight_tensors(detector, name)]
+    out_hw = pred_hw
+    if sr is not None:
+        s_checked = netweights._validated(name, sr, ops_rrdb._GSR_NET)
+        tensors.append(s_checked[2])
+        out_hw, pads = ops_gpen_sr.gpen_sr_output_size(pred_hw[0], pred_hw[1], int(s_checked[1][2]))
+        if pred_hw[0] <= pads[0] or pred_hw[1] <= pads[1] or max(out_hw) > ops_gpen_sr.GPEN_SR_MAX_SIDE:
+            raise ValueError(f"{name}: the {pred_hw[0]} x {pred_hw[1]} predictions cannot go through the x{int(s_checked[1][2])} RealESRNet pass (reflect pad "
+                             f"{pads}, output {out_hw}, sides up to {ops_gpen_sr.GPEN_SR_MAX_SIDE})")
+    for ts in tensors:
+        netweights._devices_checked(name, "source_u8", source_u8, ts)
+    return pred_hw, out_hw
+
+
+def _reenact_drivens_run(generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, enhance, channel_order, batch, chunk, kw):
+    source = ops.sk_resize(source_u8, (size, size))
+    driving = ops.sk_resize(targets_u8, (size, size))
+    pred = reenact_clip(generator, kp_detector, he_estimator, source, driving, batch=batch, **kw)
+    flip = enhance and channel_order == "reference"
+    frames = ops.frames_u8(pred, flip=flip)
+    if not enhance:
+        return frames
+    out = [gpen_face_enhancement(detector, gpen, parsenet, sr, frames[i:i + chunk]) for i in range(0, frames.shape[0], chunk)]
+    out = out[0] if len(out) == 1 else torch.cat(out)
+    return out.flip(3) if flip else out
+
+
+@torch.no_grad()
+def reenact_drivens(generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8: torch.Tensor, targets_u8: torch.Tensor, size: int = 256,
+                    enhance: bool = True, channel_order: str = "reference", batch: int = 4, chunk: int = 8, **make_animation_kw) -> torch.Tensor:
+    """The video caller's ``_process_face_reenact`` up to its D frames (face_swap_video_pipeline.py:248-257) for a clip on the device: the source image uint8
+    ``[1, H, W, 3]`` and the n target crops uint8 ``[n, Ht, Wt, 3]`` (RGB) to the driven frames D, uint8 ``[n, 4 size, 4 size, 3]`` with the x4 RealESRNet ``sr``:
+
+        source_256, targets_256 = resize(np.array(im) / 255.0, (size, size))      (:248-249; ops.sk_resize, skimage's float64 resize)
+        predictions             = drive_source_demo(...)                           (:251; reenact_clip, ``batch`` frames per generator call)
+        predictions             = (pred * 255).astype(np.uint8)                    (:253; ops.frames_u8)
+        predictions             = GPENInfer.infer_image(pred)                      (:255-257, gpen_demo.py:18-26, 59-77; gpen_face_enhancement(aligned=False),
+                                                                                   ``chunk`` frames per call: a frame's bytes do not depend on its chunk)
+
+    ``enhance=False`` stops after the third line: the ``size x size`` uint8 predictions, the image caller's ``driven`` (Face_swap_with_two_imgs.py:741-743);
+    the four GPEN networks are not looked at then.  ``sr`` None is ``use_sr=False``: D has the predictions' size.
+
+    ``channel_order``.  ``GPENInfer.infer_image`` hands ``np.array(img_lq)``, an RGB array, to ``FaceEnhancement.process``, which treats it as BGR — the
+    detector's mean, the RealESRNet pass and the generator all see the channels reversed.  The native GPEN path is RGB-convention, ``native(Y) ==
+    reference(Y[..., ::-1])[..., ::-1]``, so ``"reference"`` (the default) reproduces the reference's call as ``native(X[..., ::-1])[..., ::-1]``: the frames
+    enter channel-reversed (``frames_u8(flip=True)``) and the result is reversed back, a pass of its own over D.  ``"rgb"`` does neither: what the reference
+    would compute if it converted to BGR first.
+
+    ``GPEN_demo``'s ``alpha = 1.0`` blend, ``(img_out * alpha + img * (1 - alpha)).clip(0, 255).astype(uint8)``, and the ``cv2.resize`` that feeds it are not
+    built: for a byte x and any byte y, ``x * 1.0 + y * 0.0`` is exactly x in float64, the clip keeps it and the cast returns it.
+
+    ``make_animation_kw``: ``estimate_jacobian``, ``free_view``, ``yaw``, ``pitch``, ``roll`` of ``ops.make_animation``.  The networks as the stages take them.
+    Every argument of every stage is checked before the first launch (a stage's own refusals by running it on an empty batch, which launches nothing).  An empty
+    clip returns an empty tensor of the right shape."""
+    name = "reenact_drivens"
+    pred_hw, out_hw = _reenact_args_checked(name, generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, enhance,
+                                            channel_order, batch, chunk, make_animation_kw)
+    if targets_u8.shape[0] == 0:
+        return torch.empty((0,) + out_hw + (3,), dtype=torch.uint8, device=targets_u8.device)
+    return _reenact_drivens_run(generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, enhance, channel_order, batch, chunk,
+                                make_animation_kw)
+
+
+@torch.no_grad()
+def reenact_recolor_clip(generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, parser, blender, codeformer, esr, source_u8: torch.Tensor,
+                         targets_u8: torch.Tensor, size: int = 256, channel_order: str = "reference", batch: int = 4, chunk: int = 8, flip_target=None, w=0.8,
+                         **make_animation_kw):
+    """``_process_face_reenact(targets, source, use_recolor=True)`` (face_swap_video_pipeline.py:239-314) for a clip on the device: ``(D, D_recolor)``.  ``D`` is
+    ``reenact_drivens(...)``, uint8 ``[n, S, S, 3]``; ``D_recolor`` is ``recolor_frames(parser, blender, codeformer, esr, D, targets_u8, flip_target, w)``,
+    uint8 ``[n, 1024, 1024, 3]``, run ``chunk`` frames at a time.  D is PTI's input and D_recolor its recolor-guidance target.  ``flip_target=None`` draws once per
+    chunk (the reference draws per frame: ``chunk=1``).  The reference's per-frame PNG saves are not made.  Every argument of every stage is checked before the
+    first launch; an empty clip returns empty tensors of the right shapes."""
+    name = "reenact_recolor_clip"
+    if flip_target is not None and not isinstance(flip_target, bool):
+        raise TypeError(f"{name}: flip_target is True, False or None, got {type(flip_target).__name__}")
+    _, out_hw = _reenact_args_checked(name, generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, True, channel_order,
+                                      batch, chunk, make_animation_kw)
+    dev, n = targets_u8.device, targets_u8.shape[0]
+    w = _recolor_args_checked(name, parser, blender, codeformer, esr, torch.empty((0,) + out_hw + (3,), dtype=torch.uint8, device=dev), targets_u8[:0], w)[2]
+    if n == 0:
+        return torch.empty((0,) + out_hw + (3,), dtype=torch.uint8, device=dev), torch.empty((0, 1024, 1024, 3), dtype=torch.uint8, device=dev)
+    D = _reenact_drivens_run(generator, kp_detector, he_estimator, detector, gpen, parsenet, sr, source_u8, targets_u8, size, True, channel_order, batch, chunk,
+                             make_animation_kw)
+    rec = [recolor_frames(parser, blender, codeformer, esr, D[i:i + chunk], targets_u8[i:i + chunk], flip_target, w) for i in range(0, n, chunk)]
+    return D, (rec[0] if len(rec) == 1 else torch.cat(rec))

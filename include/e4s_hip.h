@@ -1150,6 +1150,29 @@ E4S_API int e4s_esrt_tail(uint8_t* canvas, float* out_f, const float* x, const f
 E4S_API int e4s_cv_resize_lanczos4_u8(uint8_t* out, const uint8_t* img, const int* yofs, const void* ycoef, const int* xofs, const void* xcoef, int bs, int H,
                                       int W, int Ho, int Wo, void* stream);
 
+/* f24: the two ends of the whole-clip reenactment chain (face_swap_video_pipeline.py:248-253) — skimage.transform.resize on a float64 image in front of
+ * make_animation and (pred * 255).astype(np.uint8) behind it; csrc/skresize.hip.
+ *   e4s_sk_resize_u8 : out = float32(skimage.transform.resize(img / 255.0, (Ho, Wo))) at skimage 0.19 / 0.20's defaults (order 1, mode 'reflect', clip,
+ *                      anti_aliasing where a side shrinks) for img uint8 [bs][H][W][3]; out float32 [bs][3][Ho][Wo] (chw 1) or [bs][Ho][Wo][3] (chw 0).  Both
+ *                      of skimage's steps (scipy.ndimage.gaussian_filter at sigma = max(0, (in / out - 1) / 2), truncate 4, mode 'mirror'; scipy.ndimage.zoom
+ *                      at order 1, mode 'mirror', grid_mode=True) are linear and separable: the caller passes their product per axis, made on the host in
+ *                      float64, as start int32 [dst], count int32 [dst], weight float64 [dst][T] (T = Ty, Tx: the widest count of the axis, 1 ..
+ *                      E4S_SK_MAX_TAPS; rows padded with zeros).  v = double(byte) / 255.0; tmp[r][x] = sum_k xweight[x][k] v[r][xstart[x] + k], then
+ *                      out[y][x] = sum_k yweight[y][k] tmp[ystart[y] + k][x]: float64, one rounding per product and per sum, ascending k from 0.0; clipped
+ *                      to [min, max] / 255.0 of the sample's own bytes (all channels together); one conversion to float32.  part uint8 [bs][64][2] is
+ *                      written by the call's first kernel (the byte range in 64 pieces) and read by its second.  A workgroup owns 16 x 32 output pixels;
+ *                      where their source rows number at most 80 every source row is filtered along x once into LDS, otherwise the pixels are formed
+ *                      directly in the same order: both forms give the same bits.  start and count are clamped to the source on the device: no table
+ *                      content makes an access leave a tensor.  The weight tables (float64 behind a void pointer) are 8-byte aligned.
+ *   e4s_frames_u8    : out uint8 [n][H][W][3] = the truncation toward zero of the float32 product x * 255.0f clamped to 0 .. 255 (a NaN gives 0), for x
+ *                      float32 [n][3][H][W]: numpy's (pred * 255).astype(np.uint8) on values in [0, 1].  flip != 0 stores the channels reversed.
+ * Plain vector loads and stores, no atomics, no host synchronisation, no scratch memory, grids from shapes alone: the calls can be captured in a graph.
+ * bs == 0 / n == 0 returns at once. */
+#define E4S_SK_MAX_TAPS 1024 /* composite taps per destination index a resize table may hold: a shrink of about 255 : 1 */
+E4S_API int e4s_sk_resize_u8(float* out, uint8_t* part, const uint8_t* img, const int* ystart, const int* ycount, const void* yweight, int Ty,
+                             const int* xstart, const int* xcount, const void* xweight, int Tx, int bs, int H, int W, int Ho, int Wo, int chw, void* stream);
+E4S_API int e4s_frames_u8(uint8_t* out, const float* x, int n, int H, int W, int flip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
