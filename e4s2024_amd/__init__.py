@@ -13,7 +13,7 @@ Layout
                  ``swap_face_fine/gpen/face_detect/facemodels/retinaface.py``, ``swap_face_fine/gpen/face_detect/retinaface_detection.py``,
                  ``swap_face_fine/gpen/align_faces.py``, ``swap_face_fine/gpen/sr_model/rrdbnet_arch.py``,
                  ``swap_face_fine/gpen/sr_model/real_esrnet.py``, ``swap_face_fine/gpen/face_enhancement.py``,
-                 ``swap_face_fine/face_vid2vid/modules/keypoint_detector.py``)
+                 ``swap_face_fine/face_vid2vid/modules/keypoint_detector.py``, ``swap_face_fine/face_inpainting.py``)
                  whose forward passes call the kernels
     runner.py    one-process-per-GPU frame sharding over torch.distributed (RCCL)
     seeded.py    seed-only weights/inputs used by tests, fixtures and the bench
@@ -126,15 +126,27 @@ REENACT_MOTION_OVERRIDES = {
     "swap_face_fine.face_vid2vid.modules.dense_motion": "swap_face_fine/face_vid2vid/modules/dense_motion.py",
 }
 
+# row f25: face inpainting, stage 1: ``inpainting(face_img, mask)`` (Face_swap_with_two_imgs.py imports it from there).  ``swap_face_fine.gcfsr_arch`` is not
+# redirected: the drop-in does not import it (``ops.FaceInpainting`` has its keys), and it needs basicsr and the JIT ops
+INPAINT_OVERRIDES = {
+    "swap_face_fine.face_inpainting": "swap_face_fine/face_inpainting.py",
+}
+
 
 def _redirected():
     return {**OVERRIDES, **LOSS_OVERRIDES, **RECOLOR_OVERRIDES, **RECOLOR_NET_OVERRIDES, **RECOLOR_FPN_OVERRIDES, **ENHANCE_OVERRIDES, **GPEN_OVERRIDES,
             **GPEN_PARSE_OVERRIDES, **GPEN_DETECT_OVERRIDES, **GPEN_ALIGN_OVERRIDES, **GPEN_SR_OVERRIDES, **REENACT_KP_OVERRIDES, **REENACT_MOTION_OVERRIDES}
 
 
+def _all_redirected():
+    """Every module name ``install`` redirects: ``_redirected()``, the network modules of rows up to f18 (row f21's test pins that table's size: its stage added
+    no drop-in), and the tables of later rows, which redirect a caller-level entry (``INPAINT_OVERRIDES``)."""
+    return {**_redirected(), **INPAINT_OVERRIDES}
+
+
 class _DropinFinder(importlib.abc.MetaPathFinder):
     def find_spec(self, fullname, path=None, target=None):
-        rel = _redirected().get(fullname)
+        rel = _all_redirected().get(fullname)
         if rel is None:
             return None
         file = os.path.join(DROPIN_DIR, rel)
@@ -150,14 +162,15 @@ def install(force: bool = False) -> str:
     ``RECOLOR_NET_OVERRIDES``, ``RECOLOR_FPN_OVERRIDES``), the Real-ESRGAN wrapper's (``ENHANCE_OVERRIDES``), GPEN's generator (``GPEN_OVERRIDES``), GPEN's
     face-mask network (``GPEN_PARSE_OVERRIDES``), GPEN's face detector (``GPEN_DETECT_OVERRIDES``), GPEN's 5-point alignment (``GPEN_ALIGN_OVERRIDES``) and
     GPEN's RealESRNet pass with ``FaceEnhancement`` itself (``GPEN_SR_OVERRIDES``) and face-vid2vid's keypoint detector and head-pose estimator
-    (``REENACT_KP_OVERRIDES``) and dense-motion network (``REENACT_MOTION_OVERRIDES``) to the drop-in files.
+    (``REENACT_KP_OVERRIDES``) and dense-motion network (``REENACT_MOTION_OVERRIDES``) and the face-inpainting entry ``inpainting(face_img, mask)``
+    (``INPAINT_OVERRIDES``) to the drop-in files.
 
     Parent packages (``models``, ``models.encoders``, ``swap_face_fine`` …) resolve to whatever is first on ``sys.path`` —
     the reference tree when the engine is used inside it, otherwise the empty packages under ``dropin/`` (appended at the
     END of ``sys.path``).  If an overridden module was already imported from elsewhere, raise unless ``force`` (then it is
     purged so the next import takes the drop-in)."""
     global _finder
-    stale = [m for m in _redirected() if m in sys.modules
+    stale = [m for m in _all_redirected() if m in sys.modules
              and not (getattr(sys.modules[m], "__file__", None) or "").startswith(DROPIN_DIR)]
     if stale:
         if not force:
@@ -187,5 +200,5 @@ def uninstall() -> None:
     if DROPIN_DIR in sys.path:
         sys.path.remove(DROPIN_DIR)
     for m in list(sys.modules):
-        if any(m == s or m.startswith(s + ".") for s in _redirected()):
+        if any(m == s or m.startswith(s + ".") for s in _all_redirected()):
             del sys.modules[m]

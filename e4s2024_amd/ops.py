@@ -1412,7 +1412,7 @@ def __getattr__(name):        # PEP 562
     import sys
     if not name.startswith("__"):
         for mod in ("ops_encode", "ops_post", "ops_grad", "ops_recolor", "ops_gpen", "ops_parsenet", "ops_retinaface", "ops_gpen_paste", "ops_gpen_sr", "ops_reenact",
-                    "ops_reenact_frames", "ops_codeformer", "ops_codeformer_gen", "ops_esrgan", "ops_sk"):
+                    "ops_reenact_frames", "ops_codeformer", "ops_codeformer_gen", "ops_esrgan", "ops_sk", "ops_inpaint"):
             m = sys.modules.get(f"{__package__}.{mod}") or importlib.import_module(f".{mod}", __package__)
             if name in m.__dict__:
                 globals()[name] = m.__dict__[name]

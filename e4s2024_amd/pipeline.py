@@ -361,8 +361,8 @@ def _recolor_nets_checked(ct_mode, recolor_fn, recolor_nets):
 @torch.no_grad()
 def swap_images(net, parser, driven: torch.Tensor, target_images_u8: torch.Tensor, plan, recolor_fn=None, ct_mode: Optional[str] = None,
                 recolor_nets=None, **swap_batch_kwargs) -> torch.Tensor:
-    """The two-image caller's chain (``FaceSwap.face_swap_pipeline``, Face_swap_with_two_imgs.py:796-963, without its inpainting / Blender / GPEN
-    networks) for a batch of target images, all on the device:
+    """The two-image caller's chain (``FaceSwap.face_swap_pipeline``, Face_swap_with_two_imgs.py:796-963, without its GPEN network and without its
+    inpainting step, whose network and ``inpainting()`` are ``inpaint_faces`` below while the rest of ``_inpaint_face`` is not built yet: row f25, stage 2) for a batch of target images, all on the device:
 
         crop_align -> frames_to_tensor -> swap_batch(mask_surgery=True, ear_interpolation=False, comp_indices=IMAGE_COMP_INDICES[_CT])
         [-> color_blend(swapped, recolored, labels)]                                   (:909-924, when ``ct_mode`` or ``recolor_fn`` is given)
@@ -972,3 +972,41 @@ def reenact_recolor_clip(generator, kp_detector, he_estimator, detector, gpen, p
                              make_animation_kw)
     rec = [recolor_frames(parser, blender, codeformer, esr, D[i:i + chunk], targets_u8[i:i + chunk], flip_target, w) for i in range(0, n, chunk)]
     return D, (rec[0] if len(rec) == 1 else torch.cat(rec))
+
+
+# ------------------------------------------------------------------------------------ f25: face inpainting, stage 1
+@torch.no_grad()
+def inpaint_faces(net, faces_u8: torch.Tensor, mask: torch.Tensor, noise=None, generator=None) -> torch.Tensor:
+    """The whole of ``inpainting(face_img, mask)`` (swap_face_fine/face_inpainting.py:21-51) for a batch on the device: ``ops.pil_resize(faces, (S, S))``
+    (Pillow's default BICUBIC, bit-exact), ``ops.cv_mask_support(mask, S)`` (``cv2.resize(mask.astype(float), (S, S)) > 0``, a restatement cv2 was never run
+    against) and ``ops.inpaint_image`` (the network's input with each face's own hole share, ``FaceInpaintingArch``, the clamp, the composite and the rounding).
+    ``faces_u8``: uint8 ``[n, H, W, 3]`` RGB; ``mask``: non-negative float32 or uint8 ``[n, h, w]``, anything above zero is hole; ``net``: an
+    ``ops.FaceInpainting`` in eval mode or a mapping with its keys, whose size ``S`` (256 for ``net_g_50000.pth``) is read off them; ``noise`` / ``generator`` as
+    ``ops.inpaint_forward`` takes them (None: fresh normal noise per call, as the reference draws it).  Returns uint8 ``[n, S, S, 3]``; an empty batch returns an
+    empty tensor.  The rest of the caller's ``_inpaint_face`` (the dilation and blurs of the mask, CodeFormer, the resize back and the blend) is stage 2.  Every
+    argument is checked before the first launch."""
+    from . import ops_inpaint
+    name = "inpaint_faces"
+    checked = ops_inpaint._weights_checked(name, net)
+    S = checked[1][0]
+    netweights._tensor_checked(name, "faces_u8", faces_u8, torch.uint8, 4, "uint8 [n, H, W, 3] RGB faces")
+    n, H, W, c = faces_u8.shape
+    if c != 3 or H < 1 or W < 1:
+        raise ValueError(f"{name}: faces_u8: expected uint8 [n, H, W, 3] RGB faces, got {tuple(faces_u8.shape)}")
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.float32, torch.uint8) or mask.dim() != 3:
+        raise ValueError(f"{name}: mask: expected a float32 or uint8 [n, h, w] tensor, got {getattr(mask, 'dtype', type(mask).__name__)} "
+                         f"{tuple(getattr(mask, 'shape', ()))}")
+    if mask.shape[0] != n or mask.shape[1] < 1 or mask.shape[2] < 1 or max(mask.shape[1:]) > ops_inpaint.INPAINT_MAX_SIDE:
+        raise ValueError(f"{name}: mask is {tuple(mask.shape)}: a mask of another batch or an empty or oversized one, expected [{n}, h, w] with "
+                         f"1 <= h, w <= {ops_inpaint.INPAINT_MAX_SIDE}")
+    netweights._cuda_checked(name, faces_u8=faces_u8, mask=mask)
+    netweights._devices_checked(name, "faces_u8", faces_u8, checked[2])
+    if mask.device != faces_u8.device:
+        raise RuntimeError(f"{name}: device mismatch: mask on {mask.device}, faces_u8 on {faces_u8.device}")
+    if noise is not None:
+        ops_inpaint._noise_checked(name, noise, n, S, faces_u8.device)
+    ops_inpaint._generator_checked(name, generator, faces_u8.device)
+    ops_inpaint._arith_checked(name)
+    if n == 0:
+        return torch.empty((0, S, S, 3), dtype=torch.uint8, device=faces_u8.device)
+    return ops_inpaint.inpaint_image(ops.pil_resize(faces_u8, (S, S)), ops_inpaint.cv_mask_support(mask, S), net, noise=noise, generator=generator)

@@ -40,6 +40,7 @@ __all__ = [
     "seeded_dense_motion_state_dict",
     "seeded_generator_state_dict",
     "seeded_codeformer_state_dict",
+    "seeded_inpaint_state_dict",
     "seeded_state_dict",
     "apply_seeded",
     "blocky_labels",
@@ -565,10 +566,42 @@ def seeded_codeformer_state_dict(seed: int, dim_embd: int = 512, n_head: int = 8
     return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in shapes.items()}, seed, "codeformer")
 
 
+# The GCFSR inpainting generator (swap_face_fine/gcfsr_arch.py FaceInpaintingArch; ``ops.FaceInpainting`` has its keys): equalised-lr layers, so unit-variance
+# weights.  The reference initialises the noise-injection weights, every bias and the shift convolutions' biases to zero and the condition linears' biases to one;
+# here the noise weights, both condition linears (weight: magnitude 0.3 - 0.82, either sign; bias: 0.24 - 0.76) and the shift convolutions' biases (magnitude 0.3 -
+# 0.82) are set well away from 0 and 1: a dropped noise term, a swapped scale or a missing bias then shows in the output.  The stored ``noises.noise{i}`` buffers
+# (never read by either side) are normal draws.  The ToRGB biases sum to about 0.5 along the skip chain and INPAINT_RGB_GAIN scales the ToRGB weights so that
+# the output straddles [0, 1]: at least half of the values inside a hole lie strictly inside (0, 1) on the tests' cases (tests/golden/make_golden_inpaint.py
+# asserts it and records the shares), so that the caller's clamp does not hide the network.
+INPAINT_RGB_GAIN = 0.12
+
+_RULES_INPAINT = [
+    (r"^noises\.noise\d+$", (0.0, 1.0, "normal")),
+    (r"^style_conv(1|s\.\d+)\.weight$", _gpen_noise_weight),
+    (r"^condition_scale[12]\.\d+\.weight$", _gpen_noise_weight),
+    (r"^condition_scale[12]\.\d+\.bias$", (0.5, 0.15)),
+    (r"^condition_shift\.\d+\.0\.bias$", _gpen_noise_weight),
+    (r"\.modulation\.bias$", (1.0, 0.1)),
+    (r"\.modulation\.weight$", (0.0, 1.0)),
+    (r"^to_rgb.*\.modulated_conv\.weight$", (0.0, INPAINT_RGB_GAIN)),
+    (r"^to_rgb1\.bias$", (0.5, 0.05)),
+    (r"^to_rgbs\.\d+\.bias$", (0.0, 0.05)),
+    (r"\.bias$", (0.0, 0.1)),
+    (r"\.weight$", (0.0, 1.0)),
+]
+
+
+def seeded_inpaint_state_dict(seed: int, out_size: int = 256) -> Dict[str, torch.Tensor]:
+    """Seed-only weights for ``ops.FaceInpainting(out_size)`` (the keys of ``net_g_50000.pth``'s ``params_ema`` at 256)."""
+    from .ops_inpaint import inpaint_state_dict_shapes
+    return seeded_state_dict({k: torch.empty(v, device="meta") for k, v in inpaint_state_dict_shapes(out_size).items()}, seed, "inpaint")
+
+
 def _resolve(family: str, seed: int, key: str, shape, dtype) -> torch.Tensor:
     rules = {"net3": _RULES_NET3, "lpips": _RULES_LPIPS, "irse50": _RULES_IRSE50, "unet": _RULES_UNET, "resunet": _RULES_RESUNET,
              "fpn": _RULES_FPN, "rrdb": _RULES_RRDB, "gpen": _RULES_GPEN, "parsenet": _RULES_PARSENET,
-             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM, "v2v_gen": _RULES_V2V_GEN, "codeformer": _RULES_CODEFORMER}.get(family, _RULES_BISENET)
+             "retinaface": _RULES_RETINAFACE, "v2v_kp": _RULES_V2V_KP, "v2v_dm": _RULES_V2V_DM, "v2v_gen": _RULES_V2V_GEN, "codeformer": _RULES_CODEFORMER,
+             "inpaint": _RULES_INPAINT}.get(family, _RULES_BISENET)
     for pat, rule in rules:
         if re.search(pat, key):
             break

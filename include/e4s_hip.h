@@ -1173,6 +1173,37 @@ E4S_API int e4s_sk_resize_u8(float* out, uint8_t* part, const uint8_t* img, cons
                              const int* xstart, const int* xcount, const void* xweight, int Tx, int bs, int H, int W, int Ho, int Wo, int chw, void* stream);
 E4S_API int e4s_frames_u8(uint8_t* out, const float* x, int n, int H, int W, int flip, void* stream);
 
+/* f25: face inpainting, stage 1 — what FaceInpaintingArch.forward (swap_face_fine/gcfsr_arch.py:1347-1540) and the ends of inpainting()
+ * (swap_face_fine/face_inpainting.py:21-51) need beside e4s_upfirdn2d, e4s_conv2d(_sb), e4s_grouped_linear, e4s_style_demod_batched, the single-region modulated
+ * convolutions and e4s_region_torgb; csrc/gcfsr.hip.
+ *   e4s_gcfsr_input           : x [bs][4][S][S]: planes 0 .. 2 = float32(double(byte) / 255.0) * (1 - m) of img uint8 [bs][S][S][3], plane 3 = m, for the hole mask
+ *                               uint8 [bs][S][S] (0 = keep, anything else = hole).  count [bs] = the hole pixels of a sample, summed in two levels of integers
+ *                               (part int32 [bs][64] is written by the call's first kernel and read by its second); in_size [bs] = float(count) / float(S S), one
+ *                               correctly rounded division of two exact operands (S <= 4096).
+ *   e4s_gcfsr_condition       : for every level l (w1, b1, w2, b2: HOST arrays of `levels` device pointers to condition_scale1/2[l].weight [C_l][1] and .bias [C_l];
+ *                               channels: HOST int [levels]) and sample b: s1 = fl(w1 c) + b1, s2 = fl(w2 c) + b2 with c = in_size[b]; n = fl(fl(fl(s1 s1) + fl(s2 s2))
+ *                               + 1e-8f); r = 1 / sqrt(n) (IEEE square root, then IEEE division); s1n = s1 r, s2n = s2 r.  The tables are [bs][sum C_l], the levels
+ *                               side by side in the order given.  Norm2Scale (gcfsr_arch.py:702-705) up to rsqrt's last bit.  At most 8 levels.
+ *   e4s_gcfsr_scale_shift_act : y [bs][C][hw] <- lrelu(fl(fl(fl(y s1n[b][c]) + fl(shift[b][c][p] s2n[b][c])) + bias[c]), 0.2) * float32(sqrt 2) in place: the tail
+ *                               of StyleConv_norm_scale_shift.forward (:741-744) behind the modulated convolution and the noise.  s1n / s2n point at the level's
+ *                               first channel in the tables above, table_stride is the tables' row length.  16-byte accesses when hw % 4 == 0 and y and shift are
+ *                               16-byte aligned, single elements otherwise, the same bits both ways.
+ *   e4s_gcfsr_tail            : out uint8 [bs][S][S][3] = rint(v * 255.0f), half to even, with v = float32(double(byte) / 255.0) outside the hole and
+ *                               clamp(img, 0, 1) inside it (x (1 - m) + o m for m in {0, 1}); img float32 [bs][3][S][S], in_u8 [bs][S][S][3], mask [bs][S][S].
+ *   e4s_cv_mask_support       : out uint8 [bs][S][S] = 1 where any mask value of source rows ystart[y] .. ystart[y] + ycount[y] - 1 and columns xstart[x] ..
+ *                               xstart[x] + xcount[x] - 1 is > 0, else 0: (cv2.resize(mask.astype(float64), (S, S)) > 0) for a non-negative mask [bs][H][W]
+ *                               (float32: is_f32 != 0, else uint8), given the taps with a non-zero weight, made on the host (e4s2024_amd/ops_inpaint.py).  start is
+ *                               clamped to the mask and count to 1 .. 2 on the device: no table content makes an access leave a tensor.
+ * Plain vector loads and stores, no atomics, no host synchronisation, grids from shapes alone: the calls can be captured in a graph.  bs == 0 returns at once. */
+E4S_API int e4s_gcfsr_input(float* x, int* count, float* in_size, int* part, const uint8_t* img, const uint8_t* mask, int bs, int S, void* stream);
+E4S_API int e4s_gcfsr_condition(float* s1n, float* s2n, const float* in_size, const float* const* w1, const float* const* b1, const float* const* w2,
+                                const float* const* b2, const int* channels, int levels, int bs, void* stream);
+E4S_API int e4s_gcfsr_scale_shift_act(float* y, const float* shift, const float* s1n, const float* s2n, const float* bias, int bs, int C, int hw,
+                                      int64_t table_stride, void* stream);
+E4S_API int e4s_gcfsr_tail(uint8_t* out, const float* img, const uint8_t* in_u8, const uint8_t* mask, int bs, int S, void* stream);
+E4S_API int e4s_cv_mask_support(uint8_t* out, const void* mask, int is_f32, const int* ystart, const int* ycount, const int* xstart, const int* xcount, int bs,
+                                int H, int W, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
