@@ -1,5 +1,6 @@
 """What the frozen loss networks of the PTI objective (``ops_lpips``, ``ops_id``, ``ops_fp``) have in common on the host side, and what the stage networks
-(``ops_recolor``, ``ops_rrdb``, ``ops_gpen``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``) take from it: BatchNorm folding, weight preparation for and the calls of the convolutions of csrc/conv.hip (split-bf16: ``prep_fwd`` / ``prep_dgrad`` / ``conv_sb``; exact float32:
+(``ops_recolor``, ``ops_rrdb``, ``ops_parsenet``, ``ops_retinaface``, ``ops_reenact``, and through ``sg2net`` the two StyleGAN2 generators ``ops_gpen`` and
+``ops_inpaint``) take from it: BatchNorm folding, weight preparation for and the calls of the convolutions of csrc/conv.hip (split-bf16: ``prep_fwd`` / ``prep_dgrad`` / ``conv_sb``; exact float32:
 ``prep_exact`` / ``conv_exact``), the banded resampler of csrc/idloss.hip and its adjoint, the cosine heads, two small kernels, and the checks and call
 arguments of the multi-target heads.  Taking a network's weights from a caller (validation, the cache of prepared copies) is ``netweights``'.  The library is
 resolved inside the calls only, so the module imports on a machine without it.
@@ -78,10 +79,11 @@ def prep_dgrad(w, out_scale=None, in_scale=None):
 
 
 # ------------------------------------------------------------------------------------------------ convolution
-def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, residual=None, x1=None, slope=None, out=None):
+def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, residual=None, x1=None, slope=None, out=None, stream=None):
     """Split-bf16 convolution of csrc/conv.hip on prepared ``slabs``: three-way (``prep_fwd``) or two-way (``prep_dgrad``); ``pad`` defaults to k // 2.
     Input channels come from ``x`` and then ``x1`` (a concatenation that is never formed); ``slope [cout]`` makes the activation a PReLU; ``residual`` is
-    added before it; ``out``: the ``[bs, cout, ho, wo]`` tensor (or view of a larger buffer) to write into."""
+    added before it; ``out``: the ``[bs, cout, ho, wo]`` tensor (or view of a larger buffer) to write into; ``stream``: the current stream, where the caller has looked
+    it up already."""
     bs, c0, h, w = x.shape
     cin = c0 if x1 is None else c0 + x1.shape[1]
     cout = slabs[0].shape[3]
@@ -89,20 +91,20 @@ def conv_sb(x, slabs, bias=None, *, k: int, stride: int = 1, pad: Optional[int] 
     if out is None:
         out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
     lib().call("e4s_conv2d_sb3" if len(slabs) == 3 else "e4s_conv2d_sb", _p(out), _p(x), _p(x1), c0, *[_p(s) for s in slabs], _p(bias), None, None, _p(slope),
-               _p(residual), 2 if slope is not None else 1 if relu else 0, bs, cin, cout, h, w, k, stride, pad, _stream())
+               _p(residual), 2 if slope is not None else 1 if relu else 0, bs, cin, cout, h, w, k, stride, pad, _stream() if stream is None else stream)
     return out
 
 
-def conv_exact(x, wt, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, slope=None, residual=None, out=None):
+def conv_exact(x, wt, bias=None, *, k: int, stride: int = 1, pad: Optional[int] = None, relu: bool = False, slope=None, residual=None, out=None, stream=None):
     """Exact-float32 convolution of csrc/conv.hip (``e4s_conv2d``) on a K-major weight (``prep_exact``, or ``e4s_conv_prep_weights``' copy of that layout);
-    ``pad``, ``slope``, ``residual`` and ``out`` as ``conv_sb`` takes them."""
+    ``pad``, ``slope``, ``residual``, ``out`` and ``stream`` as ``conv_sb`` takes them."""
     bs, cin, h, w = x.shape
     cout = wt.numel() // (cin * k * k)
     pad = k // 2 if pad is None else pad
     if out is None:
         out = torch.empty((bs, cout, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1), dtype=torch.float32, device=x.device)
     lib().call("e4s_conv2d", _p(out), _p(x), None, 0, _p(wt), _p(bias), None, None, _p(slope), _p(residual), 2 if slope is not None else 1 if relu else 0,
-               bs, cin, cout, h, w, k, stride, pad, _stream())
+               bs, cin, cout, h, w, k, stride, pad, _stream() if stream is None else stream)
     return out
 
 

@@ -3,13 +3,14 @@ between the tensor ends of ``FaceGAN`` (face_gan.py:49-62): ``gpen_forward``, ``
 detector, the 5-point warps, ParseNet, the RealESRNet pass, the paste mask, ``cv2.resize``) is rows f13 - f16; ``pipeline.gpen_face_enhancement`` chains them.
 
 The network is a StyleGAN2 synthesis network behind a strided-convolution encoder, with one style per sample; its contractions run on kernels the library
-has for the regional generator, in their single-region form (``nreg = 1``, no label map), the rest on csrc/gpen.hip:
+has for the regional generator, in their single-region form (``nreg = 1``, no label map), the rest on csrc/gpen.hip.  The key-mirror modules, the stock
+restatement of the layers, the weight preparation and the calls it shares with ``ops_inpaint`` are ``sg2net``'s:
 
     ecd0               e4s_gpen_stem: 1 x 1 convolution 3 -> C0, bias, leaky-relu * sqrt(2) in exact float32; from uint8 it applies img2tensor's roundings too
     ecd1 ..            e4s_upfirdn2d (4 x 4 FIR, pad (2, 2)), then e4s_conv2d_sb (3 x 3, stride 2, pad 0): sqrt(2) of the fused activation is folded into weight
                        and bias in float64 (leaky-relu is positively homogeneous), the PReLU epilogue with a 0.2 slope vector is then FusedLeakyReLU exactly
     final_linear, MLP  e4s_grouped_linear (groups = 1, act = 2) with EqualLinear's scale and lr_mul; PixelNorm between them is three stock tensor operations
-    tables             every layer's style and demodulation tables in one e4s_style_demod_batched call: the one latent is known before the first layer runs
+    tables             every layer's style and demodulation tables in one batched call (``sg2net.style_tables``): the one latent is known before the first layer runs
     StyledConv         the modulated convolution writes planes [0, C) of the layer's [2C, h, w] buffer with the first C entries of the activation bias and no
                        additive noise; e4s_gpen_noise_half writes lrelu(noise.weight * f_r + bias[C:]) * sqrt(2) into planes [C, 2C), one launch for both layers
                        of a resolution.  The concatenation is never copied.
@@ -33,23 +34,21 @@ batch-of-one call.  Forward only; no host synchronisation; the same inputs give 
 captures in a graph."""
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import netweights
-from ._lib import MAX_STYLE_JOBS, StyleJob, lib
-from .ops import _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
+from . import netweights, sg2net
+from ._lib import lib
+from .ops import _p, _stream, grouped_linear
 from .netweights import PreparedNet, _Net, _cuda_checked, _image_checked, _keys_shapes, _placed_checked, _tensor_checked, _validated, module_net, prepare
+from .sg2net import SQRT2, Bias, EqualConv, EqualLinear, Fir, ModConv, flrelu, torch_modconv, upfirdn
 
 ARITH = "sb"                                 # "sb" | "f32" (module attribute, no environment variable: tests and tools set it)
 UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form (measured: see the module text)
 LR_MLP = 0.01
-SQRT2 = math.sqrt(2.0)
-_FIR = (1.0, 3.0, 3.0, 1.0)
 
 
 def gpen_channels(channel_multiplier: int = 2, narrow: float = 1):
@@ -61,49 +60,6 @@ def gpen_channels(channel_multiplier: int = 2, narrow: float = 1):
 
 
 # ------------------------------------------------------------------------------------------------ the module: the reference's keys, a stock-PyTorch forward
-class _Fir(nn.Module):
-    """``Blur`` / ``Upsample``: the FIR buffer ``kernel``."""
-
-    def __init__(self, gain: float = 1.0):
-        super().__init__()
-        k = torch.tensor(_FIR, dtype=torch.float32)
-        k = k[None, :] * k[:, None]
-        k = k / k.sum()
-        self.register_buffer("kernel", k * gain if gain != 1.0 else k)
-
-
-class _EqualLinear(nn.Module):
-    def __init__(self, in_dim, out_dim, bias_init=0.0, lr_mul=1.0):
-        super().__init__()
-        self.weight = nn.Parameter(torch.randn(out_dim, in_dim).div_(lr_mul))
-        self.bias = nn.Parameter(torch.zeros(out_dim).fill_(bias_init))
-        self.lr_mul = lr_mul
-        self.scale = (1 / math.sqrt(in_dim)) * lr_mul
-
-
-class _EqualConv(nn.Module):
-    def __init__(self, cin, cout, k):
-        super().__init__()
-        self.weight = nn.Parameter(torch.randn(cout, cin, k, k))
-
-
-class _Bias(nn.Module):
-    """``FusedLeakyReLU``: its bias."""
-
-    def __init__(self, c):
-        super().__init__()
-        self.bias = nn.Parameter(torch.zeros(c))
-
-
-class _ModConv(nn.Module):
-    def __init__(self, cin, cout, k, style_dim, up=False):
-        super().__init__()
-        if up:
-            self.blur = _Fir(4.0)
-        self.weight = nn.Parameter(torch.randn(1, cout, cin, k, k))
-        self.modulation = _EqualLinear(style_dim, cin, bias_init=1.0)
-
-
 class _Noise(nn.Module):
     def __init__(self):
         super().__init__()
@@ -113,17 +69,17 @@ class _Noise(nn.Module):
 class _StyledConv(nn.Module):
     def __init__(self, cin, cout, style_dim, up=False):
         super().__init__()
-        self.conv = _ModConv(cin, cout, 3, style_dim, up)
+        self.conv = ModConv(cin, cout, 3, style_dim, 4.0 if up else None)
         self.noise = _Noise()
-        self.activate = _Bias(2 * cout)
+        self.activate = Bias(2 * cout)
 
 
 class _ToRGB(nn.Module):
     def __init__(self, cin, style_dim, up=True):
         super().__init__()
         if up:
-            self.upsample = _Fir(4.0)
-        self.conv = _ModConv(cin, 3, 1, style_dim)
+            self.upsample = Fir(4.0)
+        self.conv = ModConv(cin, 3, 1, style_dim)
         self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
 
 
@@ -136,7 +92,7 @@ class _Input(nn.Module):
 class _Generator(nn.Module):
     def __init__(self, size, style_dim, n_mlp, ch):
         super().__init__()
-        self.style = nn.Sequential(nn.Identity(), *[_EqualLinear(style_dim, style_dim, lr_mul=LR_MLP) for _ in range(n_mlp)])    # (0: PixelNorm)
+        self.style = nn.Sequential(nn.Identity(), *[EqualLinear(style_dim, style_dim, lr_mul=LR_MLP) for _ in range(n_mlp)])    # (0: PixelNorm)
         self.input = _Input(ch[4])
         self.conv1 = _StyledConv(ch[4], ch[4], style_dim)
         self.to_rgb1 = _ToRGB(2 * ch[4], style_dim, up=False)
@@ -175,13 +131,13 @@ class GPEN(nn.Module):
         self.log_size = int(math.log2(size))
         self.n_latent = 2 * self.log_size - 2
         self.generator = _Generator(size, style_dim, n_mlp, ch)
-        self.ecd0 = nn.Sequential(nn.Sequential(_EqualConv(3, ch[size], 1), _Bias(ch[size])))          # (a ConvLayer inside a Sequential)
+        self.ecd0 = nn.Sequential(nn.Sequential(EqualConv(3, ch[size], 1), Bias(ch[size])))          # (a ConvLayer inside a Sequential)
         cin = ch[size]
         for i in range(self.log_size, 2, -1):
             cout = ch[2 ** (i - 1)]
-            setattr(self, f"ecd{self.log_size - i + 1}", nn.Sequential(nn.Sequential(_Fir(), _EqualConv(cin, cout, 3), _Bias(cout))))
+            setattr(self, f"ecd{self.log_size - i + 1}", nn.Sequential(nn.Sequential(Fir(), EqualConv(cin, cout, 3), Bias(cout))))
             cin = cout
-        self.final_linear = nn.Sequential(_EqualLinear(16 * ch[4], style_dim))
+        self.final_linear = nn.Sequential(EqualLinear(16 * ch[4], style_dim))
         self.requires_grad_(False)
         self._loaded = False
 
@@ -199,68 +155,38 @@ class GPEN(nn.Module):
         return image, (latent if return_latents else None)
 
 
-def _flrelu(x, bias):
-    return F.leaky_relu(x + bias.view((1, -1) + (1,) * (x.dim() - 2)), 0.2) * SQRT2
-
-
-def _upfirdn(x, k, up, pad):
-    bs, c, h, w = x.shape
-    if up > 1:
-        z = x.new_zeros(bs, c, h, up, w, up)
-        z[:, :, :, 0, :, 0] = x
-        x = z.reshape(bs, c, h * up, w * up)
-    x = F.pad(x, (pad[0], pad[1], pad[0], pad[1]))
-    out = F.conv2d(x.reshape(bs * c, 1, x.shape[2], x.shape[3]), torch.flip(k, [0, 1])[None, None])
-    return out.reshape(bs, c, out.shape[2], out.shape[3])
-
-
-def _torch_modconv(sd, p, x, w, up=False, demodulate=True):
-    W = sd[p + ".weight"][0]
-    cout, cin, k, _ = W.shape
-    s = F.linear(w, sd[p + ".modulation.weight"] * (1 / math.sqrt(w.shape[1])), sd[p + ".modulation.bias"])
-    Wm = (1 / math.sqrt(cin * k * k)) * W[None] * s[:, None, :, None, None]
-    if demodulate:
-        Wm = Wm * torch.rsqrt(Wm.pow(2).sum([2, 3, 4]) + 1e-8)[:, :, None, None, None]
-    bs, _, h, wd = x.shape
-    xg = x.reshape(1, bs * cin, h, wd)
-    if up:
-        out = F.conv_transpose2d(xg, Wm.transpose(1, 2).reshape(bs * cin, cout, k, k), stride=2, groups=bs)
-        return _upfirdn(out.reshape(bs, cout, out.shape[2], out.shape[3]), sd[p + ".blur.kernel"], 1, (1, 1))
-    return F.conv2d(xg, Wm.reshape(bs * cout, cin, k, k), padding=k // 2, groups=bs).reshape(bs, cout, h, wd)
-
-
 def _torch_styled(sd, p, x, w, noise, up=False):
-    y = _torch_modconv(sd, p + ".conv", x, w, up)
-    return _flrelu(torch.cat((y, sd[p + ".noise.weight"] * noise), 1), sd[p + ".activate.bias"])
+    y = torch_modconv(sd, p + ".conv", x, w, up, blur=sd[p + ".conv.blur.kernel"] if up else None)
+    return flrelu(torch.cat((y, sd[p + ".noise.weight"] * noise), 1), sd[p + ".activate.bias"])
 
 
 def _torch_forward(sd, x, log_size):
     feats = []
     W = sd["ecd0.0.0.weight"]
-    x = _flrelu(F.conv2d(x, W * (1 / math.sqrt(W.shape[1]))), sd["ecd0.0.1.bias"])
+    x = flrelu(F.conv2d(x, W * (1 / math.sqrt(W.shape[1]))), sd["ecd0.0.1.bias"])
     feats.append(x)
     for i in range(1, log_size - 1):
         W = sd[f"ecd{i}.0.1.weight"]
-        x = _flrelu(F.conv2d(_upfirdn(x, sd[f"ecd{i}.0.0.kernel"], 1, (2, 2)), W * (1 / math.sqrt(W.shape[1] * 9)), stride=2), sd[f"ecd{i}.0.2.bias"])
+        x = flrelu(F.conv2d(upfirdn(x, sd[f"ecd{i}.0.0.kernel"], 1, (2, 2)), W * (1 / math.sqrt(W.shape[1] * 9)), stride=2), sd[f"ecd{i}.0.2.bias"])
         feats.append(x)
     W = sd["final_linear.0.weight"]
-    z = _flrelu(F.linear(x.reshape(x.shape[0], -1), W * (1 / math.sqrt(W.shape[1]))), sd["final_linear.0.bias"])
+    z = flrelu(F.linear(x.reshape(x.shape[0], -1), W * (1 / math.sqrt(W.shape[1]))), sd["final_linear.0.bias"])
     z = z * torch.rsqrt(torch.mean(z ** 2, dim=1, keepdim=True) + 1e-8)
     i = 1
     while f"generator.style.{i}.weight" in sd:
         W = sd[f"generator.style.{i}.weight"]
-        z = _flrelu(F.linear(z, W * ((1 / math.sqrt(W.shape[1])) * LR_MLP)), sd[f"generator.style.{i}.bias"] * LR_MLP)
+        z = flrelu(F.linear(z, W * ((1 / math.sqrt(W.shape[1])) * LR_MLP)), sd[f"generator.style.{i}.bias"] * LR_MLP)
         i += 1
     noise = [f for f in feats[::-1] for _ in (0, 1)][1:]
     g = "generator."
     out = sd[g + "input.input"].repeat(x.shape[0], 1, 1, 1)
     out = _torch_styled(sd, g + "conv1", out, z, noise[0])
-    skip = _torch_modconv(sd, g + "to_rgb1.conv", out, z, demodulate=False) + sd[g + "to_rgb1.bias"]
+    skip = torch_modconv(sd, g + "to_rgb1.conv", out, z, demodulate=False) + sd[g + "to_rgb1.bias"]
     for j in range(log_size - 2):
         out = _torch_styled(sd, f"{g}convs.{2 * j}", out, z, noise[1 + 2 * j], up=True)
         out = _torch_styled(sd, f"{g}convs.{2 * j + 1}", out, z, noise[2 + 2 * j])
         p = f"{g}to_rgbs.{j}"
-        skip = _torch_modconv(sd, p + ".conv", out, z, demodulate=False) + sd[p + ".bias"] + _upfirdn(skip, sd[p + ".upsample.kernel"], 2, (2, 1))
+        skip = torch_modconv(sd, p + ".conv", out, z, demodulate=False) + sd[p + ".bias"] + upfirdn(skip, sd[p + ".upsample.kernel"], 2, (2, 1))
     return skip, z[:, None].repeat(1, 2 * log_size - 2, 1)
 
 
@@ -319,8 +245,10 @@ def check_loaded(weights):
     return weights
 
 
-def _use_composed(w_in: int) -> bool:
-    return ARITH != "sb" or w_in <= UP_COMPOSED_MAX_WIDTH
+def _weights_checked(name, weights):
+    """``_validated``'s result for ``weights``, refused first if they are a module that never loaded any."""
+    check_loaded(weights)
+    return _validated(name, weights, _net_of(weights))
 
 
 class PreparedGPEN(PreparedNet):
@@ -342,45 +270,22 @@ class PreparedGPEN(PreparedNet):
         size, sdim, n_mlp, _, _ = variant
         log_size = int(math.log2(size))
         sb = ARITH == "sb"
-        st = _stream()
-        new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
 
         def enc_level(i):
-            W, b = sd[f"ecd{i}.0.1.weight"], sd[f"ecd{i}.0.2.bias"]
-            cout, cin = W.shape[:2]
-            w = (W.double() * (SQRT2 / math.sqrt(cin * 9))).float().contiguous()
-            bias = (b.double() * SQRT2).float().contiguous()
-            if sb:
-                wt = tuple(new(((cin + 15) // 16, 9, 2, cout, 8), torch.int16) for _ in range(2))
-                lib().call("e4s_conv_prep_weights_sb", _p(wt[0]), _p(wt[1]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
-            else:
-                wt = new((cin, 9, cout))
-                lib().call("e4s_conv_prep_weights", _p(wt), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
-            return dict(fir=sd[f"ecd{i}.0.0.kernel"], wt=wt, bias=bias, slope=torch.full((cout,), 0.2, dtype=torch.float32, device=dev), cin=cin, cout=cout)
+            return dict(sg2net.prep_conv3x3(sd[f"ecd{i}.0.1.weight"], sd[f"ecd{i}.0.2.bias"], SQRT2, sb, True), fir=sd[f"ecd{i}.0.0.kernel"])
 
         def styled(p, up, w_in):
             W = sd[p + ".conv.weight"]
-            _, cout, cin, _, _ = W.shape
-            composed = up and _use_composed(w_in)
+            composed = up and sg2net.use_composed(ARITH, UP_COMPOSED_MAX_WIDTH, w_in)
             blur = sd[p + ".conv.blur.kernel"] if up else None
-            wsq = new((cin, cout))
-            if sb:
-                shape = (4 if composed else 1, (cin + 15) // 16, 9, 2, cout, 8)
-                wt = (new(shape, torch.int16), new(shape, torch.int16))
-                lib().call("e4s_modconv_prep_weights_sb", _p(wt[0]), _p(wt[1]), _p(wsq), _p(W), _p(blur) if composed else None, cout, cin, 1 if composed else 0, st)
-            else:
-                wt = new((4 if composed else 1, cin, 9, cout))
-                lib().call("e4s_modconv_prep_weights", _p(wt), _p(wsq), _p(W), _p(blur) if composed else None, cout, cin, 3, 1 if composed else 0, st)
+            wt, wsq = sg2net.prep_styled(W, blur, composed, sb)
             return dict(wt=wt, wsq=wsq, mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], nw=sd[p + ".noise.weight"],
-                        bias=sd[p + ".activate.bias"], blur=blur, up=up, composed=composed, cin=cin, cout=cout)
+                        bias=sd[p + ".activate.bias"], blur=blur, up=up, composed=composed, cin=W.shape[2], cout=W.shape[1])
 
         def rgb(p, up):
             W = sd[p + ".conv.weight"]
-            cin = W.shape[2]
-            wt = new((1, cin, 1, 3))
-            lib().call("e4s_modconv_prep_weights", _p(wt), None, _p(W), None, 3, cin, 1, 0, st)
-            return dict(wt=wt, mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], bias=sd[p + ".bias"].reshape(3).contiguous(),
-                        upk=sd[p + ".upsample.kernel"] if up else None, cin=cin)
+            return dict(wt=sg2net.prep_rgb(W), mw=sd[p + ".conv.modulation.weight"], mb=sd[p + ".conv.modulation.bias"], bias=sd[p + ".bias"].reshape(3).contiguous(),
+                        upk=sd[p + ".upsample.kernel"] if up else None, cin=W.shape[2])
 
         W0 = sd["ecd0.0.0.weight"]
         g = "generator."
@@ -398,18 +303,19 @@ class PreparedGPEN(PreparedNet):
 
 # ------------------------------------------------------------------------------------------------ the forward pass
 def _scratch(P, dev):
-    """One sample's buffers, made once per call: the encoder's features (the decoder's noise), one blurred map sized for the largest level, every decoder
-    layer's [2C, h, w] output, the ToRGB chain, the style / demodulation tables and the two style vectors the linear layers alternate between."""
+    """One sample's buffers, made once per call: the encoder's features (the decoder's noise), one blurred map sized for the largest level (``blurs``: each
+    level's view of it), every decoder layer's [2C, h, w] output, the ToRGB chain, the style / demodulation tables and the two style vectors the linear layers
+    alternate between."""
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)               # noqa: E731
     size = P["size"]
     C0 = P["stem"][0].shape[0]
-    feats = [new(1, C0, size, size)]
+    feats, blurred = [new(1, C0, size, size)], []
     r = size
-    blur_floats = 1
     for L in P["enc"]:
-        blur_floats = max(blur_floats, L["cin"] * (r + 1) * (r + 1))
+        blurred.append((1, L["cin"], r + 1, r + 1))
         r //= 2
         feats.append(new(1, L["cout"], r, r))
+    blur = new(max(math.prod(shape) for shape in blurred))
     outs = []
     r = 4
     for L in P["convs"]:
@@ -418,53 +324,20 @@ def _scratch(P, dev):
         outs.append(new(1, 2 * L["cout"], r, r))
     n_s = sum(L["cin"] for L in P["convs"]) + sum(L["cin"] for L in P["rgbs"])
     n_d = sum(L["cout"] for L in P["convs"])
-    return dict(feats=feats, blur=new(blur_floats), outs=outs, rgb=[new(1, 3, 4 << j, 4 << j) for j in range(len(P["rgbs"]))], s=new(n_s), d=new(n_d),
-                z=[new(1, 1, P["sdim"]), new(1, 1, P["sdim"])])
+    return dict(feats=feats, blurs=[blur[:math.prod(shape)].view(shape) for shape in blurred], outs=outs,
+                rgb=[new(1, 3, 4 << j, 4 << j) for j in range(len(P["rgbs"]))], s=new(n_s), d=new(n_d), z=[new(1, 1, P["sdim"]), new(1, 1, P["sdim"])])
 
 
 def _tables(P, S, latent):
-    """Every layer's (s, d) from ``latent [1, 1, sdim]`` in one batched call; returns [(s, d)] for the convolutions and [s] for the ToRGBs."""
+    """Every layer's (s, d) from the one ``latent [1, 1, sdim]``; returns [(s, d)] for the convolutions and [s] for the ToRGBs."""
     layers = P["convs"] + P["rgbs"]
-    arr = (StyleJob * len(layers))()
-    so = do = 0
-    conv_t, rgb_t = [], []
-    for i, L in enumerate(layers):
-        s_t = S["s"][so:so + L["cin"]]
-        so += L["cin"]
-        d_t = None
-        if "wsq" in L:
-            d_t = S["d"][do:do + L["cout"]]
-            do += L["cout"]
-            conv_t.append((s_t, d_t))
-        else:
-            rgb_t.append(s_t)
-        arr[i] = StyleJob(s_t.data_ptr(), None if d_t is None else d_t.data_ptr(), latent.data_ptr(), latent.stride(0), latent.stride(1), L["mw"].data_ptr(),
-                          L["mb"].data_ptr(), None if d_t is None else L["wsq"].data_ptr(), 1, L["cin"], L.get("cout", 3), 0)
-    for i0 in range(0, len(layers), MAX_STYLE_JOBS):
-        lib().call("e4s_style_demod_batched", ctypes.byref(arr, i0 * ctypes.sizeof(StyleJob)), min(MAX_STYLE_JOBS, len(layers) - i0), 1, P["sdim"], _stream())
-    return conv_t, rgb_t
+    return sg2net.style_tables(layers, [(latent.data_ptr(), latent.stride(0), latent.stride(1))] * len(layers), 1, P["sdim"], S["s"], S["d"])
 
 
-def _modconv(P, L, x, out, s, d, h, w):
-    """The layer's modulated convolution on one sample into ``out`` (planes [0, C) of its buffer) with the first C activation-bias entries, leaky-relu * sqrt(2)."""
-    cin, cout = L["cin"], L["cout"]
-    st = _stream()
-    up = L["up"]
-    if up and not L["composed"]:
-        lib().call("e4s_modconv_up_fused_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), _p(L["blur"]), None, 0, None, _p(L["bias"]), 1,
-                   1, cin, cout, h, w, None, st)
-        return
-    ho, wo = (2 * h, 2 * w) if up else (h, w)
-    ws, wsn = None, 0
-    if cout * ho * wo <= SPLITK_MAX_OUT_FLOATS:
-        wsn = 16 * cout * ho * wo
-        ws = _workspace(x.device, wsn)
-    if P["sb"]:
-        lib().call("e4s_region_modconv3x3_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), None, 0, 0, None, 0, None, _p(L["bias"]), 1,
-                   1, cin, cout, h, w, 1, 1 if up else 0, _p(ws), wsn, None, None, None, None, None, None, None, None, None, st)
-    else:
-        lib().call("e4s_region_modconv3x3", _p(out), _p(x), _p(L["wt"]), _p(s), _p(d), None, 0, 0, None, 0, None, _p(L["bias"]), 1,
-                   1, cin, cout, h, w, 1, 1 if up else 0, _p(ws), wsn, st)
+def _modconv(P, L, x, out, s, d, h, st):
+    """The layer's modulated convolution on one sample into ``out`` (planes [0, C) of its buffer) with the first C activation-bias entries, leaky-relu * sqrt(2),
+    and no additive noise."""
+    sg2net.modconv(L, x, out, s, d, sb=P["sb"], blur=L["blur"], bias=L["bias"], act=1, bs=1, h=h, st=st)
 
 
 def _noise_half(f, layers, outs):
@@ -480,18 +353,12 @@ def _gpen_sample(P, S, x, x_u8, out_f, latent_row):
     """The network on one sample: ``x [1, 3, size, size]`` float32 or ``x_u8 [1, size, size, 3]``; the image goes to ``out_f [1, 3, size, size]``, the style
     vector to ``latent_row [1, 1, sdim]``."""
     st = _stream()
-    size, sdim = P["size"], P["sdim"]
+    size = P["size"]
     feats = S["feats"]
     lib().call("e4s_gpen_stem", _p(feats[0]), _p(x), _p(x_u8), _p(P["stem"][0]), _p(P["stem"][1]), 1, feats[0].shape[1], size, size, st)
     r = size
-    for L, src, dst in zip(P["enc"], feats[:-1], feats[1:]):
-        lib().call("e4s_upfirdn2d", _p(S["blur"]), _p(src), _p(L["fir"]), L["cin"], r, r, 4, 4, 1, 1, 1, 1, 2, 2, 2, 2, st)
-        if P["sb"]:
-            lib().call("e4s_conv2d_sb", _p(dst), _p(S["blur"]), None, L["cin"], _p(L["wt"][0]), _p(L["wt"][1]), _p(L["bias"]), None, None, _p(L["slope"]), None, 2,
-                       1, L["cin"], L["cout"], r + 1, r + 1, 3, 2, 0, st)
-        else:
-            lib().call("e4s_conv2d", _p(dst), _p(S["blur"]), None, L["cin"], _p(L["wt"]), _p(L["bias"]), None, None, _p(L["slope"]), None, 2,
-                       1, L["cin"], L["cout"], r + 1, r + 1, 3, 2, 0, st)
+    for L, src, dst, blur in zip(P["enc"], feats[:-1], feats[1:], S["blurs"]):
+        sg2net.conv3x3(L, src, dst, 1, r, P["sb"], st, L["fir"], blur)
         r //= 2
     f4 = feats[-1]
     za, zb = S["z"]
@@ -506,25 +373,23 @@ def _gpen_sample(P, S, x, x_u8, out_f, latent_row):
     conv_t, rgb_t = _tables(P, S, latent_row)
     convs, outs, rgbs = P["convs"], S["outs"], P["rgbs"]
     noise = feats[::-1]                                                                                 # f4, f8, ..., f_size
-    _modconv(P, convs[0], P["const"], outs[0][:, :convs[0]["cout"]], *conv_t[0], 4, 4)
+    _modconv(P, convs[0], P["const"], outs[0][:, :convs[0]["cout"]], *conv_t[0], 4, st)
     _noise_half(noise[0], convs[:1], outs[:1])
     n_rgb = len(rgbs)
 
     def torgb(j, x, skip, h):
         dst = out_f if j == n_rgb - 1 else S["rgb"][j]
-        R = rgbs[j]
-        lib().call("e4s_region_torgb", _p(dst), _p(x), _p(R["wt"]), _p(rgb_t[j]), None, 0, 0, _p(R["bias"]), _p(skip), _p(R["upk"]) if skip is not None else None,
-                   1, R["cin"], h, h, 1, st)
+        sg2net.torgb(rgbs[j], x, rgb_t[j], skip, rgbs[j]["upk"], dst, 1, h, st)
         return dst
 
     skip = torgb(0, outs[0], None, 4)
     h = 4
     for j in range(1, n_rgb):
         a, b = 2 * j - 1, 2 * j
-        _modconv(P, convs[a], outs[a - 1], outs[a][:, :convs[a]["cout"]], *conv_t[a], h, h)
+        _modconv(P, convs[a], outs[a - 1], outs[a][:, :convs[a]["cout"]], *conv_t[a], h, st)
         h *= 2
         _noise_half(noise[j], convs[a:b + 1], outs[a:b + 1])
-        _modconv(P, convs[b], outs[a], outs[b][:, :convs[b]["cout"]], *conv_t[b], h, h)
+        _modconv(P, convs[b], outs[a], outs[b][:, :convs[b]["cout"]], *conv_t[b], h, st)
         skip = torgb(j, outs[b], skip, h)
 
 
@@ -541,16 +406,14 @@ def _gpen_run(P, x, x_u8, want_latent):
 
 
 def _gpen_checked_all(name, weights, x=None, img_u8=None):
-    check_loaded(weights)
-    checked = _validated(name, weights, _net_of(weights))
+    checked = _weights_checked(name, weights)
     size = checked[1][0]
     t, nm, H, W, c = _image_checked(name, x, img_u8, "a float32 [bs, 3, size, size] image", "a uint8 [bs, size, size, 3] RGB image")
     if (c, H, W) != (3, size, size):
         expected = f"[bs, 3, {size}, {size}]" if x is not None else f"[bs, {size}, {size}, 3] (resizing to the network's size is the caller's)"
         raise ValueError(f"{name}: {nm} is {tuple(t.shape)}: the network's size is {size}, expected {expected}")
     _placed_checked(name, nm, t, checked[2])
-    if ARITH not in ("sb", "f32"):
-        raise ValueError(f"{name}: ops_gpen.ARITH is 'sb' or 'f32', got {ARITH!r}")
+    sg2net.arith_checked(name, "ops_gpen", ARITH)
     return checked
 
 

@@ -8,13 +8,14 @@ layer, and one new element: every second style convolution scales its output by 
 encoder feature of its resolution, and only then applies bias and activation.  The whole batch runs at once (nothing is concatenated, so every entry takes
 ``bs``), except the modulated convolutions on maps small enough for split-K (up to 64 x 64 at 512 channels), which run sample by sample: that entry picks its
 number of K slices from its grid, the batch included, so only a batch-of-one call gives a sample the bits it gets alone.  The contractions run on kernels the
-library has, the rest on csrc/gcfsr.hip:
+library has, the rest on csrc/gcfsr.hip.  The key-mirror modules, the stock restatement of the layers, the weight preparation and the calls it shares with
+``ops_gpen`` are ``sg2net``'s:
 
     conv_body_first, final_conv   e4s_conv2d_sb / e4s_conv2d (3 x 3, pad 1): sqrt(2) of the fused activation folded into weight and bias in float64, PReLU with a
                                   0.2 slope vector is then FusedLeakyReLU exactly (as ``ops_gpen``'s encoder levels)
     conv_body_down, final_down1/2 e4s_upfirdn2d (4 x 4 FIR, pad (2, 2)), then the strided convolution, the same folding
     final_linear                  e4s_grouped_linear (groups = 1, act = 2) on the channel-major flattening of the 4 x 4 map: the ``num_latent`` latent rows
-    tables                        every layer's style and demodulation tables in one e4s_style_demod_batched pass; layer i reads ``latent[:, i]``
+    tables                        every layer's style and demodulation tables in one batched pass (``sg2net.style_tables``); layer i reads ``latent[:, i]``
     condition_scale1/2, Norm2Scale  e4s_gcfsr_condition: every level in one launch
     condition_shift               e4s_conv2d_sb / e4s_conv2d with bias, no activation, on the encoder feature of each level
     StyleConv (the up layers)     e4s_region_modconv3x3_sb(up = 1) for inputs up to ``UP_COMPOSED_MAX_WIDTH`` wide, e4s_modconv_up_fused_sb above; the noise map
@@ -47,17 +48,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import netweights
-from ._lib import MAX_STYLE_JOBS, StyleJob, lib
-from .ops import _p, _stream, _workspace, grouped_linear, SPLITK_MAX_OUT_FLOATS
+from . import netweights, sg2net
+from ._lib import lib
+from .ops import _p, _stream, grouped_linear
 from .netweights import PreparedNet, _Net, _cuda_checked, _keys_shapes, _placed_checked, _tensor_checked, _validated, module_net, prepare
+from .sg2net import SQRT2, Bias, EqualConv, EqualLinear, ModConv, fir, flrelu, torch_modconv, upfirdn
 
 ARITH = "sb"                                 # "sb" | "f32" (module attribute: tests and tools set it)
 UP_COMPOSED_MAX_WIDTH = 32                   # up layers with an input at most this wide take the parity-composed, split-K form
 STYLE_DIM = 512
-SQRT2 = math.sqrt(2.0)
 INPAINT_MAX_SIDE = 16384                     # the largest mask side ``cv_mask_support`` takes
-_FIR = (1.0, 3.0, 3.0, 1.0)
 
 
 def inpaint_channels():
@@ -66,43 +66,13 @@ def inpaint_channels():
 
 
 # ------------------------------------------------------------------------------------------------ the module: the reference's keys, a stock-PyTorch forward
-class _Bias(nn.Module):
-    """``FusedLeakyReLU``: its bias."""
-
-    def __init__(self, c):
-        super().__init__()
-        self.bias = nn.Parameter(torch.zeros(c))
-
-
-class _EqualConv(nn.Module):
-    def __init__(self, cin, cout, bias=False):
-        super().__init__()
-        self.weight = nn.Parameter(torch.randn(cout, cin, 3, 3))
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(cout))
-
-
-class _EqualLinear(nn.Module):
-    def __init__(self, in_dim, out_dim, bias_init=0.0):
-        super().__init__()
-        self.weight = nn.Parameter(torch.randn(out_dim, in_dim))
-        self.bias = nn.Parameter(torch.zeros(out_dim).fill_(bias_init))
-
-
 def _conv_layer(cin, cout, down=False, activate=True):
     """``ConvLayer``: (the FIR, which has no keys,) the convolution, the activation's bias; without activation the bias is the convolution's."""
     layers = [nn.Identity()] if down else []
-    layers.append(_EqualConv(cin, cout, bias=not activate))
+    layers.append(EqualConv(cin, cout, bias=not activate))
     if activate:
-        layers.append(_Bias(cout))
+        layers.append(Bias(cout))
     return nn.Sequential(*layers)
-
-
-class _ModConv(nn.Module):
-    def __init__(self, cin, cout, k):
-        super().__init__()
-        self.weight = nn.Parameter(torch.randn(1, cout, cin, k, k))
-        self.modulation = _EqualLinear(STYLE_DIM, cin, bias_init=1.0)
 
 
 class _StyleConv(nn.Module):
@@ -111,15 +81,15 @@ class _StyleConv(nn.Module):
     def __init__(self, cin, cout):
         super().__init__()
         self.weight = nn.Parameter(torch.zeros(1))
-        self.modulated_conv = _ModConv(cin, cout, 3)
-        self.activate = _Bias(cout)
+        self.modulated_conv = ModConv(cin, cout, 3, STYLE_DIM)
+        self.activate = Bias(cout)
 
 
 class _ToRGB(nn.Module):
     def __init__(self, cin):
         super().__init__()
         self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
-        self.modulated_conv = _ModConv(cin, 3, 1)
+        self.modulated_conv = ModConv(cin, 3, 1, STYLE_DIM)
 
 
 def _size_checked(out_size):
@@ -148,10 +118,10 @@ class FaceInpainting(nn.Module):
         self.final_conv = _conv_layer(ch[16], ch[16])
         self.final_down1 = _conv_layer(ch[16], ch[8], down=True)
         self.final_down2 = _conv_layer(ch[8], ch[4] // 2, down=True)
-        self.final_linear = _EqualLinear(2 * 4 * 512, STYLE_DIM * self.num_latent)
+        self.final_linear = EqualLinear(2 * 4 * 512, STYLE_DIM * self.num_latent)
         levels = [ch[2 ** i] for i in range(self.log_size, 3, -1)]
-        self.condition_scale1 = nn.ModuleList(_EqualLinear(1, c, bias_init=1.0) for c in levels)
-        self.condition_scale2 = nn.ModuleList(_EqualLinear(1, c, bias_init=1.0) for c in levels)
+        self.condition_scale1 = nn.ModuleList(EqualLinear(1, c, bias_init=1.0) for c in levels)
+        self.condition_scale2 = nn.ModuleList(EqualLinear(1, c, bias_init=1.0) for c in levels)
         self.condition_shift = nn.ModuleList(_conv_layer(c, c, activate=False) for c in levels)
         self.style_conv1 = _StyleConv(ch[16], ch[16])
         self.to_rgb1 = _ToRGB(ch[16])
@@ -190,70 +160,31 @@ def noise_sizes(out_size: int):
     return [16] + [2 ** i for i in range(5, log_size + 1) for _ in (0, 1)]
 
 
-def _flrelu(x, bias):
-    return F.leaky_relu(x + bias.view((1, -1) + (1,) * (x.dim() - 2)), 0.2) * SQRT2
-
-
-@functools.lru_cache(maxsize=None)
-def _fir(gain=1.0, device=None):
-    """The 4 x 4 FIR times ``gain`` on ``device``, made once per device (no host-to-device copy inside a captured forward); read-only."""
-    k = torch.tensor(_FIR, dtype=torch.float32, device=device)
-    k = k[None, :] * k[:, None]
-    k = k / k.sum()
-    return k * gain if gain != 1.0 else k
-
-
-def _upfirdn(x, k, up, pad):
-    bs, c, h, w = x.shape
-    if up > 1:
-        z = x.new_zeros(bs, c, h, up, w, up)
-        z[:, :, :, 0, :, 0] = x
-        x = z.reshape(bs, c, h * up, w * up)
-    x = F.pad(x, (pad[0], pad[1], pad[0], pad[1]))
-    out = F.conv2d(x.reshape(bs * c, 1, x.shape[2], x.shape[3]), torch.flip(k, [0, 1])[None, None])
-    return out.reshape(bs, c, out.shape[2], out.shape[3])
-
-
 def _torch_conv_layer(sd, p, x, down=False, activate=True):
     i = 1 if down else 0
     W = sd[f"{p}.{i}.weight"]
     w = W * (1 / math.sqrt(W.shape[1] * 9))
     if down:
-        y = F.conv2d(_upfirdn(x, _fir(device=x.device), 1, (2, 2)), w, stride=2)
+        y = F.conv2d(upfirdn(x, fir(device=x.device), 1, (2, 2)), w, stride=2)
     else:
         y = F.conv2d(x, w, bias=None if activate else sd[f"{p}.{i}.bias"], padding=1)
-    return _flrelu(y, sd[f"{p}.{i + 1}.bias"]) if activate else y
-
-
-def _torch_modconv(sd, p, x, w, up=False, demodulate=True):
-    W = sd[p + ".weight"][0]
-    cout, cin, k, _ = W.shape
-    s = F.linear(w, sd[p + ".modulation.weight"] * (1 / math.sqrt(w.shape[1])), sd[p + ".modulation.bias"])
-    Wm = (1 / math.sqrt(cin * k * k)) * W[None] * s[:, None, :, None, None]
-    if demodulate:
-        Wm = Wm * torch.rsqrt(Wm.pow(2).sum([2, 3, 4]) + 1e-8)[:, :, None, None, None]
-    bs, _, h, wd = x.shape
-    xg = x.reshape(1, bs * cin, h, wd)
-    if up:
-        out = F.conv_transpose2d(xg, Wm.transpose(1, 2).reshape(bs * cin, cout, k, k), stride=2, groups=bs)
-        return _upfirdn(out.reshape(bs, cout, out.shape[2], out.shape[3]), _fir(4.0, x.device), 1, (1, 1))
-    return F.conv2d(xg, Wm.reshape(bs * cout, cin, k, k), padding=k // 2, groups=bs).reshape(bs, cout, h, wd)
+    return flrelu(y, sd[f"{p}.{i + 1}.bias"]) if activate else y
 
 
 def _torch_style_conv(sd, p, x, w, noise, up=False, cond=None):
-    out = _torch_modconv(sd, p + ".modulated_conv", x, w, up) + sd[p + ".weight"] * noise
+    out = torch_modconv(sd, p + ".modulated_conv", x, w, up, blur=fir(4.0, x.device) if up else None) + sd[p + ".weight"] * noise
     if cond is not None:
         s1, s2, shift = cond
         n = s1 ** 2 + s2 ** 2 + 1e-8
         s1, s2 = s1 * torch.rsqrt(n), s2 * torch.rsqrt(n)
         out = out * s1.view(-1, out.shape[1], 1, 1) + shift * s2.view(-1, out.shape[1], 1, 1)
-    return _flrelu(out, sd[p + ".activate.bias"])
+    return flrelu(out, sd[p + ".activate.bias"])
 
 
 def _torch_to_rgb(sd, p, x, w, skip):
-    out = _torch_modconv(sd, p + ".modulated_conv", x, w, demodulate=False) + sd[p + ".bias"]
+    out = torch_modconv(sd, p + ".modulated_conv", x, w, demodulate=False) + sd[p + ".bias"]
     if skip is not None:
-        out = out + _upfirdn(skip, _fir(4.0, x.device), 2, (2, 1))
+        out = out + upfirdn(skip, fir(4.0, x.device), 2, (2, 1))
     return out
 
 
@@ -272,7 +203,7 @@ def _torch_forward(sd, x, in_size, noise, log_size):
     cond = cond[::-1]
     tmp = _torch_conv_layer(sd, "final_down2", _torch_conv_layer(sd, "final_down1", feat, down=True), down=True)
     W = sd["final_linear.weight"]
-    latent = _flrelu(F.linear(tmp.reshape(bs, -1), W * (1 / math.sqrt(W.shape[1]))), sd["final_linear.bias"]).view(bs, -1, STYLE_DIM)
+    latent = flrelu(F.linear(tmp.reshape(bs, -1), W * (1 / math.sqrt(W.shape[1]))), sd["final_linear.bias"]).view(bs, -1, STYLE_DIM)
     out = _torch_conv_layer(sd, "final_conv", feat)
     out = _torch_style_conv(sd, "style_conv1", out, latent[:, 0], noise[0], cond=cond[0])
     skip = _torch_to_rgb(sd, "to_rgb1", out, latent[:, 1], None)
@@ -330,10 +261,6 @@ def inpaint_weight_tensors(weights, name: str = "inpaint_forward"):
     return _validated(name, weights, _net_of(weights))[2]
 
 
-def _use_composed(w_in: int) -> bool:
-    return ARITH != "sb" or w_in <= UP_COMPOSED_MAX_WIDTH
-
-
 class PreparedInpaint(PreparedNet):
     """The kernels' copies of the network's weights, rebuilt when a tensor changes version or storage or the arithmetic changes.  Per plain convolution (FIR or
     None, slabs or K-major fp32 weight, bias, slope vector or None) with sqrt(2) folded into weight and bias in float64 where an activation follows; the
@@ -354,55 +281,31 @@ class PreparedInpaint(PreparedNet):
         log_size = int(math.log2(out_size))
         n_cond = log_size - 3
         sb = ARITH == "sb"
-        st = _stream()
-        new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
-        fir1, fir4 = _fir(device=dev).contiguous(), _fir(4.0, dev).contiguous()
+        fir1, fir4 = fir(device=dev).contiguous(), fir(4.0, dev).contiguous()
 
         def conv(p, down=False, activate=True):
             i = 1 if down else 0
-            W = sd[f"{p}.{i}.weight"]
             b = sd[f"{p}.{i + 1}.bias"] if activate else sd[f"{p}.{i}.bias"]
-            cout, cin = W.shape[:2]
-            gain = SQRT2 if activate else 1.0
-            w = (W.double() * (gain / math.sqrt(cin * 9))).float().contiguous()
-            bias = (b.double() * gain).float().contiguous()
-            if sb:
-                wt = tuple(new(((cin + 15) // 16, 9, 2, cout, 8), torch.int16) for _ in range(2))
-                lib().call("e4s_conv_prep_weights_sb", _p(wt[0]), _p(wt[1]), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
-            else:
-                wt = new((cin, 9, cout))
-                lib().call("e4s_conv_prep_weights", _p(wt), None, _p(w), None, None, None, None, 0.0, None, cout, cin, 3, 3, st)
-            return dict(wt=wt, bias=bias, slope=torch.full((cout,), 0.2, dtype=torch.float32, device=dev) if activate else None, cin=cin, cout=cout, down=down)
+            return dict(sg2net.prep_conv3x3(sd[f"{p}.{i}.weight"], b, SQRT2 if activate else 1.0, sb, activate), fir=fir1 if down else None)
 
         def styled(p, up, w_in, norm):
             W = sd[p + ".modulated_conv.weight"]
-            _, cout, cin, _, _ = W.shape
-            composed = up and _use_composed(w_in)
-            wsq = new((cin, cout))
-            if sb:
-                shape = (4 if composed else 1, (cin + 15) // 16, 9, 2, cout, 8)
-                wt = (new(shape, torch.int16), new(shape, torch.int16))
-                lib().call("e4s_modconv_prep_weights_sb", _p(wt[0]), _p(wt[1]), _p(wsq), _p(W), _p(fir4) if composed else None, cout, cin, 1 if composed else 0, st)
-            else:
-                wt = new((4 if composed else 1, cin, 9, cout))
-                lib().call("e4s_modconv_prep_weights", _p(wt), _p(wsq), _p(W), _p(fir4) if composed else None, cout, cin, 3, 1 if composed else 0, st)
+            composed = up and sg2net.use_composed(ARITH, UP_COMPOSED_MAX_WIDTH, w_in)
+            wt, wsq = sg2net.prep_styled(W, fir4, composed, sb)
             return dict(wt=wt, wsq=wsq, mw=sd[p + ".modulated_conv.modulation.weight"], mb=sd[p + ".modulated_conv.modulation.bias"], nw=sd[p + ".weight"],
-                        bias=sd[p + ".activate.bias"], up=up, composed=composed, norm=norm, cin=cin, cout=cout)
+                        bias=sd[p + ".activate.bias"], up=up, composed=composed, norm=norm, cin=W.shape[2], cout=W.shape[1])
 
         def rgb(p):
             W = sd[p + ".modulated_conv.weight"]
-            cin = W.shape[2]
-            wt = new((1, cin, 1, 3))
-            lib().call("e4s_modconv_prep_weights", _p(wt), None, _p(W), None, 3, cin, 1, 0, st)
-            return dict(wt=wt, mw=sd[p + ".modulated_conv.modulation.weight"], mb=sd[p + ".modulated_conv.modulation.bias"],
-                        bias=sd[p + ".bias"].reshape(3).contiguous(), cin=cin)
+            return dict(wt=sg2net.prep_rgb(W), mw=sd[p + ".modulated_conv.modulation.weight"], mb=sd[p + ".modulated_conv.modulation.bias"],
+                        bias=sd[p + ".bias"].reshape(3).contiguous(), cin=W.shape[2])
 
         convs, rgbs = [styled("style_conv1", False, 16, True)], [rgb("to_rgb1")]
         for j in range(n_cond - 1):
             convs += [styled(f"style_convs.{2 * j}", True, 16 << j, False), styled(f"style_convs.{2 * j + 1}", False, 32 << j, True)]
             rgbs.append(rgb(f"to_rgbs.{j}"))
         order = range(n_cond - 1, -1, -1)                                                      # decoder order: the 16 x 16 level first
-        return dict(size=out_size, log_size=log_size, n_cond=n_cond, num_latent=2 * log_size - 6, sb=sb, fir1=fir1, fir4=fir4,
+        return dict(size=out_size, log_size=log_size, n_cond=n_cond, num_latent=2 * log_size - 6, sb=sb, fir4=fir4,
                     first=conv("conv_body_first"), down=[conv(f"conv_body_down.{j}", down=True) for j in range(n_cond - 1)],
                     final_conv=conv("final_conv"), fd1=conv("final_down1", down=True), fd2=conv("final_down2", down=True),
                     final=(sd["final_linear.weight"], sd["final_linear.bias"]),
@@ -412,21 +315,9 @@ class PreparedInpaint(PreparedNet):
 
 
 # ------------------------------------------------------------------------------------------------ the forward pass
-def _conv(P, L, x, out, bs, h):
+def _conv(P, L, x, out, bs, h, st):
     """A plain 3 x 3 convolution layer of the batch ``x [bs, cin, h, h]`` into ``out``; a ``down`` layer blurs into a scratch map first."""
-    st = _stream()
-    act = 2 if L["slope"] is not None else 0
-    stride, pad = 1, 1
-    if L["down"]:
-        blur = torch.empty((bs, L["cin"], h + 1, h + 1), dtype=torch.float32, device=x.device)
-        lib().call("e4s_upfirdn2d", _p(blur), _p(x), _p(P["fir1"]), bs * L["cin"], h, h, 4, 4, 1, 1, 1, 1, 2, 2, 2, 2, st)
-        x, h, stride, pad = blur, h + 1, 2, 0
-    if P["sb"]:
-        lib().call("e4s_conv2d_sb", _p(out), _p(x), None, L["cin"], _p(L["wt"][0]), _p(L["wt"][1]), _p(L["bias"]), None, None, _p(L["slope"]), None, act,
-                   bs, L["cin"], L["cout"], h, h, 3, stride, pad, st)
-    else:
-        lib().call("e4s_conv2d", _p(out), _p(x), None, L["cin"], _p(L["wt"]), _p(L["bias"]), None, None, _p(L["slope"]), None, act,
-                   bs, L["cin"], L["cout"], h, h, 3, stride, pad, st)
+    sg2net.conv3x3(L, x, out, bs, h, P["sb"], st, L["fir"])
 
 
 def _tables(P, latent, bs, dev):
@@ -436,56 +327,14 @@ def _tables(P, latent, bs, dev):
     layers = convs + rgbs
     s_all = torch.empty(bs * sum(L["cin"] for L in layers), dtype=torch.float32, device=dev)
     d_all = torch.empty(bs * sum(L["cout"] for L in convs), dtype=torch.float32, device=dev)
-    arr = (StyleJob * len(layers))()
-    so = do = 0
-    conv_t, rgb_t = [], []
-    for i, (L, row) in enumerate(zip(layers, rows)):
-        s_t = s_all[so:so + bs * L["cin"]]
-        so += bs * L["cin"]
-        d_t = None
-        if "wsq" in L:
-            d_t = d_all[do:do + bs * L["cout"]]
-            do += bs * L["cout"]
-            conv_t.append((s_t, d_t))
-        else:
-            rgb_t.append(s_t)
-        style = latent[:, row]
-        arr[i] = StyleJob(s_t.data_ptr(), None if d_t is None else d_t.data_ptr(), style.data_ptr(), latent.stride(0), 0, L["mw"].data_ptr(),
-                          L["mb"].data_ptr(), None if d_t is None else L["wsq"].data_ptr(), 1, L["cin"], L.get("cout", 3), 0)
-    for i0 in range(0, len(layers), MAX_STYLE_JOBS):
-        lib().call("e4s_style_demod_batched", ctypes.byref(arr, i0 * ctypes.sizeof(StyleJob)), min(MAX_STYLE_JOBS, len(layers) - i0), bs, STYLE_DIM, _stream())
-    return conv_t, rgb_t
+    base, row_bytes = latent.data_ptr(), 4 * latent.stride(1)
+    return sg2net.style_tables(layers, [(base + row * row_bytes, latent.stride(0), 0) for row in rows], bs, STYLE_DIM, s_all, d_all)
 
 
-def _modconv(P, L, x, out, s, d, noise, bs, h):
+def _modconv(P, L, x, out, s, d, noise, bs, h, st):
     """The layer's modulated convolution with its noise; a plain StyleConv adds bias and activation, a norm layer leaves both to the epilogue kernel."""
-    cin, cout = L["cin"], L["cout"]
-    st = _stream()
-    up = L["up"]
     bias, act = (None, 0) if L["norm"] else (L["bias"], 1)
-    if up and not L["composed"]:
-        lib().call("e4s_modconv_up_fused_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), _p(P["fir4"]), _p(noise), noise.shape[0], _p(L["nw"]),
-                   _p(bias), act, bs, cin, cout, h, h, None, st)
-        return
-    ho = 2 * h if up else h
-
-    def call(x, out, s, d, noise, n, ws, wsn):
-        if P["sb"]:
-            lib().call("e4s_region_modconv3x3_sb", _p(out), _p(x), _p(L["wt"][0]), _p(L["wt"][1]), _p(s), _p(d), None, 0, 0, _p(noise), noise.shape[0], _p(L["nw"]),
-                       _p(bias), act, n, cin, cout, h, h, 1, 1 if up else 0, _p(ws), wsn, None, None, None, None, None, None, None, None, None, st)
-        else:
-            lib().call("e4s_region_modconv3x3", _p(out), _p(x), _p(L["wt"]), _p(s), _p(d), None, 0, 0, _p(noise), noise.shape[0], _p(L["nw"]), _p(bias), act,
-                       n, cin, cout, h, h, 1, 1 if up else 0, _p(ws), wsn, st)
-
-    if cout * ho * ho > SPLITK_MAX_OUT_FLOATS:
-        call(x, out, s, d, noise, bs, None, 0)
-        return
-    # a map small enough for split-K: the entry picks the number of K slices from its grid, the batch included, and the slices set the order of the sums.  Sample
-    # by sample every call is a batch-of-one call (and fills the chip through its slices), so a sample gets the bits it gets alone
-    wsn = 16 * cout * ho * ho
-    ws = _workspace(x.device, wsn)
-    for b in range(bs):
-        call(x[b:b + 1], out[b:b + 1], s[b * cin:(b + 1) * cin], d[b * cout:(b + 1) * cout], noise[b:b + 1] if noise.shape[0] == bs else noise, 1, ws, wsn)
+    sg2net.modconv(L, x, out, s, d, sb=P["sb"], blur=P["fir4"], noise=noise, bias=bias, act=act, bs=bs, h=h, st=st)
 
 
 def _condition(P, in_size, bs, dev):
@@ -512,22 +361,22 @@ def _inpaint_run(P, x, in_size, noise, want_latent):
     # encoder: a feature per condition level (encoder order: the full size first), its shift map, then the latent rows
     feats, shifts = [], []
     f = new(bs, P["first"]["cout"], size, size)
-    _conv(P, P["first"], x, f, bs, size)
+    _conv(P, P["first"], x, f, bs, size, st)
     r = size
     for j in range(n_cond):
         if j:
             L = P["down"][j - 1]
             nxt = new(bs, L["cout"], r // 2, r // 2)
-            _conv(P, L, f, nxt, bs, r)
+            _conv(P, L, f, nxt, bs, r, st)
             f, r = nxt, r // 2
         feats.append(f)
         sh = new(bs, P["shift"][j]["cout"], r, r)
-        _conv(P, P["shift"][j], f, sh, bs, r)
+        _conv(P, P["shift"][j], f, sh, bs, r, st)
         shifts.append(sh)
     shifts = shifts[::-1]
     d1, d2 = new(bs, P["fd1"]["cout"], 8, 8), new(bs, P["fd2"]["cout"], 4, 4)
-    _conv(P, P["fd1"], f, d1, bs, 16)
-    _conv(P, P["fd2"], d1, d2, bs, 8)
+    _conv(P, P["fd1"], f, d1, bs, 16, st)
+    _conv(P, P["fd2"], d1, d2, bs, 8, st)
     W, b = P["final"]
     latent = new(bs, P["num_latent"], STYLE_DIM)
     grouped_linear(d2.view(bs, 1, -1), [W], [b], scale=1 / math.sqrt(W.shape[1]), bias_mul=1.0, act=2, out=latent.view(bs, 1, -1))
@@ -536,19 +385,18 @@ def _inpaint_run(P, x, in_size, noise, want_latent):
     # decoder
     convs, rgbs = P["convs"], P["rgbs"]
     out = new(bs, P["final_conv"]["cout"], 16, 16)
-    _conv(P, P["final_conv"], f, out, bs, 16)
+    _conv(P, P["final_conv"], f, out, bs, 16, st)
 
     def torgb(j, x, skip, h):
         R = rgbs[j]
         dst = new(bs, 3, h, h)
-        lib().call("e4s_region_torgb", _p(dst), _p(x), _p(R["wt"]), _p(rgb_t[j]), None, 0, 0, _p(R["bias"]), _p(skip), _p(P["fir4"]) if skip is not None else None,
-                   bs, R["cin"], h, h, 1, st)
+        sg2net.torgb(R, x, rgb_t[j], skip, P["fir4"], dst, bs, h, st)
         return dst
 
     def norm_layer(i, level, x, h):
         L = convs[i]
         y = new(bs, L["cout"], h, h)
-        _modconv(P, L, x, y, *conv_t[i], noise[i], bs, h)
+        _modconv(P, L, x, y, *conv_t[i], noise[i], bs, h, st)
         _scale_shift_act(y, shifts[level], s1n, s2n, begin[level], L["bias"])
         return y
 
@@ -558,7 +406,7 @@ def _inpaint_run(P, x, in_size, noise, want_latent):
     for j in range(1, len(rgbs)):
         a = 2 * j - 1
         up = new(bs, convs[a]["cout"], 2 * h, 2 * h)
-        _modconv(P, convs[a], out, up, *conv_t[a], noise[a], bs, h)
+        _modconv(P, convs[a], out, up, *conv_t[a], noise[a], bs, h, st)
         h *= 2
         out = norm_layer(a + 1, j, up, h)
         skip = torgb(j, out, skip, h)
@@ -583,8 +431,7 @@ def _noise_checked(name, noise, bs, size, dev=None):
 
 
 def _arith_checked(name):
-    if ARITH not in ("sb", "f32"):
-        raise ValueError(f"{name}: ops_inpaint.ARITH is 'sb' or 'f32', got {ARITH!r}")
+    sg2net.arith_checked(name, "ops_inpaint", ARITH)
 
 
 def _weights_checked(name, weights):

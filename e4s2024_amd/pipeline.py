@@ -605,8 +605,7 @@ def gpen_enhance_frames(detector, gpen, parsenet, frames_u8: torch.Tensor, base_
         if base_u8.shape != frames_u8.shape or base_u8.device != frames_u8.device:
             raise ValueError(f"{name}: base_u8 is {tuple(base_u8.shape)} on {base_u8.device}: expected the frames' {tuple(frames_u8.shape)} on {frames_u8.device} "
                              "(resizing the frame to a super-resolved size is the caller's)")
-    ops_gpen.check_loaded(gpen)
-    S = int(netweights._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+    S = int(ops_gpen._weights_checked(name, gpen)[1][0])
     structure = netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))[1]
     if ops_parsenet.parsenet_output_size(structure, S, S) != (S, S):
         raise ValueError(f"{name}: the ParseNet turns a {S} x {S} face into a {ops_parsenet.parsenet_output_size(structure, S, S)} mask: expected {S} x {S} "
@@ -663,8 +662,7 @@ def gpen_face_enhancement(detector, gpen, parsenet, sr, frames_u8: torch.Tensor,
         netweights._devices_checked(name, "frames_u8", frames_u8, ops_gpen_sr.gpen_sr_weight_tensors(sr, name))
     netweights._cuda_checked(name, frames_u8=frames_u8)
     if aligned:
-        ops_gpen.check_loaded(gpen)
-        S = int(netweights._validated(name, gpen, ops_gpen._net_of(gpen))[1][0])
+        S = int(ops_gpen._weights_checked(name, gpen)[1][0])
         if tuple(frames_u8.shape[1:3]) != (S, S):
             raise ValueError(f"{name}: aligned faces are {S} x {S}, the generator's size (the reference resizes them with cv2, which is not done here), "
                              f"got {tuple(frames_u8.shape)}")
@@ -674,8 +672,7 @@ def gpen_face_enhancement(detector, gpen, parsenet, sr, frames_u8: torch.Tensor,
     if sr is None:
         return gpen_enhance_frames(detector, gpen, parsenet, frames_u8, return_faces=return_faces)
     from . import ops_parsenet
-    ops_gpen.check_loaded(gpen)                                               # what gpen_enhance_frames refuses, before the RealESRNet pass runs
-    netweights._validated(name, gpen, ops_gpen._net_of(gpen))
+    ops_gpen._weights_checked(name, gpen)                                     # what gpen_enhance_frames refuses, before the RealESRNet pass runs
     netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))
     img_sr = gpen_super_resolve(sr, frames_u8)
     resized = ops.cv_resize_linear(frames_u8, (img_sr.shape[2], img_sr.shape[1]))
@@ -880,8 +877,7 @@ def _reenact_args_checked(name, generator, kp_detector, he_estimator, detector, 
     pred_hw = (4 * f3.shape[3], 4 * f3.shape[4])                               # as make_animation sizes an empty clip
     if not enhance:
         return pred_hw, pred_hw
-    ops_gpen.check_loaded(gpen)
-    g_checked = netweights._validated(name, gpen, ops_gpen._net_of(gpen))
+    g_checked = ops_gpen._weights_checked(name, gpen)
     S = int(g_checked[1][0])
     p_checked = netweights._validated(name, parsenet, ops_parsenet._net_of(parsenet))
     if ops_parsenet.parsenet_output_size(p_checked[1], S, S) != (S, S):

@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
 import gpen_model as GM
-from e4s2024_amd import netweights, ops, ops_gpen, seeded
+from e4s2024_amd import netweights, ops, ops_gpen, seeded, sg2net
 from time_resunet import alternate, graphed
 
 dev = "cuda:0"
@@ -53,7 +53,7 @@ def spread(res):
 
 def layer_table(net, x, rounds):
     """Time of every convolution entry of one native call at batch 1, each on the buffers the call leaves behind."""
-    checked = ops_gpen._validated("time_gpen", net, ops_gpen._net_of(net))
+    checked = ops_gpen._weights_checked("time_gpen", net)
     rows = []
     default_width = ops_gpen.UP_COMPOSED_MAX_WIDTH
     for width, label in ((ops_gpen.UP_COMPOSED_MAX_WIDTH, "default"), (0, "up layers fused"), (4096, "up layers composed")):
@@ -67,7 +67,8 @@ def layer_table(net, x, rounds):
         h = 4
         for i, L in enumerate(P["convs"]):
             src = P["const"] if i == 0 else S["outs"][i - 1]
-            fn = lambda L=L, src=src, i=i, h=h: ops_gpen._modconv(P, L, src, S["outs"][i][:, :L["cout"]], *conv_t[i], h, h)      # noqa: E731
+            fn = lambda L=L, src=src, i=i, h=h: sg2net.modconv(L, src, S["outs"][i][:, :L["cout"]], *conv_t[i], sb=P["sb"], blur=L["blur"],      # noqa: E731
+                                                               bias=L["bias"], act=1, bs=1, h=h, st=ops._stream())
             if label == "default" or L["up"]:
                 route = ("composed" if L["composed"] else "fused") if L["up"] else "same"
                 ms = statistics.median(alternate({"l": fn}, rounds, 20)["l"])
@@ -76,11 +77,8 @@ def layer_table(net, x, rounds):
                 h *= 2
         if label == "default":
             r = SIZE
-            for L, s_, d_ in zip(P["enc"], S["feats"][:-1], S["feats"][1:]):
-                def enc(L=L, s_=s_, d_=d_, r=r):
-                    ops.lib().call("e4s_upfirdn2d", ops._p(S["blur"]), ops._p(s_), ops._p(L["fir"]), L["cin"], r, r, 4, 4, 1, 1, 1, 1, 2, 2, 2, 2, ops._stream())
-                    ops.lib().call("e4s_conv2d_sb", ops._p(d_), ops._p(S["blur"]), None, L["cin"], ops._p(L["wt"][0]), ops._p(L["wt"][1]), ops._p(L["bias"]), None, None,
-                                   ops._p(L["slope"]), None, 2, 1, L["cin"], L["cout"], r + 1, r + 1, 3, 2, 0, ops._stream())
+            for L, s_, d_, blur in zip(P["enc"], S["feats"][:-1], S["feats"][1:], S["blurs"]):
+                enc = lambda L=L, s_=s_, d_=d_, r=r, blur=blur: sg2net.conv3x3(L, s_, d_, 1, r, P["sb"], ops._stream(), L["fir"], blur)      # noqa: E731
                 ms = statistics.median(alternate({"l": enc}, rounds, 20)["l"])
                 rows.append((label, f"encoder {L['cin']:4d} -> {L['cout']:3d} @ {r:3d} blur + conv", "sb", ms))
                 r //= 2

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
 import inpaint_model as M
-from e4s2024_amd import netweights, ops, ops_inpaint, pipeline
+from e4s2024_amd import netweights, ops, ops_inpaint, pipeline, sg2net
 from time_resunet import alternate, graphed
 
 dev = "cuda:0"
@@ -61,7 +61,9 @@ def layer_table(net, rounds):
             x, y, s, d, nz = new(1, L["cin"], h, h), new(1, L["cout"], ho, ho), new(L["cin"]), new(L["cout"]).abs(), new(1, 1, ho, ho)
             if label == "default" or L["up"]:
                 route = ("composed" if L["composed"] else "fused") if L["up"] else "same"
-                ms = statistics.median(alternate({"l": lambda: ops_inpaint._modconv(P, L, x, y, s, d, nz, 1, h)}, rounds, 20)["l"])
+                bias, act = (None, 0) if L["norm"] else (L["bias"], 1)
+                fn = lambda: sg2net.modconv(L, x, y, s, d, sb=P["sb"], blur=P["fir4"], noise=nz, bias=bias, act=act, bs=1, h=h, st=ops._stream())      # noqa: E731
+                ms = statistics.median(alternate({"l": fn}, rounds, 20)["l"])
                 rows.append((label, f"decoder {L['cin']:4d} -> {L['cout']:3d} @ {h:3d}{' up' if L['up'] else '   '}", route, ms))
             if label == "default" and L["norm"]:
                 sh, t1, t2 = new(1, L["cout"], ho, ho), new(1, L["cout"]), new(1, L["cout"])
