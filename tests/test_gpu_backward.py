@@ -1,5 +1,6 @@
 """Row f1 (interim): gradients through the drop-in modules on the GPU — fused HIP forward, stock-PyTorch backward
-(ops._TorchBackward + torch_ref.py) — against autograd through the CPU oracle."""
+(ops._TorchBackward + torch_ref.py) — against autograd through the CPU oracle.
+Each gradient kernel alone, with its own bar, model and mutants: tests/test_gpu_grad_kernels.py (tests/grad_model.py, tests/test_grad_model_cpu.py)."""
 import numpy as np
 import pytest
 import torch

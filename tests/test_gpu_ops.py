@@ -1,5 +1,6 @@
 """GPU parity of the stand-alone ops (SURVEY §8a rows a1, a2, a7 + the region-map helper) through the C ABI,
-against the golden fixtures (reference outputs) and the CPU oracle."""
+against the golden fixtures (reference outputs) and the CPU oracle.
+``e4s_grouped_linear`` at ragged shapes, strides and alignments against float64, and its backward: tests/test_gpu_grad_kernels.py."""
 import numpy as np
 import pytest
 import torch
